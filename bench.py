@@ -9,6 +9,10 @@ terminations and in-kernel Philox resets are inside the timed region).  Inputs (
 are resident in HBM before the timed region.  Envs shard across ranks with no data-path collective
 (weak scaling: 2^20 envs per GPU); `--allgather-obs` adds the optional RCCL all-gather of the
 observations for the single-policy layout.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what takes runs of its own:
+the CPU baseline (`cpu_baseline`) and the in-run PMC traffic (`roofline.traffic`, child rocprofv3 passes).
+`--dump-outputs DIR` writes what the last timed step returned (see dump_outputs).
 """
 import argparse
 import json
@@ -20,6 +24,30 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_ROWS = 65536          # --dump-outputs: at most this many env rows ...
+DUMP_BYTES = 60 * 2 ** 20  # ... and at most this many bytes in all
+
+
+def dump_outputs(path, out, n):
+    """--dump-outputs: what the last timed step returned to its caller -- obs, reward, terminated, truncated,
+    info['cost'], info['final_obs'] -- for a fixed sample of env rows (all of them when they fit, else a sorted
+    np.random.RandomState(0) choice), as float32 .npy files, plus the sampled env ids (env_index.npy, float64).
+    final_obs rows are defined where an env finished; the other rows are written as 0."""
+    import numpy as np
+    import torch
+    obs, reward, term, trunc, info = out
+    D = obs.shape[1]
+    rows = min(n, DUMP_ROWS, DUMP_BYTES // ((2 * D + 4) * 4 + 8))
+    idx = np.arange(n) if rows == n else np.sort(np.random.RandomState(0).choice(n, rows, replace=False))
+    sel = torch.from_numpy(idx).to(obs.device)
+    done = (term | trunc)[sel]
+    arrays = {"obs": obs[sel], "reward": reward[sel], "terminated": term[sel], "truncated": trunc[sel],
+              "cost": info["cost"][sel],
+              "final_obs": torch.where(done[:, None], info["final_obs"][sel], torch.zeros((), device=obs.device))}
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(path, "env_index.npy"), idx.astype(np.float64))
 
 
 def physical_cores():
@@ -176,9 +204,15 @@ def main():
                     help="after the main measurement, time the same configuration at these env counts too (one GPU, eager "
                          "mode) and report them under roofline.other_sizes -- e.g. --config 6 --also-envs 2097152: 2^21 envs per "
                          "handle is the noisy kernels' sweet spot (DESIGN section 9)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline (cpu_baseline) and roofline.traffic "
+                         "from child rocprofv3 --pmc passes; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (a fixed sample of at most "
+                         f"{DUMP_ROWS} env rows) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="do not measure roofline.traffic with child rocprofv3 --pmc passes (the children pass this)")
+                    help="with --full: do not measure roofline.traffic with child rocprofv3 --pmc passes")
     ap.add_argument("--same-device", action="store_true",
                     help="TEST ONLY: every rank uses cuda:0 and the control collectives run over gloo, so that the "
                          "multi-rank code path (incl. --allgather-obs p2p) can be exercised on a 1-GPU box; "
@@ -190,6 +224,8 @@ def main():
                          "run on this ROCm; says nothing about xGMI")
     ap.add_argument("--no-auto-reset", action="store_true", help="diagnostic only: INVALID as a benchmark number")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # No launcher around us: start the N ranks ourselves (the role of the reference's mpi_fork,
@@ -295,7 +331,7 @@ def main():
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 for s in range(T):
-                    env.step(ring[s])
+                    graph_out = env.step(ring[s])  # the last captured step's tensors: rewritten by every replay
             launch = lambda j: graph.replay()
         else:
             assert T % K == 0
@@ -320,11 +356,18 @@ def main():
     t0 = time.perf_counter()
     ev0.record()  # same stream pds_step launches on (torch's current stream)
     for j in range(args.steps // K):
-        launch(args.warmup // K + j)
+        last = launch(args.warmup // K + j)
     ev1.record()
     sync()
     wall = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / (args.steps // K)  # average launch-to-launch duration on the stream
+    if args.dump_outputs and rank == 0:  # before anything else steps the env and reuses its buffers
+        if args.mode == "graph":
+            last = graph_out
+        elif args.mode == "stepk":  # [K, N, ...] -> the launch's last step
+            o, r, te, tr, inf = last
+            last = (o[K - 1], r[K - 1], te[K - 1], tr[K - 1], {"cost": inf["cost"][K - 1], "final_obs": inf["final_obs"][K - 1]})
+        dump_outputs(args.dump_outputs, last, n)
     per_rank_ms, gather_ms = None, None
     if multi:
         mine = torch.tensor([wall], device=cdev, dtype=torch.float64)
@@ -361,8 +404,8 @@ def main():
     achieved = launch_bytes / (kernel_ms * 1e-3) / 1e9
     # HBM bytes per launch measured with the PMC counters (separate rocprofv3 passes,
     # profiles/run_profile.sh) for exactly this workload; null for workloads that were not profiled
-    traffic, traffic_src = None, None
-    if rank == 0 and world == 1 and args.mode == "eager" and not args.no_traffic and not args.no_auto_reset:
+    traffic, traffic_src = None, (None if args.full else "the in-run measurement needs --full")
+    if args.full and rank == 0 and world == 1 and args.mode == "eager" and not args.no_traffic and not args.no_auto_reset:
         tail = ["--config", str(args.config), "--task", args.task]
         if args.envs_per_gpu is not None:
             tail += ["--envs-per-gpu", str(args.envs_per_gpu)]
@@ -431,7 +474,7 @@ def main():
             line["per_rank_ms_per_step"] = per_rank_ms
         if gather_ms is not None:
             line["allgather_ms"] = gather_ms  # the exchange alone (max over ranks), for reading the scaling curve
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 line["cpu_baseline"] = cpu_baseline(task, {k: (int(v) if isinstance(v, bool) else v) for k, v in kw.items()}, n)
             except Exception as e:  # the baseline is reported, never required for the GPU number

@@ -7,8 +7,8 @@ O=$REPO/gpurun_out/r04
 mkdir -p $O
 cd $REPO
 timeout 1500 python -m pytest tests -m gpu -q > $O/gputest.log 2>&1; echo "pytest rc=$?" >> $O/gputest.log; tail -3 $O/gputest.log
-timeout 900 python bench.py > $O/bench_headline.json 2> $O/bench_headline.err
-for c in 2 3 4 6; do timeout 600 python bench.py --config $c > $O/bench_config$c.json 2> $O/bench_config$c.err; done
+timeout 900 python bench.py --full > $O/bench_headline.json 2> $O/bench_headline.err
+for c in 2 3 4 6; do timeout 600 python bench.py --config $c --full > $O/bench_config$c.json 2> $O/bench_config$c.err; done
 timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-traffic > $O/bench_driver_window.json 2>/dev/null
 for c in 0 2 3 4 6; do
   BENCH_ARGS="--config $c" bash profiles/run_profile.sh r04_c$c > $O/profile_c$c.log 2>&1

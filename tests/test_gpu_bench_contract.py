@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
-                          "--envs-per-gpu", "65536"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--envs-per-gpu", "65536", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -32,6 +32,63 @@ def test_bench_json_line():
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c and c["value_1_thread"] > 0
     assert "65536 envs" in c["sample"]  # timed at the GPU run's N
     assert 0 < r["frac_wall"] <= r["frac"] * 1.05
+
+
+def _plain_dump(dump_dir, extra=()):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
+                          "--envs-per-gpu", "65536", "--dump-outputs", str(dump_dir)] + list(extra),
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run times the steps only (no cpu_baseline, no rocprofv3 children: those need --full) and --dump-outputs
+    writes what the last timed step returned: the same arrays from run to run, and equal to an env of the same seed
+    driven through the same action ring for warmup + steps steps in this process."""
+    import numpy as np
+    import torch
+    import phoenix_drone_simulation_amd as pds
+
+    d = _plain_dump(tmp_path / "a")
+    assert "cpu_baseline" not in d and d["steps"] == 30 and d["warmup"] == 5
+    assert d["metric"] == "env-steps/sec" and d["dtype"] == "f32" and d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert "measured in this run" not in str(d["roofline"]["traffic_source"])
+    _plain_dump(tmp_path / "b")
+    names = ("obs", "reward", "terminated", "truncated", "cost", "final_obs", "env_index")
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in names}
+    assert sum(v.nbytes for v in a.values()) <= 64e6
+    for k in names:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k]), k
+    n = 65536
+    assert np.array_equal(a["env_index"], np.arange(n))  # every row fits the budget at this size
+    # bench.py's inputs, rebuilt: env seed 0, action ring [64, N, 4] = hover + 0.1 N(0, 1) from a generator seeded 0
+    dev = torch.device("cuda", 0)
+    env = pds.make("DroneHoverSimpleEnv-v0", num_envs=n, device=dev, seed=0, env_id_base=0,
+                   observation_noise=-1, domain_randomization=-1, motor_thrust_noise=0)
+    g = torch.Generator(device=dev)
+    g.manual_seed(0)
+    ring = (-1.0 + 2.0 / 2.25) + 0.1 * torch.randn(64, n, 4, generator=g, device=dev, dtype=torch.float32)
+    env.reset()
+    for s in range(35):
+        o, r, te, tr, info = env.step(ring[s % 64])
+    torch.cuda.synchronize()
+    assert np.array_equal(a["obs"], o.cpu().numpy()) and np.array_equal(a["reward"], r.cpu().numpy())
+    assert np.array_equal(a["terminated"], te.float().cpu().numpy()) and np.array_equal(a["truncated"], tr.float().cpu().numpy())
+    assert np.array_equal(a["cost"], info["cost"].cpu().numpy())
+    done = (te | tr).cpu().numpy()
+    assert np.array_equal(a["final_obs"][done], info["final_obs"].cpu().numpy()[done]) and not a["final_obs"][~done].any()
+    env.close()
+    # the diagnostic modes dump their last env-step too: bitwise the eager one (step_k and graph replay equal K eager steps)
+    c = _plain_dump(tmp_path / "c", ["--steps", "64", "--warmup", "0", "--mode", "stepk"])
+    assert c["steps"] == 64
+    e = _plain_dump(tmp_path / "e", ["--steps", "64", "--warmup", "0"])
+    for k in names:
+        assert np.array_equal(np.load(tmp_path / "c" / f"{k}.npy"), np.load(tmp_path / "e" / f"{k}.npy")), k
 
 
 def test_bench_multi_rank_code_path_on_one_gpu():
