@@ -1,0 +1,304 @@
+"""Helpers for tests/test_gpu_mlp_dispatch.py and its CPU companion: a Python restatement of the host predicates that pick a
+kernel instantiation in csrc/pds_mlp.hip (pds_mlp_forward, launch_grad) and csrc/pds_mlp_wide.hip (launch_wide, launch_nin),
+a scanner of the launch sites of those two files, the GPU case table, and float64 autograd references of the three fused
+operations (forward, PPO-clip policy gradient, value-regression gradient).
+
+A member of the dispatch set is a canonical string: the kernel's name and its template arguments with the defaults filled in
+and PDS_MLP_SPLIT replaced by its value, e.g. "mlp_kernel<LOSS_MSE,1,1,true,2,4>", "ppo_split_kernel<2,1,true>",
+"mlp_wide_kernel<LOSS_PPO,0,8>"."""
+import os
+import re
+from collections import namedtuple
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "phoenix-drone-simulation_amd", "csrc")
+MLP_SOURCES = ("pds_mlp.hip", "pds_mlp_wide.hip")
+
+# ---- constants of csrc/pds_mlp_common.h / pds_mlp.hip (the CPU test pins them against the sources) --------------------
+TILE = 16                 # kTS: samples per wave tile
+MAX_DIM = 64              # kMaxDim: d_in of pds_mlp.hip, h1, h2
+NARROW_WAVES = 8          # kWaves
+WIDE_WAVES = 4            # kWideWaves
+MAX_BLOCKS = 256          # grid_blocks / wide_grid_blocks / the split kernel's cap
+SPLIT_PAIRS = NARROW_WAVES // 2   # kPairs: tiles a split block takes per round
+MLP_SPLIT = 1             # PDS_MLP_SPLIT default
+BF16_MIN_SAMPLES = 65536  # PDS_BF16_MIN_SAMPLES default
+
+# samples one persistent grid covers before its waves stride into their second tile
+NARROW_ROUND = MAX_BLOCKS * NARROW_WAVES * TILE   # 32 768
+WIDE_ROUND = MAX_BLOCKS * WIDE_WAVES * TILE       # 16 384
+SPLIT_ROUND = MAX_BLOCKS * SPLIT_PAIRS * TILE     # 16 384
+
+LOSS = {"fwd": "LOSS_NONE", "ppo": "LOSS_PPO", "mse": "LOSS_MSE"}
+ACT = {"relu": 0, "tanh": 1}
+
+
+# ---- dispatch mirror ----------------------------------------------------------------------------------------------------
+def last_steps(dim):
+    d = dim - 16 * ((dim - 1) // 16)
+    return d if d < 4 else 4
+
+
+def two_hidden_steps(h1, h2):
+    return h1 == h2 and h1 > 48 and last_steps(h1) == 2
+
+
+def two_input_steps(d_in):
+    return 32 < d_in <= 48 and last_steps(d_in) == 2
+
+
+def _mlp(loss, act, ninb, gb, kji=4, kjh=4):
+    return f"mlp_kernel<{loss},{act},{ninb},{'true' if gb else 'false'},{kji},{kjh}>"
+
+
+def _nin(d_in):
+    """launch_nin: input tiles in steps of two"""
+    nin = (d_in + TILE - 1) // TILE
+    return 6 if nin <= 6 else 8 if nin <= 8 else 10 if nin <= 10 else 12
+
+
+def instantiation(kind, d_in, h1, h2, act, B=1, index=False, mean=False, bf16_min=BF16_MIN_SAMPLES):
+    """the kernel that pds_mlp_forward (kind "fwd") / launch_grad ("ppo", "mse") launches for this call.  `index` and `mean`
+    are the host predicate's inputs a.index != nullptr / a.mean != nullptr (the PPO entry points pass neither)."""
+    loss, a = LOSS[kind], ACT[act]
+    if kind == "fwd":
+        if d_in > MAX_DIM:
+            return f"mlp_wide_kernel<{loss},{a},{_nin(d_in)}>"
+        wide = d_in > 3 * TILE
+        ki2, kh2 = two_input_steps(d_in), two_hidden_steps(h1, h2)
+        if wide:
+            return _mlp(loss, a, 2, False)
+        if a == 0:
+            if kh2 and ki2:
+                return _mlp(loss, 0, 1, False, 2, 2)
+            if kh2:
+                return _mlp(loss, 0, 1, False, 4, 2)
+            return _mlp(loss, 0, 1, False)
+        if ki2 and not kh2:
+            return _mlp(loss, 1, 1, False, 2, 4)
+        return _mlp(loss, 1, 1, False)
+    gb = h1 == MAX_DIM or h2 == MAX_DIM or d_in == MAX_DIM
+    wide = d_in > 3 * TILE if gb else d_in >= 3 * TILE
+    ki2, kh2 = two_input_steps(d_in), two_hidden_steps(h1, h2)
+    if d_in > MAX_DIM:
+        return f"mlp_wide_kernel<{loss},{a},{_nin(d_in)}>"
+    if MLP_SPLIT and kind == "ppo" and a == 0 and not gb and not wide and kh2 and not index and not mean:
+        return f"ppo_split_kernel<{2 if ki2 else 4},{MLP_SPLIT},{'true' if B >= bf16_min else 'false'}>"
+    if kind == "ppo" and a == 0 and not gb and not wide and kh2:
+        return _mlp(loss, 0, 1, False, 2 if ki2 else 4, 2)
+    if kind == "mse" and a == 1 and gb and not wide and ki2 and not kh2:
+        return _mlp(loss, 1, 1, True, 2, 4)
+    return _mlp(loss, a, 2 if wide else 1, gb)
+
+
+def family_round(member):
+    """samples of one full round of the member's persistent grid"""
+    if member.startswith("mlp_wide_kernel"):
+        return WIDE_ROUND
+    if member.startswith("ppo_split_kernel"):
+        return SPLIT_ROUND
+    return NARROW_ROUND
+
+
+# ---- launch-site scanner ------------------------------------------------------------------------------------------------
+_SITE = re.compile(r"hipLaunchKernelGGL\(\s*(\(?)\s*(\w+)\s*(?:<([^<>]*)>)?\s*\)?\s*,")
+_DEFAULTS = {"mlp_kernel": ["4", "4"], "ppo_split_kernel": ["false"]}
+_ARITY = {"mlp_kernel": 6, "ppo_split_kernel": 3, "mlp_wide_kernel": 3}
+
+
+def _canon(name, args, subst):
+    vals = [subst.get(v.strip(), v.strip()) for v in args.split(",")] if args else []
+    vals = [str(MLP_SPLIT) if v == "PDS_MLP_SPLIT" else v for v in vals]
+    if name in _ARITY:
+        need = _ARITY[name] - len(vals)
+        if need > 0:
+            vals += _DEFAULTS.get(name, [])[len(_DEFAULTS.get(name, [])) - need:]
+    return f"{name}<{','.join(vals)}>" if vals else name
+
+
+def launch_sites():
+    """-> (list of (file, canonical member) per launch site after expanding PDS_MLP_LAUNCH and launch_nin<LOSS, ACT>,
+    raw hipLaunchKernelGGL count per file).  reduce_kernel is left out; a site whose template arguments still name something
+    that is not a literal after the expansion is returned unresolved (and so is no member of the mirror's codomain)."""
+    sites, raw = [], {}
+    for fname in MLP_SOURCES:
+        with open(os.path.join(CSRC, fname)) as f:
+            text = f.read()
+        raw[fname] = len(re.findall(r"hipLaunchKernelGGL\(", text))
+        macros = {}  # name -> (params, body)
+        for m in re.finditer(r"#define\s+(\w+)\(([^)]*)\)((?:[^\n]*\\\n)+[^\n]*)", text):
+            macros[m.group(1)] = ([p.strip() for p in m.group(2).split(",")], m.group(3), m.span())
+        covered = [span for _, _, span in macros.values()]
+        # template functions that launch on their own template parameters: template <int LOSS, int ACT> ... name(
+        templ = {}
+        for m in re.finditer(r"template\s*<([^<>]*)>\s*static\s+void\s+(\w+)\s*\(", text):
+            params = [p.split()[-1] for p in m.group(1).split(",")]
+            body_start = text.index("{", m.end())
+            depth, i = 0, body_start
+            while True:
+                depth += {"{": 1, "}": -1}.get(text[i], 0)
+                i += 1
+                if depth == 0:
+                    break
+            templ[m.group(2)] = (params, text[body_start:i], (m.start(), i))
+            covered.append((m.start(), i))
+        for mname, (params, body, _) in macros.items():
+            calls = [c for c in re.finditer(rf"\b{mname}\(([^()]*)\)", text) if not any(a <= c.start() < b for a, b in covered)]
+            for c in calls:
+                subst = dict(zip(params, [v.strip() for v in c.group(1).split(",")]))
+                sites += [(fname, _canon(s.group(2), s.group(3), subst)) for s in _SITE.finditer(body)]
+        for tname, (params, body, _) in templ.items():
+            calls = [c for c in re.finditer(rf"\b{tname}<([^<>]*)>\s*\(", text) if not any(a <= c.start() < b for a, b in covered)]
+            for c in calls:
+                subst = dict(zip(params, [v.strip() for v in c.group(1).split(",")]))
+                sites += [(fname, _canon(s.group(2), s.group(3), subst)) for s in _SITE.finditer(body)]
+        for s in _SITE.finditer(text):
+            if not any(a <= s.start() < b for a, b in covered):
+                sites.append((fname, _canon(s.group(2), s.group(3), {})))
+    return [(f, m) for f, m in sites if m != "reduce_kernel"], raw
+
+
+def launch_set():
+    return {m for _, m in launch_sites()[0]}
+
+
+# ---- the GPU case table -------------------------------------------------------------------------------------------------
+# kind: "fwd" | "ppo" | "mse"; index: None | "perm" (a permutation slice) | "rep" (a slice with repeated entries);
+# std: the forward's optional mean / std / eps standardisation
+Case = namedtuple("Case", "kind d_in h1 h2 d_out act B index std")
+
+
+def _c(kind, d_in, h1, h2, d_out, act, B, index=None, std=False):
+    return Case(kind, d_in, h1, h2, d_out, act, B, index, std)
+
+
+def _tail(rnd, k):
+    """a ragged batch past two full rounds of a grid that covers `rnd` samples per round"""
+    return 2 * rnd + TILE * (3 + k) + 5 + 2 * k
+
+
+def _case_table():
+    cases = []
+    # one net shape per instantiation, chosen to walk the d_in / hidden / d_out axes; each gets tiny batches and a ragged tail
+    # past its grid's second round (the persistent loop's stride, its accumulation across rounds and the last partial tile)
+    fwd = [(1, 16, 17, 1, "relu"), (3, 17, 1, 8, "tanh"), (15, 33, 48, 3, "relu"), (16, 49, 63, 5, "tanh"),
+           (17, 63, 49, 2, "relu"), (31, 48, 16, 6, "tanh"), (32, 64, 64, 7, "relu"), (33, 50, 50, 4, "relu"),
+           (34, 50, 50, 4, "relu"), (34, 64, 64, 1, "tanh"), (34, 50, 50, 4, "tanh"), (47, 50, 50, 8, "relu"),
+           (48, 1, 64, 4, "tanh"), (49, 33, 17, 3, "relu"), (63, 64, 50, 1, "tanh"), (64, 16, 33, 8, "relu"),
+           (65, 64, 64, 1, "tanh"), (96, 17, 33, 8, "relu"), (97, 50, 50, 4, "relu"), (128, 64, 49, 1, "tanh"),
+           (129, 33, 63, 4, "tanh"), (160, 48, 48, 2, "relu"), (161, 63, 17, 6, "relu"), (191, 49, 64, 4, "tanh"),
+           (192, 64, 64, 8, "relu"), (191, 1, 16, 1, "relu"), (97, 16, 1, 3, "tanh"), (161, 50, 50, 4, "tanh")]
+    ppo = [(1, 16, 17, 1, "relu"), (3, 64, 64, 2, "relu"), (15, 17, 33, 3, "tanh"), (16, 64, 48, 5, "tanh"),
+           (17, 50, 50, 8, "relu"), (31, 33, 63, 6, "relu"), (32, 50, 50, 4, "tanh"), (33, 64, 64, 7, "tanh"),
+           (34, 50, 50, 4, "relu"), (34, 50, 50, 6, "relu"), (47, 50, 50, 4, "relu"), (48, 50, 50, 4, "relu"),
+           (48, 49, 1, 2, "tanh"), (49, 64, 17, 4, "relu"), (63, 16, 48, 1, "relu"), (64, 50, 50, 4, "tanh"),
+           (55, 48, 63, 8, "tanh"), (65, 64, 64, 4, "relu"), (96, 17, 49, 2, "tanh"), (97, 50, 50, 4, "relu"),
+           (128, 33, 64, 1, "tanh"), (129, 64, 63, 4, "relu"), (160, 48, 16, 3, "tanh"), (161, 50, 50, 8, "relu"),
+           (192, 64, 64, 4, "tanh"), (191, 63, 33, 5, "relu"), (34, 17, 17, 4, "relu")]
+    mse = [(1, 64, 64, "tanh"), (3, 16, 17, "relu"), (15, 17, 1, "tanh"), (16, 64, 49, "relu"), (17, 33, 63, "tanh"),
+           (31, 50, 50, "relu"), (33, 49, 33, "relu"), (34, 64, 64, "tanh"), (34, 50, 50, "tanh"), (47, 63, 64, "relu"),
+           (48, 48, 48, "tanh"), (49, 64, 64, "relu"), (64, 17, 50, "tanh"), (63, 33, 16, "relu"), (48, 50, 50, "relu"),
+           (65, 64, 64, "tanh"), (96, 50, 50, "relu"), (97, 64, 64, "relu"), (128, 17, 63, "tanh"), (129, 64, 64, "tanh"),
+           (160, 49, 33, "relu"), (161, 64, 64, "tanh"), (192, 50, 50, "relu"), (191, 63, 48, "tanh"), (55, 64, 64, "tanh")]
+    small = (1, 15, 16, 17)
+    for i, (d, h1, h2, o, act) in enumerate(fwd):
+        rnd = family_round(instantiation("fwd", d, h1, h2, act))
+        cases.append(_c("fwd", d, h1, h2, o, act, small[i % 4], std=i % 2 == 1))
+        cases.append(_c("fwd", d, h1, h2, o, act, _tail(rnd, i), index=(None, "perm", "rep")[i % 3], std=i % 2 == 0))
+    for i, (d, h1, h2, o, act) in enumerate(ppo):
+        member = instantiation("ppo", d, h1, h2, act, 1)
+        cases.append(_c("ppo", d, h1, h2, o, act, small[i % 4]))
+        cases.append(_c("ppo", d, h1, h2, o, act, _tail(family_round(member), i)))
+    for i, (d, h1, h2, act) in enumerate(mse):
+        rnd = family_round(instantiation("mse", d, h1, h2, act))
+        cases.append(_c("mse", d, h1, h2, 1, act, small[i % 4], index=(None, "perm", "rep")[i % 3]))
+        cases.append(_c("mse", d, h1, h2, 1, act, _tail(rnd, i), index=(None, "perm", "rep")[(i + 1) % 3]))
+    # around the split kernel's bf16 switch (both input-step forms), and its f32 form past two of its rounds
+    for d in (34, 42):
+        cases += [_c("ppo", d, 50, 50, 4, "relu", BF16_MIN_SAMPLES - 1), _c("ppo", d, 50, 50, 4, "relu", BF16_MIN_SAMPLES),
+                  _c("ppo", d, 50, 50, 4, "relu", 2 * SPLIT_ROUND + 37), _c("ppo", d, 50, 50, 4, "relu", BF16_MIN_SAMPLES + 37)]
+    # what the trainer runs at its largest: the default critic on indexed mini-batches of B / 16 samples (2^20 x 8 / 16), the
+    # default policy and critic forward over 2^20 rows
+    cases += [_c("mse", 34, 64, 64, 1, "tanh", 524288, index="perm"), _c("mse", 34, 64, 64, 1, "tanh", 524288, index="rep"),
+              _c("fwd", 34, 50, 50, 4, "relu", 1 << 20, std=True), _c("fwd", 34, 64, 64, 1, "tanh", 1 << 20, std=True)]
+    return cases
+
+
+CASES = _case_table()
+
+
+def case_member(c):
+    return instantiation(c.kind, c.d_in, c.h1, c.h2, c.act, c.B, index=c.index is not None, mean=c.std)
+
+
+def case_id(c):
+    return (f"{c.kind}-{c.d_in}x{c.h1}x{c.h2}x{c.d_out}-{c.act}-B{c.B}" + (f"-{c.index}" if c.index else "") +
+            ("-std" if c.std else ""))
+
+
+# ---- inputs and float64 references (torch is imported lazily: the CPU test imports this module without a device) -------
+def make_net(d_in, h1, h2, d_out, act, seed):
+    import torch
+    from phoenix_drone_simulation_amd.ppo import _mlp
+    torch.manual_seed(seed)
+    return _mlp([d_in, h1, h2, d_out], act).cuda()
+
+
+def net64(net):
+    import copy
+    return copy.deepcopy(net).double()
+
+
+def make_index(kind, rows, B, seed):
+    """a permutation slice of `rows` (B <= rows), or B entries drawn with repeats from the first rows"""
+    import torch
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    if kind == "perm":
+        return torch.randperm(rows, device="cuda", generator=g)[:B]
+    return torch.randint(0, max(rows // 2, 1), (B,), device="cuda", generator=g)
+
+
+def ref_forward(net, x, index=None, mean=None, std=None, eps=1e-5):
+    n64 = net64(net)
+    xs = x.double() if index is None else x.double()[index]
+    if mean is not None:
+        xs = (xs - mean.double()) / (std.double() + eps)
+    with __import__("torch").no_grad():
+        return n64(xs)
+
+
+def ref_ppo(net, x, act, adv, logp_old, log_std, clip, round_mu=False):
+    """compute_loss_pi through float64 autograd -> (flat gradient, [loss sum, ratio sum, kl sum, count]).  round_mu: the policy
+    mean rounded to float32 on its way into the loss (the gradient still flows through it): what a kernel whose forward is
+    exact to the last float32 bit would see"""
+    import torch
+    n64 = net64(net)
+    B = x.shape[0]
+    mu = n64(x.double())
+    if round_mu:
+        mu = mu + (mu.float().double() - mu).detach()
+    d = torch.distributions.Normal(mu, torch.exp(log_std.double()))
+    ratio = torch.exp(d.log_prob(act.double()).sum(-1) - logp_old.double())
+    adv64 = adv.double()
+    per = -torch.min(ratio * adv64, adv64 * torch.clamp(ratio, 1 - clip, 1 + clip))
+    per.mean().backward()
+    grad = torch.cat([p.grad.reshape(-1) for p in n64.parameters()])
+    kl = (0.5 * (d.mean - act.double()) ** 2 / d.stddev ** 2).sum()
+    stats = torch.stack([per.sum().detach(), ratio.sum().detach(), kl.detach(), torch.tensor(float(B), device=x.device, dtype=torch.float64)])
+    return grad, stats
+
+
+def ref_mse(net, x, target, index=None):
+    """compute_loss_v through float64 autograd -> (flat gradient, sum of squared errors)"""
+    import torch
+    n64 = net64(net)
+    xs, ts = (x.double(), target.double()) if index is None else (x.double()[index], target.double()[index])
+    err = (n64(xs).squeeze(-1) - ts) ** 2
+    err.mean().backward()
+    return torch.cat([p.grad.reshape(-1) for p in n64.parameters()]), err.sum().detach()
+
+
+def grad_atol(want, B):
+    """the bar of _ppo_grad_case (tests/test_gpu_fused_mlp.py): 2e-6 of the largest entry, plus 10 / B from 20 000 samples on
+    for the relu / clip kinks a random batch puts within float32 rounding of a sample"""
+    return 2e-6 * max(float(want.abs().max()), 1.0) + (10.0 / B if B > 20000 else 0.0)
