@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Train PPO on a batched Simple env, evaluate it and leave the reference's run artefacts behind.
+"""Train PPO (or NPG / TRPO: --alg) on a batched Simple env, evaluate it and leave the reference's run artefacts behind.
 
 Counterpart of the reference's examples/train_drone_hover.py / `python -m phoenix_drone_simulation.train
 --alg ppo --env DroneHoverSimpleEnv-v0`: same env ids and kwargs, same PPO hyper-parameters
@@ -18,11 +18,14 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import phoenix_drone_simulation_amd as pds  # noqa: E402
 from phoenix_drone_simulation_amd.evaluation import evaluate  # noqa: E402
+from phoenix_drone_simulation_amd.npg import NPGTrainer, TRPOTrainer  # noqa: E402
 from phoenix_drone_simulation_amd.ppo import PPOTrainer  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--alg", choices=("ppo", "npg", "trpo"), default="ppo",
+                    help="the reference's on-policy trainers (train.py --alg): PPO, natural policy gradient, TRPO")
     ap.add_argument("--env", default="DroneHoverSimpleEnv-v0")
     ap.add_argument("--num-envs", type=int, default=8192)
     ap.add_argument("--rollout-len", type=int, default=64)
@@ -48,7 +51,8 @@ def main():
         env = make_sharded(args.env, args.num_envs * world, seed=args.seed, **env_kw)
     else:
         env = pds.make(args.env, num_envs=args.num_envs, seed=args.seed, **env_kw)  # the reference's default config
-    trainer = PPOTrainer(env, rollout_len=args.rollout_len, epochs=args.epochs, seed=args.seed, ac_kwargs=ac_kwargs)
+    cls = {"ppo": PPOTrainer, "npg": NPGTrainer, "trpo": TRPOTrainer}[args.alg]
+    trainer = cls(env, rollout_len=args.rollout_len, epochs=args.epochs, seed=args.seed, ac_kwargs=ac_kwargs)
     t0 = time.time()
     for e in range(args.epochs):
         i = trainer.learn_one_epoch()

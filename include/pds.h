@@ -421,6 +421,38 @@ int pds_ppo_policy_grad_step(const pds_mlp *m, const float *d_x, const float *d_
 int pds_value_grad_step(const pds_mlp *m, const float *d_x, const int64_t *d_index, const float *d_target, int64_t B,
                         float *d_grads, float *d_stats, float *d_workspace, const pds_adam *opt, void *stream);
 
+/* The natural-gradient policy step of NPG / TRPO (algs/npg/npg.py:52-160, algs/trpo/trpo.py:16-66; csrc/pds_npg.hip).
+ * Scratch floats the three entry points below need (per-wave partial sums), for up to num_candidates line-search
+ * candidates. */
+int64_t pds_npg_workspace_floats(const pds_mlp *m, int num_candidates);
+
+/* Fisher-vector product of the Gaussian policy with a fixed log_std: d_out = F v + damping v,
+ * F v = 1 / (B d_out) sum_i J_i^T diag(exp(-2 log_std)) J_i v with J_i = d MLP(x_i) / d theta -- the double backward of
+ * kl_divergence(p_old, p_theta).mean() at theta_old (NaturalPolicyGradientAlgorithm.Fvp, algs/npg/npg.py:52-77).
+ * x_i = row d_index[i] (or i when d_index is NULL) of the standardised rows d_x; d_v and d_out [param_count] in the flat
+ * layout of pds_mlp_param_count (d_out may alias d_v); d_workspace: pds_npg_workspace_floats(m, 0) floats.  Summed in a
+ * fixed order: the same inputs give the same bits. */
+int pds_npg_fisher_vector_product(const pds_mlp *m, const float *d_x, const int64_t *d_index, int64_t B, const float *d_log_std,
+                                  const float *d_v, float damping, float *d_out, float *d_workspace, void *stream);
+
+/* One iteration of conjugate_gradients (algs/utils.py:5-38) on n floats, one workgroup, no host sync.  d_state[2] =
+ * {r.r, stopped}.  init != 0: x = 0, r = p = d_z (= b; Avp(0) is 0), d_state = {b.b, 0}.  Otherwise d_z = Avp(p) and,
+ * unless stopped: alpha = r.r / (p.z + eps), x += alpha p, r -= alpha z; when sqrt(r.r) < residual_tol the iteration
+ * stops (the reference's break: x and r updated, then x, r, p frozen); else p = r + (r.r_new / (r.r + eps)) p. */
+int pds_npg_cg_step(int64_t n, float *d_x, float *d_r, float *d_p, const float *d_z, float *d_state, float eps,
+                    float residual_tol, int init, void *stream);
+
+/* The line-search candidates of TRPO (algs/trpo/trpo.py:16-66) in one launch: candidate j has the parameters
+ * theta_old + f_j s (theta_old = the network `m`, s = d_step [param_count], f_j = d_fracs[j]; product and sum rounded
+ * separately, as torch's `theta + f * s`).  d_out[4 j .. 4 j + 3] = {sum over samples of ratio adv, sum over samples x
+ * actions of KL(Normal(mu_old, sigma) || Normal(mu_j, sigma)), 1 if either sum is not finite else 0, sum of ratio}, ratio =
+ * exp(logp_j(act) - logp_old), sigma = exp(log_std); d_x [B, d_in] standardised, d_act / d_mu_old [B, d_out], d_adv /
+ * d_logp_old [B].  d_theta_out (optional, [num_candidates, param_count]): the candidates' parameters.  d_workspace:
+ * pds_npg_workspace_floats(m, num_candidates) floats.  Summed in a fixed order. */
+int pds_npg_surrogate_kl(const pds_mlp *m, const float *d_step, const float *d_fracs, int num_candidates, const float *d_x,
+                         const float *d_act, const float *d_adv, const float *d_logp_old, const float *d_mu_old,
+                         const float *d_log_std, int64_t B, float *d_out, float *d_theta_out, float *d_workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

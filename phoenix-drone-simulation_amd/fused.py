@@ -5,6 +5,9 @@ gradient for the update.  Each call replaces an autograd op chain of the referen
     FusedMLP.forward      ActorCritic.step / MLPGaussianActor.net / MLPCritic.net  algs/core.py:228-311,370-393
     FusedMLP.ppo_grad     compute_loss_pi + backward                                algs/ppo/ppo.py:22-40
     FusedMLP.value_grad   compute_loss_v + backward                                 algs/iwpg/iwpg.py:272-275
+    FusedMLP.fisher_vector_product  NaturalPolicyGradientAlgorithm.Fvp              algs/npg/npg.py:52-77
+    conjugate_gradients   conjugate_gradients                                       algs/utils.py:5-38
+    FusedMLP.surrogate_kl the candidates of TRPO's line search                      algs/trpo/trpo.py:16-66
 
 The gradients are written straight into the `.grad` storage of the torch parameters (one flat
 buffer, torch parameter order), so the optimiser step stays torch.optim.Adam like the reference's."""
@@ -145,6 +148,68 @@ class FusedMLP:
         if rc != native.OK:
             raise RuntimeError(f"pds_value_grad -> {rc}")
         return self.stats
+
+
+    def _npg_workspace(self, candidates):
+        n = self.lib.pds_npg_workspace_floats(C.byref(self.m), int(candidates))
+        ws = getattr(self, "npg_workspace", None)
+        if ws is None or ws.numel() < n:
+            self.npg_workspace = ws = torch.empty(n, device=self.flat_grad.device)
+        return ws
+
+    def fisher_vector_product(self, x, v, log_std, damping, index=None, out=None):
+        """F v + damping v (flat, param_count) over the standardised rows x[index] (csrc/pds_npg.hip): the Fisher matrix of
+        the Gaussian policy with the fixed log_std at the current parameters, mean over samples x action dims."""
+        self._bind()
+        B = x.shape[0] if index is None else index.shape[0]
+        out = out if out is not None else torch.empty_like(self.flat_grad)
+        ws = self._npg_workspace(0)
+        with _on(x):
+            rc = self.lib.pds_npg_fisher_vector_product(C.byref(self.m), _ptr(x), _ptr(index), B, _ptr(log_std), _ptr(v),
+                                                        float(damping), _ptr(out), _ptr(ws), self._stream(x))
+        if rc != native.OK:
+            raise RuntimeError(f"pds_npg_fisher_vector_product -> {rc}")
+        return out
+
+    def surrogate_kl(self, step, fracs, x, act, adv, logp_old, mu_old, log_std, theta_out=None):
+        """[J, 4] device tensor: per candidate theta + fracs[j] * step (fracs: float32 device tensor [J]) the sum of ratio * adv
+        over the batch, the sum of KL(Normal(mu_old, sigma) || Normal(mu_j, sigma)) over samples x action dims, a non-finite
+        flag and the sum of ratio (csrc/pds_npg.hip).  theta_out [J, param_count]: also the candidates' parameters."""
+        self._bind()
+        J = int(fracs.shape[0])
+        out = torch.empty(J, 4, device=x.device)
+        ws = self._npg_workspace(J)
+        with _on(x):
+            rc = self.lib.pds_npg_surrogate_kl(C.byref(self.m), _ptr(step), _ptr(fracs), J, _ptr(x), _ptr(act), _ptr(adv),
+                                               _ptr(logp_old), _ptr(mu_old), _ptr(log_std), x.shape[0], _ptr(out),
+                                               _ptr(theta_out), _ptr(ws), self._stream(x))
+        if rc != native.OK:
+            raise RuntimeError(f"pds_npg_surrogate_kl -> {rc}")
+        return out
+
+
+def conjugate_gradients(avp, b, iters, residual_tol=1e-10, eps=1e-6):
+    """conjugate_gradients (algs/utils.py:5-38) with one pds_npg_cg_step launch per iteration: `avp(p, out)` writes A p into
+    out.  The reference's early break is a device flag that freezes x, r and p (no host sync).  -> (x, state) with state =
+    {r.r, stopped} on the device."""
+    lib = native.load()
+    n = b.numel()
+    x, r, p, z = (torch.empty_like(b) for _ in range(4))
+    st = torch.zeros(2, device=b.device)
+    stream = FusedMLP._stream(b)
+
+    def step(zz, init):
+        with _on(b):
+            rc = lib.pds_npg_cg_step(n, _ptr(x), _ptr(r), _ptr(p), _ptr(zz), _ptr(st), float(eps), float(residual_tol),
+                                     int(init), stream)
+        if rc != native.OK:
+            raise RuntimeError(f"pds_npg_cg_step -> {rc}")
+
+    step(b, True)
+    for _ in range(int(iters)):
+        avp(p, z)
+        step(z, False)
+    return x, st
 
 
 def random_permutation(n, seed, call, device):

@@ -37,7 +37,8 @@ EXPORTS = ["pds_version", "pds_default_config", "pds_create", "pds_destroy", "pd
            "pds_latency_steps", "pds_philox4x32", "pds_noise_normals", "pds_gae", "pds_history_advance",
            "pds_mlp_param_count", "pds_mlp_workspace_floats", "pds_mlp_forward", "pds_ppo_policy_grad",
            "pds_value_grad", "pds_ppo_policy_grad_step", "pds_value_grad_step", "pds_gaussian_sample", "pds_gaussian_sample_dev", "pds_counter_add", "pds_permutation", "pds_rollout_record",
-           "pds_adam_step", "pds_rollout", "pds_rollout_history"]
+           "pds_adam_step", "pds_rollout", "pds_rollout_history",
+           "pds_npg_workspace_floats", "pds_npg_fisher_vector_product", "pds_npg_cg_step", "pds_npg_surrogate_kl"]
 
 
 class Mlp(C.Structure):
@@ -149,6 +150,12 @@ def load():
     later("pds_permutation", [vp, i64, u64, u64, vp])
     later("pds_rollout", [vp, i32, mp, mp, vp, vp, C.c_float, vp, u64, vp, u64, i32] + [vp] * 14)
     later("pds_rollout_history", [vp, i32, i32, mp, vp, vp, C.c_float, vp, u64, vp, u64, i32] + [vp] * 9 + [i32] + [vp] * 4)
+    later("pds_npg_workspace_floats", [mp, i32])
+    if hasattr(lib, "pds_npg_workspace_floats"):
+        lib.pds_npg_workspace_floats.restype = i64
+    later("pds_npg_fisher_vector_product", [mp, vp, vp, i64, vp, vp, C.c_float, vp, vp, vp])
+    later("pds_npg_cg_step", [i64, vp, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp])
+    later("pds_npg_surrogate_kl", [mp, vp, vp, i32] + [vp] * 6 + [i64, vp, vp, vp, vp])
     _lib = lib
     return lib
 

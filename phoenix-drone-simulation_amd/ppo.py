@@ -487,8 +487,8 @@ class PPOTrainer:
                             id_base=self.env.env_id_base, deterministic=not self.ac.training)
         return self.act_buf[t], self.logp_buf[t]
 
-    def update(self):
-        """algs/iwpg/iwpg.py:398-485."""
+    def _prepare_batch(self):
+        """GAE, value targets and pre_process_data of the epoch's rollout -> (data, raw_obs, disc_ret, B, mini-batch size)"""
         ac, T, N = self.ac, self.T, self.N
         scale = 0.0
         if self.use_reward_scaling:
@@ -499,21 +499,48 @@ class PPOTrainer:
         obs = ac.obs_oms(raw_obs) if self.use_standardized_obs else raw_obs  # pre_process_data
         data = dict(obs=obs, act=self.act_buf.reshape(T * N, -1), adv=adv.reshape(-1),
                     log_p=self.logp_buf.reshape(-1), target_v=target_v.reshape(-1))
-        # ---- value net: train_v_iterations x num_mini_batches shuffled mini-batches
         B = T * N
-        mbs = B // self.num_mini_batches
-        if self.fused:
-            return self._fused_update(data, raw_obs, disc_ret, B, mbs)
-        loss_v_before = value_loss(ac, data["obs"], data["target_v"]).item()
+        return data, raw_obs, disc_ret, B, B // self.num_mini_batches
+
+    def _value_steps(self, obs, target_v, B, mbs):
+        """update_value_net (algs/iwpg/iwpg.py:487-522): train_v_iterations x num_mini_batches shuffled mini-batch steps with
+        vf_lr, one per next() -- fused: pds_value_grad (+ the Adam step riding on it single-process), else PyTorch ops"""
+        multi = _collectives()  # several ranks (or FORCE_COLLECTIVES): gradients are averaged between the gradient and Adam
         for _ in range(self.train_v_iterations):
-            perm = self.perm_fn(B) if self.perm_fn is not None else torch.randperm(B, device=obs.device)
+            if self.fused:
+                # one elementwise launch (pds_permutation) where torch.randperm sorts (~160 us at 2^19 samples, 5 x per epoch)
+                self._perm_calls += 1
+                perm = (self.perm_fn(B) if self.perm_fn is not None else
+                        random_permutation(B, self._sample_seed ^ 0x5045524D, self._perm_calls, obs.device))
+            else:
+                perm = self.perm_fn(B) if self.perm_fn is not None else torch.randperm(B, device=obs.device)
             for s in range(0, mbs * self.num_mini_batches, mbs):
                 idx = perm[s:s + mbs]
-                self.vf_opt.zero_grad()
-                lv = value_loss(ac, data["obs"][idx], data["target_v"][idx])
-                lv.backward()
-                avg_grads(ac.v)
-                self.vf_opt.step()
+                if not self.fused:
+                    self.vf_opt.zero_grad()
+                    lv = value_loss(self.ac, obs[idx], target_v[idx])
+                    lv.backward()
+                    avg_grads(self.ac.v)
+                    self.vf_opt.step()
+                elif not multi:  # the Adam step rides on the gradient's partial-sum kernel (same bits, one launch less)
+                    self.fm_v.value_grad(obs, target_v, index=idx, adam_lr=self.vf_opt.param_groups[0]["lr"])
+                else:
+                    self.fm_v.value_grad(obs, target_v, index=idx)
+                    dist.all_reduce(self.fm_v.flat_grad)
+                    self.fm_v.flat_grad /= dist.get_world_size()
+                    self.fm_v.adam_step(self.vf_opt.param_groups[0]["lr"])
+                yield
+
+    def update(self):
+        """algs/iwpg/iwpg.py:398-485."""
+        ac = self.ac
+        data, raw_obs, disc_ret, B, mbs = self._prepare_batch()
+        if self.fused:
+            return self._fused_update(data, raw_obs, disc_ret, B, mbs)
+        # ---- value net: train_v_iterations x num_mini_batches shuffled mini-batches
+        loss_v_before = value_loss(ac, data["obs"], data["target_v"]).item()
+        for _ in self._value_steps(data["obs"], data["target_v"], B, mbs):
+            pass
         # ---- policy net: full-batch PPO-clip steps
         with torch.no_grad():
             loss_pi_before, _ = ppo_loss(ac, data, self.clip_ratio, self.entropy_coef)
@@ -561,22 +588,6 @@ class PPOTrainer:
         with torch.no_grad():
             loss_v_before = ((self.fm_v.forward(obs).view(-1) - target_v) ** 2).mean()
 
-        def value_steps():
-            """one mini-batch step of the value net per next()"""
-            for _ in range(self.train_v_iterations):
-                # one elementwise launch (pds_permutation) where torch.randperm sorts (~160 us at 2^19 samples, 5 x per epoch)
-                self._perm_calls += 1
-                perm = (self.perm_fn(B) if self.perm_fn is not None else
-                        random_permutation(B, self._sample_seed ^ 0x5045524D, self._perm_calls, obs.device))
-                for s in range(0, mbs * self.num_mini_batches, mbs):
-                    if not multi:  # the Adam step rides on the gradient's partial-sum kernel (same bits, one launch less)
-                        self.fm_v.value_grad(obs, target_v, index=perm[s:s + mbs], adam_lr=self.vf_opt.param_groups[0]["lr"])
-                    else:
-                        self.fm_v.value_grad(obs, target_v, index=perm[s:s + mbs])
-                        average(self.fm_v)
-                        self.fm_v.adam_step(self.vf_opt.param_groups[0]["lr"])
-                    yield
-
         # The two updates share no state (two networks, two optimisers, read-only batch): single process, the value net's 80
         # mini-batch steps -- each 10 us of work behind ~27 us of fixed latency -- run on a second stream next to the policy
         # net's 80 full-batch steps instead of in front of them, and the host feeds the two streams ALTERNATELY (one value
@@ -584,7 +595,7 @@ class PPOTrainer:
         # time).  Same launches, same bits.  (Several ranks: the two nets' all-reduces would have to be issued in one order
         # on every rank: kept sequential.)
         side = None
-        vgen = value_steps()
+        vgen = self._value_steps(obs, target_v, B, mbs)
         if not multi and self.overlap_value_update and obs.is_cuda:
             main = torch.cuda.current_stream(obs.device)
             if self._side_stream is None:
@@ -715,14 +726,18 @@ class PPOTrainer:
     def write_progress_csv(self, path):
         """The per-epoch log in the column names of the reference's progress.csv (utils/loggers.py;
         IWPGAlgorithm.log, algs/iwpg/iwpg.py:524-563) -- the subset of its columns this trainer tracks."""
-        cols = [("Epoch", "epoch"), ("EpRet/Mean", "ep_ret"), ("EpLen/Mean", "ep_len"), ("Loss/Pi", "loss_pi"),
-                ("Loss/Value", "loss_v"), ("Entropy", "entropy"), ("Misc/StopIter", "stop_iter"), ("PolicyRatio", "ratio"),
-                ("LR", "lr"), ("Misc/ExplorationNoiseStd", "noise_std"), ("TotalEnvSteps", "total_env_steps"),
-                ("Time", "time"), ("FPS", "fps")]
+        cols = self._progress_columns()
         with open(path, "w") as f:
             f.write(",".join(c for c, _ in cols) + "\n")
             for row in self.log:
                 f.write(",".join(str(row.get(k, "")) for _, k in cols) + "\n")
+
+    def _progress_columns(self):
+        """(progress.csv column, log key) pairs of write_progress_csv"""
+        return [("Epoch", "epoch"), ("EpRet/Mean", "ep_ret"), ("EpLen/Mean", "ep_len"), ("Loss/Pi", "loss_pi"),
+                ("Loss/Value", "loss_v"), ("Entropy", "entropy"), ("Misc/StopIter", "stop_iter"), ("PolicyRatio", "ratio"),
+                ("LR", "lr"), ("Misc/ExplorationNoiseStd", "noise_std"), ("TotalEnvSteps", "total_env_steps"),
+                ("Time", "time"), ("FPS", "fps")]
 
     def learn(self, epochs=None, verbose=False):
         for _ in range(epochs or self.epochs):

@@ -1,0 +1,343 @@
+"""NPG and TRPO (phoenix_drone_simulation_amd/npg.py) on the PyTorch-op path, on CPU: the conjugate-gradient restatement,
+the natural-gradient step against a dense float64 Gauss-Newton Fisher matrix, TRPO's backtracking rule, the logged columns."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import golden_util as gu
+
+
+class _Env:
+    """Stands in for a DroneVecEnv where only the trainer's update is exercised: N envs, no stepping."""
+
+    def __init__(self, n, obs_dim, device="cpu"):
+        self.num_envs, self.obs_dim, self.act_dim, self.device = int(n), int(obs_dim), 4, torch.device(device)
+        self.env_id_base = 0
+
+    def reset(self):
+        return torch.zeros(self.num_envs, self.obs_dim, device=self.device), {}
+
+
+def _cg64(A, b, nsteps, residual_tol=1e-10, eps=1e-6):
+    """algs/utils.py:5-38 in float64 numpy, A an explicit matrix"""
+    x = np.zeros_like(b)
+    r = b - A @ x
+    p = r.copy()
+    rdotr = r @ r
+    for i in range(nsteps):
+        z = A @ p
+        alpha = rdotr / (p @ z + eps)
+        x += alpha * p
+        r -= alpha * z
+        new = r @ r
+        if math.sqrt(new) < residual_tol:
+            return x, i + 1
+        p = r + new / (rdotr + eps) * p
+        rdotr = new
+    return x, nsteps
+
+
+@pytest.mark.parametrize("case", ["spd", "breaks_early"])
+def test_conjugate_gradients_matches_the_reference_restated_in_float64(case):
+    from phoenix_drone_simulation_amd.npg import conjugate_gradients
+    rs = np.random.RandomState(3)
+    n = 40
+    if case == "spd":
+        Q = rs.standard_normal((n, n))
+        A = Q @ Q.T / n + 0.1 * np.eye(n)
+    else:  # one eigenvalue: the first iteration leaves a residual of |b| eps / (2 |b|^2 + eps) < 1e-10, the loop breaks there
+        A = 2.0 * np.eye(n)
+    b = rs.standard_normal(n) * (1.0 if case == "spd" else 1e6)
+    want, iters = _cg64(A, b, 10)
+    calls = []
+
+    def avp(v):
+        calls.append(1)
+        return torch.as_tensor(A) @ v
+    got = conjugate_gradients(avp, torch.as_tensor(b), 10)
+    if case == "breaks_early":
+        assert iters < 10 and len(calls) == iters + 1  # Avp(0) and one product per iteration up to the break
+    np.testing.assert_allclose(got.numpy(), want, rtol=1e-12, atol=1e-12)
+    # and float32, as the trainer runs it
+    got32 = conjugate_gradients(lambda v: torch.as_tensor(A, dtype=torch.float32) @ v, torch.as_tensor(b, dtype=torch.float32), 10)
+    assert np.linalg.norm(got32.numpy() - want) <= 1e-4 * np.linalg.norm(want)
+
+
+def _trainer(cls, n=64, T=8, D=12, seed=0, **kw):
+    tr = cls(_Env(n, D), rollout_len=T, epochs=10, seed=seed, fused=False, graph_rollout=False, **kw)
+    g = torch.Generator().manual_seed(seed + 1)
+    tr.obs_buf.copy_(torch.randn(T, n, D, generator=g))
+    tr.act_buf.copy_(0.5 * torch.randn(T, n, 4, generator=g) - 0.1)
+    tr.rew_buf.copy_(torch.randn(T, n, generator=g))
+    tr.val_buf.copy_(0.1 * torch.randn(T, n, generator=g))
+    tr.fval_buf.copy_(0.1 * torch.randn(T, n, generator=g))
+    tr.term_buf.copy_((torch.rand(T, n, generator=g) < 0.05).to(torch.uint8))
+    tr.last_val = 0.1 * torch.randn(n, generator=g)
+    with torch.no_grad():  # log-probabilities of a slightly different behaviour policy: ratios spread around 1
+        mu = tr.ac.pi.net(tr.ac.obs_oms(tr.obs_buf.reshape(T * n, D)))
+        d = torch.distributions.Normal(mu + 0.05 * torch.randn(mu.shape, generator=g), torch.exp(tr.ac.pi.log_std))
+        tr.logp_buf.copy_(d.log_prob(tr.act_buf.reshape(T * n, 4)).sum(-1).view(T, n))
+    perms = torch.Generator().manual_seed(seed + 2)
+    tr.perm_fn = lambda B: torch.randperm(B, generator=perms)
+    return tr
+
+
+def _reference_step64(tr, cg_damping, cg_iters, target_kl):
+    """The NPG step of update_policy_net (algs/npg/npg.py:98-160) in float64 with the Fisher matrix written out densely:
+    F = J^T diag(1 / sigma^2) J / (B_f A) over obs[::4] -- the Gauss-Newton form of the reference's double backward."""
+    ac = tr.ac
+    T, N = tr.T, tr.N
+    scale = float(1.0 / (ac.ret_oms.std.item() + ac.ret_oms.eps))
+    adv, _, _ = gu.gae_torch(tr.rew_buf, tr.val_buf, tr.term_buf, tr.trunc_buf, tr.fval_buf, tr.last_val, tr.gamma, tr.lam,
+                             scale, 10.0)
+    obs = ac.obs_oms(tr.obs_buf.reshape(T * N, -1)).double()
+    act, logp_old, adv = tr.act_buf.reshape(T * N, -1).double(), tr.logp_buf.reshape(-1).double(), adv.reshape(-1).double()
+    net = [m for m in ac.pi.net]
+    params = [p.detach().double() for p in ac.pi.net.parameters()]
+    shapes = [p.shape for p in params]
+    theta = torch.cat([p.reshape(-1) for p in params]).requires_grad_(True)
+    act_fn = torch.relu
+
+    def mu(th, x):
+        ps, off = [], 0
+        for s in shapes:
+            k = int(np.prod(s))
+            ps.append(th[off:off + k].view(s))
+            off += k
+        h = act_fn(x @ ps[0].T + ps[1])
+        h = act_fn(h @ ps[2].T + ps[3])
+        return h @ ps[4].T + ps[5]
+    assert isinstance(net[1], torch.nn.ReLU)
+    log_std = ac.pi.log_std.double()
+    std = torch.exp(log_std)
+    lp = torch.distributions.Normal(mu(theta, obs), std).log_prob(act).sum(-1)
+    loss = -(torch.exp(lp - logp_old) * adv).mean()
+    g = -torch.autograd.grad(loss, theta)[0]
+    xf = obs[::4]
+    J = torch.autograd.functional.jacobian(lambda th: mu(th, xf).reshape(-1), theta.detach())  # [B_f A, P]
+    w = (1.0 / std ** 2).repeat(xf.shape[0])
+    F = (J.T * w) @ J / J.shape[0] + cg_damping * torch.eye(J.shape[1], dtype=torch.float64)
+    x, _ = _cg64(F.numpy(), g.numpy(), cg_iters)
+    xHx = float(x @ F.numpy() @ x)
+    alpha = math.sqrt(2 * target_kl / (xHx + 1e-8))
+    return dict(theta=theta.detach().numpy(), g=g.numpy(), x=x, xHx=xHx, alpha=alpha, loss=float(loss.detach()))
+
+
+def test_npg_step_equals_a_dense_float64_gauss_newton_step(monkeypatch):
+    """NPGTrainer.update (fused=False: autograd double backward, as the reference) against the step computed with the explicit
+    Fisher matrix J^T diag(sigma^-2) J / (B_f A) + damping in float64: the double backward IS the Gauss-Newton form."""
+    import phoenix_drone_simulation_amd.npg as npg
+    import phoenix_drone_simulation_amd.ppo as ppo
+    monkeypatch.setattr(ppo, "gae", gu.gae_torch)
+    tr = _trainer(npg.NPGTrainer)
+    ref = _reference_step64(tr, tr.cg_damping, tr.cg_iters, tr.target_kl)
+    info = tr.update()
+    assert info["acceptance_step"] == 1 and info["stop_iter"] == 1
+    assert abs(info["loss_pi"] - ref["loss"]) <= 1e-5 * max(1.0, abs(ref["loss"]))
+    assert abs(info["xHx"] - ref["xHx"]) <= 1e-4 * ref["xHx"]
+    assert abs(info["alpha"] - ref["alpha"]) <= 1e-4 * ref["alpha"]
+    assert abs(info["gradient_norm"] - np.linalg.norm(ref["g"])) <= 1e-5 * np.linalg.norm(ref["g"])
+    assert abs(info["h_inv_g"] - np.linalg.norm(ref["x"])) <= 1e-4 * np.linalg.norm(ref["x"])
+    new = torch.cat([p.detach().reshape(-1) for p in tr.ac.pi.net.parameters()]).double().numpy()
+    step = ref["alpha"] * ref["x"]
+    assert np.linalg.norm(new - ref["theta"] - step) <= 1e-4 * np.linalg.norm(step)
+    # KL of the accepted step: close to target_kl (the quadratic model of the trust region)
+    assert 0.2 * tr.target_kl < info["kl"] < 5 * tr.target_kl
+
+
+def test_trpo_backtracks_to_the_first_candidate_inside_the_trust_region(monkeypatch):
+    """TRPOTrainer on a batch whose Fisher rows (every 4th) are quiet and whose other rows are loud: the step sized on the
+    former overshoots the trust region of the whole batch, so the search backtracks (AcceptanceStep >= 2); every rejected
+    candidate broke the reference's rule (loss rose or KL > 1.5 target_kl), the accepted one keeps it, and the parameters
+    are theta_old + 0.8^(j-1) alpha x."""
+    import phoenix_drone_simulation_amd.npg as npg
+    import phoenix_drone_simulation_amd.ppo as ppo
+    monkeypatch.setattr(ppo, "gae", gu.gae_torch)
+    tr = _trainer(npg.TRPOTrainer)
+    tr.obs_buf[:, torch.arange(tr.N) % 4 != 0] *= 4.0
+    ref = _reference_step64(tr, tr.cg_damping, tr.cg_iters, tr.target_kl)
+    theta_old = torch.cat([p.detach().reshape(-1) for p in tr.ac.pi.net.parameters()]).clone()
+    info = tr.update()
+    fracs, _ = npg.step_fractions()
+    acc = info["acceptance_step"]
+    assert acc >= 2, info
+    cands = info["candidates"]
+    assert len(cands) == acc
+    for loss_j, kl_j in cands[:-1]:
+        assert info["loss_pi"] - loss_j < 0 or kl_j > 1.5 * tr.target_kl
+    loss_a, kl_a = cands[-1]
+    assert info["loss_pi"] - loss_a >= 0 and kl_a <= 1.5 * tr.target_kl
+    assert abs(info["kl"] - kl_a) <= 1e-6 * kl_a
+    assert abs(info["alpha"] - ref["alpha"]) <= 1e-4 * ref["alpha"]
+    new = torch.cat([p.detach().reshape(-1) for p in tr.ac.pi.net.parameters()])
+    step = torch.as_tensor(ref["x"] * ref["alpha"] * fracs[acc - 1], dtype=torch.float32)
+    assert float(torch.norm(new - theta_old - step)) <= 1e-4 * float(torch.norm(step))
+    assert abs(info["final_step_norm"] - float(torch.norm(step))) <= 1e-4 * float(torch.norm(step))
+
+
+def test_progress_csv_columns(tmp_path, monkeypatch):
+    """NPG / TRPO add the reference's algorithm_specific_logs columns and KL / Loss/DeltaPi; PPO's columns stay as they were."""
+    import phoenix_drone_simulation_amd.npg as npg
+    import phoenix_drone_simulation_amd.ppo as ppo
+    monkeypatch.setattr(ppo, "gae", gu.gae_torch)
+    tr = _trainer(npg.TRPOTrainer)
+    info = tr.update()
+    info.update(epoch=1)
+    tr.log.append(info)
+    path = tmp_path / "progress.csv"
+    tr.write_progress_csv(str(path))
+    head, row = path.read_text().splitlines()[:2]
+    cols = head.split(",")
+    for c in ("KL", "Loss/Pi", "Loss/DeltaPi", "Misc/AcceptanceStep", "Misc/Alpha", "Misc/FinalStepNorm",
+              "Misc/gradient_norm", "Misc/xHx", "Misc/H_inv_g", "Misc/StopIter"):
+        assert c in cols, c
+    vals = dict(zip(cols, row.split(",")))
+    assert int(vals["Misc/StopIter"]) == 1 and int(vals["Misc/AcceptanceStep"]) == info["acceptance_step"]
+    p = _trainer(ppo.PPOTrainer)
+    assert [c for c, _ in p._progress_columns()] == [
+        "Epoch", "EpRet/Mean", "EpLen/Mean", "Loss/Pi", "Loss/Value", "Entropy", "Misc/StopIter", "PolicyRatio", "LR",
+        "Misc/ExplorationNoiseStd", "TotalEnvSteps", "Time", "FPS"]
+
+
+def test_npg_has_no_policy_lr_schedule():
+    import phoenix_drone_simulation_amd.npg as npg
+    tr = _trainer(npg.NPGTrainer)
+    assert tr.scheduler is None and (tr.cg_damping, tr.cg_iters, tr.target_kl) == (0.1, 10, 0.01)
+    fr, end = npg.step_fractions()
+    assert len(fr) == 15 and fr[0] == 1.0 and fr[1] == 0.8 and end == fr[-1] * 0.8
+
+
+# ---- the reference's own NPG / TRPO updates replayed (tests/golden/npg_update.npz, tools/refgen/gen_golden_npg_update.py) ----
+GOLD = __import__("os").path.join(__import__("os").path.dirname(__import__("os").path.abspath(__file__)), "golden", "npg_update.npz")
+RECORDS = ("npg_", "trpo_", "trpot_")
+
+
+class _Prefixed:
+    """one record of npg_update.npz under the key names of update.npz (golden_util.load_update_epoch)"""
+
+    def __init__(self, g, prefix):
+        self.g, self.p = g, prefix
+
+    def __getitem__(self, k):
+        return self.g[self.p + k]
+
+
+def replay_reference_updates(prefix, env, fused, dtype=torch.float32, check=True):
+    """The recorded updates of one record through NPGTrainer / TRPOTrainer.update(): rollouts, path ends, bootstrap values and
+    value-net shuffles as the reference had them.  check: Loss/Pi, x.Fx, alpha, |g|, |x|, every TRPO candidate's (loss, KL)
+    and the AcceptanceStep against the reference's, every state_dict entry to 1e-5 relative.  -> (trainer, [state_dicts])"""
+    import phoenix_drone_simulation_amd.npg as npg
+    g = _Prefixed(np.load(GOLD), prefix)
+    T = int(g["steps"])
+    cls = npg.NPGTrainer if prefix == "npg_" else npg.TRPOTrainer
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(dtype)  # float64: the networks, optimisers and statistics (the rollout buffers stay float32)
+    try:
+        tr = cls(env, rollout_len=T, epochs=int(g["epochs_total"]), gamma=float(g["gamma"]), lam=float(g["lam"]),
+                 vf_lr=float(g["vf_lr"]), train_v_iterations=int(g["train_v_iterations"]),
+                 num_mini_batches=int(g["num_mini_batches"]), target_kl=float(g["target_kl"]), cg_damping=float(g["cg_damping"]),
+                 cg_iters=int(g["cg_iters"]), seed=0, fused=fused, graph_rollout=False)
+    finally:
+        torch.set_default_dtype(old)
+    dev = env.device
+    with torch.no_grad():
+        for k, p_ in tr.ac.state_dict().items():
+            p_.copy_(torch.as_tensor(g["sd_init__" + k], device=dev))
+    sds = []
+    for e in range(int(g["epochs"])):
+        d = gu.load_update_epoch(g, e, dev)
+        tr.ac.update(frac=e / tr.epochs)
+        tr.obs_buf.copy_(d["obs"]); tr.act_buf.copy_(d["act"]); tr.rew_buf.copy_(d["rew"]); tr.val_buf.copy_(d["val"])
+        tr.logp_buf.copy_(d["logp"]); tr.term_buf.copy_(d["term"]); tr.trunc_buf.copy_(d["trunc"]); tr.fval_buf.copy_(d["fval"])
+        tr.last_val = d["last_val"]
+        shuffles = iter(d["shuffles"])
+        tr.perm_fn = lambda B: next(shuffles)
+        info = tr.update()
+        assert next(shuffles, None) is None  # every recorded shuffle was consumed
+        sds.append({k: v.detach().double().cpu().clone() for k, v in tr.ac.state_dict().items()})
+        if check:
+            assert info["acceptance_step"] == int(g[f"e{e}_AcceptanceStep"]), (prefix, e, info["acceptance_step"])
+            for key, ref in (("loss_pi", "loss_pi"), ("loss_v", "loss_v")):
+                want = float(g[f"e{e}_{ref}"])
+                assert abs(info[key] - want) <= 1e-4 * max(1.0, abs(want)), (prefix, e, key, info[key], want)
+            for key, ref in (("xHx", "xHx"), ("alpha", "Alpha"), ("h_inv_g", "H_inv_g"), ("gradient_norm", "gradient_norm"),
+                             ("final_step_norm", "FinalStepNorm")):
+                want = float(g[f"e{e}_{ref}"])
+                assert abs(info[key] - want) <= 1e-4 * abs(want), (prefix, e, key, info[key], want)
+            want_c = g[f"e{e}_candidates"]
+            assert len(info["candidates"]) >= len(want_c)
+            for (loss_j, kl_j), (wl, wk) in zip(info["candidates"], want_c):
+                assert abs(loss_j - wl) <= 1e-4 * max(1.0, abs(wl)) and abs(kl_j - wk) <= 1e-4 * wk, (prefix, e, loss_j, wl, kl_j, wk)
+            for k, v in sds[-1].items():
+                gu.assert_close(v.numpy(), g[f"e{e}_sd_after__" + k], 1e-5, 1e-6, f"{prefix} epoch {e} after update: {k}")
+        tr.epoch += 1
+    return tr, sds
+
+
+@pytest.mark.parametrize("prefix", RECORDS)
+def test_reference_npg_trpo_updates_replayed_through_the_torch_path_on_cpu(prefix, monkeypatch):
+    """NPGTrainer / TRPOTrainer.update() on the PyTorch-op path (CPU) against the reference's own NaturalPolicyGradientAlgorithm
+    and TRPOAlgorithm: two NPG updates, two TRPO updates, one TRPO update whose search backtracks (AcceptanceStep 2)."""
+    import phoenix_drone_simulation_amd.npg as npg
+    import phoenix_drone_simulation_amd.ppo as ppo
+    monkeypatch.setattr(ppo, "gae", gu.gae_torch)
+    g = np.load(GOLD)
+    replay_reference_updates(prefix, _Env(1, int(g[prefix + "obs_dim"])), False)
+
+
+def _world2_worker(rank, port, B, D, q):
+    import os
+    import torch.distributed as dist
+    import phoenix_drone_simulation_amd.npg as npg
+    import phoenix_drone_simulation_amd.ppo as ppo
+    ppo.gae = gu.gae_torch
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=2)
+    try:
+        tr = _trainer(npg.NPGTrainer, n=B // 8, T=8, D=D)
+        half = B // 16
+        sl = slice(rank * half, (rank + 1) * half)
+        for name in ("obs_buf", "act_buf", "rew_buf", "val_buf", "logp_buf", "term_buf", "trunc_buf", "fval_buf"):
+            buf = getattr(tr, name)
+            setattr(tr, name, buf[:, sl].contiguous())
+        tr.last_val = tr.last_val[sl].contiguous()
+        tr.N = half
+        info = tr.update()
+        q.put((rank, torch.cat([p.detach().reshape(-1) for p in tr.ac.pi.net.parameters()]).numpy(),
+               {k: info[k] for k in ("xHx", "alpha", "loss_pi")}))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_world2_npg_update_on_halves_equals_world1_on_the_whole_batch(monkeypatch):
+    """Two gloo ranks, each with one half of the envs of a batch: g, every Fisher-vector product and Loss/Pi are rank-averaged
+    (one all-reduce each, as mpi_avg), so both ranks end with identical policy parameters, equal to one rank's update on the
+    whole batch to 1e-5.  (The value net's mini-batches are rank-local shuffles and not compared.)"""
+    import socket
+    import torch.multiprocessing as mp
+    import phoenix_drone_simulation_amd.npg as npg
+    import phoenix_drone_simulation_amd.ppo as ppo
+    monkeypatch.setattr(ppo, "gae", gu.gae_torch)
+    B, D = 512, 12
+    whole = _trainer(npg.NPGTrainer, n=B // 8, T=8, D=D)
+    whole.perm_fn = None
+    info1 = whole.update()
+    want = torch.cat([p.detach().reshape(-1) for p in whole.ac.pi.net.parameters()]).numpy()
+    with socket.socket() as s_:
+        s_.bind(("127.0.0.1", 0))
+        port = s_.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_world2_worker, args=(r, port, B, D, q)) for r in range(2)]
+    for p_ in procs:
+        p_.start()
+    res = dict((r, (th, inf)) for r, th, inf in (q.get(timeout=300) for _ in range(2)))
+    for p_ in procs:
+        p_.join(timeout=60)
+        assert p_.exitcode == 0
+    assert np.array_equal(res[0][0], res[1][0])
+    assert np.linalg.norm(res[0][0] - want) <= 1e-5 * np.linalg.norm(want)
+    for k in ("xHx", "alpha", "loss_pi"):
+        assert abs(res[0][1][k] - info1[k]) <= 1e-5 * max(1.0, abs(info1[k])), (k, res[0][1][k], info1[k])
