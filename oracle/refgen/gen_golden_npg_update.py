@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Golden vectors for the reference's NPG and TRPO updates (algs/npg/npg.py, algs/trpo/trpo.py): tests/golden/npg_update.npz.
 
-Follows oracle/refgen/gen_golden_update.py (PPO) and uses its stand-ins by path.  Runs, in the build container only, the
+Follows gen_golden_update.py (PPO) next to it and uses the same stand-ins (oracle/refgen/standins).  Runs, in the build container only, the
 reference's own `NaturalPolicyGradientAlgorithm` and `TRPOAlgorithm` on its `DroneHoverSimpleEnv-v0` at 1 000 steps per epoch
 (2 value iterations x 4 mini-batches) and records everything a restatement needs to repeat the updates without randomness of
 its own, under three prefixes:
@@ -19,7 +19,7 @@ alpha, |x| (Misc/H_inv_g), |g| (Misc/gradient_norm), AcceptanceStep, and for TRP
 generator asserts that no candidate lies within 1e-3 (relative) of either acceptance threshold, so that "the same accepted
 step" is a fair demand of a float32 restatement.  Only data is written; running it twice gives the same bytes.
 
-    python tools/refgen/gen_golden_npg_update.py /path/to/the/reference/checkout
+    python oracle/refgen/gen_golden_npg_update.py /path/to/the/reference/checkout
 """
 import io
 import os
@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.join(HERE, "..", "..")
+ROOT = os.path.join(HERE, "..", "..")  # oracle/refgen -> the repository
 ENV_ID = "DroneHoverSimpleEnv-v0"
 EPOCHS_TOTAL, STEPS, MINI, V_ITERS = 8, 1000, 4, 2
 RECORDS = (("npg_", "npg", 0.01, 2), ("trpo_", "trpo", 0.01, 2), ("trpot_", "trpo", 3.0, 1))
@@ -151,8 +151,8 @@ def run(prefix, alg_name, target_kl, epochs, out):
 def main():
     ref = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("PDS_REFERENCE", "")
     if not ref or not os.path.isdir(os.path.join(ref, "phoenix_drone_simulation")):
-        raise SystemExit("usage: gen_golden_npg_update.py REFERENCE_CHECKOUT")
-    sys.path.insert(0, os.path.join(ROOT, "oracle", "refgen", "standins"))
+        raise SystemExit("usage: oracle/refgen/gen_golden_npg_update.py REFERENCE_CHECKOUT")
+    sys.path.insert(0, os.path.join(HERE, "standins"))
     sys.path.insert(0, ref)
     tb = types.ModuleType("torch.utils.tensorboard")
     tb.SummaryWriter = object

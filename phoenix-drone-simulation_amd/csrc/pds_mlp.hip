@@ -33,7 +33,7 @@
 // weight-gradient GEMMs) so that neither carries 128 accumulator registers through phases that do not need them.
 #include <stdlib.h>
 
-#include "pds_mlp_common.h"
+#include "pds_mlp_tile.h"  // (pds_mlp_common.h; sum_partials)
 
 namespace pds_mlp_detail {
 
@@ -1451,32 +1451,12 @@ struct AdamK {
   float lr, b1, b2, eps, bc1, bc2s;
 };
 
-// block = 64 outputs x 16 slices of the wave range: 16 x fewer dependent loads per thread
+// block = 64 outputs x 16 slices of the wave range (sum_partials, pds_mlp_tile.h)
 __global__ __launch_bounds__(1024) void reduce_kernel(const float *partials, int pstride, int nwaves, int total,
                                                       float denom_scale, float *grads, float *stats, pds_mlp m, AdamK ad) {
-  __shared__ float part[16][64];
-  const int px = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const int p = blockIdx.x * 64 + px;
-  float s = 0.f;
-  if (p < total + kStats) {
-    const int per = (nwaves + 15) / 16, w0 = sl * per, w1 = min(nwaves, w0 + per);
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int w = w0;
-    for (; w + 3 < w1; w += 4) {
-      s0 += partials[(long long)w * pstride + p];
-      s1 += partials[(long long)(w + 1) * pstride + p];
-      s2 += partials[(long long)(w + 2) * pstride + p];
-      s3 += partials[(long long)(w + 3) * pstride + p];
-    }
-    for (; w < w1; ++w) s0 += partials[(long long)w * pstride + p];
-    s = (s0 + s1) + (s2 + s3);
-  }
-  part[sl][px] = s;
-  __syncthreads();
-  if (sl == 0 && p < total + kStats) {
-    float t = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) t += part[q][px];
+  const int p = blockIdx.x * 64 + (threadIdx.x & 63);
+  const float t = sum_partials(partials, pstride, nwaves, p, p < total + kStats);
+  if ((threadIdx.x >> 6) == 0 && p < total + kStats) {
     if (p < total) {
       const float gr = t * denom_scale;
       grads[p] = gr;

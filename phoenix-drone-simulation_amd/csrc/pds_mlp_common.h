@@ -1,6 +1,7 @@
 // pds_mlp_common.h -- what the trainer's dense kernels share (csrc/pds_mlp.hip: d_in <= 64, two waves per SIMD;
-// csrc/pds_mlp_wide.hip: 64 < d_in <= 192, the first layer K-tiled): argument block, parameter layout, activations,
-// LDS access helpers.  See pds_mlp.hip for the design.
+// csrc/pds_mlp_wide.hip: 64 < d_in <= 192, the first layer K-tiled; csrc/pds_npg.hip: the natural-gradient step): argument
+// block, parameter layout, activations, LDS access helpers.  See pds_mlp.hip for the design; the tile code of the K-tiled
+// kernels is csrc/pds_mlp_tile.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,7 +23,7 @@ constexpr int kMaxOut = 8;         // d_out <= 8
 constexpr int kWaves = 8;          // waves per block, two per SIMD; 1 block per CU (LDS-bound)
 constexpr int kStats = 4;          // loss sum, ratio sum, kl sum, sample count
 constexpr int kWaveFloats = 3 * kTS * kS + kTS * kSY;
-// csrc/pds_mlp_wide.hip: 64 < d_in <= 192
+// the K-tiled kernels (csrc/pds_mlp_tile.h): csrc/pds_mlp_wide.hip for 64 < d_in <= 192, csrc/pds_npg.hip for every d_in
 constexpr int kMaxDimIn = 192;     // d_in of the K-tiled kernels (twelve 16-wide input tiles)
 constexpr int kWideWaves = 4;      // waves per block there: one per SIMD, up to 512 registers each
 constexpr int kWideMaxBlocks = 256;
@@ -122,5 +123,8 @@ __device__ __forceinline__ Oct3 oct3(const Quad3 &a, const Quad3 &b) { return Oc
 // csrc/pds_mlp_wide.hip: launches mlp_wide_kernel<loss, activation, input tiles> on `s`; returns the number of partials
 // (one per wave of the grid) that the reduce kernel has to sum (gradient calls)
 int launch_wide(int loss, const Args &a, hipStream_t s);
+// csrc/pds_mlp.hip: PDS_OK for a network every kernel family covers between them (d_in <= kMaxDimIn, h1, h2 <= kMaxDim,
+// d_out <= kMaxOut, relu or tanh, no null tensor), else PDS_EINVAL
+int check(const pds_mlp *m);
 
 }  // namespace pds_mlp_detail

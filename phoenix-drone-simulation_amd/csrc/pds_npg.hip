@@ -7,28 +7,28 @@
 // the Gauss-Newton form
 //     F v = 1 / (B A) sum_i J_i^T diag(exp(-2 log_std)) J_i v,     J_i = d mu(x_i) / d theta,
 // for relu and tanh alike: per sample one forward pass with a tangent (J v), a scale, and one backward pass (J^T u).
-// Same design as mlp_wide_kernel of csrc/pds_mlp_wide.hip (read that first): a wave owns a 16-sample tile in LDS, every
-// GEMM runs on v_mfma_f32_16x16x4_f32 with the transposed chain, the weight gradients accumulate in registers over the
-// wave's tiles, every wave writes one partial, and a second kernel sums the partials in a fixed order (deterministic, no
-// atomics) and applies the 1 / (B A) scale and the damping.  One wave per SIMD and the first layer K-tiled over up to
-// twelve input tiles: every shape of the fused PPO path (d_in <= 192, h1, h2 <= 64, d_out <= 8).  The tangent's weights
+// The kernels stand on the tile core of csrc/pds_mlp_tile.h (its header states the design; shared with mlp_wide_kernel of
+// csrc/pds_mlp_wide.hip): a wave owns a 16-sample tile in LDS, every GEMM runs on v_mfma_f32_16x16x4_f32 with the transposed
+// chain, the weight gradients accumulate in registers over the wave's tiles (WideGrads), every wave writes one partial, and a
+// second kernel sums the partials in a fixed order (sum_partials: deterministic, no atomics) and applies the 1 / (B A) scale
+// and the damping.  One wave per SIMD and the first layer K-tiled over up to twelve input tiles: every shape of the fused PPO
+// path (d_in <= 192, h1, h2 <= 64, d_out <= 8).  What this file adds: the forward pass with a tangent, the f32 backward chain
+// (wide_backward<.., false>), conjugate gradients, and the candidates' staging transform.  The tangent's weights
 // v are read from global memory (L2-resident, 5-17 k floats): LDS holds W1 / W2 / W3 and the four images per wave, as in
 // the wide kernel, and would not hold a second copy of W1 at 192 inputs.
 //   tangent   dz1 = V1 x + vb1,  dz2 = V2 h1 + W2 (act'(z1) dz1) + vb2,  dmu = V3 h2 + W3 (act'(z2) dz2) + vb3
 //   scale     u = dmu exp(-2 log_std)
-//   backward  dW3 = u^T h2, dZ2 = (W3^T u) act'(z2), dW2 = dZ2^T h1, dZ1 = (W2^T dZ2) act'(z1), dW1 = dZ1^T x
+//   backward  wide_backward from u: dW3 = u^T h2, dZ2 = (W3^T u) act'(z2), dW2 = dZ2^T h1, dZ1 = (W2^T dZ2) act'(z1), dW1 = dZ1^T x
 // act' follows torch: relu' = (z > 0) = (h > 0), tanh' = 1 - h^2.
 //
 // Line-search candidates (TRPO): grid.y = candidate j, whose parameters theta_old + f_j s are formed while the weights are
 // staged into LDS -- the product and the sum rounded separately (__fmul_rn / __fadd_rn, as torch's `theta + f * s` with f
 // rounded to float32), so the trainer can write the accepted candidate with the same expression, bit for bit.  Per
 // candidate: sum(ratio adv), sum of KL(p_old || q) over samples x actions and sum(ratio), in a fixed order.
-#include "pds_mlp_common.h"
+#include "pds_mlp_tile.h"
 
 namespace pds_mlp_detail {
 
-constexpr int kNpgWaves = 4;        // one wave per SIMD (up to 512 registers: the dW1 accumulators at 192 inputs)
-constexpr int kNpgMaxBlocks = 256;  // one persistent block per CU
 constexpr int kCgThreads = 1024;
 
 struct NpgArgs {
@@ -45,25 +45,10 @@ struct NpgArgs {
   int pstride;
 };
 
-template <int NIN>
-constexpr int npg_stride() { return kTW * NIN + 4; }
-
-// C += W[16 it .. +16][:] In^T from an LDS image with row stride S (pds_mlp_wide.hip gemm_wts, with an initial value)
-template <int NK, int S>
-__device__ __forceinline__ f32x4 npg_gemm_lds(const float *Ws, int it, const f32x4 (&in)[NK], int n, int g, f32x4 c) {
-  const float *wp = Ws + (it * kTW + n) * S + 4 * g;
-#pragma unroll
-  for (int kt = 0; kt < NK; ++kt) {
-    const f32x4 a = lds4(wp + kt * kTW);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c = PDS_MFMA(a[j], in[kt][j], c);
-  }
-  return c;
-}
-// the same with the A operand read from a row-major [rows][cols] matrix in global memory (zero outside it)
+// gemm_lds (pds_mlp_tile.h) with the A operand read from a row-major [rows][cols] matrix in global memory (zero outside it)
 template <int NK>
-__device__ __forceinline__ f32x4 npg_gemm_glb(const float *V, int rows, int cols, int it, const f32x4 (&in)[NK], int n, int g,
-                                              f32x4 c) {
+__device__ __forceinline__ f32x4 gemm_glb(const float *V, int rows, int cols, int it, const f32x4 (&in)[NK], int n, int g,
+                                          f32x4 c) {
   const int r = it * kTW + n;
   const bool rin = r < rows;
 #pragma unroll
@@ -80,7 +65,7 @@ __device__ __forceinline__ f32x4 npg_gemm_glb(const float *V, int rows, int cols
 // layer 1 with the B operand (this lane's own 4 features per input tile) read back from its row of the X image instead of
 // held in 4 NK registers: what keeps the fvp kernel at 192 inputs free of spills
 template <int NK, int S>
-__device__ __forceinline__ f32x4 npg_gemm_lds_x(const float *Ws, int it, const float *xrow, int n, int g, f32x4 c) {
+__device__ __forceinline__ f32x4 gemm_lds_x(const float *Ws, int it, const float *xrow, int n, int g, f32x4 c) {
   const float *wp = Ws + (it * kTW + n) * S + 4 * g;
 #pragma unroll
   for (int kt = 0; kt < NK; ++kt) {
@@ -91,8 +76,8 @@ __device__ __forceinline__ f32x4 npg_gemm_lds_x(const float *Ws, int it, const f
   return c;
 }
 template <int NK>
-__device__ __forceinline__ f32x4 npg_gemm_glb_x(const float *V, int rows, int cols, int it, const float *xrow, int n, int g,
-                                                f32x4 c) {
+__device__ __forceinline__ f32x4 gemm_glb_x(const float *V, int rows, int cols, int it, const float *xrow, int n, int g,
+                                            f32x4 c) {
   const int r = it * kTW + n;
   const bool rin = r < rows;
 #pragma unroll
@@ -120,44 +105,20 @@ __device__ __forceinline__ float theta_at(const pds_mlp &m, const Offsets &o, in
 // candidate parameter theta + f s: product and sum rounded separately (no FMA contraction)
 __device__ __forceinline__ float cand(float theta, float f, float s) { return __fadd_rn(theta, __fmul_rn(f, s)); }
 
-// weight images [out][in] of the network (CAND: of the candidate theta + f s), zero padded; W3 keeps kMaxOut rows (rows
-// 8..15 of the MFMA tile alias rows 0..7 through `n & 7`: their outputs are never used, see pds_mlp_wide.hip)
-template <bool CAND, int S1>
-__device__ __forceinline__ void npg_stage(const pds_mlp &m, const float *s, float f, float *W1s, float *W2s, float *W3s,
-                                          float *b1s, float *b2s, float *b3s, int tid) {
-  const Offsets o = offsets(m);
-  auto val = [&](float t, int i) { return CAND ? cand(t, f, s[i]) : t; };
-  constexpr int kThreads = kNpgWaves * 64;
-  for (int i = tid; i < kMaxDim * S1; i += kThreads) {
-    const int r = i / S1, k = i - r * S1;
-    W1s[i] = (r < m.h1 && k < m.d_in) ? val(m.w1[r * m.d_in + k], o.w1 + r * m.d_in + k) : 0.f;
-  }
-  for (int i = tid; i < kMaxDim * kS; i += kThreads) {
-    const int r = i / kS, k = i - r * kS;
-    W2s[i] = (r < m.h2 && k < m.h1) ? val(m.w2[r * m.h1 + k], o.w2 + r * m.h1 + k) : 0.f;
-    if (i < kMaxOut * kS) W3s[i] = (r < m.d_out && k < m.h2) ? val(m.w3[r * m.h2 + k], o.w3 + r * m.h2 + k) : 0.f;
-  }
-  if (tid < kMaxDim) {
-    b1s[tid] = tid < m.h1 ? val(m.b1[tid], o.b1 + tid) : 0.f;
-    b2s[tid] = tid < m.h2 ? val(m.b2[tid], o.b2 + tid) : 0.f;
-  }
-  if (tid < kTW) b3s[tid] = tid < m.d_out ? val(m.b3[tid], o.b3 + tid) : 0.f;
-}
-
 template <int ACT, int NIN>
-__global__ __launch_bounds__(kNpgWaves * 64, 1) void fvp_kernel(const NpgArgs a) {
-  constexpr int S1 = npg_stride<NIN>();
+__global__ __launch_bounds__(kWideWaves * 64, 1) void fvp_kernel(const NpgArgs a) {
+  constexpr int S1 = wide_stride<NIN>();
   constexpr int kImg = kTS * S1 + 2 * kTS * kS + kTS * kSY;  // X, H1, H2, U per wave
   __shared__ __attribute__((aligned(16))) float W1s[kMaxDim * S1];
   __shared__ __attribute__((aligned(16))) float W2s[kMaxDim * kS];
   __shared__ __attribute__((aligned(16))) float W3s[kMaxOut * kS];
   __shared__ __attribute__((aligned(16))) float b1s[kMaxDim], b2s[kMaxDim], b3s[kTW], isg2[kTW];
-  __shared__ __attribute__((aligned(16))) float images[kNpgWaves * kImg];
+  __shared__ __attribute__((aligned(16))) float images[kWideWaves * kImg];
   const pds_mlp &m = a.m;
   const Offsets o = offsets(m);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = lane & 15, g = lane >> 4;  // C/D layout: column (sample) n, rows 4 g + q
-  npg_stage<false, S1>(m, nullptr, 0.f, W1s, W2s, W3s, b1s, b2s, b3s, tid);
+  stage_wide<S1>(m, W1s, W2s, W3s, b1s, b2s, b3s, tid, [](float t, int) { return t; });
   if (tid < kTW) {
     const float is = tid < m.d_out ? expf(-a.log_std[tid]) : 0.f;  // 1 / sigma
     isg2[tid] = is * is;
@@ -168,18 +129,11 @@ __global__ __launch_bounds__(kNpgWaves * 64, 1) void fvp_kernel(const NpgArgs a)
   __syncthreads();
   const float *V1 = a.v + o.w1, *vb1 = a.v + o.b1, *V2 = a.v + o.w2, *vb2 = a.v + o.b2, *V3 = a.v + o.w3, *vb3 = a.v + o.b3;
 
-  f32x4 gW1[kNT][NIN], gW2[kNT][kNT], gW3[kNT], gb1[kNT], gb2[kNT], gb3 = (f32x4)(0.f);
-#pragma unroll
-  for (int i = 0; i < kNT; ++i) {
-    gW3[i] = (f32x4)(0.f); gb1[i] = (f32x4)(0.f); gb2[i] = (f32x4)(0.f);
-#pragma unroll
-    for (int j = 0; j < kNT; ++j) gW2[i][j] = (f32x4)(0.f);
-#pragma unroll
-    for (int j = 0; j < NIN; ++j) gW1[i][j] = (f32x4)(0.f);
-  }
+  WideGrads<NIN> G;
+  G.zero();
 
   const long long ntiles = (a.B + kTS - 1) / kTS;
-  const long long wid = (long long)blockIdx.x * kNpgWaves + wave, nw = (long long)gridDim.x * kNpgWaves;
+  const long long wid = (long long)blockIdx.x * kWideWaves + wave, nw = (long long)gridDim.x * kWideWaves;
   for (long long t = wid; t < ntiles; t += nw) {
     const long long s0 = t * kTS;
     long long row = -1;
@@ -197,11 +151,11 @@ __global__ __launch_bounds__(kNpgWaves * 64, 1) void fvp_kernel(const NpgArgs a)
       sts4(xrow + kt * kTW, xv);
     }
     // ---- layer 1: h1 = act(W1 x + b1), its tangent t1 = act'(h1) (V1 x + vb1) ----------------------------------------
-    f32x4 h1r[kNT], t1[kNT], h2r[kNT], t2[kNT], cc[kNT];
+    f32x4 h1r[kNT], t1[kNT], h2r[kNT], t2[kNT];
 #pragma unroll
     for (int it = 0; it < kNT; ++it) {
-      const f32x4 z = npg_gemm_lds_x<NIN, S1>(W1s, it, xrow, n, g, (f32x4)(0.f));
-      const f32x4 dz = npg_gemm_glb_x<NIN>(V1, m.h1, m.d_in, it, xrow, n, g, (f32x4)(0.f));
+      const f32x4 z = gemm_lds_x<NIN, S1>(W1s, it, xrow, n, g, (f32x4)(0.f));
+      const f32x4 dz = gemm_glb_x<NIN>(V1, m.h1, m.d_in, it, xrow, n, g, (f32x4)(0.f));
       const f32x4 b = lds4(b1s + it * kTW + 4 * g);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -214,9 +168,9 @@ __global__ __launch_bounds__(kNpgWaves * 64, 1) void fvp_kernel(const NpgArgs a)
     // ---- layer 2: h2 = act(W2 h1 + b2), t2 = act'(h2) (V2 h1 + W2 t1 + vb2) -------------------------------------------
 #pragma unroll
     for (int it = 0; it < kNT; ++it) {
-      const f32x4 z = npg_gemm_lds<kNT, kS>(W2s, it, h1r, n, g, (f32x4)(0.f));
-      f32x4 dz = npg_gemm_lds<kNT, kS>(W2s, it, t1, n, g, (f32x4)(0.f));
-      dz = npg_gemm_glb<kNT>(V2, m.h2, m.h1, it, h1r, n, g, dz);
+      const f32x4 z = gemm_lds<kNT, kS>(W2s, it, h1r, n, g, (f32x4)(0.f));
+      f32x4 dz = gemm_lds<kNT, kS>(W2s, it, t1, n, g, (f32x4)(0.f));
+      dz = gemm_glb<kNT>(V2, m.h2, m.h1, it, h1r, n, g, dz);
       const f32x4 b = lds4(b2s + it * kTW + 4 * g);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -229,157 +183,27 @@ __global__ __launch_bounds__(kNpgWaves * 64, 1) void fvp_kernel(const NpgArgs a)
     // ---- output tangent dmu = V3 h2 + W3 t2 + vb3, u = dmu / sigma^2 (zero outside the batch and the outputs) --------
     f32x4 u;
     {
-      f32x4 dm = npg_gemm_lds<kNT, kS>(W3s, 0, t2, n & (kMaxOut - 1), g, (f32x4)(0.f));
-      dm = npg_gemm_glb<kNT>(V3, m.d_out, m.h2, 0, h2r, n, g, dm);
+      f32x4 dm = gemm_lds<kNT, kS>(W3s, 0, t2, n & (kMaxOut - 1), g, (f32x4)(0.f));
+      dm = gemm_glb<kNT>(V3, m.d_out, m.h2, 0, h2r, n, g, dm);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int j = 4 * g + q;
         u[q] = (valid && j < m.d_out) ? (dm[q] + vb3[j]) * isg2[j] : 0.f;
       }
     }
-    gb3 += u;
-    sts4(Uimg + n * kSY + 4 * g, u);
-    PDS_WAVE_SYNC();
-
-    // ---- backward from u (pds_mlp_wide.hip, f32 MFMAs throughout) ------------------------------------------------------
-    const int r = n, h = g;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {  // dW3 += U^T H2
-      const float av = Uimg[(4 * h + j) * kSY + r];
-#pragma unroll
-      for (int jt = 0; jt < kNT; ++jt) gW3[jt] = PDS_MFMA(av, H2img[(4 * h + j) * kS + jt * kTW + n], gW3[jt]);
-    }
-    f32x4 dz2[kNT];  // dZ2^T = (W3^T U^T) act'(H2^T)
-#pragma unroll
-    for (int it = 0; it < kNT; ++it) cc[it] = (f32x4)(0.f);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int it = 0; it < kNT; ++it) cc[it] = PDS_MFMA(W3s[((4 * h + j) & (kMaxOut - 1)) * kS + it * kTW + r], u[j], cc[it]);
-#pragma unroll
-    for (int it = 0; it < kNT; ++it) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) dz2[it][q] = cc[it][q] * act_grad<ACT>(h2r[it][q]);
-      gb2[it] += dz2[it];
-    }
-#pragma unroll
-    for (int it = 0; it < kNT; ++it) sts4(H2img + n * kS + it * kTW + 4 * g, dz2[it]);  // after the dW3 reads (in order)
-    PDS_WAVE_SYNC();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {  // dW2 += dZ2^T H1
-      float av[kNT], bv[kNT];
-#pragma unroll
-      for (int i = 0; i < kNT; ++i) {
-        av[i] = H2img[(4 * h + j) * kS + i * kTW + r];
-        bv[i] = H1img[(4 * h + j) * kS + i * kTW + n];
-      }
-#pragma unroll
-      for (int it = 0; it < kNT; ++it)
-#pragma unroll
-        for (int jt = 0; jt < kNT; ++jt) gW2[it][jt] = PDS_MFMA(av[it], bv[jt], gW2[it][jt]);
-    }
-    f32x4 dz1[kNT];  // dZ1^T = (W2^T dZ2^T) act'(H1^T)
-#pragma unroll
-    for (int jt = 0; jt < kNT; ++jt) cc[jt] = (f32x4)(0.f);
-#pragma unroll
-    for (int kt = 0; kt < kNT; ++kt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int jt = 0; jt < kNT; ++jt) cc[jt] = PDS_MFMA(W2s[(kt * kTW + 4 * h + j) * kS + jt * kTW + r], dz2[kt][j], cc[jt]);
-#pragma unroll
-    for (int jt = 0; jt < kNT; ++jt) {
-      const f32x4 hv = lds4(H1img + n * kS + jt * kTW + 4 * g);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) dz1[jt][q] = cc[jt][q] * act_grad<ACT>(hv[q]);
-      gb1[jt] += dz1[jt];
-    }
-#pragma unroll
-    for (int jt = 0; jt < kNT; ++jt) sts4(H1img + n * kS + jt * kTW + 4 * g, dz1[jt]);  // after the dW2 reads
-    PDS_WAVE_SYNC();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {  // dW1 += dZ1^T X
-      float av[kNT];
-#pragma unroll
-      for (int i = 0; i < kNT; ++i) av[i] = H1img[(4 * h + j) * kS + i * kTW + r];
-#pragma unroll
-      for (int kt = 0; kt < NIN; ++kt) {
-        const float bv = Ximg[(4 * h + j) * S1 + kt * kTW + n];
-#pragma unroll
-        for (int it = 0; it < kNT; ++it) gW1[it][kt] = PDS_MFMA(av[it], bv, gW1[it][kt]);
-      }
-    }
-    PDS_WAVE_SYNC();  // the images are rewritten by the next tile
+    wide_backward<ACT, NIN, false>(W2s, W3s, Ximg, H1img, H2img, Uimg, u, h2r, G, n, g);
   }
 
   // ---- this wave's partial -> partials[wave of the grid][flat parameter layout] ------------------------------------------
-  float *out = a.partials + wid * a.pstride;
-#pragma unroll
-  for (int it = 0; it < kNT; ++it) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = it * kTW + 4 * g + q;
-#pragma unroll
-      for (int jt = 0; jt < NIN; ++jt) {
-        const int j = jt * kTW + n;
-        if (i < m.h1 && j < m.d_in) out[o.w1 + i * m.d_in + j] = gW1[it][jt][q];
-      }
-#pragma unroll
-      for (int jt = 0; jt < kNT; ++jt) {
-        const int j = jt * kTW + n;
-        if (i < m.h2 && j < m.h1) out[o.w2 + i * m.h1 + j] = gW2[it][jt][q];
-      }
-      float v1 = gb1[it][q], v2 = gb2[it][q];
-#pragma unroll
-      for (int d = 8; d >= 1; d >>= 1) { v1 += __shfl_xor(v1, d); v2 += __shfl_xor(v2, d); }
-      if (n == 0) {
-        if (i < m.h1) out[o.b1 + i] = v1;
-        if (i < m.h2) out[o.b2 + i] = v2;
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int i = 4 * g + q;
-#pragma unroll
-    for (int jt = 0; jt < kNT; ++jt) {
-      const int j = jt * kTW + n;
-      if (i < m.d_out && j < m.h2) out[o.w3 + i * m.h2 + j] = gW3[jt][q];
-    }
-    float v3 = gb3[q];
-#pragma unroll
-    for (int d = 8; d >= 1; d >>= 1) v3 += __shfl_xor(v3, d);
-    if (n == 0 && i < m.d_out) out[o.b3 + i] = v3;
-  }
+  G.store(m, o, a.partials + wid * a.pstride, n, g);
 }
 
-// out[p] = scale * sum over the waves' partials (fixed order: 16 slices of the wave range, four chains each, then the
-// slices in order) + damping v[p].  out may alias v.
+// out[p] = scale * sum over the waves' partials (sum_partials) + damping v[p].  out may alias v.
 __global__ __launch_bounds__(1024) void fvp_reduce_kernel(const float *partials, int pstride, int nwaves, int total, float scale,
                                                           float damping, const float *v, float *out) {
-  __shared__ float part[16][64];
-  const int px = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const int p = blockIdx.x * 64 + px;
-  float s = 0.f;
-  if (p < total) {
-    const int per = (nwaves + 15) / 16, w0 = sl * per, w1 = min(nwaves, w0 + per);
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int w = w0;
-    for (; w + 3 < w1; w += 4) {
-      s0 += partials[(long long)w * pstride + p];
-      s1 += partials[(long long)(w + 1) * pstride + p];
-      s2 += partials[(long long)(w + 2) * pstride + p];
-      s3 += partials[(long long)(w + 3) * pstride + p];
-    }
-    for (; w < w1; ++w) s0 += partials[(long long)w * pstride + p];
-    s = (s0 + s1) + (s2 + s3);
-  }
-  part[sl][px] = s;
-  __syncthreads();
-  if (sl == 0 && p < total) {
-    float t = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) t += part[q][px];
+  const int p = blockIdx.x * 64 + (threadIdx.x & 63);
+  const float t = sum_partials(partials, pstride, nwaves, p, p < total);
+  if ((threadIdx.x >> 6) == 0 && p < total) {
     const float fv = __fmul_rn(t, scale);  // flat_grad_grad_kl + v * cg_damping: two products, one sum
     out[p] = __fadd_rn(fv, __fmul_rn(v[p], damping));
   }
@@ -440,8 +264,8 @@ __global__ __launch_bounds__(kCgThreads) void cg_kernel(long long n, float *x, f
 
 // ---- line-search candidates: sum(ratio adv) and sum KL(p_old || q) per candidate ---------------------------------------
 template <int ACT, int NIN>
-__global__ __launch_bounds__(kNpgWaves * 64, 1) void surrogate_kernel(const NpgArgs a) {
-  constexpr int S1 = npg_stride<NIN>();
+__global__ __launch_bounds__(kWideWaves * 64, 1) void surrogate_kernel(const NpgArgs a) {
+  constexpr int S1 = wide_stride<NIN>();
   __shared__ __attribute__((aligned(16))) float W1s[kMaxDim * S1];
   __shared__ __attribute__((aligned(16))) float W2s[kMaxDim * kS];
   __shared__ __attribute__((aligned(16))) float W3s[kMaxOut * kS];
@@ -452,19 +276,20 @@ __global__ __launch_bounds__(kNpgWaves * 64, 1) void surrogate_kernel(const NpgA
   const int n = lane & 15, g = lane >> 4;
   const int cj = blockIdx.y;
   const float f = a.fracs[cj];
-  npg_stage<true, S1>(m, a.v, f, W1s, W2s, W3s, b1s, b2s, b3s, tid);
+  // the candidate's parameters theta + f s are formed while the weights are staged
+  stage_wide<S1>(m, W1s, W2s, W3s, b1s, b2s, b3s, tid, [&](float t, int i) { return cand(t, f, a.v[i]); });
   if (tid < kTW) {
     const float ls = tid < m.d_out ? a.log_std[tid] : 0.f;
     const float sg = expf(ls);
     lsg[tid] = ls; sgg[tid] = sg; vrg[tid] = sg * sg;
   }
   if (a.theta_out != nullptr && blockIdx.x == 0)
-    for (int i = tid; i < o.total; i += kNpgWaves * 64) a.theta_out[(long long)cj * o.total + i] = cand(theta_at(m, o, i), f, a.v[i]);
+    for (int i = tid; i < o.total; i += kWideWaves * 64) a.theta_out[(long long)cj * o.total + i] = cand(theta_at(m, o, i), f, a.v[i]);
   __syncthreads();
 
   float st_ra = 0.f, st_kl = 0.f, st_r = 0.f;
   const long long ntiles = (a.B + kTS - 1) / kTS;
-  const long long wid = (long long)blockIdx.x * kNpgWaves + wave, nw = (long long)gridDim.x * kNpgWaves;
+  const long long wid = (long long)blockIdx.x * kWideWaves + wave, nw = (long long)gridDim.x * kWideWaves;
   for (long long t = wid; t < ntiles; t += nw) {
     const long long smp = t * kTS + n;
     const bool valid = smp < a.B;
@@ -476,22 +301,8 @@ __global__ __launch_bounds__(kNpgWaves * 64, 1) void surrogate_kernel(const NpgA
         const int k = kt * kTW + 4 * g + q;
         xin[kt][q] = (valid && k < m.d_in) ? a.x[smp * m.d_in + k] : 0.f;
       }
-    f32x4 h1r[kNT], h2r[kNT];
-#pragma unroll
-    for (int it = 0; it < kNT; ++it) {
-      const f32x4 z = npg_gemm_lds<NIN, S1>(W1s, it, xin, n, g, (f32x4)(0.f));
-      const f32x4 b = lds4(b1s + it * kTW + 4 * g);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) h1r[it][q] = act_fn<ACT>(z[q] + b[q]);
-    }
-#pragma unroll
-    for (int it = 0; it < kNT; ++it) {
-      const f32x4 z = npg_gemm_lds<kNT, kS>(W2s, it, h1r, n, g, (f32x4)(0.f));
-      const f32x4 b = lds4(b2s + it * kTW + 4 * g);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) h2r[it][q] = act_fn<ACT>(z[q] + b[q]);
-    }
-    const f32x4 y = npg_gemm_lds<kNT, kS>(W3s, 0, h2r, n & (kMaxOut - 1), g, (f32x4)(0.f)) + lds4(b3s + 4 * g);
+    f32x4 h2r[kNT];
+    const f32x4 y = wide_forward<ACT, NIN, false>(W1s, W2s, W3s, b1s, b2s, b3s, xin, nullptr, nullptr, h2r, n, g);
     // Normal(mu, sigma).log_prob(act).sum(-1) and kl_divergence(Normal(mu_old, sigma), Normal(mu, sigma)) in torch's
     // expressions: -(a - mu)^2 / (2 var) - log sigma - log sqrt(2 pi);  0.5 (1 + ((mu_old - mu) / sigma)^2 - 1 - log 1)
     float lp = 0.f, kl = 0.f;
@@ -543,24 +354,10 @@ __global__ __launch_bounds__(64) void surrogate_reduce_kernel(const float *parti
   }
 }
 
-int npg_check(const pds_mlp *m) {
-  if (!m || m->d_in < 1 || m->d_in > kMaxDimIn || m->h1 < 1 || m->h1 > kMaxDim || m->h2 < 1 || m->h2 > kMaxDim ||
-      m->d_out < 1 || m->d_out > kMaxOut || (m->activation != 0 && m->activation != 1) || !m->w1 || !m->b1 ||
-      !m->w2 || !m->b2 || !m->w3 || !m->b3)
-    return PDS_EINVAL;
-  return PDS_OK;
-}
-
-int npg_grid_blocks(long long B) {
-  const long long tiles = (B + kTS - 1) / kTS;
-  const long long blocks = (tiles + kNpgWaves - 1) / kNpgWaves;
-  return (int)(blocks < kNpgMaxBlocks ? blocks : kNpgMaxBlocks);
-}
-
 // input tiles: 2 (d_in <= 32), 4 (<= 64), 8 (<= 128), 12 (<= 192)
 template <int ACT>
 static void launch_fvp(int nin, dim3 g, hipStream_t s, const NpgArgs &a) {
-  const dim3 b(kNpgWaves * 64);
+  const dim3 b(kWideWaves * 64);
   if (nin <= 2) hipLaunchKernelGGL((fvp_kernel<ACT, 2>), g, b, 0, s, a);
   else if (nin <= 4) hipLaunchKernelGGL((fvp_kernel<ACT, 4>), g, b, 0, s, a);
   else if (nin <= 8) hipLaunchKernelGGL((fvp_kernel<ACT, 8>), g, b, 0, s, a);
@@ -568,7 +365,7 @@ static void launch_fvp(int nin, dim3 g, hipStream_t s, const NpgArgs &a) {
 }
 template <int ACT>
 static void launch_surrogate(int nin, dim3 g, hipStream_t s, const NpgArgs &a) {
-  const dim3 b(kNpgWaves * 64);
+  const dim3 b(kWideWaves * 64);
   if (nin <= 2) hipLaunchKernelGGL((surrogate_kernel<ACT, 2>), g, b, 0, s, a);
   else if (nin <= 4) hipLaunchKernelGGL((surrogate_kernel<ACT, 4>), g, b, 0, s, a);
   else if (nin <= 8) hipLaunchKernelGGL((surrogate_kernel<ACT, 8>), g, b, 0, s, a);
@@ -579,8 +376,8 @@ static void launch_surrogate(int nin, dim3 g, hipStream_t s, const NpgArgs &a) {
 using namespace pds_mlp_detail;
 
 extern "C" int64_t pds_npg_workspace_floats(const pds_mlp *m, int num_candidates) {
-  if (npg_check(m) != PDS_OK || num_candidates < 0) return PDS_EINVAL;
-  const int64_t waves = (int64_t)kNpgMaxBlocks * kNpgWaves;
+  if (check(m) != PDS_OK || num_candidates < 0) return PDS_EINVAL;
+  const int64_t waves = (int64_t)kWideMaxBlocks * kWideWaves;
   const int64_t fvp = waves * offsets(*m).total, ls = waves * 3 * (int64_t)num_candidates;
   return fvp > ls ? fvp : ls;
 }
@@ -588,17 +385,17 @@ extern "C" int64_t pds_npg_workspace_floats(const pds_mlp *m, int num_candidates
 extern "C" int pds_npg_fisher_vector_product(const pds_mlp *m, const float *d_x, const int64_t *d_index, int64_t B,
                                              const float *d_log_std, const float *d_v, float damping, float *d_out,
                                              float *d_workspace, void *stream) {
-  if (npg_check(m) != PDS_OK || !d_x || !d_log_std || !d_v || !d_out || !d_workspace || B < 1) return PDS_EINVAL;
+  if (check(m) != PDS_OK || !d_x || !d_log_std || !d_v || !d_out || !d_workspace || B < 1) return PDS_EINVAL;
   NpgArgs a{};
   a.m = *m; a.x = d_x; a.index = d_index; a.B = B; a.log_std = d_log_std; a.v = d_v; a.partials = d_workspace;
   const Offsets o = offsets(*m);
   a.pstride = o.total;
-  const int blocks = npg_grid_blocks(B), nin = (m->d_in + kTW - 1) / kTW;
+  const int blocks = wide_grid_blocks(B), nin = (m->d_in + kTW - 1) / kTW;
   hipStream_t s = (hipStream_t)stream;
   if (m->activation == 0) launch_fvp<0>(nin, dim3(blocks), s, a); else launch_fvp<1>(nin, dim3(blocks), s, a);
   const float scale = 1.0f / (float)((double)B * (double)m->d_out);
   hipLaunchKernelGGL(fvp_reduce_kernel, dim3((o.total + 63) / 64), dim3(1024), 0, s, (const float *)d_workspace, a.pstride,
-                     blocks * kNpgWaves, o.total, scale, damping, d_v, d_out);
+                     blocks * kWideWaves, o.total, scale, damping, d_v, d_out);
   return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
 }
 
@@ -614,17 +411,17 @@ extern "C" int pds_npg_surrogate_kl(const pds_mlp *m, const float *d_step, const
                                     const float *d_x, const float *d_act, const float *d_adv, const float *d_logp_old,
                                     const float *d_mu_old, const float *d_log_std, int64_t B, float *d_out, float *d_theta_out,
                                     float *d_workspace, void *stream) {
-  if (npg_check(m) != PDS_OK || !d_step || !d_fracs || num_candidates < 1 || num_candidates > 65535 || !d_x || !d_act ||
+  if (check(m) != PDS_OK || !d_step || !d_fracs || num_candidates < 1 || num_candidates > 65535 || !d_x || !d_act ||
       !d_adv || !d_logp_old || !d_mu_old || !d_log_std || !d_out || !d_workspace || B < 1)
     return PDS_EINVAL;
   NpgArgs a{};
   a.m = *m; a.x = d_x; a.B = B; a.log_std = d_log_std; a.v = d_step; a.fracs = d_fracs; a.act = d_act; a.adv = d_adv;
   a.logp_old = d_logp_old; a.mu_old = d_mu_old; a.partials = d_workspace; a.theta_out = d_theta_out;
-  const int blocks = npg_grid_blocks(B), nin = (m->d_in + kTW - 1) / kTW;
+  const int blocks = wide_grid_blocks(B), nin = (m->d_in + kTW - 1) / kTW;
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(blocks, num_candidates);
   if (m->activation == 0) launch_surrogate<0>(nin, g, s, a); else launch_surrogate<1>(nin, g, s, a);
   hipLaunchKernelGGL(surrogate_reduce_kernel, dim3(num_candidates), dim3(64), 0, s, (const float *)d_workspace,
-                     blocks * kNpgWaves, d_out);
+                     blocks * kWideWaves, d_out);
   return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
 }

@@ -20,7 +20,7 @@ import math
 import torch
 import torch.distributed as dist
 
-from .ppo import PPOTrainer, _collectives
+from .ppo import PPOTrainer, _avg, _collectives
 
 TOTAL_STEPS, DECAY = 15, 0.8  # algs/trpo/trpo.py:20-21
 
@@ -63,14 +63,6 @@ def step_fractions(total_steps=TOTAL_STEPS, decay=DECAY):
     return out, f
 
 
-def _avg(t):
-    """mpi_avg / mpi_avg_torch_tensor: in place over the ranks"""
-    if _collectives():
-        dist.all_reduce(t)
-        t /= dist.get_world_size()
-    return t
-
-
 def _flat(params):
     return torch.cat([p.data.reshape(-1) for p in params])
 
@@ -104,38 +96,15 @@ class NPGTrainer(PPOTrainer):
             v = self.fm_v.forward(data["obs"]).view(-1) if self.fused else ac.v(data["obs"])
             loss_v_before = _avg(((v - data["target_v"]) ** 2).mean())  # (read after the policy step: no sync in front of it)
         vgen = self._value_steps(data["obs"], data["target_v"], B, mbs)
-        side = None
-        if self.fused and not _collectives() and self.overlap_value_update and data["obs"].is_cuda:
-            # the value net's mini-batch steps on a second stream next to the policy step (they share no state), fed in
-            # chunks between the policy step's launches (as PPOTrainer._fused_update)
-            main = torch.cuda.current_stream(data["obs"].device)
-            if self._side_stream is None:
-                self._side_stream = torch.cuda.Stream(device=data["obs"].device)
-            side = self._side_stream
-            side.wait_stream(main)
         v_total = self.train_v_iterations * self.num_mini_batches
-
-        def feed(steps):
-            if side is None:
-                return
-            with torch.cuda.stream(side):
-                for _ in range(steps):
-                    if next(vgen, StopIteration) is StopIteration:
-                        break
-        try:
+        with self._value_stream(vgen, data["obs"]) as (_, feed):
+            # with the overlap: a chunk of value steps after each Fisher product, the rest behind the policy step
             chunk = -(-v_total // (self.cg_iters + 2))
             info = self._policy_step_fused(data, feed, chunk) if self.fused else self._policy_step_torch(data)
             feed(v_total)
-        finally:
-            if side is not None:
-                torch.cuda.current_stream(data["obs"].device).wait_stream(side)
-        if side is None:
-            for _ in vgen:
-                pass
-        if self.use_standardized_obs:
-            ac.obs_oms.update(raw_obs)
-        if self.use_reward_scaling:
-            ac.ret_oms.update(disc_ret.reshape(-1))
+        for _ in vgen:  # without the overlap: every value step, after the policy step
+            pass
+        self._update_running_statistics(raw_obs, disc_ret)
         info.update(loss_v=float(loss_v_before), stop_iter=1)
         return info
 

@@ -16,6 +16,7 @@ all-reduce per optimiser step over RCCL instead of one MPI Allreduce per paramet
 finish are auto-reset inside pds_step and bootstrap from `final_obs`.
 PyTorch is used for what it is good at here: the two tiny MLPs and Adam.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -36,6 +37,14 @@ FORCE_COLLECTIVES = False
 
 def _collectives():
     return dist.is_initialized() and (dist.get_world_size() > 1 or FORCE_COLLECTIVES)
+
+
+def _avg(t):
+    """mpi_avg / mpi_avg_torch_tensor: the mean over the ranks, in place (one rank: `t` as it is)"""
+    if _collectives():
+        dist.all_reduce(t)
+        t /= dist.get_world_size()
+    return t
 
 
 class OnlineMeanStd(nn.Module):
@@ -526,10 +535,50 @@ class PPOTrainer:
                     self.fm_v.value_grad(obs, target_v, index=idx, adam_lr=self.vf_opt.param_groups[0]["lr"])
                 else:
                     self.fm_v.value_grad(obs, target_v, index=idx)
-                    dist.all_reduce(self.fm_v.flat_grad)
-                    self.fm_v.flat_grad /= dist.get_world_size()
+                    _avg(self.fm_v.flat_grad)
                     self.fm_v.adam_step(self.vf_opt.param_groups[0]["lr"])
                 yield
+
+    @contextlib.contextmanager
+    def _value_stream(self, vgen, obs):
+        """-> (overlap, feed).  The policy and the value update share no state (two networks, two optimisers, read-only
+        batch): single process, the value net's 80 mini-batch steps -- each 10 us of work behind ~27 us of fixed latency -- can
+        run on a second stream NEXT TO the policy update instead of in front of or behind it, when the host feeds the two
+        streams alternately (enqueueing the whole value path first keeps the policy stream empty for its 2.4 ms of host time):
+        feed(steps) advances `vgen` (_value_steps) by up to `steps` steps on the side stream; when to feed how many is the
+        caller's schedule.  Same launches, same bits.  overlap False (PyTorch ops, a CPU batch, overlap_value_update off, or
+        several ranks: the two nets' all-reduces would have to be issued in one order on every rank): feed does nothing, and
+        the caller runs `vgen` where its algorithm has the value update."""
+        side = None
+        if self.fused and not _collectives() and self.overlap_value_update and obs.is_cuda:
+            if self._side_stream is None:
+                self._side_stream = torch.cuda.Stream(device=obs.device)  # (a high-priority stream: no gain, profiles/r04_ppo_overlap.txt)
+            side = self._side_stream
+            side.wait_stream(torch.cuda.current_stream(obs.device))
+
+        def feed(steps):
+            if side is None:
+                return
+            with torch.cuda.stream(side):
+                for _ in range(steps):
+                    if next(vgen, StopIteration) is StopIteration:
+                        break
+        try:
+            yield side is not None, feed
+        finally:
+            # whatever happens in the policy update (a non-finite KL, KeyboardInterrupt): the value steps already enqueued on the
+            # side stream read `obs`, `target_v` and the value net's tensors, which were allocated on the main stream -- the
+            # main stream waits for them before anything can be freed or reused.  Nothing more is enqueued here: after an
+            # exception the value net keeps the steps it had got, and a second error cannot hide the first.
+            if side is not None:
+                torch.cuda.current_stream(obs.device).wait_stream(side)
+
+    def _update_running_statistics(self, raw_obs, disc_ret):
+        """update_running_statistics: from RAW data, after the update"""
+        if self.use_standardized_obs:
+            self.ac.obs_oms.update(raw_obs)
+        if self.use_reward_scaling:
+            self.ac.ret_oms.update(disc_ret.reshape(-1))
 
     def update(self):
         """algs/iwpg/iwpg.py:398-485."""
@@ -556,17 +605,11 @@ class PPOTrainer:
             self.pi_opt.step()
             if self.use_kl_early_stopping:
                 with torch.no_grad():
-                    kl = torch.distributions.kl.kl_divergence(p_dist, ac.pi.dist(data["obs"])).mean()
-                    if _collectives():
-                        dist.all_reduce(kl); kl /= dist.get_world_size()
+                    kl = _avg(torch.distributions.kl.kl_divergence(p_dist, ac.pi.dist(data["obs"])).mean())
                 if kl.item() > self.target_kl:
                     stop_iter = i + 1
                     break
-        # ---- running statistics from RAW data, after the update (update_running_statistics)
-        if self.use_standardized_obs:
-            ac.obs_oms.update(raw_obs)
-        if self.use_reward_scaling:
-            ac.ret_oms.update(disc_ret.reshape(-1))
+        self._update_running_statistics(raw_obs, disc_ret)
         return dict(loss_pi=float(loss_pi_before), loss_v=loss_v_before, stop_iter=stop_iter,
                     entropy=float(pi_info["ent"].detach()), ratio=float(pi_info["ratio"].detach()))
 
@@ -575,58 +618,28 @@ class PPOTrainer:
         per iteration writes d loss / d theta into the parameters' .grad (a flat buffer, so the
         gradient averaging over ranks is one RCCL all-reduce of it); Adam stays torch's."""
         ac = self.ac
-        world = dist.get_world_size() if dist.is_initialized() else 1
-
         multi = _collectives()  # several ranks (or FORCE_COLLECTIVES): gradients are averaged between the gradient and Adam
-
-        def average(fm):
-            if multi:
-                dist.all_reduce(fm.flat_grad)
-                fm.flat_grad /= world
-
         obs, target_v = data["obs"].contiguous(), data["target_v"].contiguous()
         with torch.no_grad():
             loss_v_before = ((self.fm_v.forward(obs).view(-1) - target_v) ** 2).mean()
-
-        # The two updates share no state (two networks, two optimisers, read-only batch): single process, the value net's 80
-        # mini-batch steps -- each 10 us of work behind ~27 us of fixed latency -- run on a second stream next to the policy
-        # net's 80 full-batch steps instead of in front of them, and the host feeds the two streams ALTERNATELY (one value
-        # step per policy step: enqueueing the whole value path first keeps the policy stream empty for its 2.4 ms of host
-        # time).  Same launches, same bits.  (Several ranks: the two nets' all-reduces would have to be issued in one order
-        # on every rank: kept sequential.)
-        side = None
         vgen = self._value_steps(obs, target_v, B, mbs)
-        if not multi and self.overlap_value_update and obs.is_cuda:
-            main = torch.cuda.current_stream(obs.device)
-            if self._side_stream is None:
-                self._side_stream = torch.cuda.Stream(device=obs.device)  # (a high-priority stream: no gain, profiles/r04_ppo_overlap.txt)
-            side = self._side_stream
-            side.wait_stream(main)
-        else:
-            for _ in vgen:
-                pass
-
-        def feed_value_stream(steps):
-            if side is None:
-                return
-            with torch.cuda.stream(side):
-                for _ in range(steps):
-                    if next(vgen, StopIteration) is StopIteration:
-                        break
-        act, adv, logp_old = data["act"].contiguous(), data["adv"].contiguous(), data["log_p"].contiguous()
-        log_std = ac.pi.log_std
-        # entropy of Normal(., sigma): sum(0.5 + 0.5 log 2 pi + log sigma), independent of the network
-        ent = float((0.5 + 0.5 * math.log(2 * math.pi) + log_std).sum())
-        if self.use_kl_early_stopping:
-            with torch.no_grad():
-                mu_old = self.fm_pi.forward(obs)
-        first = None
-        stop_iter = self.train_pi_iterations
         v_total = self.train_v_iterations * self.num_mini_batches
-        try:
+        with self._value_stream(vgen, obs) as (overlap, feed):
+            if not overlap:  # every value step before the policy loop (IWPG's order)
+                for _ in vgen:
+                    pass
+            act, adv, logp_old = data["act"].contiguous(), data["adv"].contiguous(), data["log_p"].contiguous()
+            log_std = ac.pi.log_std
+            # entropy of Normal(., sigma): sum(0.5 + 0.5 log 2 pi + log sigma), independent of the network
+            ent = float((0.5 + 0.5 * math.log(2 * math.pi) + log_std).sum())
+            if self.use_kl_early_stopping:
+                with torch.no_grad():
+                    mu_old = self.fm_pi.forward(obs)
+            first = None
+            stop_iter = self.train_pi_iterations
             for i in range(self.train_pi_iterations):
-                # the value steps due by now: spread evenly over the policy iterations
-                feed_value_stream((i + 1) * v_total // self.train_pi_iterations - i * v_total // self.train_pi_iterations)
+                # the value steps due by now: spread evenly over the policy iterations (one value step per policy step)
+                feed((i + 1) * v_total // self.train_pi_iterations - i * v_total // self.train_pi_iterations)
                 ride = not multi and not self.use_max_grad_norm  # Adam inside the gradient call (same bits)
                 stats = self.fm_pi.ppo_grad(obs, act, adv, logp_old, log_std, self.clip_ratio,
                                             adam_lr=self.pi_opt.param_groups[0]["lr"] if ride else None)
@@ -635,28 +648,16 @@ class PPOTrainer:
                 if not ride:
                     if self.use_max_grad_norm:
                         torch.nn.utils.clip_grad_norm_(ac.pi.net.parameters(), self.max_grad_norm)
-                    average(self.fm_pi)
+                    _avg(self.fm_pi.flat_grad)
                     self.fm_pi.adam_step(self.pi_opt.param_groups[0]["lr"])  # lr follows the LambdaLR schedule
                 if self.use_kl_early_stopping:
                     with torch.no_grad():  # KL(N(mu_old, s) || N(mu_new, s)) = sum (mu_old - mu_new)^2 / (2 s^2)
-                        kl = (((mu_old - self.fm_pi.forward(obs)) ** 2) / (2 * torch.exp(2 * log_std))).sum(-1).mean()
-                        if multi:
-                            dist.all_reduce(kl); kl /= world
+                        kl = _avg((((mu_old - self.fm_pi.forward(obs)) ** 2) / (2 * torch.exp(2 * log_std))).sum(-1).mean())
                     if kl.item() > self.target_kl:
                         stop_iter = i + 1
                         break
-            feed_value_stream(v_total)  # (whatever an early stop of the policy loop has left; not on an exception)
-        finally:
-            # whatever happens in the policy loop (a non-finite KL, KeyboardInterrupt): the value steps already enqueued on the
-            # side stream read `obs`, `target_v` and the value net's tensors, which were allocated on the main stream -- the
-            # main stream waits for them before anything can be freed or reused.  Nothing more is enqueued here: after an
-            # exception the value net keeps the steps it had got, and a second error cannot hide the first.
-            if side is not None:
-                torch.cuda.current_stream(obs.device).wait_stream(side)
-        if self.use_standardized_obs:
-            ac.obs_oms.update(raw_obs)
-        if self.use_reward_scaling:
-            ac.ret_oms.update(disc_ret.reshape(-1))
+            feed(v_total)  # (whatever an early stop of the policy loop has left; not on an exception)
+        self._update_running_statistics(raw_obs, disc_ret)
         f = first.tolist()
         return dict(loss_pi=f[0] / f[3] - self.entropy_coef * ent, loss_v=float(loss_v_before), stop_iter=stop_iter,
                     entropy=ent, ratio=f[1] / f[3])

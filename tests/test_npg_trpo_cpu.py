@@ -209,7 +209,7 @@ def test_npg_has_no_policy_lr_schedule():
     assert len(fr) == 15 and fr[0] == 1.0 and fr[1] == 0.8 and end == fr[-1] * 0.8
 
 
-# ---- the reference's own NPG / TRPO updates replayed (tests/golden/npg_update.npz, tools/refgen/gen_golden_npg_update.py) ----
+# ---- the reference's own NPG / TRPO updates replayed (tests/golden/npg_update.npz, oracle/refgen/gen_golden_npg_update.py) ----
 GOLD = __import__("os").path.join(__import__("os").path.dirname(__import__("os").path.abspath(__file__)), "golden", "npg_update.npz")
 RECORDS = ("npg_", "trpo_", "trpot_")
 
