@@ -26,6 +26,8 @@
  *   pds_step_k                       <- the open-loop replay loop `for i in range(T-1): sim_env.step(acs[i])`
  *                                       of simopt (simopt/pybullet.py:163-176), K steps per launch
  *   pds_set_latency                  <- CrazyFlieAgent.set_latency (envs/agents.py:388-404)
+ *   pds_simopt_evaluate              <- ObjectiveFunctionPyBullet.evaluate / evaluate_once / loss_function /
+ *                                       set_parameters (simopt/pybullet.py:72-248), P candidates per launch
  *   pds_destroy                      <- env.close()
  *
  * All pointers named `d_*` are DEVICE pointers on the handle's device; tensors are row-major fp32.
@@ -233,6 +235,37 @@ int pds_step_k(pds_handle *h, int k_steps, const float *d_actions, float *d_obs,
  * its index are zeroed for every env.  Synchronises the device (not a hot path). */
 int pds_set_latency(pds_handle *h, double latency);
 int pds_latency_steps(const pds_handle *h); /* current buf_size, 0 when use_latency is off */
+
+/* ---- sim-opt objective (csrc/pds_simopt.hip) -------------------------------------------------------
+ * ObjectiveFunctionPyBullet.evaluate (simopt/pybullet.py:72-248) for P parameter candidates x M logged mini-trajectories of
+ * length T in ONE launch, on the SimplePhysics path with the PT1 motor model on (the recipe switches it on whatever the env was
+ * made with).  For every pair (p, m): set_parameters(params[p]) -- values clipped at 0, T clipped to >= time_step,
+ * A = 1 - T_s / T, K = 0.028 G t2w / 4 in float64 --, reset (motor state and delayed-action ring zero), pre_steps steps of
+ * pre_inputs[m], keep the motor state, reset to the logged state (ring zeroed again), T - 1 steps of actions[m] with
+ *   loss[p, m] = mean_i gamma^i (||e_i||_1 + ||e_i||_2),
+ *   e_i = [euler(quat) - rpy, 100 (xyz - xyz_real), 10 (v - v_real), omega - omega_real]  against logged row i + 1;
+ * score[p] = mean_m loss[p, m], summed in a fixed order: a candidate's score does not depend on the rest of the batch.  No
+ * termination, no TimeLimit, no auto-reset.  This is the DETERMINISTIC objective: a handle with thrust or observation noise,
+ * domain randomisation, ground effect or a PID control mode is refused with PDS_EUNSUPPORTED.
+ *
+ * `h` supplies the configuration only (model constants, time_step, aggregate_phy_steps): no state, tick or latency of the
+ * handle is read or changed (only its error text, on failure); num_envs is irrelevant.  Asynchronous on `stream`, no
+ * allocation, no synchronisation, capturable into a hipGraph.
+ *   d_params     [P,3]  thrust_to_weight_ratio, motor_time_constant [s], latency [s] (the latency is used through d_lat_steps)
+ *   d_lat_steps  [P]    int32 buf_size of every candidate = pds_simopt_latency_steps (the reference's float64
+ *                       int(latency / time_step), 0 below one time step); max_lat_steps = their maximum, by value: above
+ *                       PDS_MAX_LATENCY_STEPS the whole call is refused before anything is launched
+ *   d_actions    [T][M][4]      time-major, 16-byte aligned (row T-1 is not read)
+ *   d_obs        [T][3][M][4]   time-major quads (x y z vx | vy vz roll pitch | yaw wx wy wz): row 0 = the state the sample
+ *                               starts from (the reset's pose read-back of the logged row, body rates R^T R^T (R w)), rows
+ *                               1..T-1 = the logged rows
+ *   d_pre_inputs [pre_steps][M][4]
+ *   d_loss [P,M] out    d_score [P] out    d_sim_obs [T-1,P,M,13] out or NULL: xyz, quaternion, velocity, body rates after
+ *   every step (bitwise the first 13 observation columns of pds_step_k replaying the same actions). */
+int pds_simopt_latency_steps(const pds_handle *h, double latency);
+int pds_simopt_evaluate(pds_handle *h, int64_t P, const float *d_params, const int32_t *d_lat_steps, int max_lat_steps,
+                        int64_t M, int T, int pre_steps, double gamma, const float *d_actions, const float *d_obs,
+                        const float *d_pre_inputs, float *d_loss, float *d_score, float *d_sim_obs, void *stream);
 
 int pds_field_width(int field);
 int pds_get_state(pds_handle *h, int field, void *d_out, void *stream);

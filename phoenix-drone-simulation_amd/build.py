@@ -18,8 +18,8 @@ _UNITS = ["pds_task_hover.hip", "pds_task_circle.hip", "pds_task_takeoff.hip", "
           "pds_task_hover_pid_ge.hip", "pds_task_circle_pid_ge.hip", "pds_rollout_hover_pwm.hip", "pds_rollout_circle_pwm.hip", "pds_rollout_hover_lat.hip", "pds_rollout_circle_lat.hip",
           "pds_api.hip", "pds_rollout_hover.hip", "pds_rollout_circle.hip", "pds_rollout_takeoff.hip",
           "pds_rollout_hist_hover.hip", "pds_rollout_hist_circle.hip", "pds_rollout_hist_takeoff.hip",
-          "pds_gae.hip", "pds_train.hip", "pds_history.hip", "pds_npg.hip"]  # longest first
-_HEADERS = ["pds_device.h", "pds_types.h", "pds_reset.h", "pds_step.h", "pds_mlp_fwd.h", "pds_rollout.h", "pds_rollout_hist.h", "pds_mlp_common.h", "pds_mlp_tile.h"]
+          "pds_gae.hip", "pds_train.hip", "pds_history.hip", "pds_npg.hip", "pds_simopt.hip"]  # longest first
+_HEADERS = ["pds_device.h", "pds_types.h", "pds_reset.h", "pds_step.h", "pds_mlp_fwd.h", "pds_rollout.h", "pds_rollout_hist.h", "pds_mlp_common.h", "pds_mlp_tile.h", "pds_physics.h", "pds_simopt.h"]
 _DEPS = [os.path.join(_CSRC, f) for f in _UNITS + _HEADERS] + [os.path.join(_HERE, "..", "include", "pds.h")]
 _LIB = os.path.join(_HERE, "libpds_hip.so")
 _OBJ = os.path.join(_HERE, "build")

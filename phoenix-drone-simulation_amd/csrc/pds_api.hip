@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "pds_reset.h"  // (pds_types.h + regen_kept_obs for pds_get_state)
+#include "pds_simopt.h"
 
 namespace pds {
 
@@ -695,6 +696,59 @@ extern "C" int pds_set_latency(pds_handle *h, double latency) {
     PDS_HIP(h, hipGetLastError());
     PDS_HIP(h, hipDeviceSynchronize());
   }
+  return PDS_OK;
+}
+
+// buf_size of a sim-opt candidate: CrazyFlieAgent.set_latency's float64 form (envs/agents.py:397-401)
+extern "C" int pds_simopt_latency_steps(const pds_handle *h, double latency) {
+  if (!h) return PDS_EINVAL;
+  if (latency < h->cfg.time_step) return 0;  // (a NaN falls through like in the reference and gives 0 below)
+  const double steps = latency / h->cfg.time_step;
+  return steps >= 1.0 ? (steps > 1e6 ? 1000000 : (int)steps) : 0;
+}
+
+// ObjectiveFunctionPyBullet.evaluate for P candidates in one launch (csrc/pds_simopt.hip).  Reads the handle's configuration,
+// changes nothing in it: every check comes first, then two launches on the caller's stream.
+extern "C" int pds_simopt_evaluate(pds_handle *h, int64_t P, const float *d_params, const int32_t *d_lat_steps, int max_lat_steps,
+                                   int64_t M, int T, int pre_steps, double gamma, const float *d_actions, const float *d_obs,
+                                   const float *d_pre_inputs, float *d_loss, float *d_score, float *d_sim_obs, void *stream) {
+  if (!h) return PDS_EINVAL;
+  const LaunchFlags &f = h->flags;
+  if (f.tn || f.on || f.dr || f.ge || f.hold || f.ctrl != 0)
+    return fail(h, PDS_EUNSUPPORTED,
+                "pds_simopt_evaluate is built for the deterministic objective: control_mode PWM, motor_thrust_noise <= 0, "
+                "observation_noise <= 0, domain_randomization <= 0, no ground effect (this handle:%s%s%s%s%s)",
+                f.ctrl != 0 ? " PID control mode" : "", f.tn ? " thrust noise" : "", f.on ? " observation noise" : "",
+                f.dr ? " domain randomisation" : "", f.ge ? " ground effect" : "");
+  if (max_lat_steps > kMaxLatSteps)
+    return fail(h, PDS_EUNSUPPORTED, "a candidate's latency is %d time steps (limit %d): nothing was evaluated", max_lat_steps,
+                kMaxLatSteps);
+  if (P < 1 || M < 1 || T < 2 || pre_steps < 0 || max_lat_steps < 0)
+    return fail(h, PDS_EINVAL, "pds_simopt_evaluate: P %lld, M %lld, T %d, pre_steps %d, max_lat_steps %d", (long long)P,
+                (long long)M, T, pre_steps, max_lat_steps);
+  if (M > (1 << 24) || P > (1 << 24) || P * ((M + kWave - 1) / kWave) > (int64_t)1 << 32)
+    return fail(h, PDS_EINVAL, "pds_simopt_evaluate: P %lld x M %lld is beyond one launch: shard the candidates", (long long)P,
+                (long long)M);
+  if (!d_params || !d_lat_steps || !d_actions || !d_obs || !d_loss || !d_score || (pre_steps > 0 && !d_pre_inputs))
+    return fail(h, PDS_EINVAL, "pds_simopt_evaluate: null pointer");
+  if (((uintptr_t)d_actions | (uintptr_t)d_obs | (uintptr_t)d_pre_inputs) & 15u)
+    return fail(h, PDS_EINVAL, "pds_simopt_evaluate: the data set arrays must be 16-byte aligned");
+  DeviceGuard guard(h->cfg.device);
+  PDS_HIP(h, guard.err);
+  SimoptArgs a;
+  a.k = h->k;
+  a.time_step = h->cfg.time_step;
+  a.G = 9.81;  // envs/agents.py:150
+  a.gamma = gamma;
+  a.params = d_params;
+  a.lat_steps = d_lat_steps;
+  a.acts = reinterpret_cast<const float4 *>(d_actions);
+  a.obs = reinterpret_cast<const float4 *>(d_obs);
+  a.pre = reinterpret_cast<const float4 *>(d_pre_inputs);
+  a.P = (int)P; a.M = (int)M; a.T = T; a.pre_steps = pre_steps;
+  a.loss = d_loss; a.score = d_score; a.sim_obs = d_sim_obs;
+  launch_simopt(a, (hipStream_t)stream);
+  PDS_HIP(h, hipGetLastError());
   return PDS_OK;
 }
 

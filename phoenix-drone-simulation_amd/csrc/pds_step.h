@@ -17,6 +17,7 @@
 #pragma once
 #include <type_traits>
 #include "pds_reset.h"
+#include "pds_physics.h"
 
 namespace pds {
 
@@ -610,62 +611,15 @@ PDS_DEV bool step_once(const StepArgs &a, const long long o1, const RngKey &rk, 
     }
     float f[4], pwmv[4];
     if (V::CTRL == 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) pwmv[j] = 30000.f + clampf(av[j], -1.f, 1.f) * 30000.f;
+      PDS_PWM_FROM_ACTION()
     } else {
       control_pwm<V::CTRL>(k.dt_nom, e, av, ps, pwmv);
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float un = pwmv[j] * (1.0f / 60000.f);
-      float noise1 = 1.0f;
-      if (V::TN) {  // OUNoise.noise, envs/utils.py:104-108 (theta .15, mu 0); never reset
-        ns.ou[j] = ns.ou[j] + (0.15f * (0.f - ns.ou[j]) + k.ou_sigma * sn.ou[j]);
-        noise1 = 1.0f + ns.ou[j];
-      }
-      float n;
-      if (V::MOTOR) {
-        xm[j] = par.A[j] * xm[j] + (1.0f - par.A[j]) * fast_sqrt(un);
-        n = noise1 * (xm[j] * xm[j]);
-      } else {
-        n = noise1 * un;
-      }
-      f[j] = par.K[j] * clampf(n, 0.f, 1.f);
-    }
-    // yaw torque: sum of +-(ftf1*f_i + ftf0); ftf0 cancels (envs/agents.py:295-297)
-    const float tz_ = par.ftf1 * (-f[0] + f[1] - f[2] + f[3]);
-    float R[9];
-    matrix_from_quat(q, R);  // envs/physics.py:160 (quaternion of the PREVIOUS step)
-    if (V::GE) {
-      // BasePhysics.calculate_ground_effect, envs/physics.py:27-58, applied as extra per-motor
-      // thrust (envs/physics.py:117-120); branch-free per-env scale
-      const float ok = (fabsf(e.roll) < kHalfPi && fabsf(e.pitch) < kHalfPi) ? 1.f : 0.f;
-      const float ox[4] = {0.028f, -0.028f, -0.028f, 0.028f};
-      const float oy[4] = {-0.028f, -0.028f, 0.028f, 0.028f};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float hz = fmaxf(e.pz + (R[6] * ox[j] + R[7] * oy[j]), k.h_clip);
-        const float qq = k.prop_r * fast_rcp(4.f * hz);
-        f[j] = f[j] + ok * (f[j] * k.gec * (qq * qq));
-      }
-    }
-    const float thrust = ((f[0] + f[1]) + f[2]) + f[3];
-    const float Fx = R[2] * thrust, Fy = R[5] * thrust, Fz = R[8] * thrust - k.G * par.m;
-    const float tx_ = (-f[0] - f[1] + f[2] + f[3]) * k.Lq;  // envs/physics.py:167
-    const float ty_ = (-f[0] + f[1] + f[2] - f[3]) * k.Lq;  // envs/physics.py:168
-    const float Jwx = par.Jx * e.wx, Jwy = par.Jy * e.wy, Jwz = par.Jz * e.wz;
-    const float t0 = tx_ - (e.wy * Jwz - e.wz * Jwy);  // tau - w x (J w), envs/physics.py:170-171
-    const float t1 = ty_ - (e.wz * Jwx - e.wx * Jwz);
-    const float t2 = tz_ - (e.wx * Jwy - e.wy * Jwx);
-    const float dt = par.dt;
-    e.vx += dt * (Fx * inv_m); e.vy += dt * (Fy * inv_m); e.vz += dt * (Fz * inv_m);    // :173,175
-    e.wx += dt * (t0 * inv_Jx); e.wy += dt * (t1 * inv_Jy); e.wz += dt * (t2 * inv_Jz);  // :172,176
-    e.px += dt * e.vx; e.py += dt * e.vy; e.pz += dt * e.vz;                             // :177
-    e.roll += dt * e.wx; e.pitch += dt * e.wy; e.yaw += dt * e.wz;                       // :178
-    // :179 -- with observation noise nothing reads the TRUE quaternion after the last sub-step (the observation carries
-    // Q(noisy rpy), the next env.step rebuilds Q(rpy) from the stored angles): skip its three sincos there
-    if (!V::ON || sub + 1 < k.agg) q = quat_from_euler(e.roll, e.pitch, e.yaw);
-    e.pz = fmaxf(e.pz, 0.f);                                                             // :182
+    // the sub-step itself (csrc/pds_physics.h, shared with the sim-opt objective).  envs/physics.py:179 -- with observation
+    // noise nothing reads the TRUE quaternion after the last sub-step (the observation carries Q(noisy rpy), the next env.step
+    // rebuilds Q(rpy) from the stored angles): skip its three sincos there
+    PDS_MOTOR_THRUST(V::MOTOR, V::TN, ns.ou, sn.ou)
+    PDS_RIGID_BODY_SUBSTEP(V::GE, !V::ON || sub + 1 < k.agg)
     // envs/base.py:464: compute_observation() whose result is dropped still advances the gyro
     // bias random walk and the low-pass filter
     if (V::ON) {

@@ -38,7 +38,8 @@ EXPORTS = ["pds_version", "pds_default_config", "pds_create", "pds_destroy", "pd
            "pds_mlp_param_count", "pds_mlp_workspace_floats", "pds_mlp_forward", "pds_ppo_policy_grad",
            "pds_value_grad", "pds_ppo_policy_grad_step", "pds_value_grad_step", "pds_gaussian_sample", "pds_gaussian_sample_dev", "pds_counter_add", "pds_permutation", "pds_rollout_record",
            "pds_adam_step", "pds_rollout", "pds_rollout_history",
-           "pds_npg_workspace_floats", "pds_npg_fisher_vector_product", "pds_npg_cg_step", "pds_npg_surrogate_kl"]
+           "pds_npg_workspace_floats", "pds_npg_fisher_vector_product", "pds_npg_cg_step", "pds_npg_surrogate_kl",
+           "pds_simopt_latency_steps", "pds_simopt_evaluate"]
 
 
 class Mlp(C.Structure):
@@ -156,6 +157,8 @@ def load():
     later("pds_npg_fisher_vector_product", [mp, vp, vp, i64, vp, vp, C.c_float, vp, vp, vp])
     later("pds_npg_cg_step", [i64, vp, vp, vp, vp, vp, C.c_float, C.c_float, i32, vp])
     later("pds_npg_surrogate_kl", [mp, vp, vp, i32] + [vp] * 6 + [i64, vp, vp, vp, vp])
+    later("pds_simopt_latency_steps", [vp, C.c_double])
+    later("pds_simopt_evaluate", [vp, i64, vp, vp, i32, i64, i32, i32, C.c_double] + [vp] * 7)
     _lib = lib
     return lib
 
