@@ -972,7 +972,60 @@ extern "C" int pds_field_width(int field) {
   }
 }
 
-// number of envs whose dynamic state holds a NaN or an Inf (diagnostic, see pds_count_nonfinite)
+// ---- the one-launch rollouts: pds_rollout (csrc/pds_rollout.h) and pds_rollout_history (csrc/pds_rollout_hist.h) ----
+// What both validate about the call and the handle (`any_null`: one of the entry point's required pointers is NULL).
+static int check_rollout_call(pds_handle *h, const char *fn, bool any_null, const float *d_mean, const float *d_std) {
+  if (any_null) return fail(h, PDS_EINVAL, "%s: NULL pointer", fn);
+  if ((d_mean == nullptr) != (d_std == nullptr)) return fail(h, PDS_EINVAL, "%s: mean and std come together", fn);
+  if (!h->was_reset) return fail(h, PDS_EINVAL, "%s before pds_reset", fn);
+  // the rollout bootstraps finished episodes from V(final_obs) and restarts them in place (roll_out of the reference
+  // calls env.reset() itself, algs/iwpg/iwpg.py:382-385): without auto-reset there is no final observation to evaluate
+  if (!h->cfg.auto_reset) return fail(h, PDS_EUNSUPPORTED, "%s needs a handle created with auto_reset = 1", fn);
+  return PDS_OK;
+}
+// a network the rollout kernels can stage: d_in inputs, hidden layers <= 64, all six tensors there
+static bool rollout_net_ok(const pds_mlp *m, int d_in) {
+  return m->d_in == d_in && m->h1 >= 1 && m->h1 <= 64 && m->h2 >= 1 && m->h2 <= 64 && (m->activation == 0 || m->activation == 1) &&
+         m->w1 && m->b1 && m->w2 && m->b2 && m->w3 && m->b3;
+}
+static bool rollout_buffers_aligned(const float *d_act_buf, const float *d_obs_buf) {
+  return !((((uintptr_t)d_act_buf) & 15u) || (((uintptr_t)d_obs_buf) & 3u));
+}
+// The StepArgs head and the fields RolloutArgs and RolloutHistArgs share (csrc/pds_types.h); reward / term / trunc / cost
+// point at the [T, N] rollout buffers.  s.obs and what only one of the structs has are the caller's.
+template <class RA>
+static void fill_rollout_args(pds_handle *h, RA &ra, int T, const pds_mlp *pi, const float *d_mean, const float *d_std, float eps,
+                              const float *d_log_std, uint64_t seed, const uint64_t *d_call_base, uint64_t call_offset,
+                              int deterministic, float *d_act_buf, float *d_logp_buf, float *d_rew_buf, uint8_t *d_term_buf,
+                              uint8_t *d_trunc_buf, float *d_cost_buf, float *d_ep_ret, float *d_ep_len, float *d_stats) {
+  memset(&ra, 0, sizeof(ra));
+  base_args(h, ra.s);
+  ra.s.actions = reinterpret_cast<const float4 *>(d_act_buf);  // (load_env's action slot: valid memory, value unused)
+  ra.s.reward = d_rew_buf; ra.s.term = d_term_buf; ra.s.trunc = d_trunc_buf; ra.s.cost = d_cost_buf;
+  ra.s.final_obs = nullptr;                                     // (the finished rows stay in LDS)
+  ra.s.k_steps = T;
+  ra.pi = *pi;
+  ra.mean = d_mean; ra.stdv = d_std; ra.eps = eps; ra.log_std = d_log_std;
+  ra.seed = seed; ra.call_base = reinterpret_cast<const unsigned long long *>(d_call_base); ra.call_offset = call_offset;
+  ra.deterministic = deterministic; ra.T = T;
+  ra.act_buf = d_act_buf; ra.logp_buf = d_logp_buf;
+  ra.ep_ret = d_ep_ret; ra.ep_len = d_ep_len; ra.stats = d_stats;
+}
+// The launch: `launch(grid, stream)` is the entry point's dispatch by task, grid.x the number of 64-env tiles; T ticks
+// further.  Both entry points decide support BEFORE they get here: a refused call leaves the handle as it was.
+template <class Launch>
+static int launch_rollout(pds_handle *h, const char *fn, int T, void *stream, Launch launch) {
+  DeviceGuard guard(h->cfg.device);
+  PDS_HIP(h, guard.err);
+  // the env waves read the kept noisy observation from oh0-2 (StoredOh, like the K-step kernel)
+  if (const int rc = materialize_kept_obs(h, (hipStream_t)stream)) return rc;
+  const dim3 grid((unsigned)((h->cfg.num_envs + kWave - 1) / kWave));
+  if (!launch(grid, (hipStream_t)stream)) return fail(h, PDS_EHIP, "%s: its _supported() rule and the launchers disagree", fn);
+  PDS_HIP(h, hipGetLastError());
+  h->tick += (uint64_t)T;
+  return PDS_OK;
+}
+
 // One launch per rollout: csrc/pds_rollout.h (the caller's roll_out, algs/iwpg/iwpg.py:350-385).
 extern "C" int pds_rollout(pds_handle *h, int T, const pds_mlp *pi, const pds_mlp *vf, const float *d_mean, const float *d_std,
                            float eps, const float *d_log_std, uint64_t seed, const uint64_t *d_call_base, uint64_t call_offset,
@@ -981,56 +1034,31 @@ extern "C" int pds_rollout(pds_handle *h, int T, const pds_mlp *pi, const pds_ml
                            float *d_last_val, float *d_ep_ret, float *d_ep_len, float *d_stats, void *stream) {
   if (!h) return PDS_EINVAL;
   if (T < 1) return fail(h, PDS_EINVAL, "pds_rollout: T %d", T);
-  if (!pi || !vf || !d_log_std || !d_obs_buf || !d_act_buf || !d_logp_buf || !d_val_buf || !d_rew_buf || !d_term_buf ||
-      !d_trunc_buf || !d_cost_buf || !d_fval_buf || !d_last_val || !d_ep_ret || !d_ep_len || !d_stats)
-    return fail(h, PDS_EINVAL, "pds_rollout: NULL pointer");
-  if ((d_mean == nullptr) != (d_std == nullptr)) return fail(h, PDS_EINVAL, "pds_rollout: mean and std come together");
-  if (!h->was_reset) return fail(h, PDS_EINVAL, "pds_rollout before pds_reset");
-  // the rollout bootstraps finished episodes from V(final_obs) and restarts them in place (roll_out of the reference
-  // calls env.reset() itself, algs/iwpg/iwpg.py:382-385): without auto-reset there is no final observation to evaluate
-  if (!h->cfg.auto_reset) return fail(h, PDS_EUNSUPPORTED, "pds_rollout needs a handle created with auto_reset = 1");
+  const bool any_null = !pi || !vf || !d_log_std || !d_obs_buf || !d_act_buf || !d_logp_buf || !d_val_buf || !d_rew_buf ||
+                        !d_term_buf || !d_trunc_buf || !d_cost_buf || !d_fval_buf || !d_last_val || !d_ep_ret || !d_ep_len || !d_stats;
+  if (const int rc = check_rollout_call(h, "pds_rollout", any_null, d_mean, d_std)) return rc;
   const int D = h->obs_dim;
-  for (const pds_mlp *m : {pi, vf})
-    if (m->d_in != D || m->h1 < 1 || m->h1 > 64 || m->h2 < 1 || m->h2 > 64 || (m->activation != 0 && m->activation != 1) ||
-        !m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->w3 || !m->b3)
-      return fail(h, PDS_EINVAL, "pds_rollout: network shape (d_in must be the observation width %d, hidden <= 64)", D);
+  if (!rollout_net_ok(pi, D) || !rollout_net_ok(vf, D))
+    return fail(h, PDS_EINVAL, "pds_rollout: network shape (d_in must be the observation width %d, hidden <= 64)", D);
   if (pi->d_out != 4 || vf->d_out != 1) return fail(h, PDS_EINVAL, "pds_rollout: actor d_out 4, critic d_out 1");
-  if ((((uintptr_t)d_act_buf) & 15u) || (((uintptr_t)d_obs_buf) & 3u)) return fail(h, PDS_EINVAL, "pds_rollout: alignment");
-  DeviceGuard guard(h->cfg.device);
-  PDS_HIP(h, guard.err);
-  RolloutArgs ra;
-  memset(&ra, 0, sizeof(ra));
-  base_args(h, ra.s);
-  const long long n = h->cfg.num_envs;
-  ra.s.actions = reinterpret_cast<const float4 *>(d_act_buf);  // (load_env's action slot: valid memory, value unused)
-  ra.s.obs = d_obs_buf + n * D;                                 // step t writes o(t + 1) into row t + 1
-  ra.s.reward = d_rew_buf; ra.s.term = d_term_buf; ra.s.trunc = d_trunc_buf; ra.s.cost = d_cost_buf;
-  ra.s.final_obs = nullptr;                                     // (the finished rows stay in LDS)
-  ra.s.k_steps = T;
-  ra.pi = *pi; ra.vf = *vf;
-  ra.mean = d_mean; ra.stdv = d_std; ra.eps = eps; ra.log_std = d_log_std;
-  ra.seed = seed; ra.call_base = reinterpret_cast<const unsigned long long *>(d_call_base); ra.call_offset = call_offset;
-  ra.deterministic = deterministic; ra.T = T;
-  ra.obs0 = d_obs_buf;
-  ra.act_buf = d_act_buf; ra.logp_buf = d_logp_buf; ra.val_buf = d_val_buf; ra.fval_buf = d_fval_buf; ra.last_val = d_last_val;
-  ra.ep_ret = d_ep_ret; ra.ep_len = d_ep_len; ra.stats = d_stats;
-  const long long tiles = (n + kWave - 1) / kWave;
-  const dim3 grid((unsigned)tiles);  // (the number of tiles: the launchers pick one or two tiles per block, csrc/pds_rollout.h)
-  // support is decided BEFORE the handle is touched (a refused call leaves it as it was)
+  if (!rollout_buffers_aligned(d_act_buf, d_obs_buf)) return fail(h, PDS_EINVAL, "pds_rollout: alignment");
   if (!rollout_supported(h->cfg.task, h->flags))
     return fail(h, PDS_EUNSUPPORTED, "pds_rollout: no kernel for this env configuration (not built: the ground effect except on TakeOff with control_mode PWM; the Kalman hold or "
                                      "partial noise settings together with a PID mode or the latency ring; TakeOff with motor dynamics "
                                      "without the latency ring) -- the per-step kernels give the same bits");
-  // the env waves read the kept noisy observation from oh0-2 (StoredOh, like the K-step kernel)
-  if (const int rc = materialize_kept_obs(h, (hipStream_t)stream)) return rc;
-  bool ok;
-  if (h->cfg.task == PDS_TASK_HOVER) ok = launch_rollout_hover(h->flags, grid, (hipStream_t)stream, ra);
-  else if (h->cfg.task == PDS_TASK_CIRCLE) ok = launch_rollout_circle(h->flags, grid, (hipStream_t)stream, ra);
-  else ok = launch_rollout_takeoff(h->flags, grid, (hipStream_t)stream, ra);
-  if (!ok) return fail(h, PDS_EHIP, "pds_rollout: rollout_supported() and the launchers disagree");
-  PDS_HIP(h, hipGetLastError());
-  h->tick += (uint64_t)T;
-  return PDS_OK;
+  RolloutArgs ra;
+  fill_rollout_args(h, ra, T, pi, d_mean, d_std, eps, d_log_std, seed, d_call_base, call_offset, deterministic, d_act_buf, d_logp_buf,
+                    d_rew_buf, d_term_buf, d_trunc_buf, d_cost_buf, d_ep_ret, d_ep_len, d_stats);
+  ra.s.obs = d_obs_buf + (long long)h->cfg.num_envs * D;  // step t writes o(t + 1) into row t + 1
+  ra.vf = *vf;
+  ra.obs0 = d_obs_buf;
+  ra.val_buf = d_val_buf; ra.fval_buf = d_fval_buf; ra.last_val = d_last_val;
+  // (grid.x = the number of tiles: the launchers pick one or two tiles per block, csrc/pds_rollout.h)
+  return launch_rollout(h, "pds_rollout", T, stream, [&](dim3 grid, hipStream_t s) {
+    if (h->cfg.task == PDS_TASK_HOVER) return launch_rollout_hover(h->flags, grid, s, ra);
+    if (h->cfg.task == PDS_TASK_CIRCLE) return launch_rollout_circle(h->flags, grid, s, ra);
+    return launch_rollout_takeoff(h->flags, grid, s, ra);
+  });
 }
 
 // One launch per rollout for observation histories other than 2: csrc/pds_rollout_hist.h.
@@ -1042,57 +1070,37 @@ extern "C" int pds_rollout_history(pds_handle *h, int T, int history, const pds_
                                    float *d_ep_len, float *d_stats, void *stream) {
   if (!h) return PDS_EINVAL;
   if (T < 1 || history < 1 || slots < 1) return fail(h, PDS_EINVAL, "pds_rollout_history: T %d, history %d, slots %d", T, history, slots);
-  if (!pi || !d_log_std || !d_obs_buf || !d_act_buf || !d_logp_buf || !d_rew_buf || !d_term_buf || !d_trunc_buf || !d_cost_buf ||
-      !d_fin_rows || !d_fin_step || !d_ep_ret || !d_ep_len || !d_stats)
-    return fail(h, PDS_EINVAL, "pds_rollout_history: NULL pointer");
-  if ((d_mean == nullptr) != (d_std == nullptr)) return fail(h, PDS_EINVAL, "pds_rollout_history: mean and std come together");
-  if (!h->was_reset) return fail(h, PDS_EINVAL, "pds_rollout_history before pds_reset");
-  if (!h->cfg.auto_reset) return fail(h, PDS_EUNSUPPORTED, "pds_rollout_history needs a handle created with auto_reset = 1");
+  const bool any_null = !pi || !d_log_std || !d_obs_buf || !d_act_buf || !d_logp_buf || !d_rew_buf || !d_term_buf || !d_trunc_buf ||
+                        !d_cost_buf || !d_fin_rows || !d_fin_step || !d_ep_ret || !d_ep_len || !d_stats;
+  if (const int rc = check_rollout_call(h, "pds_rollout_history", any_null, d_mean, d_std)) return rc;
   const int half = h->obs_dim / 2, HS = history * half;
   if (HS > 192) return fail(h, PDS_EUNSUPPORTED, "pds_rollout_history: %d x %d = %d network inputs (<= 192)", history, half, HS);
-  if (pi->d_in != HS || pi->h1 < 1 || pi->h1 > 64 || pi->h2 < 1 || pi->h2 > 64 || (pi->activation != 0 && pi->activation != 1) ||
-      !pi->w1 || !pi->b1 || !pi->w2 || !pi->b2 || !pi->w3 || !pi->b3 || pi->d_out != 4)
+  if (!rollout_net_ok(pi, HS) || pi->d_out != 4)
     return fail(h, PDS_EINVAL, "pds_rollout_history: actor shape (d_in must be history x half = %d, hidden <= 64, d_out 4)", HS);
   // max_episode_steps bounds how often the TimeLimit can cut one env within T steps; + the rollout's last step
   if (slots < T / h->cfg.max_episode_steps + 2)
     return fail(h, PDS_EINVAL, "pds_rollout_history: slots %d < T / max_episode_steps + 2 = %d", slots, T / h->cfg.max_episode_steps + 2);
-  if ((((uintptr_t)d_act_buf) & 15u) || (((uintptr_t)d_obs_buf) & 3u)) return fail(h, PDS_EINVAL, "pds_rollout_history: alignment");
-  // support is decided BEFORE the handle is touched (a refused call leaves it as it was)
+  if (!rollout_buffers_aligned(d_act_buf, d_obs_buf)) return fail(h, PDS_EINVAL, "pds_rollout_history: alignment");
   if (!rollout_hist_supported(h->cfg.task, h->flags))
     return fail(h, PDS_EUNSUPPORTED, "pds_rollout_history: no kernel for this env configuration (built: control_mode PWM without latency ring, "
                                      "Kalman hold or ground effect; noise off or the reference's default; TakeOff without motor dynamics) "
                                      "-- the per-step kernels give the same bits");
-  DeviceGuard guard(h->cfg.device);
-  PDS_HIP(h, guard.err);
   RolloutHistArgs ra;
-  memset(&ra, 0, sizeof(ra));
-  base_args(h, ra.s);
-  ra.s.actions = reinterpret_cast<const float4 *>(d_act_buf);  // (load_env's action slot: valid memory, value unused)
-  ra.s.obs = nullptr;                                           // (the kernel's own [o(k), o(k + 1)] row stays in LDS)
-  ra.s.reward = d_rew_buf; ra.s.term = d_term_buf; ra.s.trunc = d_trunc_buf; ra.s.cost = d_cost_buf;
-  ra.s.final_obs = nullptr;
-  ra.s.k_steps = T;
-  ra.pi = *pi;
-  ra.mean = d_mean; ra.stdv = d_std; ra.eps = eps; ra.log_std = d_log_std;
-  ra.seed = seed; ra.call_base = reinterpret_cast<const unsigned long long *>(d_call_base); ra.call_offset = call_offset;
-  ra.deterministic = deterministic; ra.T = T; ra.H = history; ra.half = half; ra.slots = slots;
-  ra.obs_buf = d_obs_buf; ra.act_buf = d_act_buf; ra.logp_buf = d_logp_buf;
+  fill_rollout_args(h, ra, T, pi, d_mean, d_std, eps, d_log_std, seed, d_call_base, call_offset, deterministic, d_act_buf, d_logp_buf,
+                    d_rew_buf, d_term_buf, d_trunc_buf, d_cost_buf, d_ep_ret, d_ep_len, d_stats);
+  ra.s.obs = nullptr;  // (the kernel's own [o(k), o(k + 1)] row stays in LDS)
+  ra.H = history; ra.half = half; ra.slots = slots;
+  ra.obs_buf = d_obs_buf;
   ra.fin_rows = d_fin_rows; ra.fin_step = d_fin_step;
-  ra.ep_ret = d_ep_ret; ra.ep_len = d_ep_len; ra.stats = d_stats;
-  const long long n = h->cfg.num_envs;
-  const dim3 grid((unsigned)((n + kWave - 1) / kWave));
-  if (const int rc = materialize_kept_obs(h, (hipStream_t)stream)) return rc;  // (StoredOh, like pds_rollout)
   const int hn = rollout_hist_tiles(HS);
-  bool ok;
-  if (h->cfg.task == PDS_TASK_HOVER) ok = launch_rollout_hist_hover(h->flags, hn, grid, (hipStream_t)stream, ra);
-  else if (h->cfg.task == PDS_TASK_CIRCLE) ok = launch_rollout_hist_circle(h->flags, hn, grid, (hipStream_t)stream, ra);
-  else ok = launch_rollout_hist_takeoff(h->flags, hn, grid, (hipStream_t)stream, ra);
-  if (!ok) return fail(h, PDS_EHIP, "pds_rollout_history: rollout_hist_supported() and the launchers disagree");
-  PDS_HIP(h, hipGetLastError());
-  h->tick += (uint64_t)T;
-  return PDS_OK;
+  return launch_rollout(h, "pds_rollout_history", T, stream, [&](dim3 grid, hipStream_t s) {
+    if (h->cfg.task == PDS_TASK_HOVER) return launch_rollout_hist_hover(h->flags, hn, grid, s, ra);
+    if (h->cfg.task == PDS_TASK_CIRCLE) return launch_rollout_hist_circle(h->flags, hn, grid, s, ra);
+    return launch_rollout_hist_takeoff(h->flags, hn, grid, s, ra);
+  });
 }
 
+// number of envs whose dynamic state holds a NaN or an Inf (diagnostic, see pds_count_nonfinite)
 __global__ __launch_bounds__(256) void nonfinite_kernel(DevState st, long long n, unsigned long long *count) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   bool bad = false;

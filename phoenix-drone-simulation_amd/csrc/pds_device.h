@@ -178,6 +178,15 @@ PDS_DEV void box_muller(uint32_t a, uint32_t b, float &z0, float &z1) {
   z0 = r * __builtin_amdgcn_cosf(u2);
   z1 = r * __builtin_amdgcn_sinf(u2);
 }
+// The Gaussian policy's sampling, stated once for pds_gaussian_sample (csrc/pds_train.hip) and the network waves of the fused
+// rollouts (csrc/pds_rollout.h) -- as macros: the forced-inline functions tried in their place changed those kernels' schedules.
+// The Philox block behind action dimensions 4 block .. 4 block + 3 of sample `id` in call `call`:
+// counter = (sample id lo, sample id hi << 8 | block, call lo, call hi), key = seed
+#define PDS_GAUSSIAN_PHILOX(id, block, call, seed)                                                                      \
+  pds::philox4x32_10((uint32_t)(id), ((uint32_t)((id) >> 32) << 8) | (block), (uint32_t)(call), (uint32_t)((call) >> 32), \
+                     (uint32_t)(seed), (uint32_t)((seed) >> 32))
+// ... and one dimension's term of the log-probability at a = mu + sigma z: -(0.5 z^2 + log sigma + 0.5 log 2 pi)
+#define PDS_GAUSSIAN_LOGP_TERM(z, log_std) (-0.5f * (z) * (z) - (log_std) - 0.91893853320467274178f)
 
 // Per-step noise: ONE Philox word per Box-Muller pair -- radius from the high 20 bits (|z| <= 5.26),
 // angle from the low 12 bits (a 4096-point rule integrates the smooth periodic angle dependence of

@@ -16,7 +16,7 @@
 //           action into LDS, SIGNAL; then, while the env wave steps: the critic V(o(t)) and V(final_obs) of the envs that
 //           finished in step t - 1;
 //   E      (wave 4: the 64 envs of the tile in registers, step_once of csrc/pds_step.h -- the code path of pds_step /
-//           pds_step_k, same bits):        wait for the four action signals -> env.step -> o(t + 1), the finished
+//           pds_step_k, same bits):  wait for the four action signals -> env.step -> o(t + 1), the finished
 //           envs' last rows and flags into LDS, SIGNAL.
 // Only the actor is on the critical path of a step (action -> env step -> next observation); the critic, the TimeLimit
 // bootstrap V(final_obs) (algs/iwpg/iwpg.py:375-385), the action-noise draws of the NEXT step and all buffer writes of
@@ -91,6 +91,83 @@ PDS_DEV void rollout_post(int *flag, int lane) {  // +1, after every lane's LDS 
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   if (lane == 0) __hip_atomic_fetch_add(flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+
+// ---- the env wave's prologue, episode bookkeeping and epilogue, for both rollout kernels (PDS_NEXT_TICK: csrc/pds_step.h).  Macros
+// that expand to the statements the kernels had, over the kernels' own locals (a, ra, ix, t, active, T, lane; ep_ret, ep_len: running
+// return and length of this lane's env; st0-2: return, length and count of the episodes that finished): as forced-inline functions
+// over a struct the bookkeeping cost two Circle rollout_hist_kernels a VGPR (profiles/rollout_refactor_resources.txt). ----
+// The env state of tile `t` into registers, in front of the loop: declares cur, rk (the key of the current tick), parity, rk0 (the
+// key of the first tick, for advance_clock behind the loop) and S.
+#define PDS_ENV_WAVE_BEGIN                                                   \
+  Loaded cur;                                                                \
+  RngKey rk{a.seed_lo, a.seed_hi, 0u, 0u};                                   \
+  load_env<V>(a, ix, t, cur);                                                \
+  rk.tick_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.clk.x);     \
+  rk.tick_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.clk.y);     \
+  int parity = __builtin_amdgcn_readfirstlane((int)cur.clk.z) & 1;           \
+  const RngKey rk0 = rk;                                                     \
+  EnvState S;                                                                \
+  unpack_state<V>(a.k, cur, parity, S);                                      \
+  init_kept_obs<V>(a, rk, ix, S);
+// pds_rollout_record (csrc/pds_train.hip record_kernel) for this lane's env; declares dn: the env finished in this step
+#define PDS_RECORD_STEP(so)                                   \
+  const bool dn = (so.done || so.trunc) && active;            \
+  const float er = ep_ret + so.reward, el = ep_len + 1.f;     \
+  if (dn) { st0 += er; st1 += el; st2 += 1.f; }               \
+  ep_ret = dn ? 0.f : er;                                     \
+  ep_len = dn ? 0.f : el;
+// Behind the loop: state, running return / length and the tile's clock back to memory, the finished episodes' sums into
+// stats[0..2] (one atomic triple per tile).  RA: the kernel's argument struct, ID: its reload_args tag.
+#define PDS_ENV_WAVE_END(RA, ID)                                                                                              \
+  const RA &rl = *reinterpret_cast<const RA *>(&reload_args<ID, true>(ra.s, T));                                              \
+  if (active) {                                                                                                               \
+    store_state<V>(rl.s, ix, parity, S, true);                                                                                \
+    *at(rl.ep_ret, ix) = ep_ret;                                                                                              \
+    *at(rl.ep_len, ix) = ep_len;                                                                                              \
+  }                                                                                                                           \
+  advance_clock(rl.s.st.clk, t, rk0, parity, (uint32_t)T, lane);                                                              \
+  for (int d = 32; d >= 1; d >>= 1) { st0 += __shfl_xor(st0, d); st1 += __shfl_xor(st1, d); st2 += __shfl_xor(st2, d); }      \
+  if (lane == 0 && st2 != 0.f) {                                                                                              \
+    atomicAdd(rl.stats + 0, st0);                                                                                             \
+    atomicAdd(rl.stats + 1, st1);                                                                                             \
+    atomicAdd(rl.stats + 2, st2);                                                                                             \
+  }
+
+// ---- the network waves' sampling (both rollout kernels): ActorCritic.step's dist.sample() + log_prob().sum(-1), the
+// values of pds_gaussian_sample (csrc/pds_train.hip sample_kernel; draw and log-probability term: csrc/pds_device.h) ----
+// (Macros again: as forced-inline functions -- arrays by reference or a struct by value, either of the two alone -- they moved the
+// register allocation of every TakeOff rollout_hist_kernel, profiles/rollout_refactor_resources.txt.)
+// PDS_DRAW_ACTION_NOISE declares z[4] (standard normals; 0 where deterministic), lsd[4] = log_std and sig[4] = exp(log_std) of
+// the lanes with `live`.  The noise of step s depends on (env, call) only: drawn while the env wave is still stepping.
+#define PDS_DRAW_ACTION_NOISE(rl, live, call_, env, d_out)                                                    \
+  float z[4] = {0.f, 0.f, 0.f, 0.f}, sig[4], lsd[4];                                                          \
+  if (live) {                                                                                                 \
+    if (!rl.deterministic) {                                                                                  \
+      const unsigned long long gid = rl.s.env_id_base + (unsigned long long)env;                              \
+      const unsigned long long call = call_;                                                                  \
+      const U4 r = PDS_GAUSSIAN_PHILOX(gid, 0u, call, rl.seed);                                               \
+      box_muller(r.x, r.y, z[0], z[1]);                                                                       \
+      box_muller(r.z, r.w, z[2], z[3]);                                                                       \
+    }                                                                                                         \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                           \
+      lsd[q] = (q < d_out) ? rl.log_std[q] : 0.f;                                                             \
+      sig[q] = expf(lsd[q]);                                                                                  \
+    }                                                                                                         \
+  }
+// a = mu + sigma z and its log-probability: the action into the env wave's LDS slot, both into row `row` of the buffers
+#define PDS_EMIT_ACTION(rl, mu, d_out, slot, row, row_ok)                                                     \
+  do {                                                                                                        \
+    float av[4], lp = 0.f;                                                                                    \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                           \
+      av[q] = fmaf(sig[q], z[q], mu[q]);                                                                      \
+      if (q < d_out) lp += PDS_GAUSSIAN_LOGP_TERM(z[q], lsd[q]);                                              \
+    }                                                                                                         \
+    slot = make_float4(av[0], av[1], av[2], av[3]);                                                           \
+    if (row_ok) {                                                                                             \
+      *reinterpret_cast<float4 *>(rl.act_buf + (row) * 4) = make_float4(av[0], av[1], av[2], av[3]);          \
+      rl.logp_buf[row] = lp;                                                                                  \
+    }                                                                                                         \
+  } while (0)
 
 // TEAMS: tiles (= teams of 4 network waves + 1 env wave) per block.  One team per block is the latency form (8 192 envs:
 // 128 blocks on 256 CUs); with more tiles than CUs the network waves' idle time -- they work 5-9 of a step's 14 us -- is
@@ -176,16 +253,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void rollout_kernel(con
     const bool active = rem_ >= kWave || lane < (int)rem_;
     const Idx<V> ix{wave_base, active ? (uint32_t)lane : (uint32_t)rem_ - 1u};
     float *tile = tile_all[grp], *fin = fin_all[grp];
-    Loaded cur;
-    RngKey rk{a.seed_lo, a.seed_hi, 0u, 0u};
-    load_env<V>(a, ix, t, cur);
-    rk.tick_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.clk.x);
-    rk.tick_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.clk.y);
-    int parity = __builtin_amdgcn_readfirstlane((int)cur.clk.z) & 1;
-    const RngKey rk0 = rk;
-    EnvState S;
-    unpack_state<V>(a.k, cur, parity, S);
-    init_kept_obs<V>(a, rk, ix, S);
+    PDS_ENV_WAVE_BEGIN
     float ep_ret = *at(ra.ep_ret, ix), ep_len = *at(ra.ep_len, ix), st0 = 0.f, st1 = 0.f, st2 = 0.f;
     int qcount = 0;
 #ifdef PDS_ROLLOUT_TIMING
@@ -214,20 +282,15 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void rollout_kernel(con
 #endif
         step_once<V, kWave, RM, false>(rl.s, o1, rks, parity, nullptr, tile, nullptr, queue_all[grp], scratch_all[grp], lane_s,
                                        wave_base, ix, active, act, S, qcount, fin, &so PDS_STAMP_ARG);
-        parity ^= 1;
-        rk.tick_lo += 1u;
-        if (rk.tick_lo == 0u) rk.tick_hi += 1u;
-        // pds_rollout_record (csrc/pds_train.hip record_kernel)
-        const bool dn = (so.done || so.trunc) && active;
-        const float er = ep_ret + so.reward, el = ep_len + 1.f;
-        if (dn) { st0 += er; st1 += el; st2 += 1.f; }
-        ep_ret = dn ? 0.f : er;
-        ep_len = dn ? 0.f : el;
+        PDS_NEXT_TICK(rk, parity)
+        PDS_RECORD_STEP(so)
         // V(final_obs) is the bootstrap of an episode the TimeLimit cut (algs/iwpg/iwpg.py:374-379: also when it terminated
         // on the same step); one that only terminated bootstraps with 0 and pds_gae never reads its fval entry: only the
         // truncated envs ask the network waves for a pass (a young policy ends ~5 % of its episodes per step, nearly all of
         // them by termination).  The LAST step of the rollout hands over every finished env: a caller that mirrors the
         // reference's epoch-end cut (`epoch_ended` takes V(o) for a terminated path too; ppo.py reset_each_rollout) reads it.
+        // (`want` of rollout_hist_kernel is this rule, dn && (trunc || last step); each kernel keeps its wording: in the
+        //  other's, 20 of 24 Hover latency-ring kernels here and 12 of 16 Circle kernels there change their SGPR spills.)
         done_all[grp][lane] = ((so.trunc || (so.done && s == T - 1)) && active) ? 1u : 0u;
       }
 #ifdef PDS_ROLLOUT_TIMING
@@ -250,19 +313,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void rollout_kernel(con
     if (blockIdx.x == 0 && team == 0 && lane == 0) { ra.stats[8] = (float)tw / T; ra.stats[9] = (float)ts / T; ra.stats[10] = (float)tp / T;
       ra.stats[11] = (float)tph / T; ra.stats[12] = (float)tout / T; ra.stats[13] = (float)trst / T; ra.stats[14] = (float)tfin / T; ra.stats[15] = (float)tev / T; ra.stats[48] = (float)tfill / T; ra.stats[49] = (float)teval / T; }
 #endif
-    const RolloutArgs &rl = *reinterpret_cast<const RolloutArgs *>(&reload_args<202, true>(ra.s, T));
-    if (active) {
-      store_state<V>(rl.s, ix, parity, S, true);
-      *at(rl.ep_ret, ix) = ep_ret;
-      *at(rl.ep_len, ix) = ep_len;
-    }
-    advance_clock(rl.s.st.clk, t, rk0, parity, (uint32_t)T, lane);
-    for (int d = 32; d >= 1; d >>= 1) { st0 += __shfl_xor(st0, d); st1 += __shfl_xor(st1, d); st2 += __shfl_xor(st2, d); }
-    if (lane == 0 && st2 != 0.f) {
-      atomicAdd(rl.stats + 0, st0);
-      atomicAdd(rl.stats + 1, st1);
-      atomicAdd(rl.stats + 2, st2);
-    }
+    PDS_ENV_WAVE_END(RolloutArgs, 202)
     return;
   }
 
@@ -285,24 +336,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void rollout_kernel(con
     const RolloutArgs &rl = *reinterpret_cast<const RolloutArgs *>(&reload_args<203, true>(ra.s, s));
     const long long o1 = (long long)s * rl.s.n;
     f32x4 x_own[NIN], x_r0[NIN], f_own[NIN], f_r0[NIN];
-    // the action noise of step s depends on (env, call) only: drawn while the env wave is still stepping
-    // pds_gaussian_sample (csrc/pds_train.hip sample_kernel): counter = (sample id lo, id hi << 8 | block, call lo, call hi)
-    float z[4] = {0.f, 0.f, 0.f, 0.f}, sig[4], lsd[4];
-    if (s < T && g == 0) {
-      if (!rl.deterministic) {
-        const unsigned long long gid = rl.s.env_id_base + (unsigned long long)env_own;
-        const unsigned long long call = call0 + (unsigned long long)s + 1ull;
-        const U4 r = philox4x32_10((uint32_t)gid, ((uint32_t)(gid >> 32) << 8) | 0u, (uint32_t)call, (uint32_t)(call >> 32),
-                                   (uint32_t)rl.seed, (uint32_t)(rl.seed >> 32));
-        box_muller(r.x, r.y, z[0], z[1]);
-        box_muller(r.z, r.w, z[2], z[3]);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        lsd[q] = (q < d_out) ? rl.log_std[q] : 0.f;
-        sig[q] = expf(lsd[q]);
-      }
-    }
+    PDS_DRAW_ACTION_NOISE(rl, s < T && g == 0, call0 + (unsigned long long)s + 1ull, env_own, d_out)
 #ifdef PDS_ROLLOUT_TIMING
     const unsigned long long r0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -331,19 +365,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void rollout_kernel(con
     if (s < T) {
       if (!(PDS_ROLLOUT_SKIP & 1)) {
         const f32x4 mu = (rl.pi.activation == 0) ? forward16_shape<0, NIN>(wpi, rl.pi, x_own, n16, g) : forward16_shape<1, NIN>(wpi, rl.pi, x_own, n16, g);
-        if (g == 0) {  // lane n16 owns sample `own`: outputs 0..3 of the actor
-          float av[4], lp = 0.f;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            av[q] = fmaf(sig[q], z[q], mu[q]);
-            if (q < d_out) lp += -0.5f * z[q] * z[q] - lsd[q] - 0.91893853320467274178f;
-          }
-          act_all[j][own] = make_float4(av[0], av[1], av[2], av[3]);
-          if (own_ok) {
-            *reinterpret_cast<float4 *>(rl.act_buf + (o1 + env_own) * 4) = make_float4(av[0], av[1], av[2], av[3]);
-            rl.logp_buf[o1 + env_own] = lp;
-          }
-        }
+        if (g == 0) PDS_EMIT_ACTION(rl, mu, d_out, act_all[j][own], o1 + env_own, own_ok);  // lane n16 owns sample `own`: outputs 0..3 of the actor
       }
 #ifdef PDS_ROLLOUT_TIMING
       r3 = __builtin_amdgcn_s_memtime();

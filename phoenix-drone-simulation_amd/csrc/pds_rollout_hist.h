@@ -5,8 +5,9 @@
 // Rounds 2-5 ran such a rollout as 8 launches per step (critic, actor, sample, env step, pds_history_advance, V(final_obs),
 // record, + copies); csrc/pds_rollout.h -- the one-launch form for H = 2 -- keeps both networks' weights and the observation
 // tile in LDS, which at 160 inputs would take 233 KB.  Here:
-//   * the ACTOR, the sampling, the env step (step_once of csrc/pds_step.h: the code path of pds_step, same bits), the history
-//     update of pds_history_advance (csrc/pds_history.hip, same values) and the episode bookkeeping run in the kernel: one
+//   * the ACTOR, the sampling (PDS_DRAW_ACTION_NOISE / PDS_EMIT_ACTION of csrc/pds_rollout.h), the env step (step_once inside the
+//     prologue PDS_ENV_WAVE_BEGIN of csrc/pds_rollout.h), the history update of pds_history_advance
+//     (csrc/pds_history.hip, same values) and the episode bookkeeping (PDS_RECORD_STEP of csrc/pds_rollout.h) run in the kernel: one
 //     block per 64-env tile, four network waves (16 rows each, csrc/pds_mlp_fwd.h forward16_wide: the code path of
 //     pds_mlp_forward, same bits) + one env wave, hand-over through LDS counters as in csrc/pds_rollout.h;
 //   * the CRITIC does not: V(o(t)) for all t is one pds_mlp_forward over obs_buf after the kernel (it is off the step's
@@ -94,16 +95,7 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
     const long long wave_base = t * kWave;
     const bool active = rem0 >= kWave || lane < (int)rem0;
     const Idx<V> ix{wave_base, active ? (uint32_t)lane : (uint32_t)rem0 - 1u};
-    Loaded cur;
-    RngKey rk{a.seed_lo, a.seed_hi, 0u, 0u};
-    load_env<V>(a, ix, t, cur);
-    rk.tick_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.clk.x);
-    rk.tick_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.clk.y);
-    int parity = __builtin_amdgcn_readfirstlane((int)cur.clk.z) & 1;
-    const RngKey rk0 = rk;
-    EnvState S;
-    unpack_state<V>(a.k, cur, parity, S);
-    init_kept_obs<V>(a, rk, ix, S);
+    PDS_ENV_WAVE_BEGIN
     float ep_ret = *at(ra.ep_ret, ix), ep_len = *at(ra.ep_len, ix), st0 = 0.f, st1 = 0.f, st2 = 0.f;
     int qcount = 0, nfin = 0;
     float *hrow = hist + lane * S1;
@@ -111,22 +103,15 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
       const RolloutHistArgs &rl = *reinterpret_cast<const RolloutHistArgs *>(&reload_args<211, true>(ra.s, s));
       const long long o1 = (long long)s * rl.s.n;
       rollout_wait_ge(&act_ready, kRolloutMlpWaves * (s + 1));  // the network waves have read the histories and written a(s)
-      RngKey rks = rk;
+      RngKey rks = rk;  // (opaque per-iteration copies: see step_k_kernel)
       int lane_s = lane;
       if (PDS_STEPK_OPAQUE_KEY) asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
       const float4 act = act_all[lane_s];
       StepOut so;
       step_once<V, kWave, RM, false>(rl.s, o1, rks, parity, nullptr, tile, nullptr, queue, scratch, lane_s, wave_base, ix, active, act, S,
                                      qcount, fin, &so PDS_STAMP_ARG);
-      parity ^= 1;
-      rk.tick_lo += 1u;
-      if (rk.tick_lo == 0u) rk.tick_hi += 1u;
-      // pds_rollout_record (csrc/pds_train.hip record_kernel)
-      const bool dn = (so.done || so.trunc) && active;
-      const float er = ep_ret + so.reward, el = ep_len + 1.f;
-      if (dn) { st0 += er; st1 += el; st2 += 1.f; }
-      ep_ret = dn ? 0.f : er;
-      ep_len = dn ? 0.f : el;
+      PDS_NEXT_TICK(rk, parity)
+      PDS_RECORD_STEP(so)
       // pds_history_advance (csrc/pds_history.hip), this lane's own row: shift by one half, append the newest half -- of the
       // env's LAST observation where it finished (`fin`: the row that goes to final_obs), of the step's row otherwise
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -165,7 +150,8 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
         for (int c = 0; c < HALF; ++c) hrow[keep + c] = nb[c];
       }
       // the final history of an env the TimeLimit cut bootstraps its path with V (also when it terminated on that step, and
-      // for every env that finished on the rollout's last step: algs/iwpg/iwpg.py:374-379) -> the caller's slot list
+      // for every env that finished on the rollout's last step: algs/iwpg/iwpg.py:374-379; the rule behind done_all[] of
+      // rollout_kernel, where the reason for the two wordings is) -> the caller's slot list
       const bool want = dn && (so.trunc || s == T - 1);
       unsigned long long wm = __ballot(want);
       if (wm != 0ull) {  // wave-uniform, rare
@@ -239,19 +225,7 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
       }
       rollout_post(&obs_ready, lane);  // the histories of step s + 1 are in LDS
     }
-    const RolloutHistArgs &rl = *reinterpret_cast<const RolloutHistArgs *>(&reload_args<212, true>(ra.s, T));
-    if (active) {
-      store_state<V>(rl.s, ix, parity, S, true);
-      *at(rl.ep_ret, ix) = ep_ret;
-      *at(rl.ep_len, ix) = ep_len;
-    }
-    advance_clock(rl.s.st.clk, t, rk0, parity, (uint32_t)T, lane);
-    for (int d = 32; d >= 1; d >>= 1) { st0 += __shfl_xor(st0, d); st1 += __shfl_xor(st1, d); st2 += __shfl_xor(st2, d); }
-    if (lane == 0 && st2 != 0.f) {
-      atomicAdd(rl.stats + 0, st0);
-      atomicAdd(rl.stats + 1, st1);
-      atomicAdd(rl.stats + 2, st2);
-    }
+    PDS_ENV_WAVE_END(RolloutHistArgs, 212)
     return;
   }
 
@@ -263,43 +237,14 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
     const RolloutHistArgs &rl = *reinterpret_cast<const RolloutHistArgs *>(&reload_args<213, true>(ra.s, s));
     const long long o1 = (long long)s * rl.s.n;
     f32x4 x_own[HN];
-    // the action noise of step s depends on (env, call) only: drawn while the env wave is still stepping
-    // pds_gaussian_sample (csrc/pds_train.hip sample_kernel): counter = (sample id lo, id hi << 8 | block, call lo, call hi)
-    float z[4] = {0.f, 0.f, 0.f, 0.f}, sig[4], lsd[4];
-    if (g == 0) {
-      if (!rl.deterministic) {
-        const unsigned long long gid = rl.s.env_id_base + (unsigned long long)env_own;
-        const unsigned long long call = call0 + (unsigned long long)s + 1ull;
-        const U4 r = philox4x32_10((uint32_t)gid, ((uint32_t)(gid >> 32) << 8) | 0u, (uint32_t)call, (uint32_t)(call >> 32),
-                                   (uint32_t)rl.seed, (uint32_t)(rl.seed >> 32));
-        box_muller(r.x, r.y, z[0], z[1]);
-        box_muller(r.z, r.w, z[2], z[3]);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        lsd[q] = (q < d_out) ? rl.log_std[q] : 0.f;
-        sig[q] = expf(lsd[q]);
-      }
-    }
+    PDS_DRAW_ACTION_NOISE(rl, g == 0, call0 + (unsigned long long)s + 1ull, env_own, d_out)
     rollout_wait_ge(&obs_ready, s);  // the histories of step s are in LDS
     gather_hist<HN>(hist + own * S1, HS, mus, iss, g, x_own);
     const bool kh2 = rl.pi.h1 == rl.pi.h2 && last_tile_steps(rl.pi.h1, kNT) == 2;
     f32x4 mu;
     if (rl.pi.activation == 0) mu = kh2 ? forward16_wide<0, HN, S1, 2>(wpi, x_own, n16, g) : forward16_wide<0, HN, S1, 4>(wpi, x_own, n16, g);
     else mu = kh2 ? forward16_wide<1, HN, S1, 2>(wpi, x_own, n16, g) : forward16_wide<1, HN, S1, 4>(wpi, x_own, n16, g);
-    if (g == 0) {  // lane n16 owns sample `own`: outputs 0..3 of the actor
-      float av[4], lp = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        av[q] = fmaf(sig[q], z[q], mu[q]);
-        if (q < d_out) lp += -0.5f * z[q] * z[q] - lsd[q] - 0.91893853320467274178f;
-      }
-      act_all[own] = make_float4(av[0], av[1], av[2], av[3]);
-      if (own_ok) {
-        *reinterpret_cast<float4 *>(rl.act_buf + (o1 + env_own) * 4) = make_float4(av[0], av[1], av[2], av[3]);
-        rl.logp_buf[o1 + env_own] = lp;
-      }
-    }
+    if (g == 0) PDS_EMIT_ACTION(rl, mu, d_out, act_all[own], o1 + env_own, own_ok);  // lane n16 owns sample `own`: outputs 0..3 of the actor
     rollout_post(&act_ready, lane);  // this wave is done with the histories of step s
   }
 }

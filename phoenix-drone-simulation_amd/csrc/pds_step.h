@@ -1071,6 +1071,21 @@ PDS_DEV void prefetch_kernargs() {
 #define PDS_STAMP_FLUSH do { } while (0)
 #endif
 
+// ---- shared by the kernels that step a tile whose clock word they have loaded: step_kernel, step_k_kernel and, with the
+// prologue and episode macros of csrc/pds_rollout.h, the env waves of rollout_kernel and rollout_hist_kernel.  Macros that
+// expand to the statements the kernels had: as forced-inline functions (clock_to_key + env_loop_begin, next_tick) each of them
+// alone moved the SGPR spills of the most loaded step_k_kernel or rollout_kernel (profiles/rollout_refactor_resources.txt). ----
+// The tile's clock word -> the tick of the Philox key and the parity of the state ring (wave-uniform: SGPRs).
+#define PDS_CLOCK_TO_KEY(clk, rk, parity)                                  \
+  rk.tick_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)clk.x);       \
+  rk.tick_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)clk.y);       \
+  parity = __builtin_amdgcn_readfirstlane((int)clk.z) & 1;
+// one env step further: the other half of the state ring, the 64-bit tick + 1
+#define PDS_NEXT_TICK(rk, parity) \
+  parity ^= 1;                    \
+  rk.tick_lo += 1u;               \
+  if (rk.tick_lo == 0u) rk.tick_hi += 1u;
+
 // One 64-env tile per wave, one block per 4 tiles, no tile loop.  Round 3 re-tried persistent waves (at most the
 // resident number of blocks, each wave walking over several tiles with a static XCD-aware schedule; the kernel
 // arguments re-read per tile through reload_args(), so the loop no longer costs SGPR spills as it did in rounds 1-2):
@@ -1095,9 +1110,7 @@ __global__ __launch_bounds__(kBlock, (PDS_MIN_WAVES) * (256 / kBlock)) void step
   PDS_STAMP_WAIT(2);
   RngKey rk{a.seed_lo, a.seed_hi, 0u, 0u};
   int parity;
-  rk.tick_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.clk.x);
-  rk.tick_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.clk.y);
-  parity = __builtin_amdgcn_readfirstlane((int)cur.clk.z) & 1;
+  PDS_CLOCK_TO_KEY(cur.clk, rk, parity)
   EnvState S;
   unpack_state<V>(a.k, cur, parity, S);
   init_kept_obs<V>(a, rk, ix, S);
@@ -1145,9 +1158,7 @@ __global__ __launch_bounds__(kBlock, (PDS_STEPK_MIN_WAVES_OF(V_)) * (256 / kBloc
   load_env<W>(a, ix, t, cur);
   RngKey rk{a.seed_lo, a.seed_hi, 0u, 0u};
   int parity;
-  rk.tick_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.clk.x);
-  rk.tick_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.clk.y);
-  parity = __builtin_amdgcn_readfirstlane((int)cur.clk.z) & 1;
+  PDS_CLOCK_TO_KEY(cur.clk, rk, parity)
   const RngKey rk0 = rk;
   EnvState S;
   unpack_state<W>(a.k, cur, parity, S);
@@ -1159,7 +1170,9 @@ __global__ __launch_bounds__(kBlock, (PDS_STEPK_MIN_WAVES_OF(V_)) * (256 / kBloc
     // a fresh view of the kernel arguments per iteration: what the loop body needs is re-read (scalar-cache
     // hits) instead of being hoisted out of the loop into SGPRs that do not exist (41-79 spills in round 2)
     const StepArgs &al = reload_args<106, PDS_STEPK_OPAQUE_KEY || heavy_variant<W>()>(a, s);
-    // ... and the Philox key: the 2 x 10 round keys (seed + r x Weyl constant) are loop-invariant, so the compiler forms
+    // ... and the Philox key (the env waves of both rollout kernels make the same two copies, in one statement; as one
+    // forced-inline function for the three kernels, in either form, they moved registers: profiles/rollout_refactor_resources.txt):
+    // the 2 x 10 round keys (seed + r x Weyl constant) are loop-invariant, so the compiler forms
     // them in the loop header and -- with the 102 SGPRs taken -- spills them to VGPR lanes there and reads them back in
     // every round of every Philox call of every iteration (2-45 spilled SGPRs per step_k kernel in round 3).  An opaque
     // copy of the seed per iteration makes the schedule part of the iteration: ~20 scalar adds, live only where used.
@@ -1173,9 +1186,7 @@ __global__ __launch_bounds__(kBlock, (PDS_STEPK_MIN_WAVES_OF(V_)) * (256 / kBloc
     if (s + 1 < K) act_next = nt_load4(at(al.actions + (long long)(s + 1) * al.n, ix));  // in flight during step s
     step_once<W, TR, RM, false>(al, (long long)s * al.n, rks, parity, ref_lds, tile, park, queue, scratch, lane_s, wave_base, ix, active, act, S, qcount, nullptr, nullptr PDS_STAMP_ARG);
     act = act_next;
-    parity ^= 1;
-    rk.tick_lo += 1u;
-    if (rk.tick_lo == 0u) rk.tick_hi += 1u;
+    PDS_NEXT_TICK(rk, parity)
   }
   const StepArgs &az = reload_args<107, heavy_variant<W>()>(a);
   if (active) store_state<W>(az, ix, parity, S, true);

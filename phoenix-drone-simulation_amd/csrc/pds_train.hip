@@ -28,9 +28,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float *mu, const floa
   if (!deterministic) {
     const unsigned long long gid = id_base + (unsigned long long)i;
     for (int b = 0; b * 4 < d; ++b) {
-      // counter = (sample id lo, sample id hi << 8 | block, call lo, call hi), key = seed
-      const pds::U4 r = pds::philox4x32_10((uint32_t)gid, ((uint32_t)(gid >> 32) << 8) | (uint32_t)b, (uint32_t)call,
-                                           (uint32_t)(call >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
+      const pds::U4 r = PDS_GAUSSIAN_PHILOX(gid, (uint32_t)b, call, seed);
       pds::box_muller(r.x, r.y, z[4 * b], z[4 * b + 1]);
       pds::box_muller(r.z, r.w, z[4 * b + 2], z[4 * b + 3]);
     }
@@ -39,7 +37,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float *mu, const floa
   for (int j = 0; j < d; ++j) {
     const float ls = log_std[j];
     act[i * d + j] = fmaf(expf(ls), z[j], mu[i * d + j]);
-    lp += -0.5f * z[j] * z[j] - ls - 0.91893853320467274178f;
+    lp += PDS_GAUSSIAN_LOGP_TERM(z[j], ls);
   }
   logp[i] = lp;
 }
