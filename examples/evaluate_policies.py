@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Score a set of trained checkpoints: every run directory's actor flies E episodes, all actors of one shape in ONE launch.
+
+A run directory is what PPOTrainer.save_checkpoint and the reference's logger leave behind: `torch_save/model.pt` (the
+ActorCritic state_dict) and, optionally, `config.json` (`ac_kwargs.pi.activation` / `hidden_sizes`, `env_id`).  The
+directories are grouped by actor shape (inputs, hidden sizes, activation); each group is one PolicyPopulation and one call of
+evaluate_population (the evaluation loop of the reference's utils/evaluation.py, for the whole group at once).
+
+  python examples/evaluate_policies.py runs/*/seed_*              # prints mean return, length and cost per checkpoint
+  python examples/evaluate_policies.py runs/ --episodes 256 --env DroneCircleSimpleEnv-v0 --log-dir eval_out
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import phoenix_drone_simulation_amd as pds  # noqa: E402
+from phoenix_drone_simulation_amd.evaluation import PolicyPopulation, evaluate_population  # noqa: E402
+from phoenix_drone_simulation_amd.ppo import ActorCritic  # noqa: E402
+
+
+def find_run_dirs(paths):
+    """every directory under `paths` that holds torch_save/model.pt, sorted"""
+    found = []
+    for path in paths:
+        for root, _, _ in os.walk(path):
+            if os.path.isfile(os.path.join(root, "torch_save", "model.pt")):
+                found.append(root)
+    return sorted(set(found))
+
+
+def load_run(run_dir):
+    """-> (ActorCritic, env id or None).  The activation is not in the state_dict: config.json names it (default relu)."""
+    conf = {}
+    conf_path = os.path.join(run_dir, "config.json")
+    if os.path.isfile(conf_path):
+        with open(conf_path) as f:
+            conf = json.load(f)
+    kw = conf.get("ac_kwargs", {})
+    sd = torch.load(os.path.join(run_dir, "torch_save", "model.pt"), map_location="cpu")
+    ac = ActorCritic.from_reference_state_dict(sd, pi_activation=kw.get("pi", {}).get("activation", "relu"),
+                                               val_activation=kw.get("val", {}).get("activation", "tanh"))
+    want = kw.get("pi", {}).get("hidden_sizes")
+    have = tuple(l.out_features for l in ac.pi.net if isinstance(l, torch.nn.Linear))[:-1]
+    if want is not None and tuple(want) != have:
+        raise ValueError(f"{run_dir}: config.json says hidden_sizes {tuple(want)}, model.pt holds {have}")
+    return ac, conf.get("env_id")
+
+
+def group_by_shape(runs):
+    """{(d_in, hidden sizes, activation, with standardisation): [(run_dir, ActorCritic), ...]}"""
+    groups = {}
+    for run_dir, ac in runs:
+        lin = [l for l in ac.pi.net if isinstance(l, torch.nn.Linear)]
+        act = type(ac.pi.net[1]).__name__.lower()
+        key = (lin[0].in_features, tuple(l.out_features for l in lin[:-1]), act, ac.obs_oms is not None)
+        groups.setdefault(key, []).append((run_dir, ac))
+    return groups
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("paths", nargs="+", help="run directories, or directories to search for them")
+    ap.add_argument("--env", default=None, help="env id (default: config.json's env_id, else DroneHoverSimpleEnv-v0)")
+    ap.add_argument("--episodes", type=int, default=128, help="episodes per checkpoint, a multiple of 64")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--fused", default="auto", choices=["auto", "on", "off"])
+    ap.add_argument("--log-dir", default=None, help="write returns.csv / costs.csv per checkpoint under <log-dir>/<group>/<p>/")
+    args = ap.parse_args()
+    fused = {"auto": "auto", "on": True, "off": False}[args.fused]
+
+    loaded = [(d, *load_run(d)) for d in find_run_dirs(args.paths)]
+    if not loaded:
+        sys.exit("no run directory with torch_save/model.pt under " + ", ".join(args.paths))
+    env_ids = {e for _, _, e in loaded if e}
+    env_id = args.env or (env_ids.pop() if len(env_ids) == 1 else "DroneHoverSimpleEnv-v0")
+    groups = group_by_shape([(d, ac) for d, ac, _ in loaded])
+    print(f"{len(loaded)} checkpoints in {len(groups)} group(s) on {env_id}, {args.episodes} episodes each")
+    for gi, (key, members) in enumerate(sorted(groups.items(), key=lambda kv: str(kv[0]))):
+        d_in, hidden, act, _ = key
+        pop = PolicyPopulation.from_actor_critics([ac for _, ac in members])
+        env = pds.make(env_id, num_envs=pop.P * args.episodes, seed=args.seed)
+        if env.obs_dim != d_in:
+            print(f"group {gi} {key}: the actors read {d_in} inputs, {env_id} observes {env.obs_dim}: skipped")
+            env.close()
+            continue
+        ret, length, cost = evaluate_population(env, pop, fused=fused,
+                                                log_dir=os.path.join(args.log_dir, str(gi)) if args.log_dir else None)
+        env.close()
+        print(f"group {gi}: {d_in} -> {hidden} -> 4, {act}; {pop.P} checkpoint(s)")
+        for p, (run_dir, _) in enumerate(members):
+            print(f"  {run_dir}: return {float(ret[p].mean()):9.3f} +- {float(ret[p].std()):7.3f}   "
+                  f"length {float(length[p].mean()):6.1f}   cost {float(cost[p].mean()):7.2f}")
+
+
+if __name__ == "__main__":
+    main()

@@ -379,6 +379,33 @@ int pds_rollout_history(pds_handle *h, int T, int history, const pds_mlp *pi, co
                         uint8_t *d_term_buf, uint8_t *d_trunc_buf, float *d_cost_buf, float *d_fin_rows, int32_t *d_fin_step,
                         int slots, float *d_ep_ret, float *d_ep_len, float *d_stats, void *stream);
 
+/* ONE launch evaluates a POPULATION of policies (csrc/pds_evaluate.h): the evaluation loop of the reference
+ * (EnvironmentEvaluator.eval / eval_once, utils/evaluation.py:52-107: reset, act deterministically until terminated or truncated,
+ * sum reward and info['cost']; ActorCritic.step in eval mode, algs/core.py:370-393) for P policies x E = episodes_per_policy
+ * episodes.  The handle's N = P x E envs are P contiguous blocks of E envs (E a multiple of 64); block p flies policy p with
+ * action = actor mean.  Every env plays ONE episode from the observation it holds on entry (d_obs0 [N, D]: what pds_reset
+ * returned): return, length and cost accumulate in registers, freeze at the env's first terminated | truncated (the env itself
+ * is reset in place and flies on, as under a per-step loop) and go to d_ret, d_len, d_cost [N] -- the only outputs; episodes
+ * still running after max_steps steps are cut there.  Bitwise what max_steps x (pds_mlp_forward per policy + pds_step) and the
+ * same sums in the same order give.
+ *   shape     d_in = D, h1, h2 <= 64, d_out = 4, activation of EVERY policy; its pointers are ignored
+ *   d_params  [P, pds_mlp_param_count(shape)]: row p = W1 b1 W2 b2 W3 b3 of policy p, torch order
+ *   d_mean, d_std [P, D] (both or none), eps: (o - mean[p]) / (std[p] + eps) in front of policy p (OnlineMeanStd.forward)
+ * PDS_EINVAL: a NULL pointer, P x episodes_per_policy != num_envs, episodes_per_policy not a multiple of 64, a wrong network
+ * shape, max_steps < 1, a handle that was never reset.  PDS_EUNSUPPORTED: a handle without auto_reset, or an env
+ * configuration pds_rollout is not built for (pds_evaluate_supported says so beforehand: 1 / 0).  A refused call leaves the
+ * handle as it was.  After a successful call the tick and every tile's device clock are max_steps further -- also for a tile
+ * that stopped early: a tile stops once none of its 64 envs is in its first episode -- and the handle is back in the "not
+ * reset" state: tiles stopped at different steps, so pds_step, pds_rollout and the rest answer PDS_EINVAL "before pds_reset"
+ * until pds_reset has run for EVERY env: a pds_reset with a mask is refused (PDS_EINVAL) until then, and an edit of a state
+ * field (pds_set_state) does not lift the state either.  The parity of the state ring (which slot holds the last action) is
+ * the same in every tile afterwards, as after max_steps steps.  Asynchronous on `stream`; the first call on a handle allocates 16 N bytes that the steps' per-step
+ * outputs stream into. */
+int pds_evaluate_supported(const pds_handle *h);
+int pds_evaluate_policies(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape, const float *d_params,
+                          const float *d_mean, const float *d_std, float eps, int max_steps, const float *d_obs0, float *d_ret,
+                          float *d_len, float *d_cost, void *stream);
+
 /* number of parameters; flat gradient layout = [W1, b1, W2, b2, W3, b3] (torch parameter order) */
 int pds_mlp_param_count(const pds_mlp *m);
 /* floats of scratch the *_grad entry points need (per-wave partial sums) */

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "pds_reset.h"  // (pds_types.h + regen_kept_obs for pds_get_state)
+#include "pds_evaluate_args.h"
 #include "pds_simopt.h"
 
 namespace pds {
@@ -251,10 +252,12 @@ struct pds_handle {
   float4 *lat_buf;  // [PDS_MAX_LATENCY_STEPS][N] delayed-action ring, allocated when latency is first enabled
   unsigned long long *d_count;  // pds_count_nonfinite result word (in the slab)
   unsigned long long *d_stamps;  // diagnostic builds: pds_debug_stamps
+  void *eval_sink;  // 16 N bytes: the [N] reward, cost (float), term, trunc (u8) rows the steps of pds_evaluate_policies stream into, allocated by its first call
   int obs_dim;
   int num_cus;    // hipDeviceProp.multiProcessorCount (256 on MI355X): drives the half-tile rule
   uint64_t tick;  // host mirror of the device clock words (pds_sync_tick refreshes it)
   bool was_reset;
+  bool after_evaluate;  // pds_evaluate_policies ran and no unmasked reset since: every tile stopped at a step of its own
   int stored_from_agg;  // (set in pds_create) aggregate_phy_steps from which pds_step keeps the noisy observation in memory
   bool split_reset;   // pds_step launches the SplitReset form + post_reset_kernel where the variant has one (PDS_SPLIT_RESET != 0)
   bool stored_ready;  // kLaunchStepStored handles: the one materialize_oh_kernel pass in front of their first step is done
@@ -633,6 +636,7 @@ extern "C" int pds_destroy(pds_handle *h) {
   if (h->slab) (void)hipFree(h->slab);
   if (h->lat_buf) (void)hipFree(h->lat_buf);
   if (h->d_stamps) (void)hipFree(h->d_stamps);
+  if (h->eval_sink) (void)hipFree(h->eval_sink);
   delete h;
   return PDS_OK;
 }
@@ -830,6 +834,9 @@ static int do_reset(pds_handle *h, const uint8_t *d_mask, const float *d_samples
   if (!h) return PDS_EINVAL;
   DeviceGuard guard(h->cfg.device);
   PDS_HIP(h, guard.err);
+  // the envs outside a mask would keep what pds_evaluate_policies left: tiles that stopped at different steps
+  if (d_mask != nullptr && h->after_evaluate)
+    return fail(h, PDS_EINVAL, "pds_reset with a mask after pds_evaluate_policies: reset every env first (d_mask = NULL)");
   StepArgs a;
   base_args(h, a);
   a.mask = d_mask; a.samples = d_samples; a.obs = d_obs;
@@ -840,6 +847,7 @@ static int do_reset(pds_handle *h, const uint8_t *d_mask, const float *d_samples
   PDS_HIP(h, hipGetLastError());
   h->tick += 1;
   h->was_reset = true;
+  h->after_evaluate = false;
   return PDS_OK;
 }
 
@@ -1100,6 +1108,72 @@ extern "C" int pds_rollout_history(pds_handle *h, int T, int history, const pds_
   });
 }
 
+// whether pds_evaluate_policies has a kernel for this handle (the two PDS_EUNSUPPORTED conditions of check_rollout_call and below)
+extern "C" int pds_evaluate_supported(const pds_handle *h) {
+  if (!h) return PDS_EINVAL;
+  return h->cfg.auto_reset && rollout_supported(h->cfg.task, h->flags) ? 1 : 0;
+}
+
+// P policies x E episodes in one launch: csrc/pds_evaluate.h (the caller's evaluation loop, utils/evaluation.py:52-107).
+extern "C" int pds_evaluate_policies(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                                     const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                                     const float *d_obs0, float *d_ret, float *d_len, float *d_cost, void *stream) {
+  if (!h) return PDS_EINVAL;
+  const char *fn = "pds_evaluate_policies";
+  if (max_steps < 1) return fail(h, PDS_EINVAL, "%s: max_steps %d", fn, max_steps);
+  const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost;
+  if (const int rc = check_rollout_call(h, fn, any_null, d_mean, d_std)) return rc;
+  const long long n = h->cfg.num_envs;
+  if (P < 1 || episodes_per_policy < 1 || episodes_per_policy > n || P > n || P * episodes_per_policy != n)
+    return fail(h, PDS_EINVAL, "%s: P %lld x episodes_per_policy %lld is not the handle's %lld envs", fn, (long long)P,
+                (long long)episodes_per_policy, n);
+  if (episodes_per_policy % kWave != 0)
+    return fail(h, PDS_EINVAL, "%s: episodes_per_policy %lld is not a multiple of %d (one tile)", fn, (long long)episodes_per_policy, kWave);
+  const int D = h->obs_dim;
+  if (shape->d_in != D || shape->h1 < 1 || shape->h1 > 64 || shape->h2 < 1 || shape->h2 > 64 || shape->d_out != 4 ||
+      (shape->activation != 0 && shape->activation != 1))
+    return fail(h, PDS_EINVAL, "%s: network shape (d_in must be the observation width %d, hidden <= 64, d_out 4, activation 0 or 1)", fn, D);
+  if (!rollout_supported(h->cfg.task, h->flags))
+    return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: what pds_rollout is built for) -- "
+                                     "pds_mlp_forward + pds_step give the same bits", fn);
+  DeviceGuard guard(h->cfg.device);
+  PDS_HIP(h, guard.err);
+  // 16 N bytes: load_env reads an action quad per env through StepArgs::actions (unused here); the outcome streams take 10 N of them
+  if (!h->eval_sink) {
+    if (hipMalloc(&h->eval_sink, (size_t)n * 16) != hipSuccess) {
+      h->eval_sink = nullptr;
+      (void)hipGetLastError();
+      return fail(h, PDS_ENOMEM, "%s: %lld bytes for the per-step sink row", fn, n * 16);
+    }
+    PDS_HIP(h, hipMemsetAsync(h->eval_sink, 0, (size_t)n * 16, (hipStream_t)stream));  // (no uninitialised read in load_env)
+  }
+  EvalArgs ea;
+  memset(&ea, 0, sizeof(ea));
+  base_args(h, ea.s);
+  ea.s.actions = reinterpret_cast<const float4 *>(h->eval_sink);  // (load_env's action slot: valid memory, value unused)
+  ea.s.reward = reinterpret_cast<float *>(h->eval_sink);
+  ea.s.cost = ea.s.reward + n;
+  ea.s.term = reinterpret_cast<uint8_t *>(ea.s.cost + n);
+  ea.s.trunc = ea.s.term + n;
+  ea.s.k_steps = max_steps;
+  ea.shape = *shape;
+  ea.params = d_params;
+  ea.param_count = pds_mlp_param_count(shape);
+  ea.mean = d_mean; ea.stdv = d_std; ea.eps = eps;
+  ea.tiles_per_policy = (int)(episodes_per_policy / kWave);
+  ea.T = max_steps;
+  ea.obs0 = d_obs0;
+  ea.ret = d_ret; ea.len = d_len; ea.cost = d_cost;
+  const int rc = launch_rollout(h, fn, max_steps, stream, [&](dim3 grid, hipStream_t s) {
+    if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hover(h->flags, grid, s, ea);
+    if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_circle(h->flags, grid, s, ea);
+    return launch_evaluate_takeoff(h->flags, grid, s, ea);
+  });
+  // tiles stopped at different steps: not a state to continue from -- every stepping entry point asks for pds_reset first
+  if (rc == PDS_OK) { h->was_reset = false; h->after_evaluate = true; }
+  return rc;
+}
+
 // number of envs whose dynamic state holds a NaN or an Inf (diagnostic, see pds_count_nonfinite)
 __global__ __launch_bounds__(256) void nonfinite_kernel(DevState st, long long n, unsigned long long *count) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1133,7 +1207,7 @@ static int do_field(pds_handle *h, int field, void *d_ptr, int set, void *stream
   const dim3 grid((unsigned)((a.n + kBlock - 1) / kBlock));
   hipLaunchKernelGGL(field_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
   PDS_HIP(h, hipGetLastError());
-  if (set) h->was_reset = true;
+  if (set && !h->after_evaluate) h->was_reset = true;  // (an edit does not mend what an evaluation left: only a reset does)
   return PDS_OK;
 }
 

@@ -1,0 +1,297 @@
+// pds_evaluate.h -- ONE launch evaluates a POPULATION of policies (gfx950): P policies fly E episodes each,
+//     o -> standardise(p) -> actor(p) mean -> env.step(a) -> return, length, cost of the episode
+// of the caller's evaluation loop (utils/evaluation.py:52-107, EnvironmentEvaluator.eval_once: act deterministically until
+// terminated or truncated, sum reward and info['cost']; ActorCritic.step in eval mode, algs/core.py:370-393).  It is the
+// evaluation counterpart of rollout_kernel (csrc/pds_rollout.h) and keeps its wave roles -- four network waves on
+// forward16_shape (csrc/pds_mlp_fwd.h: the code path of pds_mlp_forward, same bits), one env wave on step_once (csrc/pds_step.h:
+// the code path of pds_step, same bits), LDS counters between them -- without what an evaluation does not need: no critic
+// image and no critic pass, no V(final_obs) and no `fin` rows, no action noise and no log-probability, no [T, N] buffer.
+//
+// The policy is per TILE, not per launch: the N = P x E envs are P contiguous blocks of E envs (E a multiple of 64), tile t
+// belongs to policy p = t / (E / 64) and stages that policy's six tensors from row p of the flat [P, param_count] block and its
+// standardisation from row p of the [P, D] mean / std.  Two teams of a block may fly different policies, so each team has its own
+// weight image and its own mus / iss (the critic's LDS pays for the second image): per team 39 744 B of weights + 512 B of
+// statistics + the observation tile (8.7-13.3 KB) + 1 KB of actions + the reset scratch: 52.9-55.9 KB per team, 105.9-111.8 KB for
+// two -- of the CU's 160 KB, below the two-team rollout_kernel's 123-134 KB (profiles/evaluate_kernel_resources.txt has the compiler's figure per kernel).
+//
+// Return, length and cost of an env accumulate in the env wave's registers and freeze at the env's first `terminated |
+// truncated` (the env itself goes on: auto-reset in place, as under the composed loop).  A tile STOPS once none of its 64 lanes
+// is still in its first episode -- a population holds many policies that fall within 50-150 of the 500 steps.
+//
+// Hand-over (rollout_wait_ge / rollout_post of csrc/pds_rollout.h; all five waves of a team are resident together):
+//   act_ready: +1 per network wave and step, after the wave has read o(s) and written its 16 actions of step s.  The env wave
+//              waits for 4 (s + 1) in front of step s.
+//   obs_ready: posted ONCE by the env wave at the end of every iteration s, after o(s + 1) is in the tile: +1 when it will run
+//              step s + 1, + kEvalStop when it will not (no lane in its first episode, or s + 1 == T).  After iteration s the
+//              counter is therefore either s + 1 or >= kEvalStop, never anything else, and the one atomic add makes the
+//              decision and the signal the same event.
+//   A network wave waits for obs_ready >= s in front of step s and looks at the value that ended its wait: s (the env wave
+//   will wait for this step's actions: compute and post them) or >= kEvalStop (it will not: leave).  So every wait has its post:
+//   the env wave only waits for actions of a step it announced with +1, the network waves only wait for an iteration's end, and
+//   the env wave ends EVERY iteration it starts with a post and its last one with the stop.  No wave waits for a signal that never
+//   comes; the env wave never waits after its stop, so the team drains without it.  Teams share no counter: one team of a block
+//   leaves while the other flies on (there is no block barrier behind the prologue).
+//   LDS images: the tile is written by the env wave between its act_ready wait and its obs_ready post, and read by the network
+//   waves between their obs_ready wait and their act_ready post; the action slots the other way round.
+//
+// The cost of a step: StepOut carries reward and flags only, and step_once stores the cost through StepArgs::cost like every
+// per-step stream.  The env wave reads its own lane's word back from the sink row BEHIND its post (same lane, same address:
+// program order), so the round trip runs while the network waves compute, and adds it in front of the next step.
+#pragma once
+#include "pds_evaluate_args.h"
+#include "pds_rollout.h"
+
+namespace pds {
+
+constexpr int kEvalStop = 1 << 30;  // added to obs_ready instead of 1: the env wave has left
+
+// rollout_wait_ge that also says what it saw
+PDS_DEV int eval_wait_ge(int *flag, int need) {
+  int v;
+  while ((v = __builtin_amdgcn_readfirstlane(__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP))) < need)
+    __builtin_amdgcn_s_sleep(1);
+  return v;
+}
+PDS_DEV void eval_post(int *flag, int lane, int inc) {  // + inc, after every lane's LDS accesses of this phase
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  if (lane == 0) __hip_atomic_fetch_add(flag, inc, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+template <class V_, int TEAMS>
+__global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(const EvalArgs ea) {
+  using namespace pds_mlpf;
+  using V = std::conditional_t<regen_obs_variant<V_>(), StoredOh<V_>, V_>;
+  constexpr int D = V::D;
+  constexpr int TS = tile_stride<D>();
+  constexpr int NIN = (D + 15) / 16;
+  constexpr int RM = merged_reset_variant<V>() ? RM_MERGED : RM_INLINE;
+  constexpr int kScratchU4_ = (RM == RM_MERGED) ? kMergedScratchU4 : (inline_coop_variant<V>() ? inline_envs<V, false>() * scratch_stride<V>() : 0);
+  static_assert(D <= 64, "network input <= 64 features");
+  __shared__ __attribute__((aligned(16))) float net_all[TEAMS][kNetFloats];
+  __shared__ __attribute__((aligned(16))) float mus_all[TEAMS][64], iss_all[TEAMS][64];
+  __shared__ __attribute__((aligned(16))) float tile_all[TEAMS][kWave * TS];
+  __shared__ __attribute__((aligned(16))) float4 act_all[TEAMS][kWave];
+  __shared__ uint32_t queue_all[TEAMS][kQueueCap];
+  __shared__ U4 scratch_all[TEAMS][kScratchU4_ > 0 ? kScratchU4_ : 1];
+  __shared__ int obs_ready[TEAMS], act_ready[TEAMS];
+#ifdef PDS_STAMPS
+  unsigned long long stamp_[kStampSlots];
+#endif
+  prefetch_kernargs();
+  const StepArgs &a = ea.s;
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
+  const int team = __builtin_amdgcn_readfirstlane(tid / kRolloutThreads);  // wave-uniform
+  const int ttid = tid - team * kRolloutThreads;                           // thread within its team
+  const int wave = __builtin_amdgcn_readfirstlane(ttid >> 6);              // wave within its team
+  const bool is_env = wave >= kRolloutMlpWaves;
+  const int n16 = lane & 15, g = lane >> 4;
+  const long long ntiles = a.n / kWave;  // (N = P x E, E a multiple of 64: every tile is full)
+  const long long t = (long long)blockIdx.x * TEAMS + team;  // this team's tile; >= ntiles: the last block of an odd tile count
+  const int T = ea.T;
+  const NetLds w = net_lds(net_all[team]);
+  float *mus = mus_all[team], *iss = iss_all[team], *tile = tile_all[team];
+
+  // ---- prologue, per team: policy p's network and statistics and the tile's o(0) into LDS -----------------------------
+  if (t < ntiles) {
+    const long long p = t / ea.tiles_per_policy;
+    pds_mlp m = ea.shape;
+    const float *row = ea.params + p * ea.param_count;  // W1 b1 W2 b2 W3 b3, torch order (pds_mlp_param_count)
+    m.w1 = row;
+    m.b1 = m.w1 + m.h1 * m.d_in;
+    m.w2 = m.b1 + m.h1;
+    m.b2 = m.w2 + m.h2 * m.h1;
+    m.w3 = m.b2 + m.h2;
+    m.b3 = m.w3 + m.d_out * m.h2;
+    stage_net(m, w, ttid, kRolloutThreads);
+    if (ttid < 64) {
+      const bool on = ea.mean != nullptr && ttid < D;
+      mus[ttid] = on ? ea.mean[p * D + ttid] : 0.f;
+      iss[ttid] = on ? 1.0f / (ea.stdv[p * D + ttid] + ea.eps) : 1.f;
+    }
+    for (int idx = ttid; idx < kWave * D; idx += kRolloutThreads) {
+      const int r = idx / D, c = idx - r * D;
+      tile[r * TS + c] = ea.obs0[(t * kWave + r) * D + c];
+    }
+  }
+  if (tid < TEAMS) { obs_ready[tid] = 0; act_ready[tid] = 0; }
+  __syncthreads();  // (the only block barrier: from here on the roles meet through the counters)
+  if (t >= ntiles) return;
+
+  if (is_env) {
+    // ================================ env wave: the tile's 64 envs in registers =================================
+#if PDS_ROLLOUT_ENV_PRIO
+    __builtin_amdgcn_s_setprio(PDS_ROLLOUT_ENV_PRIO);  // the env wave's instructions before its SIMD-mates' (network waves)
+#endif
+    const long long wave_base = t * kWave;
+    const bool active = true;
+    const Idx<V> ix{wave_base, (uint32_t)lane};
+    PDS_ENV_WAVE_BEGIN
+    float ep_ret = 0.f, ep_len = 0.f, ep_cost = 0.f;
+    bool alive = true;          // this lane's env is in its first episode
+    float c_step = 0.f;         // the last step's cost, on its way back from the sink row ...
+    bool c_counts = false;      // ... and whether it belongs to the first episode
+    int qcount = 0;
+    bool stopped = false;  // wave-uniform: this tile has posted its stop
+    for (int s = 0; s < T; ++s) {
+      const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<301, true>(ea.s, s));
+      // A stopped tile falls through its remaining iterations (a scalar compare and a branch each) instead of leaving the loop:
+      // the loop stays a counted one.  With a data-dependent exit -- `if (!more) break;` below -- the compiler gave the env wave
+      // of the observation-noise variants 40 more VGPRs (Hover at its defaults: 202 against 149), and their two-team form
+      // spilled (profiles/evaluate_kernel_resources.txt).  The parity of the state ring goes on toggling there: behind the loop it is
+      // parity(entry) ^ (T & 1) in EVERY tile, as after a rollout of T steps -- the library reads tile 0's parity for all envs
+      // between launches (csrc/pds_api.hip field_kernel: which hist slot is the last action, which the one before).
+      if (stopped) { parity ^= 1; continue; }
+      rollout_wait_ge(&act_ready[team], kRolloutMlpWaves * (s + 1));  // the network waves have read o(s) and written a(s)
+      ep_cost += c_counts ? c_step : 0.f;
+      // (opaque per-iteration copies of the seed and the lane index: see step_k_kernel)
+      RngKey rks = rk;
+      int lane_s = lane;
+      if (PDS_STEPK_OPAQUE_KEY) asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
+      // every step's outputs go to the SAME sink row: offset 0, but opaque -- step_once renews its late views of the kernel
+      // arguments per iteration by this offset (reload_args' tag); a constant would hoist them out of the loop, into registers
+      long long o1 = 0;
+      asm volatile("" : "+s"(o1));
+      const float4 act = act_all[team][lane_s];
+      StepOut so;
+      step_once<V, kWave, RM, false>(el.s, o1, rks, parity, nullptr, tile, nullptr, queue_all[team], scratch_all[team], lane_s,
+                                     wave_base, ix, active, act, S, qcount, nullptr, &so PDS_STAMP_ARG);
+      PDS_NEXT_TICK(rk, parity)
+      // the accumulator updates of evaluation.evaluate, in its order and its form (x + 0 for an env that has finished)
+      ep_ret += alive ? so.reward : 0.f;
+      ep_len += alive ? 1.f : 0.f;
+      c_counts = alive;
+      alive = alive && !(so.done || so.trunc);
+      const bool more = __ballot(alive) != 0ull && s + 1 < T;  // wave-uniform
+      eval_post(&obs_ready[team], lane, more ? 1 : kEvalStop);  // o(s + 1) is in the tile / this team's env wave has left
+      c_step = *at(el.s.cost, ix);  // (behind the post: see the head of this file)
+      stopped = !more;
+    }
+    ep_cost += c_counts ? c_step : 0.f;
+    // The state as the tile left it and the clock T ticks on, whichever step the tile stopped at: the caller resets before it
+    // steps again (pds_evaluate_policies leaves the handle "not reset").
+    const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<302, true>(ea.s, T));
+    store_state<V>(el.s, ix, parity, S, true);
+    advance_clock(el.s.st.clk, t, rk0, parity, (uint32_t)T, lane);
+    *at(el.ret, ix) = ep_ret;
+    *at(el.len, ix) = ep_len;
+    *at(el.cost, ix) = ep_cost;
+    return;
+  }
+
+  // ================================ network waves: 16 rows of the tile each ====================================
+  const int own = wave * 16 + n16;  // this lane's sample row
+  for (int s = 0;; ++s) {
+    const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<303, true>(ea.s, s));
+    if (eval_wait_ge(&obs_ready[team], s) >= kEvalStop) break;  // o(s) is in the tile, or the env wave has left
+#if PDS_ROLLOUT_ACTOR_PRIO
+    __builtin_amdgcn_s_setprio(PDS_ROLLOUT_ACTOR_PRIO);
+#endif
+    f32x4 x_own[NIN];
+    gather_input<NIN>(tile, TS, own, D, mus, iss, g, x_own);
+    const f32x4 mu = (el.shape.activation == 0) ? forward16_shape<0, NIN>(w, el.shape, x_own, n16, g) : forward16_shape<1, NIN>(w, el.shape, x_own, n16, g);
+    if (g == 0) act_all[team][own] = make_float4(mu[0], mu[1], mu[2], mu[3]);  // lane n16 owns sample `own`: the actor's four outputs
+    rollout_post(&act_ready[team], lane);  // this wave is done with the tile of step s
+  }
+}
+
+// grid.x = number of 64-env tiles; more tiles than CUs: two teams per block (launch_rollout_variant's rule) -- unless the two-team
+// form of this variant spills where the one-team form does not.  One launch bound covers every wave of a block, so the ten waves
+// of two teams get the env wave's registers cut to 168 (three waves per SIMD) where one team's five leave it 256; the
+// observation-noise variants need 190-250 there (profiles/evaluate_kernel_resources.txt).  The rule is read off the code objects
+// instead of being listed by hand: the two-team form is launched where it needs no more scratch memory per lane than the
+// one-team form.
+template <class RV_>
+inline bool eval_two_teams_fit() {
+  static const bool fit = [] {
+    hipFuncAttributes one, two;
+    if (hipFuncGetAttributes(&one, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 1>)) != hipSuccess ||
+        hipFuncGetAttributes(&two, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 2>)) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    return two.localSizeBytes <= one.localSizeBytes;
+  }();
+  return fit;
+}
+struct EvalLaunch {
+  dim3 grid;
+  hipStream_t s;
+  const EvalArgs &ea;
+  template <class RV_>
+  void run() const {
+    if (grid.x > (unsigned)kRolloutTwoTeamsAbove && eval_two_teams_fit<RV_>())
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 2>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, ea);
+    else
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 1>), grid, dim3(kRolloutThreads), 0, s, ea);
+  }
+};
+
+// ---- flags -> variant, family by family: the variants launch_rollout_*_family (csrc/pds_rollout.h) instantiates, i.e. the
+// configurations rollout_supported() names.  `l.template run<Variant>()` launches. ----
+template <int TASK, int CTRL, bool LAT, class L>
+inline bool eval_lean_or_full(const LaunchFlags &f, const L &l) {
+  const bool lean = !f.dr && !f.tn && !f.on, full = f.dr && f.tn && f.on;
+  if (!lean && !full) return false;
+  if (f.motor) {
+    if (full) l.template run<Variant<TASK, true, true, false, true, true, CTRL, LAT, false>>();
+    else l.template run<Variant<TASK, true, false, false, false, false, CTRL, LAT, false>>();
+  } else {
+    if (full) l.template run<Variant<TASK, false, true, false, true, true, CTRL, LAT, false>>();
+    else l.template run<Variant<TASK, false, false, false, false, false, CTRL, LAT, false>>();
+  }
+  return true;
+}
+template <int TASK, bool MOTOR, bool GE, class L>
+inline void eval_pwm(const LaunchFlags &f, const L &l) {
+#define PDS_EVAL_CASE(DR, TN, ON) \
+  if (f.dr == DR && f.tn == TN && f.on == ON) return l.template run<Variant<TASK, MOTOR, DR, GE, TN, ON, 0, false, false>>()
+  PDS_EVAL_CASE(false, false, false); PDS_EVAL_CASE(true, true, true);
+  PDS_EVAL_CASE(true, false, false); PDS_EVAL_CASE(false, true, false); PDS_EVAL_CASE(false, false, true);
+  PDS_EVAL_CASE(true, true, false); PDS_EVAL_CASE(true, false, true); PDS_EVAL_CASE(false, true, true);
+#undef PDS_EVAL_CASE
+}
+template <int TASK, bool MOTOR, class L>
+inline bool eval_hold(const LaunchFlags &f, const L &l) {
+  if (!f.on || f.dr != f.tn) return false;
+  if (f.dr) l.template run<Variant<TASK, MOTOR, true, false, true, true, 0, false, true>>();
+  else l.template run<Variant<TASK, MOTOR, false, false, false, true, 0, false, true>>();
+  return true;
+}
+// The families are instantiated in translation units of their own (csrc/pds_evaluate_<task>[_pwm|_lat].hip);
+// launch_evaluate_<task> is the dispatcher in csrc/pds_evaluate_<task>.hip.
+template <int TASK, class L>
+inline bool eval_pwm_family(const LaunchFlags &f, const L &l) {
+  constexpr bool kMotor = TASK != PDS_TASK_TAKEOFF;  // (TakeOff + motor dynamics: only with the latency ring)
+  if (f.ge) {
+    if constexpr (TASK == PDS_TASK_TAKEOFF) { eval_pwm<TASK, false, true>(f, l); return true; }
+    return false;
+  }
+  if constexpr (kMotor) { if (f.motor) { eval_pwm<TASK, true, false>(f, l); return true; } }
+  eval_pwm<TASK, false, false>(f, l);
+  return true;
+}
+template <int TASK, class L>
+inline bool eval_lat_family(const LaunchFlags &f, const L &l) {
+  if (f.ctrl == 0) return eval_lean_or_full<TASK, 0, true>(f, l);
+  if constexpr (TASK != PDS_TASK_TAKEOFF) {  // TakeOff fixes control_mode = 'PWM' (envs/takeoff.py:225)
+    if (f.ctrl == 1) return eval_lean_or_full<TASK, 1, true>(f, l);
+    return eval_lean_or_full<TASK, 2, true>(f, l);
+  }
+  return false;
+}
+template <int TASK, class L>
+inline bool eval_pid_hold_family(const LaunchFlags &f, const L &l) {
+  constexpr bool kMotor = TASK != PDS_TASK_TAKEOFF;
+  if (f.hold) {
+    if constexpr (kMotor) { if (f.motor) return eval_hold<TASK, true>(f, l); }
+    return eval_hold<TASK, false>(f, l);
+  }
+  if constexpr (TASK != PDS_TASK_TAKEOFF) {
+    if (f.ctrl == 1) return eval_lean_or_full<TASK, 1, false>(f, l);
+    if (f.ctrl == 2) return eval_lean_or_full<TASK, 2, false>(f, l);
+  }
+  return false;
+}
+
+}  // namespace pds

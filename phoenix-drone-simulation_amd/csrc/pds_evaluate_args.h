@@ -1,0 +1,35 @@
+// pds_evaluate_args.h -- launch interface of the fused policy evaluation (csrc/pds_evaluate.h; entry point pds_evaluate_policies
+// in csrc/pds_api.hip).
+#pragma once
+#include "pds_types.h"
+
+namespace pds {
+
+// Arguments of evaluate_kernel.  The env configurations it is built for are the fused rollout's: rollout_supported()
+// (csrc/pds_types.h) is the one statement of that rule, for pds_rollout and for pds_evaluate_policies.
+struct EvalArgs {
+  StepArgs s;  // FIRST member (reload_args reads the kernarg segment as a StepArgs).  obs and final_obs are NULL (the rows stay in
+               // LDS); reward / cost / term / trunc point at the handle's [N] sink row: step_once (csrc/pds_step.h) streams every
+               // step's outcome out, and the evaluation keeps that code path as it is -- each step overwrites the same row
+  pds_mlp shape;             // d_in, h1, h2, d_out, activation of every policy; its pointers are not read
+  const float *params;       // [P, param_count] W1 b1 W2 b2 W3 b3 of policy p in row p (pds_mlp_param_count layout)
+  const float *mean, *stdv;  // [P, D] optional standardisation of policy p's inputs (both or none)
+  float eps;
+  int param_count;
+  int tiles_per_policy;      // E / 64: tile t flies policy t / tiles_per_policy
+  int T;                     // steps after which every episode still running is cut
+  const float *obs0;         // [N, D] the observation every env holds on entry
+  float *ret, *len, *cost;   // [N] return, length and cost of every env's first episode
+};
+static_assert(offsetof(EvalArgs, s) == 0, "reload_args() reads the head of the kernarg segment as a StepArgs");
+
+bool launch_evaluate_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
+bool launch_evaluate_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
+bool launch_evaluate_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
+// (their families, one translation unit each, like the rollout's: control_mode PWM with every noise setting / the latency ring)
+bool launch_evaluate_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
+bool launch_evaluate_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
+bool launch_evaluate_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
+bool launch_evaluate_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
+
+}  // namespace pds

@@ -5,10 +5,17 @@ The reference runs `num_evaluations` episodes one after the other (`eval_once`: 
 deterministically until terminated or truncated, sum reward and info['cost']) and writes one value
 per line to `returns.csv` / `costs.csv`.  Here every env of the vector env plays exactly one
 episode: the accumulators of an env freeze at its first `terminated | truncated`, and the loop ends
-after `max_episode_steps` steps at the latest (TimeLimit)."""
+after `max_episode_steps` steps at the latest (TimeLimit).
+
+`evaluate_population` scores a whole POPULATION of policies that way -- a checkpoint sweep, model selection during training,
+an evolution strategy over actor weights -- in one launch: P policies x E episodes (include/pds.h pds_evaluate_policies)."""
+import ctypes as C
 import os
 
 import torch
+import torch.nn as nn
+
+from . import native
 
 
 def _as_policy(policy):
@@ -69,3 +76,229 @@ def get_batch(env, policy, steps):
         done = (term | trunc).unsqueeze(-1)
         Y[t] = torch.where(done, info["final_obs"], obs)
     return X, Y
+
+
+# ---- a population of policies in one launch ----------------------------------------------------------------------------
+_ACT_ID = {"relu": 0, "tanh": 1}
+_ACT_MODULE = {"relu": nn.ReLU, "tanh": nn.Tanh}
+
+
+def _ptr(t, byte_offset=0):
+    return C.c_void_p(t.data_ptr() + byte_offset) if t is not None else None
+
+
+def _actor_shape(net):
+    """(d_in, (h1, h2), d_out, activation name) of an nn.Sequential(Linear, act, Linear, act, Linear[, Identity])."""
+    lin = [l for l in net if isinstance(l, nn.Linear)]
+    acts = [l for l in net if not isinstance(l, (nn.Linear, nn.Identity))]
+    if len(lin) != 3 or len(acts) != 2 or type(acts[0]) is not type(acts[1]):
+        raise ValueError("a population holds actors with two hidden layers and one activation")
+    name = {nn.ReLU: "relu", nn.Tanh: "tanh"}.get(type(acts[0]))
+    if name is None:
+        raise ValueError(f"activation {type(acts[0]).__name__}: relu or tanh")
+    return lin[0].in_features, (lin[0].out_features, lin[1].out_features), lin[2].out_features, name
+
+
+def _flat_params(net):
+    """W1, b1, W2, b2, W3, b3 in torch parameter order: the layout of pds_mlp_param_count."""
+    lin = [l for l in net if isinstance(l, nn.Linear)]
+    return torch.cat([t.detach().reshape(-1).float().cpu() for l in lin for t in (l.weight, l.bias)])
+
+
+class PolicyPopulation:
+    """P actors of ONE shape as data: `theta` [P, param_count] float32 (row p = W1, b1, W2, b2, W3, b3 of policy p in torch
+    order), the shape (d_in, hidden_sizes, d_out = 4), the activation, optional observation standardisation `mean`, `std`
+    [P, D] (both or none) and its eps.  Mixed shapes or activations raise ValueError: group by shape, one population each."""
+
+    def __init__(self, theta, d_in, hidden_sizes, activation, mean=None, std=None, eps=1e-5, d_out=4):
+        hidden_sizes = tuple(int(h) for h in hidden_sizes)
+        if len(hidden_sizes) != 2:
+            raise ValueError("two hidden layers")
+        if activation not in _ACT_ID:
+            raise ValueError(f"activation {activation!r}: relu or tanh")
+        self.d_in, self.hidden_sizes, self.d_out, self.activation = int(d_in), hidden_sizes, int(d_out), activation
+        h1, h2 = hidden_sizes
+        self.param_count = h1 * self.d_in + h1 + h2 * h1 + h2 + self.d_out * h2 + self.d_out
+        theta = torch.as_tensor(theta, dtype=torch.float32)
+        if theta.dim() == 1:
+            theta = theta.unsqueeze(0)
+        if theta.dim() != 2 or theta.shape[1] != self.param_count:
+            raise ValueError(f"theta must be [P, {self.param_count}] for this shape, got {tuple(theta.shape)}")
+        self.theta = theta.contiguous()
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std come together")
+        self.mean = self.std = None
+        if mean is not None:
+            mean, std = torch.as_tensor(mean, dtype=torch.float32), torch.as_tensor(std, dtype=torch.float32)
+            want = (self.P, self.d_in)
+            if mean.dim() == 1:  # one standardisation for every policy
+                mean, std = mean.expand(*want), std.expand(*want)
+            if tuple(mean.shape) != want or tuple(std.shape) != want:
+                raise ValueError(f"mean and std must be {list(want)}")
+            self.mean, self.std = mean.contiguous(), std.contiguous()
+        self.eps = float(eps)
+
+    @property
+    def P(self):
+        return int(self.theta.shape[0])
+
+    def __len__(self):
+        return self.P
+
+    @classmethod
+    def _from_nets(cls, nets, means, stds, epss):
+        if len(nets) == 0:
+            raise ValueError("an empty population")
+        shapes = [_actor_shape(n) for n in nets]
+        if any(s != shapes[0] for s in shapes[1:]):
+            raise ValueError(f"mixed actor shapes or activations in one population: {sorted(set(shapes))}")
+        with_stats = [m is not None for m in means]
+        if any(w != with_stats[0] for w in with_stats[1:]):
+            raise ValueError("policies with and without observation standardisation in one population")
+        if with_stats[0] and any(e != epss[0] for e in epss[1:]):
+            raise ValueError(f"mixed standardisation eps in one population: {sorted(set(epss))}")
+        d_in, hidden, d_out, act = shapes[0]
+        theta = torch.stack([_flat_params(n) for n in nets])
+        mean = torch.stack([m.detach().float().cpu() for m in means]) if with_stats[0] else None
+        std = torch.stack([s.detach().float().cpu() for s in stds]) if with_stats[0] else None
+        return cls(theta, d_in, hidden, act, mean, std, epss[0] if with_stats[0] else 1e-5, d_out=d_out)
+
+    @classmethod
+    def from_actor_critics(cls, acs):
+        """ActorCritic list (ppo.py): the actors `pi.net`, standardisation from `obs_oms`."""
+        acs = list(acs)
+        oms = [getattr(ac, "obs_oms", None) for ac in acs]
+        return cls._from_nets([ac.pi.net for ac in acs], [o.mean if o is not None else None for o in oms],
+                              [o.std if o is not None else None for o in oms], [o.eps if o is not None else None for o in oms])
+
+    @classmethod
+    def from_json_policies(cls, policies):
+        """policy_io.JsonPolicy list: `net`, `mean`, `std`, `eps`."""
+        ps = list(policies)
+        return cls._from_nets([p.net for p in ps], [p.mean for p in ps], [p.std for p in ps], [p.eps for p in ps])
+
+    @classmethod
+    def from_flat(cls, theta, d_in, hidden_sizes, activation, mean=None, std=None, eps=1e-5):
+        """theta [P, param_count] as an evolution strategy holds it."""
+        return cls(theta, d_in, hidden_sizes, activation, mean, std, eps)
+
+    def to(self, device):
+        """A population whose tensors live on `device`; this one stays where it is."""
+        has = self.mean is not None
+        return PolicyPopulation(self.theta.to(device), self.d_in, self.hidden_sizes, self.activation,
+                                self.mean.to(device) if has else None, self.std.to(device) if has else None, self.eps, d_out=self.d_out)
+
+    def policy(self, p):
+        """The p-th actor as nn.Sequential(Linear, act, Linear, act, Linear, Identity) on the CPU (no standardisation)."""
+        h1, h2 = self.hidden_sizes
+        sizes = [self.d_in, h1, h2, self.d_out]
+        row, off, layers = self.theta[p].detach().cpu(), 0, []
+        for j in range(3):
+            lin = nn.Linear(sizes[j], sizes[j + 1])
+            nw, nb = sizes[j + 1] * sizes[j], sizes[j + 1]
+            lin.weight.data = row[off:off + nw].reshape(sizes[j + 1], sizes[j]).clone()
+            lin.bias.data = row[off + nw:off + nw + nb].clone()
+            off += nw + nb
+            layers += [lin, _ACT_MODULE[self.activation]() if j < 2 else nn.Identity()]
+        return nn.Sequential(*layers)
+
+    def mlp(self, p=0):
+        """struct pds_mlp of policy p: pointers into row p of theta."""
+        m = native.Mlp()
+        m.d_in, (m.h1, m.h2), m.d_out, m.activation = self.d_in, self.hidden_sizes, self.d_out, _ACT_ID[self.activation]
+        h1, h2 = self.hidden_sizes
+        base = self.theta.data_ptr() + 4 * p * self.param_count
+        for name, n in (("w1", h1 * self.d_in), ("b1", h1), ("w2", h2 * h1), ("b2", h2), ("w3", self.d_out * h2), ("b3", self.d_out)):
+            setattr(m, name, base)
+            base += 4 * n
+        return m
+
+
+def _check_population_call(env, population):
+    P, n = population.P, int(env.num_envs)
+    if n % P != 0:
+        raise ValueError(f"env.num_envs = {n} is not P x E for the population's P = {P}")
+    E = n // P
+    if E % 64 != 0:
+        raise ValueError(f"episodes per policy E = {n} / {P} = {E} is not a multiple of 64 (one tile)")
+    return P, E
+
+
+def fused_evaluation_built(env):
+    """Whether pds_evaluate_policies has a kernel for this env: a handle with auto_reset whose configuration is one the fused
+    rollout is built for, and observation_history_size == 2."""
+    return getattr(env, "observation_history_size", 2) == 2 and bool(env.lib.pds_evaluate_supported(env._handle))
+
+
+@torch.no_grad()
+def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None):
+    """-> (returns, ep_lengths, costs), each [P, E] float32 on the CPU: policy p of `population` flies the E = num_envs / P
+    envs of block p, one episode per env, deterministically (action = actor mean), as `evaluate` does for one policy.
+
+    fused=True: one launch (pds_evaluate_policies, csrc/pds_evaluate.h); NotImplementedError where no kernel is built --
+    observation_history_size != 2 included -- with the env untouched.  fused=False: the composed path, per step one
+    pds_mlp_forward per policy on its block of the observation + env.step + the accumulator updates of `evaluate`: the same
+    bits.  fused="auto": the kernel where it is built, the composed path elsewhere.
+    The env is reset first and not afterwards: after the fused path it refuses to step until the next reset() of every env
+    (a masked reset is refused as well).  `population` is not modified: the call works on device copies of its tensors.
+    max_steps: the number of steps flown, by default the env's max_episode_steps (the TimeLimit ends every episode by then)."""
+    P, E = _check_population_call(env, population)
+    if population.d_in != env.obs_dim:
+        raise ValueError(f"the population's actors read {population.d_in} inputs, the env observes {env.obs_dim}")
+    if isinstance(fused, str):
+        if fused != "auto":
+            raise ValueError("fused: True, False or 'auto'")
+    else:
+        fused = bool(fused)  # (1, 0, numpy.bool_: below `fused is True` must mean what it says)
+    T = int(env._max_episode_steps if max_steps is None else max_steps)
+    if T < 1:
+        raise ValueError(f"max_steps = {T}")
+    use_kernel = False
+    if fused is not False:
+        built = fused_evaluation_built(env)
+        if fused is True and not built:
+            raise NotImplementedError("pds_evaluate_policies has no kernel for this env (built: observation_history_size 2, auto_reset, "
+                                      "the env configurations of the fused rollout); fused='auto' runs the composed path")
+        use_kernel = built
+    population = population.to(env.device)
+    dev, n, D = env.device, env.num_envs, env.obs_dim
+    lib = env.lib
+    ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
+    obs, _ = env.reset()
+    if use_kernel:
+        shape = population.mlp(0)
+        with torch.cuda.device(dev):
+            rc = lib.pds_evaluate_policies(env._handle, P, E, C.byref(shape), _ptr(population.theta), _ptr(population.mean),
+                                           _ptr(population.std), population.eps, T, _ptr(obs), _ptr(ret), _ptr(length), _ptr(cost),
+                                           env._stream())
+        native.check(env._handle, rc, "pds_evaluate_policies")
+    else:
+        mlps = [population.mlp(p) for p in range(P)]
+        act = torch.empty(n, 4, device=dev)
+        alive = torch.ones(n, dtype=torch.bool, device=dev)
+        has = population.mean is not None
+        for _ in range(T):
+            stream = env._stream()
+            with torch.cuda.device(dev):
+                for p in range(P):
+                    rc = lib.pds_mlp_forward(C.byref(mlps[p]), _ptr(obs, 4 * p * E * D), None, E,
+                                             _ptr(population.mean, 4 * p * D) if has else None,
+                                             _ptr(population.std, 4 * p * D) if has else None, population.eps,
+                                             _ptr(act, 16 * p * E), stream)
+                    if rc != native.OK:
+                        raise RuntimeError(f"pds_mlp_forward -> {rc}")
+            obs, r, term, trunc, info = env.step(act)
+            ret += torch.where(alive, r, torch.zeros_like(r))
+            cost += torch.where(alive, info["cost"], torch.zeros_like(r))
+            length += alive.float()
+            alive &= ~(term | trunc)
+    ret, length, cost = ret.cpu().reshape(P, E), length.cpu().reshape(P, E), cost.cpu().reshape(P, E)
+    if log_dir is not None:
+        for p in range(P):
+            d = os.path.join(log_dir, str(p))
+            os.makedirs(d, exist_ok=True)
+            with open(os.path.join(d, "returns.csv"), "w") as f:
+                f.write("\n".join(str(float(x)) for x in ret[p]) + "\n")
+            with open(os.path.join(d, "costs.csv"), "w") as f:
+                f.write("\n".join(str(float(x)) for x in cost[p]) + "\n")
+    return ret, length, cost

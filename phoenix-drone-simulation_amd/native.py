@@ -39,7 +39,7 @@ EXPORTS = ["pds_version", "pds_default_config", "pds_create", "pds_destroy", "pd
            "pds_value_grad", "pds_ppo_policy_grad_step", "pds_value_grad_step", "pds_gaussian_sample", "pds_gaussian_sample_dev", "pds_counter_add", "pds_permutation", "pds_rollout_record",
            "pds_adam_step", "pds_rollout", "pds_rollout_history",
            "pds_npg_workspace_floats", "pds_npg_fisher_vector_product", "pds_npg_cg_step", "pds_npg_surrogate_kl",
-           "pds_simopt_latency_steps", "pds_simopt_evaluate"]
+           "pds_simopt_latency_steps", "pds_simopt_evaluate", "pds_evaluate_supported", "pds_evaluate_policies"]
 
 
 class Mlp(C.Structure):
@@ -159,6 +159,8 @@ def load():
     later("pds_npg_surrogate_kl", [mp, vp, vp, i32] + [vp] * 6 + [i64, vp, vp, vp, vp])
     later("pds_simopt_latency_steps", [vp, C.c_double])
     later("pds_simopt_evaluate", [vp, i64, vp, vp, i32, i64, i32, i32, C.c_double] + [vp] * 7)
+    later("pds_evaluate_supported", [vp])
+    later("pds_evaluate_policies", [vp, i64, i64, mp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp])
     _lib = lib
     return lib
 
