@@ -1,0 +1,118 @@
+"""The dispatch table of pds_evaluate_policies, swept: csrc/pds_evaluate.h restates rollout_supported() (csrc/pds_types.h) by hand
+as template-flag lists (eval_pwm, eval_lean_or_full, eval_hold and the three families), in seven translation units, with a one-team
+and a two-team form per variant (256 against 168 registers for the env wave: different generated code).  A swapped flag in one
+PDS_EVAL_CASE flies another env than the handle's; a family whose launcher says `false` for what pds_evaluate_supported promised
+is an error code.  tests/variant_cases.py enumerates every configuration the constructor accepts and states the rule in its own
+words; here the library must agree with it, and EVERY supported configuration is flown in both forms, bit for bit against the
+composed path (whose env steps are pds_step's: the per-step kernels of that configuration)."""
+import collections
+
+import pytest
+import torch
+
+import variant_cases as vc
+
+pytestmark = pytest.mark.gpu
+LIMIT, MAX_STEPS, E = 9, 12, 64  # episodes end by termination and by the TimeLimit, tiles stop at steps of their own, before max_steps
+
+
+def test_the_supported_set_has_the_size_the_rule_gives():
+    """102 = 40 (PWM, every noise setting) + 8 (TakeOff with the ground effect) + 28 (latency ring) + 16 (PID) + 10 (hold)"""
+    count = collections.Counter(fam for _, _, _, fam in vc.SUPPORTED)
+    assert dict(count) == {"pwm": 40, "takeoff_ge": 8, "latency": 28, "pid": 16, "hold": 10} == vc.FAMILY_COUNTS
+    assert len(vc.SUPPORTED) == 102 and len(vc.VARIANTS) == 544
+
+
+@pytest.mark.parametrize("task,env_id", vc.TASKS)
+def test_the_library_agrees_with_the_rule_on_every_configuration(task, env_id):
+    """fused_evaluation_built(env) == the rule of tests/variant_cases.py, for every accepted combination of this task"""
+    import phoenix_drone_simulation_amd as pds
+    from phoenix_drone_simulation_amd.evaluation import fused_evaluation_built
+    wrong, n = [], 0
+    for vid, eid, kw, fam in vc.VARIANTS:
+        if eid != env_id:
+            continue
+        env = pds.make(eid, num_envs=64, seed=1, **kw)
+        if fused_evaluation_built(env) != (fam is not None):
+            wrong.append(vid)
+        env.close()
+        n += 1
+    assert n == {"hover": 224, "circle": 224, "takeoff": 96}[task]
+    assert not wrong, wrong
+
+
+def _population(env, P, seed):
+    """seeded random actors of the env's width (vc.random_rows).  Policy 0 gets output biases of +3, +3, -3, -3: on Hover with
+    control_mode PWM that is two motors at full thrust and two at none, the 300 deg/s bound ends every episode of its tile
+    within three steps, and tile 0 stops there while its neighbours -- the other team of block 0 in the two-team form -- fly on
+    to the limit (test_the_sweep_holds_both_endings_where_the_task_terminates)."""
+    from phoenix_drone_simulation_amd.evaluation import PolicyPopulation
+    rows = vc.random_rows(P, env.obs_dim, seed=seed)
+    rows[0, -4:] = torch.tensor([3.0, 3.0, -3.0, -3.0])
+    return PolicyPopulation.from_flat(rows, env.obs_dim, (32, 48), "tanh")
+
+
+@pytest.mark.parametrize("P", [3, 257], ids=["one_team", "257_tiles"])
+@pytest.mark.parametrize("vid,env_id,kw,fam", vc.SUPPORTED, ids=[v[0] for v in vc.SUPPORTED])
+def test_every_supported_configuration_fused_equals_composed(vid, env_id, kw, fam, P):
+    """P = 3: three tiles, one team per block.  P = 257: 257 tiles -- above 256 the launcher puts two teams in a block where the
+    two-team form of the variant fits (eval_two_teams_fit), and the last block is half filled."""
+    import phoenix_drone_simulation_amd as pds
+    from phoenix_drone_simulation_amd.evaluation import evaluate_population, fused_evaluation_built
+    from test_gpu_evaluate import _equal
+    env_f = pds.make(env_id, num_envs=P * E, seed=17, max_episode_steps=LIMIT, **kw)
+    env_c = pds.make(env_id, num_envs=P * E, seed=17, max_episode_steps=LIMIT, **kw)
+    assert fused_evaluation_built(env_f)
+    pop = _population(env_f, P, seed=P)
+    fused = evaluate_population(env_f, pop, fused=True, max_steps=MAX_STEPS)
+    composed = evaluate_population(env_c, pop, fused=False, max_steps=MAX_STEPS)
+    assert _equal(fused, composed), (vid, P, [int((a.view(torch.int32) != b.view(torch.int32)).sum()) for a, b in zip(fused, composed)])
+    length = fused[1]
+    assert float(length.min()) >= 1 and float(length.max()) <= LIMIT  # every episode finished: at the limit at the latest
+    assert int((length == LIMIT).sum()) >= 1
+    assert env_f.sync_tick() == env_c.sync_tick() == 1 + MAX_STEPS
+    env_f.close(); env_c.close()
+
+
+@pytest.mark.parametrize("P", [3, 257])
+def test_the_sweep_holds_both_endings_where_the_task_terminates(P):
+    """the sweep's sizes on Hover lean, as a statement about the sweep itself: with a limit of 9 under these actors some
+    episodes terminate and some are cut, and the tiles of a launch stop at different steps (tile 0 by step 3, others at 9), all
+    before max_steps = 12"""
+    import phoenix_drone_simulation_amd as pds
+    from phoenix_drone_simulation_amd.evaluation import evaluate_population
+    vid, env_id, kw, _ = next(v for v in vc.SUPPORTED if v[0] == "pwm/hover-pwm-lean")
+    env = pds.make(env_id, num_envs=P * E, seed=17, max_episode_steps=LIMIT, **kw)
+    _, length, _ = evaluate_population(env, _population(env, P, seed=P), fused=True, max_steps=MAX_STEPS)
+    env.close()
+    stops = length.max(dim=1).values.int().tolist()  # E = 64: one tile per policy
+    assert int((length < LIMIT).sum()) >= 1 and int((length == LIMIT).sum()) >= 1
+    assert stops[0] <= 3 and max(stops) == LIMIT < MAX_STEPS, stops[:8]
+
+
+UNSUPPORTED = [
+    ("hover_ground_effect", vc.HOVER, dict(use_ground_effect=True)),
+    ("latency_dr_only", vc.HOVER, dict(use_latency=True, latency=0.02, motor_thrust_noise=0, observation_noise=-1)),
+    ("pid_observation_noise_only", vc.CIRCLE, dict(control_mode="AttitudeRate", domain_randomization=-1, motor_thrust_noise=0)),
+    ("hold_dr_without_thrust_noise", vc.HOVER, dict(observation_frequency=50, motor_thrust_noise=0)),
+    ("takeoff_motor_dynamics_no_latency", vc.TAKEOFF, dict(use_motor_dynamics=True)),
+]
+
+
+@pytest.mark.parametrize("name,env_id,kw", UNSUPPORTED, ids=[u[0] for u in UNSUPPORTED])
+def test_unsupported_configurations_are_refused_with_the_env_untouched(name, env_id, kw):
+    import phoenix_drone_simulation_amd as pds
+    from phoenix_drone_simulation_amd.evaluation import evaluate_population, fused_evaluation_built
+    from test_gpu_evaluate import _snapshot, _unchanged
+    assert vc.family(*vc.flags_of(env_id, kw)) is None  # the rule says so, too
+    env = pds.make(env_id, num_envs=2 * E, seed=3, max_episode_steps=LIMIT, **kw)
+    env.reset()
+    env.step(torch.zeros(2 * E, 4, device=env.device))
+    assert not fused_evaluation_built(env)
+    pop = _population(env, 2, seed=0)
+    snap = _snapshot(env)
+    with pytest.raises(NotImplementedError):
+        evaluate_population(env, pop, fused=True, max_steps=MAX_STEPS)
+    _unchanged(env, snap)
+    env.step(torch.zeros(2 * E, 4, device=env.device))  # still a handle that steps
+    env.close()

@@ -344,8 +344,8 @@ def test_value_update_on_a_second_stream_equals_the_sequential_update_bitwise():
     a.env.close(); b.env.close()
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("task,kw,n", [
+# the configurations of test_fused_rollout_equals_per_step_rollout_bitwise (a name of its own: the sweep below flies what is NOT here)
+_ROLLOUT_BITWISE_CASES = [
     ("DroneHoverSimpleEnv-v0", dict(observation_noise=-1, domain_randomization=-1, motor_thrust_noise=0), 512),
     ("DroneHoverSimpleEnv-v0", dict(), 1000),                                   # reference defaults, ragged last tile
     ("DroneCircleSimpleEnv-v0", dict(use_motor_dynamics=True), 256),            # PT1 + DR + noise
@@ -391,21 +391,28 @@ def test_value_update_on_a_second_stream_equals_the_sequential_update_bitwise():
     ("DroneHoverSimpleEnv-v0", dict(observation_history_size=6, use_motor_dynamics=True, observation_noise=-1,
                                     domain_randomization=-1, motor_thrust_noise=0), 64 * 300),                      # 102, > 256 tiles
     ("DroneCircleSimpleEnv-v0", dict(observation_history_size=6), 70),                                              # 120
-])
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("task,kw,n", _ROLLOUT_BITWISE_CASES)
 def test_fused_rollout_equals_per_step_rollout_bitwise(task, kw, n):
     """pds_rollout (ONE launch for the T closed-loop steps: both networks on the matrix cores, Gaussian sampling, env
     step with the state in registers, V(final_obs), episode bookkeeping; csrc/pds_rollout.h) against the per-step
     kernels of round 2 (7 launches per step): every rollout buffer bit for bit, over two consecutive rollouts with an
     update of the running statistics in between, short episodes so that resets and TimeLimit truncations occur."""
+    _fused_rollout_against_per_step_rollout(task, kw, n, rollouts=2)
+
+
+def _fused_rollout_against_per_step_rollout(task, kw, n, rollouts, T=12):
     import phoenix_drone_simulation_amd as pds
     from phoenix_drone_simulation_amd.ppo import PPOTrainer
-    T = 12
     tr = []
     for fused_rollout in (True, False):
         env = pds.make(task, num_envs=n, seed=3, max_episode_steps=9, **kw)
         tr.append(PPOTrainer(env, rollout_len=T, epochs=4, seed=5, fused=True, graph_rollout=False, fused_rollout=fused_rollout))
     a, b = tr
-    for rnd in range(2):
+    for rnd in range(rollouts):
         sa, sb = a.roll_out(), b.roll_out()
         torch.cuda.synchronize()
         assert a.fused_rollout is True and b.fused_rollout is False
@@ -440,6 +447,22 @@ def test_fused_rollout_equals_per_step_rollout_bitwise(task, kw, n):
                     p_.mul_(1.01)
     for t_ in tr:
         t_.env.close()
+
+
+def _rollout_sweep_cases():
+    """every supported configuration of tests/variant_cases.py (pds_rollout and pds_evaluate_policies share one rule) whose
+    variant flags none of _ROLLOUT_BITWISE_CASES has"""
+    import variant_cases as vc
+    flown = {vc.flags_of(task, kw) for task, kw, _ in _ROLLOUT_BITWISE_CASES if kw.get("observation_history_size", 2) == 2}
+    return [(vid, env_id, kw) for vid, env_id, kw, _ in vc.SUPPORTED if vc.flags_of(env_id, kw) not in flown]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("vid,task,kw", _rollout_sweep_cases(), ids=[c[0] for c in _rollout_sweep_cases()])
+def test_fused_rollout_equals_per_step_rollout_bitwise_on_every_other_supported_configuration(vid, task, kw):
+    """the holes of the list above: the body of test_fused_rollout_equals_per_step_rollout_bitwise at n = 128 (two tiles), T = 12,
+    one rollout, for every configuration rollout_supported() (csrc/pds_types.h) names and that list does not fly"""
+    _fused_rollout_against_per_step_rollout(task, kw, 128, rollouts=1)
 
 
 @pytest.mark.gpu
