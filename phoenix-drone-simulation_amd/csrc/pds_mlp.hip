@@ -25,70 +25,47 @@
 //   weight grads dW3 = dY^T H2, dW2 = dZ2^T H1, dW1 = dZ1^T X       (K = the tile's 16 samples)
 // Bound: MFMA f32 (157 TFLOP/s dense peak on MI355X = the f32 vector rate; MI355X_MICROARCH.md).
 //
-// Round 6: from 65 536 samples on, four of ppo_split_kernel's eight GEMMs run on v_mfma_f32_16x16x32_bf16 with every operand in
-// three bf16 pieces (x = hi + mid + lo, six exact products per K = 32: more accurate than the f32 MFMA, 2.67 x its rate); see
-// PDS_SPLIT_BF16 below and DESIGN.md section 9.
-// Round 3: the PPO gradient of the reference's default policy (50-50 relu) runs on ppo_split_kernel below instead --
-// the two waves of a SIMD take different ROLES on the same tiles (forward / loss / small GEMMs vs. the large
-// weight-gradient GEMMs) so that neither carries 128 accumulator registers through phases that do not need them.
+// The PPO gradient of the reference's default policy (50-50 relu) runs on ppo_split_kernel below instead: the two
+// waves of a SIMD take different ROLES on the same tiles (forward / loss / small GEMMs vs. the large weight-gradient
+// GEMMs) so that neither carries 128 accumulator registers through phases that do not need them.  From 65 536 samples
+// on (PDS_BF16_MIN_SAMPLES) five of its eight GEMMs run on v_mfma_f32_16x16x32_bf16 with every operand in three bf16
+// pieces (x = hi + mid + lo, six exact products per K = 32: more accurate than the f32 MFMA, 2.67 x its rate); see
+// the BFP parameter below and DESIGN.md section 9.
 #include <stdlib.h>
 
 #include "pds_mlp_tile.h"  // (pds_mlp_common.h; sum_partials)
 
 namespace pds_mlp_detail {
 
-#ifndef PDS_SPLIT_WRES
-#define PDS_SPLIT_WRES 1
-#endif
-#ifndef PDS_SPLIT_DYNPRIO
-#define PDS_SPLIT_DYNPRIO 1
-#endif
-#if PDS_SPLIT_DYNPRIO  // A/B: the forward role raises its priority for its MFMA bursts only
-#define PDS_FPRIO_MFMA() __builtin_amdgcn_s_setprio(2)
-#define PDS_FPRIO_VALU() __builtin_amdgcn_s_setprio(0)
-#else
-#define PDS_FPRIO_MFMA() do { } while (0)
-#define PDS_FPRIO_VALU() do { } while (0)
-#endif
-#ifndef PDS_SPLIT_SIMD_ROLES
-#define PDS_SPLIT_SIMD_ROLES 0
-#endif
-#ifndef PDS_SPLIT_GPRIO
-#define PDS_SPLIT_GPRIO 0
-#endif
-#ifndef PDS_SPLIT_FPRIO
-#define PDS_SPLIT_FPRIO 3
-#endif
+// measuring instruments of ppo_split_kernel (profiling builds only; results of a PDS_SPLIT_DEBUG build are invalid)
 #ifndef PDS_SPLIT_STAMPS
 #define PDS_SPLIT_STAMPS 0
 #endif
 #ifndef PDS_SPLIT_DEBUG
 #define PDS_SPLIT_DEBUG 0
 #endif
-#ifndef PDS_MLP_SPLIT
-#define PDS_MLP_SPLIT 1  // weight-gradient roles of ppo_split_kernel; A/B: 2 = three waves per SIMD (measured: 454 us against 341 us at
-                         // 1 M samples -- 168 registers per wave undo F's operand prefetch), 0 = the round-2 route through mlp_kernel
-#endif
-#ifndef PDS_MLP_EDGE
-#define PDS_MLP_EDGE 1  // A/B: 0 = the fourth output tile of the 50-wide layers on the matrix cores as well
-#endif
+// the forward role of ppo_split_kernel raises its priority for its MFMA bursts only
+#define PDS_FPRIO_MFMA() __builtin_amdgcn_s_setprio(2)
+#define PDS_FPRIO_VALU() __builtin_amdgcn_s_setprio(0)
 // v_mfma_f32_4x4x1_16b_f32: 16 independent 4 x 4 outer products per instruction (block b = lane / 4: D_b[i][j] += A_b[i] B_b[j],
 // lane 4 b + i supplies A_b[i], lane 4 b + j supplies B_b[j] and holds D_b[0..3][j] in its four registers), 8 cycles
-// against 32 for a 16x16x4 tile at the same flop rate: the right shape for a 4-row or 4-column STRIP of a weight
+// against 32 for a 16x16x4 tile at the same flop rate: the right shape for a 4-row or 4-column strip of a weight
 // gradient (rank-1 update per sample), where a 16-row tile would carry 2 useful rows.
 #define PDS_MFMA44(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 0, 0, 0)
-#ifndef PDS_MLP_STRIPS
-#define PDS_MLP_STRIPS 1  // round 4, ppo_split_kernel: rows / columns 48..51 of dW2, rows 48..51 of dW1 and the whole dW3 as 4x4x1 strips; A/B: 0
-#endif
-#ifndef PDS_SPLIT_BF16_L1
-#define PDS_SPLIT_BF16_L1 1  // the forward role's layer 1 on the bf16 instruction too (W1 as an LDS image of its operand pieces, 18 KB in place of the f32 image); A/B: 0
-#endif
-#ifndef PDS_SPLIT_BF16_L2
-#define PDS_SPLIT_BF16_L2 1  // the forward role's layer 2 on the bf16 instruction too (its A operand in pieces stays in registers, layer 1's then comes from LDS); A/B: 0
-#endif
-#ifndef PDS_SPLIT_BF16
-#define PDS_SPLIT_BF16 1  // round 6, ppo_split_kernel: the weight-gradient role's three GEMMs (dZ1, dW2, dW1) as split-bf16 MFMAs; A/B: 0 = f32 MFMAs
-#endif
+// One K = 32 step of a split-bf16 GEMM: the six products of two operands in three bf16 pieces (mid mid, hi lo, lo hi,
+// hi mid, mid hi, hi hi: smallest first) onto the kNT - 1 accumulation chains cc[], which alternate.  ahi / amid / alo
+// name the A pieces of chain i_; b is the Oct3 all chains share.  A macro: the statements the kernel had, in their order.
+#define PDS_SPLIT6_(cc, ap, bp) \
+  _Pragma("unroll") for (int i_ = 0; i_ < kNT - 1; ++i_) (cc)[i_] = PDS_MFMA_BF(ap, bp, (cc)[i_])
+#define PDS_SPLIT6(cc, ahi, amid, alo, b) \
+  do {                                    \
+    PDS_SPLIT6_(cc, amid, (b).mid);       \
+    PDS_SPLIT6_(cc, ahi, (b).lo);         \
+    PDS_SPLIT6_(cc, alo, (b).hi);         \
+    PDS_SPLIT6_(cc, ahi, (b).mid);        \
+    PDS_SPLIT6_(cc, amid, (b).hi);        \
+    PDS_SPLIT6_(cc, ahi, (b).hi);         \
+  } while (0)
 #if PDS_SPLIT_DEBUG == 3  // profiling: the forward role WITHOUT its MFMAs -- operands stay alive, no instruction is
                            // issued: what the rest of its instruction stream costs the pair (results invalid)
 typedef float pds_f32x4_ __attribute__((ext_vector_type(4)));
@@ -143,47 +120,6 @@ __device__ __forceinline__ void gemm_wt2(const float *Ws, int it, const f32x4 (&
   }
 }
 
-// ---- the two edge features of a 50-wide layer on the vector ALU (round 3) --------------------------------------
-// 50 hidden units fill three 16-row MFMA tiles and TWO rows of a fourth: that tile is 12-14 MFMAs (384-448 cycles of
-// the matrix pipe) for 2 useful rows of 16.  The gradient kernels of the reference's default policy net (h1 = h2 = 50:
-// KJH == 2) compute features 48 and 49 as plain dot products instead -- each lane over the 12-16 input features it
-// holds, the four lane groups of a sample added up with two cross-lane exchanges -- ~45 vector instructions that
-// run on the OTHER pipe while the co-resident wave issues MFMAs.  Result in the C/D layout of tile 3: lanes of group
-// 0 hold (feature 48, feature 49, 0, 0), the other groups zeros (features 52..63 are padding).
-// edge_rows: rows 48, 49 of W (forward: z = W in);  edge_cols: columns 48, 49 of W (backward: dz1 = W^T dz2).
-template <int NK>
-__device__ __forceinline__ f32x4 edge_rows(const float *Ws, const f32x4 (&in)[NK], int g) {
-  float e0 = 0.f, e1 = 0.f;
-  const float *w0 = Ws + 48 * kS + 4 * g;
-#pragma unroll
-  for (int kt = 0; kt < NK; ++kt) {
-    const f32x4 a0 = lds4(w0 + kt * kTW), a1 = lds4(w0 + kS + kt * kTW);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { e0 = fmaf(a0[q], in[kt][q], e0); e1 = fmaf(a1[q], in[kt][q], e1); }
-  }
-  e0 += __shfl_xor(e0, 16); e1 += __shfl_xor(e1, 16);
-  e0 += __shfl_xor(e0, 32); e1 += __shfl_xor(e1, 32);
-  f32x4 r = (f32x4)(0.f);
-  if (g == 0) { r[0] = e0; r[1] = e1; }
-  return r;
-}
-__device__ __forceinline__ f32x4 edge_cols(const float *Ws, const f32x4 (&in)[kNT], int g) {
-  float e0 = 0.f, e1 = 0.f;
-#pragma unroll
-  for (int kt = 0; kt < kNT; ++kt) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float2 w = *reinterpret_cast<const float2 *>(Ws + (kt * kTW + 4 * g + q) * kS + 48);
-      e0 = fmaf(w.x, in[kt][q], e0); e1 = fmaf(w.y, in[kt][q], e1);
-    }
-  }
-  e0 += __shfl_xor(e0, 16); e1 += __shfl_xor(e1, 16);
-  e0 += __shfl_xor(e0, 32); e1 += __shfl_xor(e1, 32);
-  f32x4 r = (f32x4)(0.f);
-  if (g == 0) { r[0] = e0; r[1] = e1; }
-  return r;
-}
-
 // The weight images of a block: [out][in] rows of kS floats, zero padded (W1, W2: 64 rows -- W1 may be cut to W1ROWS --,
 // W3: 16 rows).  All loads of a thread are issued before its first LDS store (nine L2 round trips in flight instead of
 // one after the other: the prologue is most of a small batch's time).
@@ -218,7 +154,6 @@ __device__ __forceinline__ void stage_weights(const pds_mlp &m, float *W1s, floa
 template <int LOSS, int ACT, int NINB, bool GB, int KJI = 4, int KJH = 4>
 __global__ __launch_bounds__(kWaves * 64, 2) void mlp_kernel(const Args a) {
   constexpr int NIN = 2 + NINB;
-  constexpr bool EDGE = PDS_MLP_EDGE && LOSS != LOSS_NONE && KJH == 2;  // h1 == h2 == 50: features 48, 49 on the vector ALU
   // ---- LDS images ---------------------------------------------------------------------------------
   __shared__ __attribute__((aligned(16))) float W1s[kMaxDim * kS];  // [out][in], zero padded
   __shared__ __attribute__((aligned(16))) float W2s[kMaxDim * kS];
@@ -310,14 +245,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void mlp_kernel(const Args a) {
     // ---- forward: activations stay in registers from layer to layer -------------------------------
     f32x4 h1r[kNT], h2r[kNT];
     f32x4 cc[kNT];
-    if constexpr (EDGE) {
-      gemm_wt2<NIN, KJI>(W1s, 0, xin, n, g, cc[0], cc[1]);
-      cc[2] = gemm_wt<NIN, KJI>(W1s, 2, xin, n, g);
-      cc[3] = edge_rows<NIN>(W1s, xin, g);
-    } else {
 #pragma unroll
-      for (int it = 0; it < kNT; it += 2) gemm_wt2<NIN, KJI>(W1s, it, xin, n, g, cc[it], cc[it + 1]);
-    }
+    for (int it = 0; it < kNT; it += 2) gemm_wt2<NIN, KJI>(W1s, it, xin, n, g, cc[it], cc[it + 1]);
 #pragma unroll
     for (int it = 0; it < kNT; ++it) {  // H1^T = act(W1 X^T + b1); rows >= h1: act(0) = 0
       const f32x4 c = cc[it];
@@ -333,14 +262,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void mlp_kernel(const Args a) {
         sts4(H1img + n * kS + it * kTW + 4 * g, v);
       }
     }
-    if constexpr (EDGE) {
-      gemm_wt2<kNT, KJH>(W2s, 0, h1r, n, g, cc[0], cc[1]);
-      cc[2] = gemm_wt<kNT, KJH>(W2s, 2, h1r, n, g);
-      cc[3] = edge_rows<kNT>(W2s, h1r, g);
-    } else {
 #pragma unroll
-      for (int it = 0; it < kNT; it += 2) gemm_wt2<kNT, KJH>(W2s, it, h1r, n, g, cc[it], cc[it + 1]);
-    }
+    for (int it = 0; it < kNT; it += 2) gemm_wt2<kNT, KJH>(W2s, it, h1r, n, g, cc[it], cc[it + 1]);
 #pragma unroll
     for (int it = 0; it < kNT; ++it) {  // H2^T = act(W2 H1^T + b2)
       const f32x4 c = cc[it];
@@ -462,9 +385,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void mlp_kernel(const Args a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int jt = 0; jt < (EDGE ? kNT - 1 : kNT); ++jt)
-          if (kt < kNT - 1 || j < KJH) cc[jt] = PDS_MFMA(W2s[(kt * kTW + 4 * h + j) * kS + jt * kTW + r], dz2[kt][j], cc[jt]);
-    if constexpr (EDGE) cc[kNT - 1] = edge_cols(W2s, dz2, g);
+        for (int jt = 0; jt < kNT; ++jt) cc[jt] = PDS_MFMA(W2s[(kt * kTW + 4 * h + j) * kS + jt * kTW + r], dz2[kt][j], cc[jt]);
 #pragma unroll
     for (int jt = 0; jt < kNT; ++jt) {
       const f32x4 c = cc[jt];
@@ -590,22 +511,33 @@ __global__ __launch_bounds__(kWaves * 64, 2) void mlp_kernel(const Args a) {
   }
 }
 
-// ---- round 3: the PPO gradient of the reference's default policy net (50-50 relu, d_in < 48), wave roles ---------
+// ---- the PPO gradient of the reference's default policy net (50-50 relu, d_in < 48): wave roles -------------------
 // mlp_kernel keeps 128 weight-gradient accumulator registers live through the forward and backward GEMMs of every
 // tile; at two waves per SIMD (256 registers each) that leaves the compiler no room to fetch LDS operands ahead of
 // the MFMAs that use them -- its schedule is read -> wait -> 2 MFMAs, the waves sit in s_waitcnt for ~20 % of their
 // cycles and the matrix pipe idles a third of the time (profiles/r01_mlp_bench.txt: SQ_VALU_MFMA_BUSY 67 %).
 // Here the two waves of a SIMD take different ROLES on the same tile stream instead of different tiles:
-//   F (waves 0-3): forward, loss, dZ2 and the small dW3                -- no large accumulators, 112 MFMAs per tile
-//                    plus all the vector-ALU work of the activations and of the loss;
-//   G (waves 4-7): dZ1, dW2 += dZ2^T H1 and dW1 += dZ1^T X           -- 112 accumulator registers, 154 MFMAs per tile.
+//   F (waves 0-3): forward, loss, dZ2 and the small dW3                -- no large accumulators, plus all the
+//                    vector-ALU work of the activations and of the loss;
+//   G (waves 4-7): dZ1, dW2 += dZ2^T H1 and dW1 += dZ1^T X           -- the large accumulators (rows / columns 0..47).
+// Waves w and w + 4 share a SIMD (profiles/r03_mlp_microbench.txt), so every SIMD hosts one F and one G of the same pair.
 // F hands a tile to its G through a set of three [16 samples][52] LDS images (X, H1, dZ2); two sets per pair, so F
 // works on tile k + 1 while G consumes tile k.  Hand-over: monotonic counters in LDS (full / empty per set), release
 // fence + store after the last image write, acquire load in a sleep loop -- the 8 waves of the block are resident
 // together (one block per CU), so the wait cannot deadlock.  Measured alone (profiling builds, PDS_SPLIT_DEBUG) F needs
 // ~2 x the cycles of its MFMAs (epilogues, loss, stores), G ~1.15 x: hence dZ1 on G's side.
+// The edge of the 50-wide layers (50 = 3 x 16 + 2) never takes a 16-wide tile: F computes features 48, 49 of layers 1
+// and 2 on the vector ALU (edge_pair), G their part of dZ1 likewise; rows / columns 48..51 of dW2, rows 48..51 of dW1
+// and the whole of dW3 (4 x 50, F's) are 4x4x1 strips (PDS_MFMA44), one rank-1 update per sample.
+// BFP: dZ1, dW2, dW1 and F's layers 1 and 2 on v_mfma_f32_16x16x32_bf16, every operand in three bf16 pieces; the
+// launcher chooses it from PDS_BF16_MIN_SAMPLES samples on.  KJI: as in mlp_kernel.
+// Measured and rejected, one sentence each (verdicts: DESIGN.md sections 8b and 9; the profiles named there quote -D
+// switches of the tree up to commit fc3622f): a third wave per SIMD with dW2 as a role of its own; forward and
+// weight-gradient roles on separate SIMDs; a static priority for either role; per-tile reloads of F's weight operands;
+// 16-wide tiles for the edge; f32 MFMAs at every batch size, or for F's layers only.
 constexpr int kSI = 52;                       // image row stride: 50 features + ones column, 4 * kSI == 16 (mod 32)
 constexpr int kPairs = kWaves / 2;
+constexpr int kPrioG = 0, kPrioF = 3;         // s_setprio of the roles at entry (F: PDS_FPRIO_MFMA / _VALU from its first tile on)
 constexpr int kSetFloats = 3 * kTS * kSI;     // X, H1, dZ2
 constexpr int kPrivFloats = kTS * kSI + kTS * kSY;  // F's own H2 and dY images
 constexpr int kPrivGFloats = kTS * kSI;             // G's own dZ1 image
@@ -647,8 +579,10 @@ __device__ __forceinline__ float act_fast(float v) { return ACT == 0 ? relu1(v) 
 template <int ACT>
 __device__ __forceinline__ float act_back(float c, float h) { return ACT == 0 ? (h > 0.f ? c : 0.f) : c * (1.f - h * h); }
 
-// rows 48, 49 of a 50-wide layer on the vector ALU (see edge_rows), bias included: even / odd feature slots accumulate
-// in the two halves of v_pk_fma_f32 -- the operand pairs are adjacent registers, no moves.  wp: row 48 at this lane
+// rows 48, 49 of a 50-wide layer on the vector ALU, bias included (a fourth 16-row MFMA tile would be 12-14 MFMAs for 2
+// useful rows; these ~45 vector instructions run on the other pipe while the co-resident wave issues MFMAs): each lane
+// over the input features it holds, the four lane groups of a sample added up with two cross-lane exchanges.  Even / odd
+// feature slots accumulate in the two halves of v_pk_fma_f32 -- the operand pairs are adjacent registers, no moves.  wp: row 48 at this lane
 // group's column offset; result in the C/D layout of tile 3 (lane group 0: features 48, 49, then zeros).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int NK>
@@ -670,17 +604,14 @@ __device__ __forceinline__ f32x4 edge_pair(const float *wp, const f32x4 (&in)[NK
   return r;
 }
 
-// NG = 2 (not the default: slower, see PDS_MLP_SPLIT): the weight-gradient role split once more -- G1 (waves 4-7: dZ1,
-// dW1), G2 (waves 8-11: dW2) -- three waves per SIMD (12 per block, <= 168 registers each).
-template <int KJI, int NG, bool BFP = false>
-__global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const Args a) {
+template <int KJI, bool BFP = false>
+__global__ __launch_bounds__(512, 2) void ppo_split_kernel(const Args a) {
   constexpr int NIN = 3, KJH = 2, ACT = 0;
-  constexpr int kThreads = (1 + NG) * 256;
-  // L1B (PDS_SPLIT_BF16_L1): layer 1 of the forward role on the bf16 instruction -- W1 as an image of its A operands in pieces
-  // ([row tile][k step][piece][lane] x 16 bytes, 18 KB) INSTEAD of the f32 image (13.6 KB), of which only rows 48, 49 remain
-  constexpr bool L1B = BFP && PDS_SPLIT_BF16 != 0 && PDS_SPLIT_BF16_L1 != 0 && PDS_SPLIT_BF16_L2 != 0 && PDS_SPLIT_WRES != 0 && PDS_MLP_STRIPS != 0 && NG == 1;
-  __shared__ __attribute__((aligned(16))) float W1s[(L1B ? 2 : kW1Rows) * kS];  // rows 48, 49: the vector-ALU features
-  __shared__ __attribute__((aligned(16))) uint32_t W1b[L1B ? (kNT - 1) * 2 * 3 * 64 * 4 : 4];
+  constexpr int kThreads = 512;
+  // BFP: layer 1 of the forward role reads W1 as an image of its A operands in pieces ([row tile][k step][piece][lane]
+  // x 16 bytes, 18 KB) INSTEAD of the f32 image (13.6 KB), of which only rows 48, 49 remain
+  __shared__ __attribute__((aligned(16))) float W1s[(BFP ? 2 : kW1Rows) * kS];  // rows 48, 49: the vector-ALU features
+  __shared__ __attribute__((aligned(16))) uint32_t W1b[BFP ? (kNT - 1) * 2 * 3 * 64 * 4 : 4];
   __shared__ __attribute__((aligned(16))) float W2s[kMaxDim * kS];
   __shared__ __attribute__((aligned(16))) float W3s[kTW * kS];
   __shared__ __attribute__((aligned(16))) float b1s[kMaxDim], b2s[kMaxDim], b3s[kTW];
@@ -688,24 +619,15 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
   __shared__ __attribute__((aligned(16))) float sets[kPairs * 2 * kSetFloats];
   __shared__ __attribute__((aligned(16))) float priv[kPairs * kPrivFloats];
   __shared__ __attribute__((aligned(16))) float privg[kPairs * kPrivGFloats];
-  __shared__ int flags[kPairs * 8];  // per pair: full[2], empty[2] (G / G1), empty2[2] (G2)
+  __shared__ int flags[kPairs * 8];  // per pair: full[2], empty[2] (stride 8)
   const pds_mlp &m = a.m;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // Which waves share a SIMD: w and w + 4 (profiles/r03_mlp_microbench.txt).  PDS_SPLIT_SIMD_ROLES = 0 (rounds 3-4): F_p = wave p,
-  // G_p = wave p + 4 -- every SIMD hosts one F and one G.  1: the two F waves of pairs (p, p + 2) on one SIMD and their G waves
-  // on another -- SIMDs 0, 1 run forward roles only, SIMDs 2, 3 weight-gradient roles only (NG == 1).  Same tiles per pair and the
-  // same reduction order by pair index: bit-identical results either way.
-#if PDS_SPLIT_SIMD_ROLES
-  const int pair = NG == 1 ? ((wave & 1) | ((wave >> 2) << 1)) : (wave & 3);
-  const int role = NG == 1 ? ((wave >> 1) & 1) : (wave >> 2);
-#else
   const int pair = wave & 3;
-  const int role = wave >> 2;  // 0: F, 1: G (NG = 1) or G1, 2: G2
-#endif
+  const int role = wave >> 2;  // 0: F, 1: G
   const int n = lane & 15, g = lane >> 4;
-  stage_weights<L1B ? 0 : kW1Rows, kThreads>(m, W1s, W2s, W3s, tid);
-  if constexpr (L1B) {
+  stage_weights<BFP ? 0 : kW1Rows, kThreads>(m, W1s, W2s, W3s, tid);
+  if constexpr (BFP) {
     for (int i = tid; i < 2 * kS; i += kThreads) {
       const int rr = 48 + i / kS, k = i % kS;
       W1s[i] = (rr < m.h1 && k < m.d_in) ? m.w1[rr * m.d_in + k] : 0.f;
@@ -741,70 +663,40 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
 
   const long long ntiles = (a.B + kTS - 1) / kTS;
   const long long pid = (long long)blockIdx.x * kPairs + pair, np = (long long)gridDim.x * kPairs;
-  int *full = flags + pair * 8, *empty = full + 2, *empty2 = full + 4;
+  int *full = flags + pair * 8, *empty = full + 2;
   float *pset = sets + pair * 2 * kSetFloats;
   const int r = n, h = g;  // A-operand lane roles of the weight-gradient GEMMs (k-slot (j, h) = sample 4 h + j)
-  const int n3 = min(n, 3);  // column tile 3 of a 52-wide image holds columns 48..51 only
 
-  f32x4 gW1[kNT][NIN], gW2[kNT][kNT], gW3[kNT];
+  // Weight-gradient accumulators.  Full 16-wide tiles cover rows / columns 0..47 of dW2 and rows 0..47 of dW1 (G); the
+  // edge is 4x4x1 strips: gW2r = rows 48..51 of dW2 x all columns (lane l: column l), gW2c = all rows x columns 48..51
+  // (lane l: rows 4 (l / 4) .. + 3, column 48 + l % 4), gW1r = rows 48..51 of dW1 x all input columns (G), and dW3
+  // (d_out x 50) is gW3s (outputs 0..3) and gW3s2 (outputs 4..7) on F's side: 16 rank-1 updates (one per sample) of
+  // 8 cycles each per strip.
+  constexpr int NTF = kNT - 1;  // full 16-wide tiles per hidden dimension
+  f32x4 gW1[NTF][NIN], gW2[kNT][kNT];  // (gW2: tile row / column 3 stay zero, see the block sums)
   float st_loss = 0.f, st_ratio = 0.f, st_kl = 0.f, st_cnt = 0.f;
 #pragma unroll
-  for (int i = 0; i < kNT; ++i) {
-    gW3[i] = (f32x4)(0.f);
+  for (int i = 0; i < kNT; ++i) {  // (one loop, gW2 first: two loops move the scalar registers of the prologue)
 #pragma unroll
     for (int j = 0; j < kNT; ++j) gW2[i][j] = (f32x4)(0.f);
 #pragma unroll
-    for (int j = 0; j < NIN; ++j) gW1[i][j] = (f32x4)(0.f);
+    for (int j = 0; j < NIN; ++j) if (i < NTF) gW1[i][j] = (f32x4)(0.f);
   }
-
-  // Round 4 (NG = 1): the edge of the 50-wide layers as 4x4x1 strips.  50 = 3 x 16 + 2, so row tile 3 / column tile 3 of
-  // dW2 and row tile 3 of dW1 were 16-wide tiles with 2 (3 with the bias column) useful rows or columns: 7 of dW2's 16
-  // tiles and 3 of dW1's 12, 40 of G's 154 MFMAs per 16 samples.  Now: gW2r = rows 48..51 x all columns (lane l: column
-  // l), gW2c = all rows x columns 48..51 (lane l: rows 4 (l / 4) .. + 3, column 48 + l % 4), gW1r = rows 48..51 of dW1
-  // x all input columns; 16 rank-1 updates (one per sample) of 8 cycles each per strip instead of 4 k-steps x 32 cycles
-  // per tile.  The full tiles cover rows / columns 0..47.  dW3 (4 x 50) is one such strip on F's side (gW3s).
-  constexpr bool STRIP = PDS_MLP_STRIPS != 0 && NG == 1;
-  constexpr int NTF = STRIP ? kNT - 1 : kNT;  // full 16-wide tiles per hidden dimension
-  constexpr bool BF = BFP && PDS_SPLIT_BF16 != 0 && STRIP;  // the weight-gradient role's full-tile GEMMs on v_mfma_f32_16x16x32_bf16 (three pieces per operand)
   f32x4 gW2r = (f32x4)(0.f), gW2c = (f32x4)(0.f), gW1r = (f32x4)(0.f), gW3s = (f32x4)(0.f), gW3s2 = (f32x4)(0.f);
   const int lc = lane < kSI ? lane : kSI - 1;  // column of a 52-wide image row (lanes 52..63: clamped, their results are dropped)
 
-  if (NG == 2 && role == 2) {
-    // ================= G2 (NG = 2): dW2 += dZ2^T H1 =========================================================
-    const int r3 = min(r, 3);
-    int k = 0;
-    for (long long t = pid; t < ntiles; t += np, ++k) {
-      const int s = k & 1;
-      const float *H1img = pset + s * kSetFloats + kTS * kSI, *dZ2img = H1img + kTS * kSI;
-      wait_ge(full + s, (k >> 1) + 1);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float av[kNT], bv[kNT];
-        const int row = (4 * h + j) * kSI;
-#pragma unroll
-        for (int i = 0; i < kNT; ++i) {
-          av[i] = dZ2img[row + i * kTW + (i == kNT - 1 ? r3 : r)];
-          bv[i] = H1img[row + i * kTW + (i == kNT - 1 ? n3 : n)];
-        }
-#pragma unroll
-        for (int it = 0; it < kNT; ++it)
-#pragma unroll
-          for (int jt = 0; jt < kNT; ++jt) gW2[it][jt] = PDS_MFMA(av[it], bv[jt], gW2[it][jt]);
-      }
-      signal(empty2 + s, (k >> 1) + 1, lane);
-    }
-  } else if (role == 1) {
-    // ================= G (NG = 1) / G1: dZ1 and the weight-gradient GEMMs =========================================
-    __builtin_amdgcn_s_setprio(PDS_SPLIT_GPRIO);
+  if (role == 1) {
+    // ================= G: dZ1 and the weight-gradient GEMMs ====================================================
+    __builtin_amdgcn_s_setprio(kPrioG);
     float *dZ1img = privg + pair * kPrivGFloats;
     float wz1[kNT][4][kNT - 1];  // W2^T read column-wise: tile invariant, kept in registers
-    // BF (PDS_SPLIT_BF16): the same operand for the K = 32 instruction, in three bf16 pieces.  The k index of an MFMA is a dummy
+    // BFP: the same operand for the K = 32 instruction, in three bf16 pieces.  The k index of an MFMA is a dummy
     // index, so its slots can be assigned freely as long as A and B agree: slot (lane group h, i) of step ks carries h2 feature
     // 16 (2 ks) + 4 h + i for i < 4 and 16 (2 ks + 1) + 4 h + (i - 4) for i >= 4 -- the B operand is then the lane's own dZ2
     // registers of two feature tiles (the C/D layout), exactly as in the f32 form; no cross-lane movement.
     // Tile invariant, kept in registers like wz1 (72 instead of 48; an LDS image of it would be 18 KB the block does not have).
     Oct3 wzb[2][kNT - 1];
-    if constexpr (BF) {
+    if constexpr (BFP) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -826,7 +718,6 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
           for (int jt = 0; jt < kNT - 1; ++jt)
             wz1[kt][j][jt] = (kt < kNT - 1 || j < KJH) ? W2s[(kt * kTW + 4 * h + j) * kS + jt * kTW + r] : 0.f;
     }
-    const int r3 = min(r, 3);
     int k = 0;
     for (long long t = pid; t < ntiles; t += np, ++k) {
       const int s = k & 1;
@@ -847,7 +738,7 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
         for (int q = 0; q < 4; ++q) we[kt][q] = *reinterpret_cast<const float2 *>(W2s + (kt * kTW + 4 * g + q) * kS + 48);
       // ---- dZ1^T = (W2^T dZ2^T) * act'(H1^T): three chains ----
       f32x4 cc[kNT];
-      if constexpr (BF) {
+      if constexpr (BFP) {
         Oct3 bz[2];
         bz[0] = oct3(split4(dz2[0]), split4(dz2[1]));
         bz[1] = oct3(split4(dz2[2]), split4(dz2[3]));
@@ -855,18 +746,7 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
         for (int jt = 0; jt < kNT - 1; ++jt) cc[jt] = (f32x4)(0.f);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {  // six products per step, smallest first; the three chains alternate
-#pragma unroll
-          for (int jt = 0; jt < kNT - 1; ++jt) cc[jt] = PDS_MFMA_BF(wzb[ks][jt].mid, bz[ks].mid, cc[jt]);
-#pragma unroll
-          for (int jt = 0; jt < kNT - 1; ++jt) cc[jt] = PDS_MFMA_BF(wzb[ks][jt].hi, bz[ks].lo, cc[jt]);
-#pragma unroll
-          for (int jt = 0; jt < kNT - 1; ++jt) cc[jt] = PDS_MFMA_BF(wzb[ks][jt].lo, bz[ks].hi, cc[jt]);
-#pragma unroll
-          for (int jt = 0; jt < kNT - 1; ++jt) cc[jt] = PDS_MFMA_BF(wzb[ks][jt].hi, bz[ks].mid, cc[jt]);
-#pragma unroll
-          for (int jt = 0; jt < kNT - 1; ++jt) cc[jt] = PDS_MFMA_BF(wzb[ks][jt].mid, bz[ks].hi, cc[jt]);
-#pragma unroll
-          for (int jt = 0; jt < kNT - 1; ++jt) cc[jt] = PDS_MFMA_BF(wzb[ks][jt].hi, bz[ks].hi, cc[jt]);
+          PDS_SPLIT6(cc, wzb[ks][i_].hi, wzb[ks][i_].mid, wzb[ks][i_].lo, bz[ks]);
         }
       } else {
 #pragma unroll
@@ -879,12 +759,12 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
                 cc[jt] = PDS_MFMA(wz1[kt][j][jt], dz2[kt][j], (kt == 0 && j == 0) ? (f32x4)(0.f) : cc[jt]);
       }
       PDS_SSTAMP(1, 2);
-      // ---- dW2 += dZ2^T H1 (covers the result latency of dZ1; G2's job when there is one) ----
-      // BF: K = the tile's 16 samples x TWO piece combinations -- slot (h, i < 4) = sample 4 h + i with pieces (a, b), slot
+      // ---- dW2 += dZ2^T H1 (covers the result latency of dZ1) ----
+      // BFP: K = the tile's 16 samples x TWO piece combinations -- slot (h, i < 4) = sample 4 h + i with pieces (a, b), slot
       // (h, i >= 4) = the same sample with pieces (a', b'): (hi hi | hi mid), (mid hi | hi lo), (lo hi | mid mid) are the six
       // products in three instructions.  Operands: the same four dword reads per lane and 16 x 16 block as the f32 form
       // (samples 4 h .. 4 h + 3 of one feature), split in registers.
-      if constexpr (BF) {
+      if constexpr (BFP) {
         Quad3 qa[NTF], qb[NTF];
 #pragma unroll
         for (int i = 0; i < NTF; ++i) {
@@ -897,41 +777,28 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
           qa[i] = split4(va);
           qb[i] = split4(vb);
         }
-#pragma unroll
-        for (int it = 0; it < NTF; ++it)
-#pragma unroll
-          for (int jt = 0; jt < NTF; ++jt) gW2[it][jt] = PDS_MFMA_BF(cat8(qa[it].lo, qa[it].mid), cat8(qb[jt].hi, qb[jt].mid), gW2[it][jt]);
-#pragma unroll
-        for (int it = 0; it < NTF; ++it)
-#pragma unroll
-          for (int jt = 0; jt < NTF; ++jt) gW2[it][jt] = PDS_MFMA_BF(cat8(qa[it].mid, qa[it].hi), cat8(qb[jt].hi, qb[jt].lo), gW2[it][jt]);
-#pragma unroll
-        for (int it = 0; it < NTF; ++it)
-#pragma unroll
-          for (int jt = 0; jt < NTF; ++jt) gW2[it][jt] = PDS_MFMA_BF(cat8(qa[it].hi, qa[it].hi), cat8(qb[jt].hi, qb[jt].mid), gW2[it][jt]);
+        outer_bf16(qa, qb, [&](int it, int jt) -> f32x4 & { return gW2[it][jt]; });
       }
 #pragma unroll
-      for (int j = 0; j < ((NG == 1 && !BF) ? 4 : 0); ++j) {
-        float av[kNT], bv[kNT];
+      for (int j = 0; j < (BFP ? 0 : 4); ++j) {
+        float av[NTF], bv[NTF];
         const int row = (4 * h + j) * kSI;
 #pragma unroll
         for (int i = 0; i < NTF; ++i) {
-          av[i] = dZ2img[row + i * kTW + (i == kNT - 1 ? r3 : r)];
-          bv[i] = H1img[row + i * kTW + (i == kNT - 1 ? n3 : n)];
+          av[i] = dZ2img[row + i * kTW + r];
+          bv[i] = H1img[row + i * kTW + n];
         }
 #pragma unroll
         for (int it = 0; it < NTF; ++it)
 #pragma unroll
           for (int jt = 0; jt < NTF; ++jt) gW2[it][jt] = PDS_MFMA(av[it], bv[jt], gW2[it][jt]);
       }
-      if constexpr (STRIP) {  // rows and columns 48..51 of dW2: one rank-1 update per sample and strip
 #pragma unroll
-        for (int sm = 0; sm < kTS; ++sm) {
-          const float dzr = dZ2img[sm * kSI + 48 + (lane & 3)], dzc = dZ2img[sm * kSI + lc];
-          const float h1r_ = H1img[sm * kSI + lc], h1c = H1img[sm * kSI + 48 + (lane & 3)];
-          gW2r = PDS_MFMA44(dzr, h1r_, gW2r);
-          gW2c = PDS_MFMA44(dzc, h1c, gW2c);
-        }
+      for (int sm = 0; sm < kTS; ++sm) {  // rows and columns 48..51 of dW2: one rank-1 update per sample and strip
+        const float dzr = dZ2img[sm * kSI + 48 + (lane & 3)], dzc = dZ2img[sm * kSI + lc];
+        const float h1r_ = H1img[sm * kSI + lc], h1c = H1img[sm * kSI + 48 + (lane & 3)];
+        gW2r = PDS_MFMA44(dzr, h1r_, gW2r);
+        gW2c = PDS_MFMA44(dzc, h1c, gW2c);
       }
       PDS_SSTAMP(1, 3);
       {
@@ -956,7 +823,7 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
       }
       PDS_WAVE_SYNC();
       PDS_SSTAMP(1, 4);
-      if constexpr (BF) {  // dW1 += dZ1^T X, as dW2 above
+      if constexpr (BFP) {  // dW1 += dZ1^T X, as dW2 above
         Quad3 qa[NTF], qb[NIN];
 #pragma unroll
         for (int i = 0; i < NTF; ++i) {
@@ -972,25 +839,14 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
           for (int j = 0; j < 4; ++j) vb[j] = Ximg[(4 * h + j) * kSI + i * kTW + n];
           qb[i] = split4(vb);
         }
-#pragma unroll
-        for (int it = 0; it < NTF; ++it)
-#pragma unroll
-          for (int kt = 0; kt < NIN; ++kt) gW1[it][kt] = PDS_MFMA_BF(cat8(qa[it].lo, qa[it].mid), cat8(qb[kt].hi, qb[kt].mid), gW1[it][kt]);
-#pragma unroll
-        for (int it = 0; it < NTF; ++it)
-#pragma unroll
-          for (int kt = 0; kt < NIN; ++kt) gW1[it][kt] = PDS_MFMA_BF(cat8(qa[it].mid, qa[it].hi), cat8(qb[kt].hi, qb[kt].lo), gW1[it][kt]);
-#pragma unroll
-        for (int it = 0; it < NTF; ++it)
-#pragma unroll
-          for (int kt = 0; kt < NIN; ++kt) gW1[it][kt] = PDS_MFMA_BF(cat8(qa[it].hi, qa[it].hi), cat8(qb[kt].hi, qb[kt].mid), gW1[it][kt]);
+        outer_bf16(qa, qb, [&](int it, int kt) -> f32x4 & { return gW1[it][kt]; });
       }
 #pragma unroll
-      for (int j = 0; j < (BF ? 0 : 4); ++j) {  // dW1 += dZ1^T X
-        float av[kNT], bv[NIN];
+      for (int j = 0; j < (BFP ? 0 : 4); ++j) {  // dW1 += dZ1^T X
+        float av[NTF], bv[NIN];
         const int row = (4 * h + j) * kSI;
 #pragma unroll
-        for (int i = 0; i < NTF; ++i) av[i] = dZ1img[row + i * kTW + (i == kNT - 1 ? r3 : r)];
+        for (int i = 0; i < NTF; ++i) av[i] = dZ1img[row + i * kTW + r];
 #pragma unroll
         for (int i = 0; i < NIN; ++i) bv[i] = Ximg[row + i * kTW + n];
 #pragma unroll
@@ -998,10 +854,9 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
 #pragma unroll
           for (int kt = 0; kt < NIN; ++kt) gW1[it][kt] = PDS_MFMA(av[it], bv[kt], gW1[it][kt]);
       }
-      if constexpr (STRIP) {  // rows 48..51 of dW1
 #pragma unroll
-        for (int sm = 0; sm < kTS; ++sm) gW1r = PDS_MFMA44(dZ1img[sm * kSI + 48 + (lane & 3)], Ximg[sm * kSI + lc], gW1r);
-      }
+      for (int sm = 0; sm < kTS; ++sm)  // rows 48..51 of dW1
+        gW1r = PDS_MFMA44(dZ1img[sm * kSI + 48 + (lane & 3)], Ximg[sm * kSI + lc], gW1r);
       PDS_SSTAMP(1, 5);
 #endif
       signal(empty + s, (k >> 1) + 1, lane);
@@ -1010,10 +865,10 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
   } else {
     // ================= F: forward, loss, backward through the activations, dW3 ================================
     // Source order = issue order here (the compiler keeps it when registers allow).  F's weights are tile invariant:
-    // the A operands of the three forward GEMMs (PDS_SPLIT_WRES) and W3^T (dZ2's operand) stay in registers; what is
-    // left in LDS (the two vector-ALU rows, the images) is read a phase ahead of its use.
+    // the A operands of the three forward GEMMs and W3^T (dZ2's operand) stay in registers (100 registers instead of 25
+    // b128 LDS reads per tile); what is left in LDS (the two vector-ALU rows, the images) is read a phase ahead of its use.
     // F's MFMAs come in bursts between vector-ALU phases; it raises its priority for the bursts (PDS_FPRIO_MFMA).
-    __builtin_amdgcn_s_setprio(PDS_SPLIT_FPRIO);
+    __builtin_amdgcn_s_setprio(kPrioF);
     float *H2img = priv + pair * kPrivFloats, *dYimg = H2img + kTS * kSI;
     float wz2[kNT];
 #pragma unroll
@@ -1027,29 +882,25 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
         for (int q = 0; q < 4; ++q) raw[kt][q] = xr[min(kt * kTW + 4 * g + q, m.d_in - 1)];
     };
     const float *w1p = W1s + n * kS + 4 * g, *w2p = W2s + n * kS + 4 * g, *w3p = W3s + n * kS + 4 * g;
-    const float *e1p = W1s + (L1B ? 0 : 48) * kS + 4 * g, *e2p = W2s + 48 * kS + 4 * g;
-#if PDS_SPLIT_WRES  // the forward GEMMs' weight operands are tile invariant: 100 registers instead of 25 b128 LDS reads per tile
+    const float *e1p = W1s + (BFP ? 0 : 48) * kS + 4 * g, *e2p = W2s + 48 * kS + 4 * g;
     f32x4 a1[kNT - 1][NIN], a2[kNT - 1][kNT], a3[kNT];
 #pragma unroll
     for (int kt = 0; kt < NIN; ++kt)
 #pragma unroll
-      for (int it = 0; it < kNT - 1; ++it) a1[it][kt] = L1B ? (f32x4)(0.f) : lds4(w1p + it * kTW * kS + kt * kTW);
+      for (int it = 0; it < kNT - 1; ++it) a1[it][kt] = BFP ? (f32x4)(0.f) : lds4(w1p + it * kTW * kS + kt * kTW);
 #pragma unroll
     for (int kt = 0; kt < kNT; ++kt) {
 #pragma unroll
       for (int it = 0; it < kNT - 1; ++it) a2[it][kt] = lds4(w2p + it * kTW * kS + kt * kTW);
       a3[kt] = lds4(w3p + kt * kTW);
     }
-#endif
-#if PDS_SPLIT_BF16_L2 && PDS_SPLIT_WRES  // A/B: layer 2 of the forward role on the bf16 instruction as well (k-slots as in G's dZ1)
-    Oct3 a2b[kNT - 1][2];
-    if constexpr (BF) {
+    Oct3 a2b[kNT - 1][2];  // BFP: layer 2's operand in pieces (k-slots as in G's dZ1)
+    if constexpr (BFP) {
 #pragma unroll
       for (int it = 0; it < kNT - 1; ++it)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) a2b[it][ks] = oct3(split4(a2[it][2 * ks]), split4(a2[it][2 * ks + 1]));
     }
-#endif
     f32x4 xraw[NIN];
     load_x(pid, xraw);
     int k = 0;
@@ -1057,21 +908,13 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
       const int s = k & 1;
       float *Ximg = pset + s * kSetFloats, *H1img = Ximg + kTS * kSI, *dZ2img = H1img + kTS * kSI;
 #if PDS_SPLIT_DEBUG == 2
-      if (k >= 2) { wait_ge(empty + s, k >> 1); if (NG == 2) wait_ge(empty2 + s, k >> 1); }
+      if (k >= 2) wait_ge(empty + s, k >> 1);
       signal(full + s, (k >> 1) + 1, lane);
       continue;
 #endif
       PDS_SSTAMP(0, 0);
       const long long s0 = t * kTS;
       const bool valid = s0 + n < a.B;
-      // operands of layer 1 (and of its two vector-ALU rows)
-#if !PDS_SPLIT_WRES
-      f32x4 a1[kNT - 1][NIN];
-#pragma unroll
-      for (int kt = 0; kt < NIN; ++kt)
-#pragma unroll
-        for (int it = 0; it < kNT - 1; ++it) a1[it][kt] = lds4(w1p + it * kTW * kS + kt * kTW);
-#endif
       // no masking of the input: a sample outside the batch carries gcoef = 0 (its forward pass runs on the clamped
       // row and is discarded), and a feature slot >= d_in (a clamped re-read) meets a zero column of W1 on the way
       // forward and a discarded column of dW1 on the way back
@@ -1085,29 +928,18 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
           if (4 * g + q < m.d_out) c_act[q] = a.act[(s0 + n) * m.d_out + 4 * g + q];
         c_adv = a.adv[s0 + n]; c_old = a.logp_old[s0 + n];
       }
-      if (k >= 2) {  // the weight-gradient waves are done with the tile that used this set
-        wait_ge(empty + s, k >> 1);
-        if (NG == 2) wait_ge(empty2 + s, k >> 1);
-      }
+      if (k >= 2) wait_ge(empty + s, k >> 1);  // the weight-gradient wave is done with the tile that used this set
       PDS_SSTAMP(0, 1);
 #pragma unroll
       for (int kt = 0; kt < NIN; ++kt) sts4(Ximg + n * kSI + kt * kTW + 4 * g, xin[kt]);
       if (g == 0) Ximg[n * kSI + m.d_in] = 1.f;  // the bias column of dW1 (after the row's b128 stores: LDS keeps a wave's order)
-      // operands of layer 2: in flight during the MFMAs of layer 1
-#if !PDS_SPLIT_WRES
-      f32x4 a2[kNT - 1][kNT];
-#pragma unroll
-      for (int kt = 0; kt < kNT; ++kt)
-#pragma unroll
-        for (int it = 0; it < kNT - 1; ++it) a2[it][kt] = lds4(w2p + it * kTW * kS + kt * kTW);
-#endif
       PDS_FPRIO_MFMA();
       // ---- layer 1: three accumulation chains alternate (tiles 0..2), each started from its bias; features 48, 49
       // on the vector ALU (packed pairs: even / odd feature slots) ----
       f32x4 h1r[kNT], h2r[kNT], cc[kNT];
 #pragma unroll
       for (int it = 0; it < kNT - 1; ++it) cc[it] = lds4(b1s + it * kTW + 4 * g);
-      if constexpr (L1B) {
+      if constexpr (BFP) {
         static_assert(NIN == 3, "two k steps: input tiles (0, 1) and (2, none)");
         Oct3 bx[2];
         bx[0] = oct3(split4(xin[0]), split4(xin[1]));
@@ -1117,47 +949,21 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
         };
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(w1b(it, ks, 1), bx[ks].mid, cc[it]);
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(w1b(it, ks, 0), bx[ks].lo, cc[it]);
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(w1b(it, ks, 2), bx[ks].hi, cc[it]);
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(w1b(it, ks, 0), bx[ks].mid, cc[it]);
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(w1b(it, ks, 1), bx[ks].hi, cc[it]);
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(w1b(it, ks, 0), bx[ks].hi, cc[it]);
+          PDS_SPLIT6(cc, w1b(i_, ks, 0), w1b(i_, ks, 1), w1b(i_, ks, 2), bx[ks]);
         }
       } else {
-#if PDS_SPLIT_BF16_L2 && PDS_SPLIT_WRES  // (layer 2's operand is 72 registers in pieces: layer 1's then comes from LDS per tile, 9 b128 reads)
-      f32x4 a1t[kNT - 1][NIN];
 #pragma unroll
-      for (int kt = 0; kt < NIN; ++kt)
+        for (int kt = 0; kt < NIN; ++kt)
 #pragma unroll
-        for (int it = 0; it < kNT - 1; ++it) a1t[it][kt] = BF ? lds4(w1p + it * kTW * kS + kt * kTW) : a1[it][kt];
-#else
-      f32x4 (&a1t)[kNT - 1][NIN] = a1;
-#endif
+          for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int kt = 0; kt < NIN; ++kt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it)
-            if (kt < NIN - 1 || j < KJI) cc[it] = PDS_MFMA_F(a1t[it][kt][j], xin[kt][j], cc[it]);
+            for (int it = 0; it < kNT - 1; ++it)
+              if (kt < NIN - 1 || j < KJI) cc[it] = PDS_MFMA_F(a1[it][kt][j], xin[kt][j], cc[it]);
       }
       PDS_FPRIO_VALU();
       PDS_SSTAMP(0, 2);
       load_x(t + np, xraw);  // the next tile's rows: in flight during the rest of this tile
       cc[kNT - 1] = edge_pair<NIN>(e1p, xin, b1s + 48, g);
-      // operands of layer 3
-#if !PDS_SPLIT_WRES
-      f32x4 a3[kNT];
-#pragma unroll
-      for (int kt = 0; kt < kNT; ++kt) a3[kt] = lds4(w3p + kt * kTW);
-#endif
 #pragma unroll
       for (int it = 0; it < kNT; ++it) {
 #pragma unroll
@@ -1171,36 +977,22 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
       // ---- layer 2 ----
 #pragma unroll
       for (int it = 0; it < kNT - 1; ++it) cc[it] = lds4(b2s + it * kTW + 4 * g);
-#if PDS_SPLIT_BF16_L2 && PDS_SPLIT_WRES
-      if constexpr (BF) {
+      if constexpr (BFP) {
         Oct3 bh[2];
         bh[0] = oct3(split4(h1r[0]), split4(h1r[1]));
         bh[1] = oct3(split4(h1r[2]), split4(h1r[3]));
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(a2b[it][ks].mid, bh[ks].mid, cc[it]);
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(a2b[it][ks].hi, bh[ks].lo, cc[it]);
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(a2b[it][ks].lo, bh[ks].hi, cc[it]);
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(a2b[it][ks].hi, bh[ks].mid, cc[it]);
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(a2b[it][ks].mid, bh[ks].hi, cc[it]);
-#pragma unroll
-          for (int it = 0; it < kNT - 1; ++it) cc[it] = PDS_MFMA_BF(a2b[it][ks].hi, bh[ks].hi, cc[it]);
+          PDS_SPLIT6(cc, a2b[i_][ks].hi, a2b[i_][ks].mid, a2b[i_][ks].lo, bh[ks]);
         }
-      } else
-#endif
-      {
+      } else {
 #pragma unroll
-      for (int kt = 0; kt < kNT; ++kt)
+        for (int kt = 0; kt < kNT; ++kt)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+          for (int j = 0; j < 4; ++j)
 #pragma unroll
-          for (int it = 0; it < kNT - 1; ++it)
-            if (kt < kNT - 1 || j < KJH) cc[it] = PDS_MFMA_F(a2[it][kt][j], h1r[kt][j], cc[it]);
+            for (int it = 0; it < kNT - 1; ++it)
+              if (kt < kNT - 1 || j < KJH) cc[it] = PDS_MFMA_F(a2[it][kt][j], h1r[kt][j], cc[it]);
       }
       PDS_FPRIO_VALU();
       PDS_SSTAMP(0, 4);
@@ -1265,19 +1057,9 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
       PDS_SSTAMP(0, 7);
       // operands of dZ2 (B: one dword of dY) and of dW3
       const float dyb = dYimg[n * kSY + h];
-      float av3[4], bv3[4][kNT];
-      float sa3[kTS], sb3[kTS];  // STRIP: dY[sample][lane % 4], H2[sample][lane]
-      if constexpr (STRIP) {
+      float sa3[kTS], sb3[kTS];  // dY[sample][lane % 4], H2[sample][lane]
 #pragma unroll
-        for (int sm = 0; sm < kTS; ++sm) { sa3[sm] = dYimg[sm * kSY + (lane & 3)]; sb3[sm] = H2img[sm * kSI + lc]; }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          av3[j] = dYimg[(4 * h + j) * kSY + r];
-#pragma unroll
-          for (int jt = 0; jt < kNT; ++jt) bv3[j][jt] = H2img[(4 * h + j) * kSI + jt * kTW + (jt == kNT - 1 ? n3 : n)];
-        }
-      }
+      for (int sm = 0; sm < kTS; ++sm) { sa3[sm] = dYimg[sm * kSY + (lane & 3)]; sb3[sm] = H2img[sm * kSI + lc]; }
       PDS_FPRIO_MFMA();
       // ---- dZ2^T = (W3^T dY^T) * act'(H2^T): the k-slot (step jj, lane group h) carries output 4 jj + h, so one
       // step covers the 4 action dimensions of the drone (mlp_kernel's slot order needs 4 steps for them) ----
@@ -1289,18 +1071,11 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
         for (int it = 0; it < kNT; ++it) cc[it] = PDS_MFMA_F(W3s[(4 + h) * kS + it * kTW + r], dyb2, cc[it]);
       }
       // ---- dW3 += dY^T H2 (its MFMAs cover the result latency of dZ2): a 4-row strip, one rank-1 update per sample ----
-      if constexpr (STRIP) {
 #pragma unroll
-        for (int sm = 0; sm < kTS; ++sm) gW3s = PDS_MFMA44(sa3[sm], sb3[sm], gW3s);
-        if (m.d_out > 4) {
+      for (int sm = 0; sm < kTS; ++sm) gW3s = PDS_MFMA44(sa3[sm], sb3[sm], gW3s);
+      if (m.d_out > 4) {
 #pragma unroll
-          for (int sm = 0; sm < kTS; ++sm) gW3s2 = PDS_MFMA44(dYimg[sm * kSY + 4 + (lane & 3)], sb3[sm], gW3s2);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int jt = 0; jt < kNT; ++jt) gW3[jt] = PDS_MFMA_F(av3[j], bv3[j][jt], gW3[jt]);
+        for (int sm = 0; sm < kTS; ++sm) gW3s2 = PDS_MFMA44(dYimg[sm * kSY + 4 + (lane & 3)], sb3[sm], gW3s2);
       }
       PDS_FPRIO_VALU();
       PDS_SSTAMP(0, 8);
@@ -1317,11 +1092,16 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
     }
   }
 
-  // ---- block sums: the 4 waves of each role add up what that role accumulates (F: dW3, statistics; G / G1: dW1 (+ dW2);
-  // G2: dW2); rounds 2,3 -> 0,1 and 1 -> 0 through LDS (the images are free now) -------------------------------------
+  // ---- block sums: the 4 waves of each role add up what that role accumulates (F: dW3, statistics; G: dW1, dW2);
+  // rounds 2,3 -> 0,1 and 1 -> 0 through LDS (the images are free now) ------------------------------------------------
+  // A block has 8 waves, so role is 0 or 1; the compiler cannot see that through readfirstlane, and the code objects
+  // have always carried a `role == 2` arm here (it served the retired three-role form and never runs).  It stays, word
+  // for word, with its kRegs2 and the role tests inside the write-out loops below: without the arm each of the
+  // four kernels is 250 to 390 instructions shorter (profiles/mlp_variant_retirement.txt), which is a change of the
+  // running code to measure on its own, not a deletion.  Only this arm reads tile row / column 3 of gW2 (zero).
   {
-    constexpr int kRegs1 = 4 * (kNT * NIN + (NG == 1 ? kNT * kNT : 0)), kRegs2 = 4 * kNT * kNT, kRegsF = 4 * kNT + kStats;  // (upper bounds with STRIP)
-    static_assert(2 * (kRegs1 + (NG == 2 ? kRegs2 : 0)) * 64 <= kPairs * 2 * kSetFloats, "the register images of the weight-gradient roles must fit in the tile sets");
+    constexpr int kRegs1 = 4 * (kNT * NIN + kNT * kNT), kRegs2 = 4 * kNT * kNT, kRegsF = 4 * kNT + kStats;  // (slot strides: upper bounds)
+    static_assert(2 * kRegs1 * 64 <= kPairs * 2 * kSetFloats, "two G register images must fit in the tile sets");
     static_assert(2 * kRegsF * 64 <= kPairs * kPrivFloats, "two F register images must fit in the private images");
     auto xfer = [&](float *slot, bool add) {
       int c = 0;  // 16-byte slots (see mlp_kernel)
@@ -1335,24 +1115,17 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
         for (int i = 0; i < NTF; ++i) {
 #pragma unroll
           for (int j = 0; j < NIN; ++j) four(gW1[i][j]);
-          if (NG == 1) {
 #pragma unroll
-            for (int j = 0; j < NTF; ++j) four(gW2[i][j]);
-          }
+          for (int j = 0; j < NTF; ++j) four(gW2[i][j]);
         }
-        if (STRIP) { four(gW2r); four(gW2c); four(gW1r); }
+        four(gW2r); four(gW2c); four(gW1r);
       } else if (role == 2) {
 #pragma unroll
         for (int i = 0; i < kNT; ++i)
 #pragma unroll
           for (int j = 0; j < kNT; ++j) four(gW2[i][j]);
       } else {
-        if (STRIP) {
-          four(gW3s); four(gW3s2);
-        } else {
-#pragma unroll
-          for (int i = 0; i < kNT; ++i) four(gW3[i]);
-        }
+        four(gW3s); four(gW3s2);
         f32x4 st = {st_loss, st_ratio, st_kl, st_cnt};
         four(st);
         st_loss = st[0]; st_ratio = st[1]; st_kl = st[2]; st_cnt = st[3];
@@ -1374,26 +1147,25 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
   float *out = a.partials + (long long)blockIdx.x * a.pstride;
   const Offsets o = offsets(m);
   if (role != 0) {
+    static_assert(NIN == NTF, "one column loop serves dW1 and dW2");
 #pragma unroll
     for (int it = 0; it < NTF; ++it) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int i = it * kTW + 4 * g + q;
 #pragma unroll
-        for (int jt = 0; jt < kNT; ++jt) {
+        for (int jt = 0; jt < NTF; ++jt) {
           const int j = jt * kTW + n;
           if (role == 1) {
-            if (jt < NIN && i < m.h1 && j < m.d_in) out[o.w1 + i * m.d_in + j] = gW1[it][jt < NIN ? jt : 0][q];
-            if (jt < NIN && i < m.h1 && j == m.d_in) out[o.b1 + i] = gW1[it][jt < NIN ? jt : 0][q];
-          }
-          if (role == (NG == 1 ? 1 : 2) && jt < NTF) {
+            if (i < m.h1 && j < m.d_in) out[o.w1 + i * m.d_in + j] = gW1[it][jt][q];
+            if (i < m.h1 && j == m.d_in) out[o.b1 + i] = gW1[it][jt][q];
             if (i < m.h2 && j < m.h1) out[o.w2 + i * m.h1 + j] = gW2[it][jt][q];
             if (i < m.h2 && j == m.h1) out[o.b2 + i] = gW2[it][jt][q];
           }
         }
       }
     }
-    if (STRIP && role == 1) {
+    if (role == 1) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         // row strips: lane l holds rows 48 + q at column l
@@ -1408,31 +1180,13 @@ __global__ __launch_bounds__((1 + NG) * 256, 1 + NG) void ppo_split_kernel(const
         if (ic < 48 && jc == m.h1) out[o.b2 + ic] = gW2c[q];
       }
     }
-  } else if (STRIP) {
+  } else {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {  // lane l holds outputs q (gW3s) and 4 + q (gW3s2) at column l
       if (q < m.d_out && lane < m.h2) out[o.w3 + q * m.h2 + lane] = gW3s[q];
       if (q < m.d_out && lane == m.h2) out[o.b3 + q] = gW3s[q];
       if (4 + q < m.d_out && lane < m.h2) out[o.w3 + (4 + q) * m.h2 + lane] = gW3s2[q];
       if (4 + q < m.d_out && lane == m.h2) out[o.b3 + 4 + q] = gW3s2[q];
-    }
-    float s4[kStats] = {st_loss, st_ratio, st_kl, st_cnt};
-#pragma unroll
-    for (int q = 0; q < kStats; ++q) {
-      float v = s4[q];
-      for (int d = 8; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-      if (lane == 0) out[o.total + q] = v;
-    }
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = 4 * g + q;
-#pragma unroll
-      for (int jt = 0; jt < kNT; ++jt) {
-        const int j = jt * kTW + n;
-        if (i < m.d_out && j < m.h2) out[o.w3 + i * m.h2 + j] = gW3[jt][q];
-        if (i < m.d_out && j == m.h2) out[o.b3 + i] = gW3[jt][q];
-      }
     }
     float s4[kStats] = {st_loss, st_ratio, st_kl, st_cnt};
 #pragma unroll
@@ -1581,26 +1335,23 @@ static int launch_grad(int loss, Args &a, float *d_grads, float *d_stats, float 
   // inputs: hidden k-tile 3 holds features 48, 49 only, input k-tile 2 of the 34-input net 32, 33 only
   if (ktiled) {
     blocks = launch_wide(loss, a, s);
-  } else if (PDS_MLP_SPLIT && loss == LOSS_PPO && a.m.activation == 0 && !gb && !wide && two_hidden_steps(a.m) &&
+  } else if (loss == LOSS_PPO && a.m.activation == 0 && !gb && !wide && two_hidden_steps(a.m) &&
       a.index == nullptr && a.mean == nullptr) {
-    // wave roles (ppo_split_kernel): a block takes 4 tiles at a time, not 8
+    // wave roles (ppo_split_kernel, which takes neither a row index nor input statistics): a block takes 4 tiles at a time, not 8
     const long long tiles = (a.B + kTS - 1) / kTS;
     blocks = (int)((tiles + kPairs - 1) / kPairs < kMaxGridBlocks ? (tiles + kPairs - 1) / kPairs : kMaxGridBlocks);
     const dim3 gs(blocks);
-    const dim3 bs((1 + PDS_MLP_SPLIT) * 256);  // PDS_MLP_SPLIT = number of weight-gradient roles
+    const dim3 bs(2 * kPairs * 64);
     // the split-bf16 form of the weight-gradient role wins where a wave pair streams many tiles (its per-tile LATENCY is longer:
     // the splits sit in front of the MFMAs), the f32 form below ~4 tiles per pair (measured crossover: 32 000 .. 65 536 samples, profiles/r06_bf16_threshold.txt)
     static const long long bf16_min = [] { const char *e = getenv("PDS_BF16_MIN_SAMPLES"); return e ? atoll(e) : 65536ll; }();
-    if (PDS_SPLIT_BF16 && a.B >= bf16_min) {
-      if (two_input_steps(a.m)) hipLaunchKernelGGL((ppo_split_kernel<2, PDS_MLP_SPLIT, true>), gs, bs, 0, s, a);
-      else hipLaunchKernelGGL((ppo_split_kernel<4, PDS_MLP_SPLIT, true>), gs, bs, 0, s, a);
+    if (a.B >= bf16_min) {
+      if (two_input_steps(a.m)) hipLaunchKernelGGL((ppo_split_kernel<2, true>), gs, bs, 0, s, a);
+      else hipLaunchKernelGGL((ppo_split_kernel<4, true>), gs, bs, 0, s, a);
     } else {
-      if (two_input_steps(a.m)) hipLaunchKernelGGL((ppo_split_kernel<2, PDS_MLP_SPLIT>), gs, bs, 0, s, a);
-      else hipLaunchKernelGGL((ppo_split_kernel<4, PDS_MLP_SPLIT>), gs, bs, 0, s, a);
+      if (two_input_steps(a.m)) hipLaunchKernelGGL((ppo_split_kernel<2, false>), gs, bs, 0, s, a);
+      else hipLaunchKernelGGL((ppo_split_kernel<4, false>), gs, bs, 0, s, a);
     }
-  } else if (loss == LOSS_PPO && a.m.activation == 0 && !gb && !wide && two_hidden_steps(a.m)) {
-    if (two_input_steps(a.m)) hipLaunchKernelGGL((mlp_kernel<LOSS_PPO, 0, 1, false, 2, 2>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((mlp_kernel<LOSS_PPO, 0, 1, false, 4, 2>), g, b, 0, s, a);
   } else if (loss == LOSS_MSE && a.m.activation == 1 && gb && !wide && two_input_steps(a.m) && !two_hidden_steps(a.m)) {
     hipLaunchKernelGGL((mlp_kernel<LOSS_MSE, 1, 1, true, 2, 4>), g, b, 0, s, a);  // default critic, 34 inputs
   } else if (loss == LOSS_PPO) {

@@ -3,8 +3,8 @@ kernel instantiation in csrc/pds_mlp.hip (pds_mlp_forward, launch_grad) and csrc
 a scanner of the launch sites of those two files, the GPU case table, and float64 autograd references of the three fused
 operations (forward, PPO-clip policy gradient, value-regression gradient).
 
-A member of the dispatch set is a canonical string: the kernel's name and its template arguments with the defaults filled in
-and PDS_MLP_SPLIT replaced by its value, e.g. "mlp_kernel<LOSS_MSE,1,1,true,2,4>", "ppo_split_kernel<2,1,true>",
+A member of the dispatch set is a canonical string: the kernel's name and its template arguments with the defaults filled in,
+e.g. "mlp_kernel<LOSS_MSE,1,1,true,2,4>", "ppo_split_kernel<2,true>",
 "mlp_wide_kernel<LOSS_PPO,0,8>"."""
 import os
 import re
@@ -21,7 +21,6 @@ NARROW_WAVES = 8          # kWaves
 WIDE_WAVES = 4            # kWideWaves
 MAX_BLOCKS = 256          # grid_blocks / wide_grid_blocks / the split kernel's cap
 SPLIT_PAIRS = NARROW_WAVES // 2   # kPairs: tiles a split block takes per round
-MLP_SPLIT = 1             # PDS_MLP_SPLIT default
 BF16_MIN_SAMPLES = 65536  # PDS_BF16_MIN_SAMPLES default
 
 # samples one persistent grid covers before its waves stride into their second tile
@@ -82,10 +81,8 @@ def instantiation(kind, d_in, h1, h2, act, B=1, index=False, mean=False, bf16_mi
     ki2, kh2 = two_input_steps(d_in), two_hidden_steps(h1, h2)
     if d_in > MAX_DIM:
         return f"mlp_wide_kernel<{loss},{a},{_nin(d_in)}>"
-    if MLP_SPLIT and kind == "ppo" and a == 0 and not gb and not wide and kh2 and not index and not mean:
-        return f"ppo_split_kernel<{2 if ki2 else 4},{MLP_SPLIT},{'true' if B >= bf16_min else 'false'}>"
-    if kind == "ppo" and a == 0 and not gb and not wide and kh2:
-        return _mlp(loss, 0, 1, False, 2 if ki2 else 4, 2)
+    if kind == "ppo" and a == 0 and not gb and not wide and kh2 and not index and not mean:
+        return f"ppo_split_kernel<{2 if ki2 else 4},{'true' if B >= bf16_min else 'false'}>"
     if kind == "mse" and a == 1 and gb and not wide and ki2 and not kh2:
         return _mlp(loss, 1, 1, True, 2, 4)
     return _mlp(loss, a, 2 if wide else 1, gb)
@@ -103,12 +100,11 @@ def family_round(member):
 # ---- launch-site scanner ------------------------------------------------------------------------------------------------
 _SITE = re.compile(r"hipLaunchKernelGGL\(\s*(\(?)\s*(\w+)\s*(?:<([^<>]*)>)?\s*\)?\s*,")
 _DEFAULTS = {"mlp_kernel": ["4", "4"], "ppo_split_kernel": ["false"]}
-_ARITY = {"mlp_kernel": 6, "ppo_split_kernel": 3, "mlp_wide_kernel": 3}
+_ARITY = {"mlp_kernel": 6, "ppo_split_kernel": 2, "mlp_wide_kernel": 3}
 
 
 def _canon(name, args, subst):
     vals = [subst.get(v.strip(), v.strip()) for v in args.split(",")] if args else []
-    vals = [str(MLP_SPLIT) if v == "PDS_MLP_SPLIT" else v for v in vals]
     if name in _ARITY:
         need = _ARITY[name] - len(vals)
         if need > 0:

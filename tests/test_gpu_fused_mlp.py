@@ -433,7 +433,7 @@ print("ERR", float(want.abs().max()), float(((got - want) ** 2).sum().sqrt() / (
 def test_split_bf16_weight_gradient_role_is_no_less_accurate_than_the_f32_form(tmp_path):
     """ppo_split_kernel's weight-gradient role (dZ1, dW2, dW1) runs on v_mfma_f32_16x16x32_bf16 with every operand in three bf16
     pieces (six products: exact, one f32 rounding per 32 terms) from 65 536 samples on -- and layers 1 and 2 of the forward role with it --, on v_mfma_f32_16x16x4_f32 below
-    (csrc/pds_mlp.hip, PDS_SPLIT_BF16).  The same 262 144-sample policy gradient through both forms (PDS_BF16_MIN_SAMPLES, read
+    (csrc/pds_mlp.hip, the BFP form of ppo_split_kernel).  The same 262 144-sample policy gradient through both forms (PDS_BF16_MIN_SAMPLES, read
     once per process: two child processes) against float64 autograd.  Measured: relative L2 error 9.4e-4 for the f32 form --
     two or three of the 13 M layer-1 relu units take the other branch than in float64, because v_mfma_f32_16x16x4_f32 leaves
     ~1e-7 on a pre-activation, and each such sample moves the gradient by O(1 / B) -- and 3.7e-7 for the bf16 form, whose

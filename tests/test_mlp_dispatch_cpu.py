@@ -38,7 +38,7 @@ def test_constants_of_the_mirror_match_the_sources():
     assert re.search(rf"constexpr int kMaxGridBlocks = {mc.MAX_BLOCKS};", narrow)
     assert re.search(r"constexpr int kPairs = kWaves / 2;", narrow)
     assert re.search(rf"return \(int\)\(blocks < {mc.MAX_BLOCKS} \? blocks : {mc.MAX_BLOCKS}\);", narrow)
-    assert re.search(rf"#define PDS_MLP_SPLIT {mc.MLP_SPLIT}\b", narrow)
+    assert "PDS_MLP_SPLIT" not in narrow  # the split route is unconditional: no switch back to mlp_kernel, no third role
     assert re.search(rf'getenv\("PDS_BF16_MIN_SAMPLES"\); return e \? atoll\(e\) : {mc.BF16_MIN_SAMPLES}ll;', narrow)
     # the predicates restated in mlp_cases.py, as the host code spells them today
     for frag in ("const bool gb = a.m.h1 == kMaxDim || a.m.h2 == kMaxDim || a.m.d_in == kMaxDim;",
@@ -55,15 +55,15 @@ def test_constants_of_the_mirror_match_the_sources():
 
 
 def test_every_launch_site_resolves_to_an_instantiation():
-    """19 sites in pds_mlp.hip (reduce_kernel one of them), 4 in pds_mlp_wide.hip: a new one must be added to the mirror
+    """17 sites in pds_mlp.hip (reduce_kernel one of them), 4 in pds_mlp_wide.hip: a new one must be added to the mirror
     and to the case table"""
     sites, raw = mc.launch_sites()
-    assert raw == {"pds_mlp.hip": 19, "pds_mlp_wide.hip": 4}, raw
-    pat = re.compile(r"^(mlp_kernel<LOSS_(PPO|MSE|NONE),[01],[12],(true|false),[24],[24]>|ppo_split_kernel<[24],1,(true|false)>|"
+    assert raw == {"pds_mlp.hip": 17, "pds_mlp_wide.hip": 4}, raw
+    pat = re.compile(r"^(mlp_kernel<LOSS_(PPO|MSE|NONE),[01],[12],(true|false),[24],[24]>|ppo_split_kernel<[24],(true|false)>|"
                      r"mlp_wide_kernel<LOSS_(PPO|MSE|NONE),[01],(6|8|10|12)>)$")
     for f, m in sites:
         assert pat.match(m), (f, m)
-    assert len(sites) == 16 + 7 + 4 + 2 + 1 + 24  # PDS_MLP_LAUNCH x 4 calls, forward, split, PPO fallback, critic, wide
+    assert len(sites) == 16 + 7 + 4 + 1 + 24  # PDS_MLP_LAUNCH x 4 calls, forward, split, critic, wide
     assert len(set(m for _, m in sites)) == len(sites)
 
 
@@ -76,8 +76,9 @@ def test_mirror_codomain_equals_the_launch_sites():
 
 
 def _abi_unreachable():
-    """instantiations that only a PPO call WITH an index or a standardisation reaches -- the host predicate asks for them, but
-    the PPO entry points never pass either (checked against pds_ppo_policy_grad_step's body)"""
+    """instantiations that only a PPO call WITH an index or a standardisation would reach (the PPO entry points never pass
+    either: checked against pds_ppo_policy_grad_step's body).  There is none: such a call falls through to the generic
+    PDS_MLP_LAUNCH(LOSS_PPO, 0), which plain calls reach too."""
     text = _src("pds_mlp.hip")
     body = text[text.index('extern "C" int pds_ppo_policy_grad_step'):text.index('extern "C" int pds_ppo_policy_grad(')]
     assert "a.index" not in body and "a.mean" not in body
@@ -93,7 +94,7 @@ def _abi_unreachable():
 
 def test_case_table_reaches_every_instantiation():
     unreachable = _abi_unreachable()
-    assert unreachable == {"mlp_kernel<LOSS_PPO,0,1,false,2,2>", "mlp_kernel<LOSS_PPO,0,1,false,4,2>"}, unreachable
+    assert unreachable == set(), unreachable  # every instantiation the library launches has a GPU case
     for c in mc.CASES:
         assert not (c.kind == "ppo" and (c.index or c.std)), c
         assert c.kind != "mse" or c.d_out == 1, c

@@ -168,7 +168,7 @@ def test_ppo_learns_hover_end_to_end(fused):
 @pytest.mark.parametrize("task,H,ac_kwargs", [
     ("DroneCircleSimpleEnv-v0", 2, None),
     # round 6: 8 192 envs x 16 steps = 131 072 samples -- the size from which the policy gradient runs five of its GEMMs on split-bf16 MFMAs
-    # (csrc/pds_mlp.hip PDS_SPLIT_BF16; "big": num_envs 8 192 instead of 1 024)
+    # (csrc/pds_mlp.hip: the BFP form of ppo_split_kernel, from PDS_BF16_MIN_SAMPLES on; "big": num_envs 8 192 instead of 1 024)
     ("DroneHoverSimpleEnv-v0", 2, "big"),
     # round 6: more than 64 network inputs (csrc/pds_mlp_wide.hip) -- the widths and layer sizes of the reference's
     # experiments/04_history_of_state_action_inputs/04_train_with_history.py:34-42 (H = 4 / 6 / 8; policy 32-32 / 48-48 / 64-64)
