@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""Train an actor with an evolution strategy (OpenAI-ES) on a batched Simple env and leave the reference's run artefacts behind.
+
+A generation is P policies x E episodes in one launch (evaluation.evaluate_population); the population is written on the device
+from the centre (pds_es_perturb) and the search gradient regenerates the noise from its counters (pds_es_gradient,
+csrc/pds_es.hip).  The reference has no such trainer: this stands where it spreads independent evaluations over MPI cores.
+The checkpoint is PPOTrainer's (`torch_save/model.pt` + `model.json`): examples/evaluate_policies.py reads it.
+
+    python examples/train_es.py --env DroneHoverSimpleEnv-v0 --population 4096 --episodes 64 --generations 5 --log-dir /tmp/es_run
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import phoenix_drone_simulation_amd as pds  # noqa: E402
+from phoenix_drone_simulation_amd.es import ESTrainer  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--env", default="DroneHoverSimpleEnv-v0")
+    ap.add_argument("--population", type=int, default=4096, help="policies per generation (even: antithetic pairs)")
+    ap.add_argument("--episodes", type=int, default=64, help="episodes per policy, a multiple of 64")
+    ap.add_argument("--generations", type=int, default=100)
+    ap.add_argument("--sigma", type=float, default=0.02, help="standard deviation of the parameter noise")
+    ap.add_argument("--lr", type=float, default=0.01, help="Adam's learning rate on the centre")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--log-dir", default=None)
+    ap.add_argument("--eval-every", type=int, default=10, help="every that many generations the centre alone flies all envs")
+    args = ap.parse_args()
+    env = pds.make(args.env, num_envs=args.population * args.episodes, seed=args.seed)  # the reference's default config
+    trainer = ESTrainer(env, args.population, sigma=args.sigma, lr=args.lr, seed=args.seed, obs_stats="warmup",
+                        eval_every=args.eval_every)
+    t0 = time.time()
+    steps = 0.0
+    for g in range(args.generations):
+        i = trainer.learn_one_generation()
+        steps += i["env_steps"]
+        if g % max(1, args.generations // 20) == 0 or g == args.generations - 1:
+            print(f"generation {i['generation']:4d}  fitness {i['fitness_mean']:9.2f} [{i['fitness_min']:9.2f} .. {i['fitness_max']:9.2f}]  "
+                  f"EpLen {i['ep_len']:6.1f}  centre {i['centre_return']:9.2f}  |g| {i['grad_norm']:.3e}  "
+                  f"perturb {1e3 * i['t_perturb']:.2f} ms  evaluate {1e3 * i['t_evaluate']:.2f} ms  update {1e3 * i['t_update']:.2f} ms",
+                  flush=True)
+    torch.cuda.synchronize()
+    print(f"{steps:.0f} env-steps in {time.time() - t0:.1f} s")
+    ret, length, cost = trainer.evaluate_centre()
+    print(f"centre: mean return {float(ret.mean()):.2f}  mean episode length {float(length.mean()):.1f}  mean cost {float(cost.mean()):.2f}")
+    if args.log_dir:
+        trainer.save_checkpoint(args.log_dir)          # torch_save/model.pt + model.json (firmware format)
+        trainer.write_progress_csv(os.path.join(args.log_dir, "progress.csv"))
+        print("saved to", args.log_dir)
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -513,6 +513,29 @@ int pds_npg_surrogate_kl(const pds_mlp *m, const float *d_step, const float *d_f
                          const float *d_act, const float *d_adv, const float *d_logp_old, const float *d_mu_old,
                          const float *d_log_std, int64_t B, float *d_out, float *d_theta_out, float *d_workspace, void *stream);
 
+/* An evolution strategy over the flat parameters of one actor (es.py ESTrainer; csrc/pds_es.hip).  No
+ * handle: like pds_gaussian_sample the entry points run on the current device, asynchronously on `stream`.
+ * Noise contract: a population of 2 * pairs policies is `pairs` antithetic pairs; with Q = ceil(n / 8), element j = 8 q + r of
+ * the noise vector eps_i of GLOBAL pair i = pair_base + row is variate r (of d_out = 8) that pds_gaussian_sample draws for
+ * sample id i * Q + q in call `generation` under `seed` -- so a slice (pair_base, pairs) of a population is bitwise those rows
+ * of the whole one.  (pair_base + pairs) * Q must stay below 2^56 (the sample ids of pds_gaussian_sample).
+ *
+ * pds_es_perturb: d_theta[2 i, j] = fmaf(sigma, eps_i[j], mu[j]), d_theta[2 i + 1, j] = fmaf(-sigma, eps_i[j], mu[j]);
+ * d_theta is [2 pairs, n], the layout of pds_evaluate_policies' d_params for n = pds_mlp_param_count.  sigma > 0.
+ *
+ * pds_es_gradient: d_grad[j] = scale * sum_i d_pair_weights[i] * eps_i[j] + l2 * d_mu[j] (no l2 term when d_mu is NULL), the
+ * noise REGENERATED from the contract -- it is never stored and theta is not read.  Summed in a fixed order (chunks of pairs
+ * into [n] partial slabs in d_workspace, the slabs added in chunk order; no atomics): the same inputs give the same bits on
+ * every run and for every grid.  d_workspace: pds_es_workspace_floats(n, pairs) = ceil(pairs / chunk) * n floats.
+ * PDS_EINVAL (before any device call): a NULL pointer (other than d_mu of pds_es_gradient), n < 1, pairs < 1, ids beyond
+ * 2^56, sigma not finite or <= 0, scale or l2 not finite. */
+int64_t pds_es_workspace_floats(int64_t n, int64_t pairs); /* host only */
+int pds_es_perturb(const float *d_mu, int64_t n, int64_t pairs, float sigma, uint64_t seed, uint64_t generation,
+                   uint64_t pair_base, float *d_theta /* [2 pairs, n] */, void *stream);
+int pds_es_gradient(const float *d_pair_weights /* [pairs] */, const float *d_mu /* [n] or NULL */, int64_t n, int64_t pairs,
+                    float scale, float l2, uint64_t seed, uint64_t generation, uint64_t pair_base, float *d_grad /* [n] */,
+                    float *d_workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
