@@ -229,6 +229,12 @@ int pds_step_with_variates(pds_handle *h, const float *d_actions, const float *d
  *   d_final_obs [K,N,D] or NULL */
 int pds_step_k(pds_handle *h, int k_steps, const float *d_actions, float *d_obs, float *d_reward,
                uint8_t *d_terminated, uint8_t *d_truncated, float *d_cost, float *d_final_obs, void *stream);
+/* 1 when pds_step_k is ONE launch for this handle, 0 when it loops over pds_step (same bits, K launches, the state through
+ * HBM every step).  One launch: control_mode PWM in every configuration, and the PID modes (AttitudeRate / Attitude, the PID
+ * integrals and previous errors in registers with the rest of the state) with and without the latency ring.  The loop: a PID
+ * mode together with the ground effect or with the Kalman hold (observation_frequency below the simulation frequency).
+ * pds_bytes_per_env_step_k prices the handle accordingly. */
+int pds_step_k_fused(const pds_handle *h);
 
 /* CrazyFlieAgent.set_latency (envs/agents.py:388-404; called by simopt/pybullet.py:248): latency <
  * time_step disables the delay, otherwise buf_size = int(latency / time_step) and the action buffer and
@@ -297,7 +303,8 @@ int pds_set_tick(pds_handle *h, uint64_t tick);
 
 /* Algorithmic HBM bytes one pds_step moves per env for this configuration. */
 int pds_bytes_per_env_step(const pds_handle *h);
-/* the same for pds_step_k with k_steps per launch (state traffic amortised over the K steps) */
+/* the same for pds_step_k with k_steps per launch (state traffic amortised over the K steps where pds_step_k_fused is 1;
+ * pds_bytes_per_env_step where it loops) */
 int pds_bytes_per_env_step_k(const pds_handle *h, int k_steps);
 
 const char *pds_last_error(const pds_handle *h);
@@ -372,7 +379,10 @@ int pds_rollout(pds_handle *h, int T, const pds_mlp *pi, const pds_mlp *vf, cons
  * step T - 1: algs/iwpg/iwpg.py:374-379), one slot list per env -- d_fin_rows [slots, N, history x half], d_fin_step
  * [slots, N] = the step t whose d_fval_buf[t] entry the row's value is; the caller presets d_fin_step to -1 (unused);
  * slots >= T / max_episode_steps + 2.  d_obs_buf [T + 1, N, history x half]: row 0 = the histories on entry, rows 1..T
- * written.  Other buffers as pds_rollout.  PDS_EUNSUPPORTED where no kernel is built (the per-step path gives the same bits). */
+ * written.  Other buffers as pds_rollout.  Built for every control mode (PWM, AttitudeRate, Attitude; TakeOff fixes PWM) with
+ * noise off or at the reference's default (domain randomisation + thrust noise + observation noise), with and without motor
+ * dynamics (TakeOff: without).  PDS_EUNSUPPORTED, before the handle is touched, for the rest -- the latency ring, the Kalman hold,
+ * the ground effect, partial noise settings -- (the per-step path gives the same bits). */
 int pds_rollout_history(pds_handle *h, int T, int history, const pds_mlp *pi, const float *d_mean, const float *d_std, float eps,
                         const float *d_log_std, uint64_t seed, const uint64_t *d_call_base, uint64_t call_offset,
                         int deterministic, float *d_obs_buf, float *d_act_buf, float *d_logp_buf, float *d_rew_buf,

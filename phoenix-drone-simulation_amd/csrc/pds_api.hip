@@ -778,15 +778,23 @@ extern "C" int pds_bytes_per_env_step(const pds_handle *h) {
   return b;
 }
 
+// Whether pds_step_k is ONE launch for this handle (a step_k_kernel exists: step_k_rule, csrc/pds_types.h) or a loop of
+// pds_step.  The single statement of that rule for pds_step_k, pds_bytes_per_env_step_k and the tests.
+extern "C" int pds_step_k_fused(const pds_handle *h) {
+  if (!h) return PDS_EINVAL;
+  return step_k_supported(h->flags) ? 1 : 0;
+}
+
 // Algorithmic bytes per env-step of pds_step_k: the env state is read and written once per launch.
 extern "C" int pds_bytes_per_env_step_k(const pds_handle *h, int k_steps) {
   if (!h || k_steps < 1) return PDS_EINVAL;
   const LaunchFlags &f = h->flags;
   const int full = pds_bytes_per_env_step(h);
-  // the PID control modes have no K-step kernel: pds_step_k loops over pds_step for them (below), every step moves the
-  // single-step kernel's bytes (rounds 2-5 priced those rows with the K-step formula: 0.26-0.36 "of their own roofline"
-  // for what is pds_step at 0.57-0.86)
-  if (f.ctrl != 0) return full;
+  // where pds_step_k loops over pds_step (pds_step_k_fused: a PID mode with the ground effect or the Kalman hold) every step
+  // moves the single-step kernel's bytes (rounds 2-5 priced those rows with the K-step formula: 0.26-0.36 "of their own
+  // roofline" for what is pds_step at 0.57-0.86).  Elsewhere the PID integrals and previous errors (inside `full`) amortise
+  // with the rest of the state.
+  if (!pds_step_k_fused(h)) return full;
   const int stream = 16 + 4 * h->obs_dim + 10 + (f.lat ? 32 * h->cfg.aggregate_phy_steps : 0);
   // once per launch: the state read + written, both ring slots and the randomised parameters written back
   // (+ the kept noisy observation, which the K-step kernel reads from and leaves in oh0-2: materialize_oh_kernel)
@@ -938,8 +946,8 @@ extern "C" int pds_step_k(pds_handle *h, int k_steps, const float *d_actions, fl
   if (const int rc = check_step_pointers(h, d_actions, d_obs, d_reward, d_terminated, d_truncated, d_cost)) return rc;
   const long long n = h->cfg.num_envs;
   const int D = h->obs_dim;
-  if (h->flags.ctrl != 0) {
-    // PID control modes (no K-step kernel): K single-step launches, same results
+  if (!pds_step_k_fused(h)) {
+    // a PID mode with the ground effect or the Kalman hold (no K-step kernel): K single-step launches, same results
     for (int s = 0; s < k_steps; ++s) {
       const long long o1 = (long long)s * n;
       const int rc = pds_step(h, d_actions + o1 * 4, d_obs + o1 * D, d_reward + o1, d_terminated + o1, d_truncated + o1,
@@ -1090,7 +1098,7 @@ extern "C" int pds_rollout_history(pds_handle *h, int T, int history, const pds_
     return fail(h, PDS_EINVAL, "pds_rollout_history: slots %d < T / max_episode_steps + 2 = %d", slots, T / h->cfg.max_episode_steps + 2);
   if (!rollout_buffers_aligned(d_act_buf, d_obs_buf)) return fail(h, PDS_EINVAL, "pds_rollout_history: alignment");
   if (!rollout_hist_supported(h->cfg.task, h->flags))
-    return fail(h, PDS_EUNSUPPORTED, "pds_rollout_history: no kernel for this env configuration (built: control_mode PWM without latency ring, "
+    return fail(h, PDS_EUNSUPPORTED, "pds_rollout_history: no kernel for this env configuration (built: every control mode without latency ring, "
                                      "Kalman hold or ground effect; noise off or the reference's default; TakeOff without motor dynamics) "
                                      "-- the per-step kernels give the same bits");
   RolloutHistArgs ra;
@@ -1102,6 +1110,10 @@ extern "C" int pds_rollout_history(pds_handle *h, int T, int history, const pds_
   ra.fin_rows = d_fin_rows; ra.fin_step = d_fin_step;
   const int hn = rollout_hist_tiles(HS);
   return launch_rollout(h, "pds_rollout_history", T, stream, [&](dim3 grid, hipStream_t s) {
+    if (h->flags.ctrl != 0) {  // (TakeOff fixes control_mode PWM)
+      if (h->cfg.task == PDS_TASK_HOVER) return launch_rollout_hist_hover_pid(h->flags, hn, grid, s, ra);
+      return h->cfg.task == PDS_TASK_CIRCLE && launch_rollout_hist_circle_pid(h->flags, hn, grid, s, ra);
+    }
     if (h->cfg.task == PDS_TASK_HOVER) return launch_rollout_hist_hover(h->flags, hn, grid, s, ra);
     if (h->cfg.task == PDS_TASK_CIRCLE) return launch_rollout_hist_circle(h->flags, hn, grid, s, ra);
     return launch_rollout_hist_takeoff(h->flags, hn, grid, s, ra);

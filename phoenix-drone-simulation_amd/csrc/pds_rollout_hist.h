@@ -256,20 +256,28 @@ inline void launch_rollout_hist_variant(int hn, dim3 grid, hipStream_t s, const 
   else if (hn == 8) hipLaunchKernelGGL((rollout_hist_kernel<RV_, 8>), grid, dim3(kRolloutThreads), 0, s, ra);
   else hipLaunchKernelGGL((rollout_hist_kernel<RV_, 12>), grid, dim3(kRolloutThreads), 0, s, ra);
 }
-template <int TASK>
+// CTRL 0: control_mode PWM (csrc/pds_rollout_hist_<task>.hip); 1 / 2: AttitudeRate / Attitude, the PID state in the env wave's
+// registers like the rest of the env (csrc/pds_rollout_hist_<task>_pid.hip, translation units of their own)
+template <int TASK, int CTRL = 0>
 inline bool launch_rollout_hist_task(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra) {
-  if (!rollout_hist_supported(TASK, f)) return false;
+  static_assert(CTRL == 0 || TASK != PDS_TASK_TAKEOFF, "TakeOff fixes control_mode PWM (envs/takeoff.py:225)");
+  if (!rollout_hist_supported(TASK, f) || f.ctrl != CTRL) return false;
   const bool full = f.on;
   if constexpr (TASK != PDS_TASK_TAKEOFF) {
     if (f.motor) {
-      if (full) launch_rollout_hist_variant<Variant<TASK, true, true, false, true, true, 0, false, false>>(hn, grid, s, ra);
-      else launch_rollout_hist_variant<Variant<TASK, true, false, false, false, false, 0, false, false>>(hn, grid, s, ra);
+      if (full) launch_rollout_hist_variant<Variant<TASK, true, true, false, true, true, CTRL, false, false>>(hn, grid, s, ra);
+      else launch_rollout_hist_variant<Variant<TASK, true, false, false, false, false, CTRL, false, false>>(hn, grid, s, ra);
       return true;
     }
   }
-  if (full) launch_rollout_hist_variant<Variant<TASK, false, true, false, true, true, 0, false, false>>(hn, grid, s, ra);
-  else launch_rollout_hist_variant<Variant<TASK, false, false, false, false, false, 0, false, false>>(hn, grid, s, ra);
+  if (full) launch_rollout_hist_variant<Variant<TASK, false, true, false, true, true, CTRL, false, false>>(hn, grid, s, ra);
+  else launch_rollout_hist_variant<Variant<TASK, false, false, false, false, false, CTRL, false, false>>(hn, grid, s, ra);
   return true;
+}
+template <int TASK>
+inline bool launch_rollout_hist_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra) {
+  if (f.ctrl == 1) return launch_rollout_hist_task<TASK, 1>(f, hn, grid, s, ra);
+  return launch_rollout_hist_task<TASK, 2>(f, hn, grid, s, ra);
 }
 
 }  // namespace pds

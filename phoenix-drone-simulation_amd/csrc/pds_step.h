@@ -1134,6 +1134,13 @@ __global__ __launch_bounds__(kBlock, (PDS_MIN_WAVES) * (256 / kBlock)) void step
 // they need 144-186, and at the 168 cap 45 of the 288 kernels spill 1-15 registers: 3 blocks per CU for all of them.  Same
 // box, 2^20 envs, K = 8, us per env-step, cap 168 vs 256: Hover latency ring + noise 69.0 vs 83.6, Kalman hold 74.2 vs 86.9, Circle
 // PT1 + noise 61.5 vs 70.7, Circle latency 77.9 vs 81.6, everything else equal (profiles/r04_ab_stepk_regen.txt).
+// The PID control modes (step_k_rule, csrc/pds_types.h: the pid family and the latency ring under a PID mode; a PID mode with the
+// ground effect or the Kalman hold keeps the loop of pds_step): PidState adds 6 / 12 live floats across the loop.  At the 168 cap
+// 34 of the 128 kernels spill 1-13 VGPRs (profiles/stepk_pid_resources.txt), the range of the control_mode PWM kernels above, and
+// all of them keep the cap: same box and session against the loop of pds_step they replace, 2^20 envs, K = 8, us per env-step --
+// Circle AttitudeRate 61.0 -> 45.0, Hover Attitude default noise, 4 sub-steps 99.6 -> 80.4, Circle AttitudeRate PT1 + DR
+// 75.6 -> 47.6, Hover AttitudeRate + latency ring, default noise (3-9 spilled) 87.1 -> 63.7, Circle Attitude + latency ring + PT1
+// 89.7 -> 59.1; spread of the repeats <= 2.3 (profiles/stepk_pid_timing.txt).  No variant is left to the loop for its registers.
 #ifndef PDS_STEPK_OPAQUE_KEY
 #define PDS_STEPK_OPAQUE_KEY 1  // A/B: 0 = round-3 form (key schedule hoisted out of the K loop and spilled)
 #endif
@@ -1205,8 +1212,10 @@ inline void launch_variant(int kind, bool half_tile, dim3 grid, hipStream_t s, c
       else abort();
     } else abort();
   } else if (kind == kLaunchStepK) {
-    // (the PID control modes have no K-step kernel: pds_step_k loops over pds_step for them)
-    if constexpr (V::CTRL == 0) hipLaunchKernelGGL((step_k_kernel<V>), grid, dim3(kBlock), 0, s, a);
+    // (a PID mode with the ground effect or the Kalman hold has no K-step kernel: pds_step_k loops over pds_step there and
+    //  never gets here -- step_k_rule, csrc/pds_types.h)
+    if constexpr (step_k_rule(V::CTRL, V::GE, V::HOLD)) hipLaunchKernelGGL((step_k_kernel<V>), grid, dim3(kBlock), 0, s, a);
+    else abort();
   } else {
 #if PDS_STORED_OH_FROM_AGG > 0
     if constexpr (regen_obs_variant<V>()) {

@@ -383,6 +383,11 @@ inline bool split_reset_supported(int task, const LaunchFlags &f) { return inlin
 // kLaunchStepSplit / kLaunchPostReset: the single-step kernel without its in-place reset (SplitReset<V>) and the dense reset
 // launched behind it.
 enum LaunchKind { kLaunchStep = 0, kLaunchStepK = 1, kLaunchReset = 2, kLaunchStepStored = 3, kLaunchStepSplit = 4, kLaunchPostReset = 5 };
+// Which variants have a step_k_kernel (csrc/pds_step.h launch_variant instantiates by this rule, pds_step_k_fused states it for
+// the host): every control_mode PWM variant, and the PID modes in the pid family and on the latency ring -- not a PID mode
+// with the ground effect or with the Kalman hold, for which pds_step_k loops over pds_step.
+constexpr bool step_k_rule(int ctrl, bool ge, bool hold) { return ctrl == 0 || (!ge && !hold); }
+inline bool step_k_supported(const LaunchFlags &f) { return step_k_rule(f.ctrl, f.ge, f.hold); }
 #ifndef PDS_POST_RESET_ENVS
 #define PDS_POST_RESET_ENVS 1024  // envs per wave of post_reset_kernel (A/B: 512, 256)
 #endif
@@ -436,12 +441,14 @@ struct RolloutHistArgs {
 };
 static_assert(offsetof(RolloutHistArgs, s) == 0, "reload_args() reads the head of the kernarg segment as a StepArgs");
 
-// The env configurations the history rollout is built for: control_mode PWM, no latency ring, no Kalman hold, no ground effect;
-// noise {none, reference default (DR + thrust noise + observation noise)} x {with, without motor dynamics; TakeOff: without}.
+// The env configurations the history rollout is built for: every control mode (TakeOff fixes PWM), no latency ring, no Kalman
+// hold, no ground effect; noise {none, reference default (DR + thrust noise + observation noise)} x {with, without motor
+// dynamics; TakeOff: without}.
 inline bool rollout_hist_supported(int task, const LaunchFlags &f) {
-  if (f.ge || f.hold || f.lat || f.ctrl != 0) return false;
+  if (f.ge || f.hold || f.lat) return false;
   const bool lean = !f.dr && !f.tn && !f.on, full = f.dr && f.tn && f.on;
   if (!lean && !full) return false;
+  if (f.ctrl != 0) return task != PDS_TASK_TAKEOFF;  // (csrc/pds_rollout_hist_*_pid.hip)
   return !(task == PDS_TASK_TAKEOFF && f.motor);
 }
 // input tiles the kernels are instantiated for (d_in <= 64 / 96 / 128 / 192)
@@ -450,6 +457,8 @@ inline int rollout_hist_tiles(int d_in) { return d_in <= 64 ? 4 : (d_in <= 96 ? 
 bool launch_rollout_hist_hover(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
 bool launch_rollout_hist_circle(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
 bool launch_rollout_hist_takeoff(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
+bool launch_rollout_hist_hover_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
+bool launch_rollout_hist_circle_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
 bool launch_rollout_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra);
 bool launch_rollout_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra);
 bool launch_rollout_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra);

@@ -526,6 +526,11 @@ class DroneVecEnv:
         return self.lib.pds_bytes_per_env_step_k(self._handle, int(k_steps))
 
     @property
+    def step_k_fused(self):
+        """True where step_k is ONE launch (pds_step_k_fused), False where it loops over the single-step kernel (same bits)."""
+        return self.lib.pds_step_k_fused(self._handle) == 1
+
+    @property
     def tick(self):
         return int(self.lib.pds_tick(self._handle))
 

@@ -1,0 +1,175 @@
+"""pds_step_k under the PID control modes (AttitudeRate / Attitude, envs/control.py:120-287; the reference's
+experiments/07_control_structures crosses them with the motor time constant and the latency): one launch with the PID
+state in registers wherever pds_step_k_fused says so, bit for bit the trajectory of K pds_step calls -- the same device
+functions, so every comparison here is torch.equal."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+DET = dict(observation_noise=-1, domain_randomization=-1, motor_thrust_noise=0)
+
+# (task, kwargs): the pid family (motor x DR x noise, merged and inline reset) and the latency ring under a PID mode
+FUSED = [
+    ("circle", dict(DET, control_mode="AttitudeRate")),                                              # merged reset
+    ("hover", dict(control_mode="Attitude", aggregate_phy_steps=4)),                                 # reference defaults: noise + DR
+    ("circle", dict(DET, control_mode="AttitudeRate", use_motor_dynamics=True, domain_randomization=0.1)),  # inline reset
+    ("hover", dict(control_mode="AttitudeRate", use_latency=True, latency=0.02)),                    # latency ring, noise + DR
+    ("circle", dict(DET, control_mode="Attitude", use_latency=True, latency=0.03, use_motor_dynamics=True)),
+]
+# what keeps the loop of pds_step: a PID mode with the ground effect or with the Kalman hold
+LOOPED = [
+    ("hover", dict(DET, control_mode="AttitudeRate", use_ground_effect=True)),
+    ("circle", dict(control_mode="Attitude", observation_frequency=50)),
+    ("hover", dict(control_mode="AttitudeRate", observation_frequency=50, use_latency=True, latency=0.02)),
+]
+PWM = [("hover", dict()), ("takeoff", dict(DET, use_ground_effect=True)), ("circle", dict(observation_frequency=50))]
+
+
+def _make(task, **kw):
+    import phoenix_drone_simulation_amd as pds
+    from test_gpu_stepk_graph import ENV_ID
+    return pds.make(ENV_ID[task], **kw)
+
+
+def test_rule_and_price():
+    """pds_step_k_fused is the one statement of where pds_step_k is a single launch; pds_bytes_per_env_step_k prices exactly
+    that set with the K-step formula (the state, PID integrals included, read and written once per launch) and the rest with
+    the single-step kernel's bytes."""
+    for task, kw in FUSED:
+        env = _make(task, num_envs=64, **kw)
+        assert env.step_k_fused is True, (task, kw)
+        assert env.bytes_per_env_step_k(8) < env.bytes_per_env_step, (task, kw)
+        assert env.bytes_per_env_step_k(1) >= env.bytes_per_env_step_k(8)
+        env.close()
+    for task, kw in LOOPED:
+        env = _make(task, num_envs=64, **kw)
+        assert env.step_k_fused is False, (task, kw)
+        assert env.bytes_per_env_step_k(8) == env.bytes_per_env_step, (task, kw)
+        env.close()
+    for task, kw in PWM:
+        env = _make(task, num_envs=64, **kw)
+        assert env.step_k_fused is True, (task, kw)
+        assert env.bytes_per_env_step_k(8) < env.bytes_per_env_step, (task, kw)
+        env.close()
+
+
+@pytest.mark.parametrize("task,kw", FUSED)
+def test_step_k_equals_k_single_steps_bitwise_pid(task, kw):
+    """Short episodes (max_episode_steps=9) so that auto-resets, TimeLimit truncations and final_obs rows occur inside the
+    K-step launches; N = 1000: 15 full tiles and a ragged one."""
+    from test_gpu_stepk_graph import _actions
+    N, K, rounds = 1000, 7, 3
+    mk = lambda: _make(task, num_envs=N, seed=11, max_episode_steps=9, **kw)
+    e1, ek = mk(), mk()
+    assert ek.step_k_fused is True
+    o1, _ = e1.reset()
+    ok, _ = ek.reset()
+    assert torch.equal(o1, ok)
+    nfin = 0
+    for r in range(rounds):
+        acts = _actions(K, N, e1.device, seed=r)
+        obs_k, rew_k, term_k, trunc_k, info_k = ek.step_k(acts)
+        for s in range(K):
+            o, rw, te, tr, info = e1.step(acts[s])
+            w = f"{task} round {r} step {s}"
+            assert torch.equal(te, term_k[s]) and torch.equal(tr, trunc_k[s]), w
+            assert torch.equal(o, obs_k[s]), w
+            assert torch.equal(rw, rew_k[s]) and torch.equal(info["cost"], info_k["cost"][s]), w
+            fin = te | tr
+            nfin += int(fin.sum())
+            assert torch.equal(info["final_obs"][fin], info_k["final_obs"][s][fin]), w
+    assert nfin > N  # every env finished at least once on average
+    assert e1.tick == ek.tick == 1 + K * rounds
+    for name in ("pos", "rpy", "vel", "omega", "last_action", "prev_action", "step_count", "quat_sign", "ref_offset", "pid"):
+        assert torch.equal(e1.get_state(name), ek.get_state(name)), name
+    for name, on in (("motor_x", kw.get("use_motor_dynamics")), ("params", kw.get("domain_randomization", 0.1) > 0),
+                     ("motor_A", kw.get("use_motor_dynamics") and kw.get("domain_randomization", 0.1) > 0),
+                     ("motor_K", kw.get("use_motor_dynamics") and kw.get("domain_randomization", 0.1) > 0),
+                     ("ou", kw.get("motor_thrust_noise", 0.05) > 0), ("gyro_bias", kw.get("observation_noise", 1) > 0),
+                     ("gyro_lpf", kw.get("observation_noise", 1) > 0), ("noisy_obs", kw.get("observation_noise", 1) > 0),
+                     ("action_buffer", kw.get("use_latency")), ("action_idx", kw.get("use_latency"))):
+        if on:
+            assert torch.equal(e1.get_state(name), ek.get_state(name)), name
+    # the two envs continue identically on the single-step path
+    a = _actions(1, N, e1.device, seed=99)[0]
+    assert torch.equal(e1.step(a)[0], ek.step(a)[0])
+    e1.close(); ek.close()
+
+
+def test_step_k_between_single_steps_bitwise_pid():
+    """pds_step and pds_step_k interleaved on Hover AttitudeRate at the reference defaults: the kept noisy observation is
+    materialised for the K-step kernel and found flagged by the single-step kernel behind it, and the PID integrals and
+    previous errors go through pid0-3 from either kernel to the other."""
+    from test_gpu_stepk_graph import _actions
+    N = 1500
+    mk = lambda: _make("hover", num_envs=N, seed=21, max_episode_steps=7, control_mode="AttitudeRate")
+    e1, em = mk(), mk()
+    assert em.step_k_fused is True
+    e1.reset(); em.reset()
+    plan = [1, 1, 5, 1, 4, 3, 1, 1, 6]  # 1 = pds_step, K > 1 = pds_step_k
+    for r, K in enumerate(plan):
+        acts = _actions(K, N, e1.device, seed=50 + r)
+        if K == 1:
+            o, rw, te, tr, info = em.step(acts[0])
+            got = (o[None], rw[None], te[None], tr[None], info["cost"][None], info["final_obs"][None])
+        else:
+            o, rw, te, tr, info = em.step_k(acts)
+            got = (o, rw, te, tr, info["cost"], info["final_obs"])
+        for s in range(K):
+            o1, rw1, te1, tr1, info1 = e1.step(acts[s])
+            w = f"call {r} step {s}"
+            fin = te1 | tr1
+            assert torch.equal(o1, got[0][s]) and torch.equal(rw1, got[1][s]), w
+            assert torch.equal(te1, got[2][s]) and torch.equal(tr1, got[3][s]) and torch.equal(info1["cost"], got[4][s]), w
+            assert torch.equal(info1["final_obs"][fin], got[5][s][fin]), w
+        for name in ("pos", "rpy", "omega", "gyro_bias", "gyro_lpf", "noisy_obs", "step_count", "pid"):
+            assert torch.equal(e1.get_state(name), em.get_state(name)), (r, name)
+    assert e1.tick == em.tick
+    e1.close(); em.close()
+
+
+def test_step_k_ragged_and_no_autoreset_pid():
+    from test_gpu_stepk_graph import _actions
+    for N in (1, 63, 321):
+        kw = dict(DET, num_envs=N, seed=3, auto_reset=False, control_mode="Attitude")
+        e1, ek = _make("hover", **kw), _make("hover", **kw)
+        e1.reset(); ek.reset()
+        acts = _actions(5, N, e1.device, seed=1, scale=0.05)
+        obs_k = ek.step_k(acts)[0]
+        for s in range(5):
+            assert torch.equal(e1.step(acts[s])[0], obs_k[s]), (N, s)
+        assert torch.equal(e1.get_state("pid"), ek.get_state("pid")), N
+        e1.close(); ek.close()
+
+
+def test_captured_step_k_replays_bitwise_pid():
+    """One pds_step_k (K = 6) of Circle AttitudeRate at the reference defaults, captured after one eager call and replayed
+    twice (a linear graph: the materialise launch, then the K-step kernel) == the eager call + 12 eager single steps."""
+    from test_gpu_stepk_graph import _actions
+    N, K = 4096, 6
+    mk = lambda: _make("circle", num_envs=N, seed=5, max_episode_steps=8, control_mode="AttitudeRate")
+    ee, eg = mk(), mk()
+    acts = _actions(K, N, ee.device, seed=4)
+    ee.reset(); eg.reset()
+    first = eg.step_k(acts)
+    for s in range(K):
+        assert torch.equal(ee.step(acts[s])[0], first[0][s]), s
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        obs_k, rew_k, term_k, trunc_k, _ = eg.step_k(acts)
+    nfin = 0
+    for rep in range(2):
+        graph.replay()
+        torch.cuda.synchronize()
+        for s in range(K):
+            o, r, te, tr, _ = ee.step(acts[s])
+            assert torch.equal(o, obs_k[s]) and torch.equal(r, rew_k[s]), (rep, s)
+            assert torch.equal(te, term_k[s]) and torch.equal(tr, trunc_k[s]), (rep, s)
+            nfin += int((te | tr).sum())
+    assert nfin > 0
+    assert eg.sync_tick() == ee.tick == 1 + 3 * K
+    assert torch.equal(ee.get_state("pid"), eg.get_state("pid"))
+    assert torch.equal(ee.step(acts[0])[0], eg.step(acts[0])[0])  # eager again after the replays
+    ee.close(); eg.close()
