@@ -258,9 +258,6 @@ struct pds_handle {
   uint64_t tick;  // host mirror of the device clock words (pds_sync_tick refreshes it)
   bool was_reset;
   bool after_evaluate;  // pds_evaluate_policies ran and no unmasked reset since: every tile stopped at a step of its own
-  int stored_from_agg;  // (set in pds_create) aggregate_phy_steps from which pds_step keeps the noisy observation in memory
-  bool split_reset;   // pds_step launches the SplitReset form + post_reset_kernel where the variant has one (PDS_SPLIT_RESET != 0)
-  bool stored_ready;  // kLaunchStepStored handles: the one materialize_oh_kernel pass in front of their first step is done
   char err[512];
 };
 
@@ -305,7 +302,7 @@ static thread_local char g_create_err[512] = "";
 // the mask), pds_set_tick, the pds_set_state edits -- and in front of the K-step / rollout kernels, which read it from memory.
 // The history half of the next observation is then the observation that was returned, as in the reference (envs/base.py:303-319).
 static int materialize_kept_obs(pds_handle *h, hipStream_t s) {
-  if (!(PDS_REGEN_OBS && h->flags.on && !h->flags.hold)) return PDS_OK;
+  if (!(h->flags.on && !h->flags.hold)) return PDS_OK;
   const long long n = h->cfg.num_envs;
   hipLaunchKernelGGL(pds::materialize_oh_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, h->st, h->k, n,
                      (unsigned long long)h->cfg.env_id_base, (uint32_t)h->cfg.seed, (uint32_t)(h->cfg.seed >> 32));
@@ -540,14 +537,6 @@ extern "C" int pds_create(const pds_config *cfg, pds_handle **out) {
   h->flags.hold = h->k.obs_rate != 1;
   h->flags.half_tile = false;
   if (const char *ft = getenv("PDS_FORCE_TILE")) h->force_tile = (ft[0] == 'h') ? 1 : ((ft[0] == 'f') ? 2 : 0);
-  // Round 6 built the reset OUT of the single-step kernel (SplitReset<V> + post_reset_kernel, csrc/pds_types.h) and measured it
-  // SLOWER than the in-place reset on every configuration (profiles/r06_ab_split_reset.txt: config 6 85 -> 108-117 us), so it is
-  // off unless PDS_SPLIT_RESET=1 asks for it (same bits either way: tests/test_gpu_properties.py)
-  h->split_reset = false;
-  if (const char *sr = getenv("PDS_SPLIT_RESET")) h->split_reset = sr[0] == '1';
-  h->stored_from_agg = PDS_STORED_OH_FROM_AGG;  // (the memset above wiped the member initialisers)
-  if (PDS_STORED_OH_FROM_AGG > 0)
-    if (const char *sa = getenv("PDS_STORED_OH_FROM_AGG")) h->stored_from_agg = atoi(sa);  // (A/B builds: 0 = always regenerate)
   const size_t n = (size_t)cfg->num_envs;
   const size_t ntiles = (n + kWave - 1) / kWave;
   const LaunchFlags &f = h->flags;
@@ -771,7 +760,7 @@ extern "C" int pds_bytes_per_env_step(const pds_handle *h) {
   if (f.motor) b += 32;
   if (f.motor && f.dr) b += 32;
   if (f.tn) b += 32;
-  if (f.on) b += 48 + ((f.hold || !PDS_REGEN_OBS || (h->stored_from_agg > 0 && h->cfg.aggregate_phy_steps >= h->stored_from_agg)) ? 80 : 0);
+  if (f.on) b += 48 + (f.hold ? 80 : 0);
   if (f.ctrl >= 1) b += 48;  // rate-PID integral + last error, R+W
   if (f.ctrl == 2) b += 48;  // attitude-PID integral + last error, R+W
   if (f.lat) b += 32 * h->cfg.aggregate_phy_steps;
@@ -798,7 +787,7 @@ extern "C" int pds_bytes_per_env_step_k(const pds_handle *h, int k_steps) {
   const int stream = 16 + 4 * h->obs_dim + 10 + (f.lat ? 32 * h->cfg.aggregate_phy_steps : 0);
   // once per launch: the state read + written, both ring slots and the randomised parameters written back
   // (+ the kept noisy observation, which the K-step kernel reads from and leaves in oh0-2: materialize_oh_kernel)
-  const int state = full - stream + 16 + (f.dr ? 24 : 0) + (f.dr && f.motor ? 32 : 0) + ((PDS_REGEN_OBS && f.on && !f.hold) ? 80 : 0);
+  const int state = full - stream + 16 + (f.dr ? 24 : 0) + (f.dr && f.motor ? 32 : 0) + ((f.on && !f.hold) ? 80 : 0);
   return stream + (state + k_steps - 1) / k_steps;
 }
 
@@ -816,7 +805,7 @@ static void base_args(pds_handle *h, StepArgs &a) {
 
 static void launch_family(pds_handle *h, int kind, const LaunchFlags &lf, dim3 grid, hipStream_t s, const StepArgs &a) {
   const int task = h->cfg.task;
-  const bool reset_kind = kind == kLaunchReset || kind == kLaunchPostReset;
+  const bool reset_kind = kind == kLaunchReset;
   if (lf.hold && !reset_kind) {  // (a reset observes at iteration 0: always a fresh observation)
     if (task == PDS_TASK_HOVER) launch_hover_hold(kind, lf, grid, s, a);
     else if (task == PDS_TASK_CIRCLE) launch_circle_hold(kind, lf, grid, s, a);
@@ -904,29 +893,7 @@ extern "C" int pds_step_with_variates(pds_handle *h, const float *d_actions, con
   lf.half_tile = grid.x > (unsigned)kFullTileBlocksPerCU * cus * (256 / kBlock) && grid.x <= (merged ? 5u : 8u) * cus * (256 / kBlock);
   if (h->force_tile) lf.half_tile = h->force_tile == 1;
   if (lf.on || lf.lat) lf.half_tile = false;  // (no half-tile instantiation)
-  // observation noise with two or more physics sub-steps: the StoredOh form of the same kernel (kLaunchStepStored); such a
-  // handle never runs the regenerating form, so every env's kept observation is in memory from the first call on
-  int kind = kLaunchStep;
-  if (PDS_REGEN_OBS && h->stored_from_agg > 0 && lf.on && !lf.hold && h->cfg.aggregate_phy_steps >= h->stored_from_agg &&
-      d_variates == nullptr) {
-    kind = kLaunchStepStored;
-    if (!h->stored_ready) {
-      if (const int rc = materialize_kept_obs(h, (hipStream_t)stream)) return rc;
-      h->stored_ready = true;
-    }
-  }
-  // Round 6 (opt-in, PDS_SPLIT_RESET=1: measured slower, see pds_create): where the single-step kernel resets finished envs IN
-  // PLACE (observation noise / latency ring: no merged form), it is launched in its SplitReset form instead and post_reset_kernel
-  // behind it resets them densely (csrc/pds_types.h SplitReset: same draws, same bits).  Not with injected variates (parity
-  // replays) -- their reset rows carry the kCtrOhBit bookkeeping of the in-place path.
-  const bool split = h->split_reset && h->cfg.auto_reset && d_variates == nullptr && kind == kLaunchStep &&
-                     split_reset_supported(h->cfg.task, lf);
-  launch_family(h, split ? kLaunchStepSplit : kind, lf, grid, (hipStream_t)stream, a);
-  if (split) {
-    a.k_steps = lf.hold ? 2 : ((PDS_REGEN_OBS && lf.on) ? 0 : 1);  // reset_store's oh_mode
-    const dim3 pgrid((unsigned)((a.n + kPostResetEnvsPerBlock - 1) / kPostResetEnvsPerBlock));
-    launch_family(h, kLaunchPostReset, lf, pgrid, (hipStream_t)stream, a);
-  }
+  launch_family(h, kLaunchStep, lf, grid, (hipStream_t)stream, a);
   PDS_HIP(h, hipGetLastError());
   h->tick += 1;
   return PDS_OK;
@@ -1209,7 +1176,7 @@ static int do_field(pds_handle *h, int field, void *d_ptr, int set, void *stream
   memset(&a, 0, sizeof(a));
   a.st = h->st; a.k = h->k; a.user = d_ptr; a.n = h->cfg.num_envs; a.field = field; a.task = h->cfg.task; a.set = set;
   a.has_motor = h->flags.motor; a.has_dr = h->flags.dr; a.has_tn = h->flags.tn; a.has_on = h->flags.on; a.ctrl = h->flags.ctrl;
-  a.regen_obs = PDS_REGEN_OBS && h->flags.on && !h->flags.hold;
+  a.regen_obs = h->flags.on && !h->flags.hold;
   // an edit of the state / step counter does not change what the env has OBSERVED: the kept observation is regenerated from the
   // unedited state first and stays in oh0-2 (the reference's history keeps the row that was returned, envs/base.py:303-319)
   if (set && field != PDS_F_NOISY_OBS)

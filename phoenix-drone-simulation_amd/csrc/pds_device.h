@@ -101,16 +101,7 @@ struct U4 { uint32_t x, y, z, w; };
 
 // a ^ b ^ c in ONE vector instruction (gfx950 v_bitop3_b32, truth table 0x96): the compiler emits two v_xor_b32 for the
 // three-input xor of a Philox round (it reserves BITOP3 for mixed and/or/xor trees) -- 2 of the ~14 vector instructions of a round
-#ifndef PDS_XOR3
-#define PDS_XOR3 1
-#endif
-PDS_DEV uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-#if PDS_XOR3
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-#else
-  return a ^ b ^ c;
-#endif
-}
+PDS_DEV uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
 
 // X3: see philox4x32_10_or_7 below (default: the 7-round per-step noise blocks use v_bitop3_b32, the 10-round reset / sampling
 // blocks plain xors)
@@ -209,52 +200,22 @@ PDS_DEV float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), h
 
 // Streamed-once tensors (actions in; observation, reward, cost, flags out) use the non-temporal
 // cache policy so they do not evict the state quads that the next step re-reads (measured on the
-// traffic-shape microbenchmark: +1.5 %).  -DPDS_NT=0 builds the plain-policy variant for A/B runs.
-#ifndef PDS_NT
-#define PDS_NT 1
-#endif
+// traffic-shape microbenchmark: +1.5 %).
 typedef float pds_v4f __attribute__((ext_vector_type(4)));
 PDS_DEV float4 nt_load4(const float4 *p) {
-#if PDS_NT
   const pds_v4f t = __builtin_nontemporal_load(reinterpret_cast<const pds_v4f *>(p));
   return make_float4(t.x, t.y, t.z, t.w);
-#else
-  return *p;
-#endif
 }
 PDS_DEV void nt_store4(float4 *p, const float4 v) {
-#if PDS_NT
   const pds_v4f t = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(t, reinterpret_cast<pds_v4f *>(p));
-#else
-  *p = v;
-#endif
 }
-// cache policy of the per-env STATE quads (re-read by the next step): tuning knob
-#ifndef PDS_NT_STATE
-#define PDS_NT_STATE 0
-#endif
-PDS_DEV float4 st_load4(const float4 *p) {
-#if PDS_NT_STATE >= 2
-  return nt_load4(p);
-#else
-  return *p;
-#endif
-}
-PDS_DEV void st_store4(float4 *p, const float4 v) {
-#if PDS_NT_STATE >= 1
-  nt_store4(p, v);
-#else
-  *p = v;
-#endif
-}
+// the per-env STATE quads (re-read by the next step) keep the plain cache policy
+PDS_DEV float4 st_load4(const float4 *p) { return *p; }
+PDS_DEV void st_store4(float4 *p, const float4 v) { *p = v; }
 template <typename T>
 PDS_DEV void nt_store(T *p, const T v) {
-#if PDS_NT
   __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
 }
 
 }  // namespace pds

@@ -147,7 +147,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
       // (opaque per-iteration copies of the seed and the lane index: see step_k_kernel)
       RngKey rks = rk;
       int lane_s = lane;
-      if (PDS_STEPK_OPAQUE_KEY) asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
+      asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
       // every step's outputs go to the SAME sink row: offset 0, but opaque -- step_once renews its late views of the kernel
       // arguments per iteration by this offset (reload_args' tag); a constant would hoist them out of the loop, into registers
       long long o1 = 0;

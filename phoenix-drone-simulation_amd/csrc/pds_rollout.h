@@ -274,7 +274,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void rollout_kernel(con
         //  derivatives would otherwise be formed in the loop header and spilled)
         RngKey rks = rk;
         int lane_s = lane;
-        if (PDS_STEPK_OPAQUE_KEY) asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
+        asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
         const float4 act = act_all[grp][lane_s];
         StepOut so;
 #ifdef PDS_STAMPS_RESET

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
       rollout_wait_ge(&act_ready, kRolloutMlpWaves * (s + 1));  // the network waves have read the histories and written a(s)
       RngKey rks = rk;  // (opaque per-iteration copies: see step_k_kernel)
       int lane_s = lane;
-      if (PDS_STEPK_OPAQUE_KEY) asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
+      asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
       const float4 act = act_all[lane_s];
       StepOut so;
       step_once<V, kWave, RM, false>(rl.s, o1, rks, parity, nullptr, tile, nullptr, queue, scratch, lane_s, wave_base, ix, active, act, S,

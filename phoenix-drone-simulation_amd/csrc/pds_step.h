@@ -58,23 +58,24 @@ constexpr bool heavy_variant() { return V::MOTOR || V::DR || V::TN || V::ON || V
 // remove and paid for it: same box, round-2 vs round-3 library, headline 55.6 -> 56.1 us, Hover 65 536 (half tile)
 // 6.98 -> 7.2 us, TakeOff + ground effect 57.8 -> 58.5 us (profiles/r03_ab_final_vs_round2.txt).  They keep the
 // round-2 forms: 64-bit per-lane addresses, and on the half tile the whole row in registers until its pass.
-#ifndef PDS_SADDR_LEAN
-#define PDS_SADDR_LEAN 0  // A/B: 1 = round-3 form for every variant
-#endif
 template <class V>
-constexpr bool saddr_variant() { return PDS_SADDR_LEAN || heavy_variant<V>(); }
+constexpr bool saddr_variant() { return heavy_variant<V>(); }
 template <class V>
-constexpr bool park_variant() { return PDS_SADDR_LEAN || heavy_variant<V>(); }
+constexpr bool park_variant() { return heavy_variant<V>(); }
 template <class V>
 using Idx = EnvIdxT<saddr_variant<V>()>;
 
 // Observation-noise variants without the Kalman hold do not keep the noisy o(k) in memory: it is regenerated
-// (regen_kept_obs, csrc/pds_reset.h) unless the env's counter word says it was stored (kCtrOhBit; PDS_REGEN_OBS in pds_types.h).
+// (regen_kept_obs, csrc/pds_reset.h) unless the env's counter word says it was stored (kCtrOhBit, csrc/pds_types.h).
+// The single-step kernel regenerates whatever the number of physics sub-steps: its StoredOh form, built and measured in round 5,
+// was the slower one at every sub-step count -- same box, Hover default 2^20: 2 sub-steps 113.5 (regenerating) vs 120.9 us,
+// 4 sub-steps 197.5 vs 205.4 (profiles/r05_ab_stored_vs_regen.txt): the regenerating form runs four blocks per CU
+// (four_block_variant below), the stored form three.
 template <class V>
-constexpr bool regen_obs_variant() { return PDS_REGEN_OBS && V::ON && !V::HOLD && !V::OH_STORED; }
+constexpr bool regen_obs_variant() { return V::ON && !V::HOLD && !V::OH_STORED; }
 // ... and a kernel that leaves every env's kept observation in oh0-2 says so in the counter word (StoredOh)
 template <class V>
-constexpr bool flags_oh_variant() { return PDS_REGEN_OBS && V::ON && !V::HOLD && V::OH_STORED; }
+constexpr bool flags_oh_variant() { return V::ON && !V::HOLD && V::OH_STORED; }
 
 // Wave-cooperative copy of this wave's [rows, D] LDS tile to global memory (contiguous region).
 template <int D, int TR, bool SADDR>
@@ -132,10 +133,8 @@ PDS_DEV void flush_tile(const float *tile, float *gdst, int rows, int lane) {
 //  2  action FIRST and waited for before the other loads are issued: paces the 12-20 streams of the
 //     heavy variants when the whole grid starts at once (Circle 262 144 + PT1 + DR: 20.7 vs 22.8 us;
 //     Hover 2^20 with noise + DR: 89.4 vs 90.0 us).
-// 0 = action first without the wait (A/B only).  Default: by variant.
-#ifndef PDS_ACT_LOAD_ORDER
-#define PDS_ACT_LOAD_ORDER ((V::MOTOR || V::DR || V::TN || V::ON || V::CTRL != 0 || V::LAT) ? 2 : 1)
-#endif
+template <class V>
+constexpr int act_load_order() { return heavy_variant<V>() ? 2 : 1; }
 // Inputs of one env-step, loaded 16 B/lane.
 struct Loaded {
   float4 act, q0, q1, q2, hA, hB, mx, p0, mA, mK, ou, nz0, oh0, oh1, pid0, pid2;
@@ -149,9 +148,11 @@ struct Loaded {
 // loads -- no load address depends on another load.
 template <class V>
 PDS_DEV void load_env(const StepArgs &a, const Idx<V> ix, long long tile, Loaded &L) {
-  constexpr int kOrder = PDS_ACT_LOAD_ORDER;
-  if (kOrder == 0 || kOrder == 2) L.act = nt_load4(at(a.actions, ix));  // read once per step: keep it out of the caches
-  if (kOrder == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  constexpr int kOrder = act_load_order<V>();
+  if (kOrder == 2) {
+    L.act = nt_load4(at(a.actions, ix));  // read once per step: keep it out of the caches
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
   L.q0 = st_load4(at(a.st.s0, ix));
   L.q1 = st_load4(at(a.st.s1, ix));
   L.q2 = st_load4(at(a.st.s2, ix));
@@ -715,8 +716,7 @@ PDS_DEV bool step_once(const StepArgs &a, const long long o1, const RngKey &rk, 
   // ---- auto-reset.  ~2 % of the envs finish per step under random actions, i.e. 3 of 4 waves
   // hold one or two finished envs.  Their last observation goes to final_obs (below, out of the
   // LDS tile); the reset itself: see RM_* above.
-  // SplitReset<V> (round 6): the finished envs are reset by post_reset_kernel behind this launch, nothing of it is compiled in
-  const bool need_reset = (V::SPLIT_RESET && STORE) ? false : (a.auto_reset && (done || trunc) && active);
+  const bool need_reset = a.auto_reset && (done || trunc) && active;
   const unsigned long long reset_mask = __ballot(need_reset);  // wave-uniform
   const unsigned long long done_mask = (a.final_obs != nullptr || fin_lds != nullptr) ? reset_mask : 0ull;  // -> final_obs
   if (so != nullptr) { so->reward = reward; so->done = done; so->trunc = trunc; }
@@ -979,13 +979,11 @@ constexpr bool inline_reset_single_step() {  // (the rule itself: csrc/pds_types
   return TR == kWave && inline_single_step_rule(V::TASK, V::ON, V::LAT, V::CTRL);
 }
 
-#ifndef PDS_MERGED_HALF_PT1DR
-#define PDS_MERGED_HALF_PT1DR 1  // round 3: fits since the half tile parks the first row half in LDS (A/B: 0 = deferred drain)
-#endif
 template <class V, int TR = kWave>
 constexpr bool merged_reset_variant() {
-  // (the half tile keeps the whole observation row in registers: PT1 + DR would spill 61 VGPRs there)
-  return PDS_MERGED_RESET && !V::ON && !V::LAT && V::TASK != PDS_TASK_TAKEOFF && (TR == kWave || !(V::MOTOR && V::DR) || (PDS_MERGED_HALF_PT1DR && V::CTRL == 0 && !V::TN));  // (PID / thrust-noise + PT1 + DR: 6-22 spilled VGPRs under the half tile's cap)
+  // (half tile, PT1 + DR: fits since round 3, when the half tile began to park the first row half in LDS -- with the whole
+  //  observation row in registers it spilled 61 VGPRs there)
+  return !V::ON && !V::LAT && V::TASK != PDS_TASK_TAKEOFF && (TR == kWave || !(V::MOTOR && V::DR) || (V::CTRL == 0 && !V::TN));  // (PID / thrust-noise + PT1 + DR: 6-22 spilled VGPRs under the half tile's cap)
 }
 
 // The kernel arguments (StepArgs, ~10 cache lines) are read with scalar loads that the compiler
@@ -994,11 +992,7 @@ constexpr bool merged_reset_variant() {
 // the spot: measured with the s_memtime stamps, ~250 cycles each, a third of a wave's lifetime when
 // one wave runs per SIMD (65 536 envs).  Touching every line once at kernel entry (all misses in
 // flight together, one wait) turns the later loads into scalar-cache hits.
-#ifndef PDS_KERNARG_PREFETCH
-#define PDS_KERNARG_PREFETCH 1
-#endif
 PDS_DEV void prefetch_kernargs() {
-#if PDS_KERNARG_PREFETCH
   // one dword from every 64-byte line that starts inside the kernarg segment
   static_assert(sizeof(StepArgs) > 8 * 64 && sizeof(StepArgs) <= 9 * 64, "prefetch_kernargs touches lines 0..8: adjust");
   const auto p = __builtin_amdgcn_kernarg_segment_ptr();
@@ -1011,7 +1005,6 @@ PDS_DEV void prefetch_kernargs() {
       : "=&s"(t0), "=&s"(t1), "=&s"(t2), "=&s"(t3), "=&s"(t4), "=&s"(t5), "=&s"(t6), "=&s"(t7), "=&s"(t8)
       : "s"(p)
       : "memory");
-#endif
 }
 
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share one; MI355X_MICROARCH.md,
@@ -1020,16 +1013,13 @@ PDS_DEV void prefetch_kernargs() {
 // contiguous eighth of each array.  Speed only (any permutation of blocks over tiles is correct; grids that are
 // not a multiple of 8 keep the identity).  Same-box A/B: Hover 2^20 56.4 -> 55.5 us, TakeOff + GE 58.6 -> 57.8,
 // Hover 2^21 107.7 -> 105.3 (86 % of the HBM peak), neutral at 2^19 and on the single-round configs.
-#ifndef PDS_XCD_REMAP
-#define PDS_XCD_REMAP 1
-#endif
 #define PDS_WAVE_LDS(V, TR, RM, ST)                                                                      \
   __shared__ __attribute__((aligned(16))) float tile_all[(kBlock / kWave) * TR * tile_stride<V::D>()]; \
   constexpr int kParkFloats_ = (TR == kWave || !park_variant<V>()) ? 0 : (kWave - TR) * park_stride<V::O + 4>(); \
   __shared__ __attribute__((aligned(16))) float park_all[kParkFloats_ > 0 ? (kBlock / kWave) * kParkFloats_ : 4]; \
   const float2 *ref_lds = nullptr; /* (the Circle table of rounds 1-2: the reference point is evaluated now) */ \
   __shared__ uint32_t queue_all[(kBlock / kWave) * kQueueCap];                                        \
-  constexpr int kScratchU4_ = (RM == RM_MERGED) ? kMergedScratchU4 : ((RM == RM_INLINE && inline_coop_variant<V>() && !(V::SPLIT_RESET && ST)) ? inline_envs<V, ST>() * scratch_stride<V>() : 0); \
+  constexpr int kScratchU4_ = (RM == RM_MERGED) ? kMergedScratchU4 : ((RM == RM_INLINE && inline_coop_variant<V>()) ? inline_envs<V, ST>() * scratch_stride<V>() : 0); \
   __shared__ U4 scratch_all[kScratchU4_ > 0 ? (kBlock / kWave) * kScratchU4_ : 1];                     \
   const int tid = threadIdx.x;                                                                         \
   const int lane = tid & (kWave - 1);                                                                  \
@@ -1043,7 +1033,7 @@ PDS_DEV void prefetch_kernargs() {
   PDS_WAVE_LDS(V, TR, RM, ST)                                                                            \
   const long long ntiles = (a.n + kWave - 1) / kWave;                                                  \
   long long blk_ = blockIdx.x;                                                                         \
-  if (PDS_XCD_REMAP) { /* blocks b, b + 8, ... (one XCD) take consecutive tiles */                     \
+  { /* blocks b, b + 8, ... (one XCD) take consecutive tiles */                                        \
     const long long nb_ = gridDim.x, per_ = nb_ / 8;                                                   \
     if (per_ * 8 == nb_) blk_ = (blk_ % 8) * per_ + blk_ / 8;                                          \
   }                                                                                                    \
@@ -1141,9 +1131,6 @@ __global__ __launch_bounds__(kBlock, (PDS_MIN_WAVES) * (256 / kBlock)) void step
 // Circle AttitudeRate 61.0 -> 45.0, Hover Attitude default noise, 4 sub-steps 99.6 -> 80.4, Circle AttitudeRate PT1 + DR
 // 75.6 -> 47.6, Hover AttitudeRate + latency ring, default noise (3-9 spilled) 87.1 -> 63.7, Circle Attitude + latency ring + PT1
 // 89.7 -> 59.1; spread of the repeats <= 2.3 (profiles/stepk_pid_timing.txt).  No variant is left to the loop for its registers.
-#ifndef PDS_STEPK_OPAQUE_KEY
-#define PDS_STEPK_OPAQUE_KEY 1  // A/B: 0 = round-3 form (key schedule hoisted out of the K loop and spilled)
-#endif
 #ifndef PDS_STEPK_MIN_WAVES_OF
 #define PDS_STEPK_MIN_WAVES_OF(V) 3
 #endif
@@ -1176,7 +1163,7 @@ __global__ __launch_bounds__(kBlock, (PDS_STEPK_MIN_WAVES_OF(V_)) * (256 / kBloc
   for (int s = 0; s < K; ++s) {
     // a fresh view of the kernel arguments per iteration: what the loop body needs is re-read (scalar-cache
     // hits) instead of being hoisted out of the loop into SGPRs that do not exist (41-79 spills in round 2)
-    const StepArgs &al = reload_args<106, PDS_STEPK_OPAQUE_KEY || heavy_variant<W>()>(a, s);
+    const StepArgs &al = reload_args<106>(a, s);
     // ... and the Philox key (the env waves of both rollout kernels make the same two copies, in one statement; as one
     // forced-inline function for the three kernels, in either form, they moved registers: profiles/rollout_refactor_resources.txt):
     // the 2 x 10 round keys (seed + r x Weyl constant) are loop-invariant, so the compiler forms
@@ -1184,11 +1171,11 @@ __global__ __launch_bounds__(kBlock, (PDS_STEPK_MIN_WAVES_OF(V_)) * (256 / kBloc
     // every round of every Philox call of every iteration (2-45 spilled SGPRs per step_k kernel in round 3).  An opaque
     // copy of the seed per iteration makes the schedule part of the iteration: ~20 scalar adds, live only where used.
     RngKey rks = rk;
-    if (PDS_STEPK_OPAQUE_KEY) asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi));
+    asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi));
     // ... and the lane index: every lane predicate of the body (tile flush bounds, row ownership, `lane < D`) is
     // loop-invariant too and would be kept as a 64-bit mask in an SGPR pair from the loop header on
     int lane_s = lane;
-    if (PDS_STEPK_OPAQUE_KEY) asm volatile("" : "+v"(lane_s));
+    asm volatile("" : "+v"(lane_s));
     float4 act_next = act;
     if (s + 1 < K) act_next = nt_load4(at(al.actions + (long long)(s + 1) * al.n, ix));  // in flight during step s
     step_once<W, TR, RM, false>(al, (long long)s * al.n, rks, parity, ref_lds, tile, park, queue, scratch, lane_s, wave_base, ix, active, act, S, qcount, nullptr, nullptr PDS_STAMP_ARG);
@@ -1203,38 +1190,20 @@ __global__ __launch_bounds__(kBlock, (PDS_STEPK_MIN_WAVES_OF(V_)) * (256 / kBloc
 // ---- host-side dispatch: runtime flags -> template instantiation ----------------------------------
 template <class V>
 inline void launch_variant(int kind, bool half_tile, dim3 grid, hipStream_t s, const StepArgs &a) {
-  if (kind == kLaunchReset || kind == kLaunchPostReset) {
-    // the reset kernels do not depend on GE / TN / CTRL / HOLD: the launch_* families fold those flags before
+  if (kind == kLaunchReset) {
+    // the reset kernel does not depend on GE / TN / CTRL / HOLD: the launch_* families fold those flags before
     // they get here, so only the folded variants are instantiated (48 kernels instead of 472)
-    if constexpr (!V::GE && !V::TN && V::CTRL == 0 && !V::HOLD) {
-      if (kind == kLaunchReset) hipLaunchKernelGGL((reset_kernel<V>), grid, dim3(kBlock), 0, s, a);
-      else if constexpr (V::ON || V::LAT) hipLaunchKernelGGL((post_reset_kernel<V>), grid, dim3(kWave), 0, s, a);
-      else abort();
-    } else abort();
+    if constexpr (!V::GE && !V::TN && V::CTRL == 0 && !V::HOLD) hipLaunchKernelGGL((reset_kernel<V>), grid, dim3(kBlock), 0, s, a);
+    else abort();
   } else if (kind == kLaunchStepK) {
     // (a PID mode with the ground effect or the Kalman hold has no K-step kernel: pds_step_k loops over pds_step there and
     //  never gets here -- step_k_rule, csrc/pds_types.h)
     if constexpr (step_k_rule(V::CTRL, V::GE, V::HOLD)) hipLaunchKernelGGL((step_k_kernel<V>), grid, dim3(kBlock), 0, s, a);
     else abort();
   } else {
-#if PDS_STORED_OH_FROM_AGG > 0
-    if constexpr (regen_obs_variant<V>()) {
-      // stored vs regenerated kept observation as a per-launch choice (same bits either way): see kLaunchStepStored
-      if (kind == kLaunchStepStored) {
-        hipLaunchKernelGGL((step_kernel<StoredOh<V>, kWave>), grid, dim3(kBlock), 0, s, a);
-        return;
-      }
-    }
-#endif
     if constexpr (!V::ON && !V::LAT) {
       if (half_tile) {
         hipLaunchKernelGGL((step_kernel<V, kHalfTileRows>), grid, dim3(kBlock), 0, s, a);
-        return;
-      }
-    }
-    if constexpr (inline_reset_single_step<V, kWave>()) {
-      if (kind == kLaunchStepSplit) {  // the host launches post_reset_kernel behind it (csrc/pds_api.hip)
-        hipLaunchKernelGGL((step_kernel<SplitReset<V>, kWave>), grid, dim3(kBlock), 0, s, a);
         return;
       }
     }
@@ -1268,7 +1237,7 @@ struct VariantDispatch {
 // The reset kernel does not depend on GE / TN / CTRL: those flags are folded to false / 0 for it.
 template <int TASK>
 inline void launch_base(int kind, const LaunchFlags &f, dim3 grid, hipStream_t s, const StepArgs &a) {
-  if (kind == kLaunchReset || kind == kLaunchPostReset) VariantDispatch<TASK, 0, false, false>::run(kind, false, grid, s, a, f.motor, f.dr, false, false, f.on);
+  if (kind == kLaunchReset) VariantDispatch<TASK, 0, false, false>::run(kind, false, grid, s, a, f.motor, f.dr, false, false, f.on);
   else VariantDispatch<TASK, 0, false, false>::run(kind, f.half_tile, grid, s, a, f.motor, f.dr, f.ge, f.tn, f.on);
 }
 template <int TASK>
@@ -1296,7 +1265,7 @@ inline void launch_pid_ge(int kind, const LaunchFlags &f, dim3 grid, hipStream_t
 }
 template <int TASK>
 inline void launch_lat(int kind, const LaunchFlags &f, dim3 grid, hipStream_t s, const StepArgs &a) {
-  if (kind == kLaunchReset || kind == kLaunchPostReset) { VariantDispatch<TASK, 0, true, false>::run(kind, false, grid, s, a, f.motor, f.dr, false, false, f.on); return; }
+  if (kind == kLaunchReset) { VariantDispatch<TASK, 0, true, false>::run(kind, false, grid, s, a, f.motor, f.dr, false, false, f.on); return; }
   if (TASK == PDS_TASK_TAKEOFF || f.ctrl == 0) VariantDispatch<TASK, 0, true, false>::run(kind, false, grid, s, a, f.motor, f.dr, f.ge, f.tn, f.on);
   else if constexpr (TASK != PDS_TASK_TAKEOFF) {  // TakeOff fixes control_mode='PWM', envs/takeoff.py:225
     if (f.ctrl == 1) VariantDispatch<TASK, 1, true, false>::run(kind, false, grid, s, a, f.motor, f.dr, false, f.tn, f.on);

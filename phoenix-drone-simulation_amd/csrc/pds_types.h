@@ -13,9 +13,6 @@ namespace pds {
 #define PDS_BLOCK 256
 #endif
 constexpr int kBlock = PDS_BLOCK;  // 4 waves; each wave owns a private LDS tile (no block barrier needed)
-#ifndef PDS_MERGED_RESET
-#define PDS_MERGED_RESET 1  // A/B: 0 = deferred drain everywhere
-#endif
 constexpr int kWave = 64;
 // Rows of the per-wave LDS observation tile: the step kernel exists with a full tile (64 rows,
 // 43 KB LDS per block for Hover => 3 blocks per CU) and, for the variants without observation
@@ -50,12 +47,9 @@ PDS_DEV uint32_t ctr_lat(uint32_t c) { return (c >> 26) & 0x7u; }
 // oh0-2".  Clear = it is REGENERATED from the stored true state and the previous tick's Philox blocks (round 4: the
 // Philox-driven single-step kernel neither reads nor writes oh0-2, -80 B per env-step).  Set by whatever produced o(k) from
 // draws that Philox cannot replay -- pds_reset / pds_reset_from_samples, pds_step_with_variates, pds_set_state(NOISY_OBS), the
-// deferred-drain resets --, by the kernels that keep it in memory (StoredOh: pds_step_k, pds_rollout, pds_step with two or more
-// physics sub-steps) and by materialize_oh_kernel, which csrc/pds_api.hip runs in front of everything that would otherwise
+// deferred-drain resets --, by the kernels that keep it in memory (StoredOh: pds_step_k, pds_rollout, pds_evaluate_policies)
+// and by materialize_oh_kernel, which csrc/pds_api.hip runs in front of everything that would otherwise
 // invalidate the regeneration's inputs: a masked reset (the clock of every tile advances), pds_set_tick, any pds_set_state.
-#ifndef PDS_REGEN_OBS
-#define PDS_REGEN_OBS 1  // A/B: 0 = the kept observation always lives in oh0-2 (rounds 1-3)
-#endif
 constexpr uint32_t kCtrOhBit = 1u << 29;
 PDS_DEV uint32_t ctr_oh(uint32_t c) { return (c >> 29) & 1u; }
 PDS_DEV uint32_t circle_ref_offset(uint32_t c, int ref_points) {  // not on the hot path
@@ -213,9 +207,6 @@ struct StepArgs {
 // round 2).  Reading the late phases' arguments through an OPAQUE copy of the kernarg pointer makes those
 // values new loads (scalar-cache hits: the segment was prefetched at entry) instead of live ranges.
 // (Kernels only: the calling kernel's first parameter must be the StepArgs struct.)
-#ifndef PDS_RELOAD_ARGS
-#define PDS_RELOAD_ARGS 1
-#endif
 // ID: one per call site (the asm is not volatile, see fresh(); equal calls would be merged); `tag`: a loop
 // counter when the view has to be renewed per iteration (otherwise the asm is loop-invariant and hoisted).
 // ENABLE = false: the lean variants (no PT1 / DR / noise / PID / latency) fit the SGPR file as they are, and on
@@ -226,7 +217,7 @@ struct StepArgs {
 // static_assert below).
 template <int ID, bool ENABLE = true>
 PDS_DEV const StepArgs &reload_args(const StepArgs &passed, int tag = 0) {
-  if (!ENABLE || !PDS_RELOAD_ARGS) return passed;
+  if (!ENABLE) return passed;
   auto kp = __builtin_amdgcn_kernarg_segment_ptr();
   asm("" : "+s"(kp) : "n"(ID), "s"(tag));
   return *(const StepArgs *)kp;  // (C cast: address space 4 -> generic; the loads are inferred back to scalar loads)
@@ -257,7 +248,6 @@ struct Variant {
                                : (TASK_ == PDS_TASK_HOVER ? 17 : (TASK_ == PDS_TASK_CIRCLE ? 16 : 20));
   static constexpr int D = 2 * (O + 4);
   static constexpr bool OH_STORED = false;  // see StoredOh
-  static constexpr bool SPLIT_RESET = false;  // see SplitReset
 };
 
 // The same variant for a kernel that finds the kept noisy observation of EVERY env in oh0-2 (flagged kCtrOhBit by
@@ -266,17 +256,6 @@ struct Variant {
 template <class V>
 struct StoredOh : V {
   static constexpr bool OH_STORED = true;
-};
-
-// The same variant for a single-step kernel that does NOT reset the envs that finish (round 6): it stores their terminal
-// state, leaves their last observation in the obs row and sets the flags; post_reset_kernel (csrc/pds_reset.h), launched behind it
-// on the same stream, compacts the finished envs of 1024-env blocks and resets them DENSELY, one env per lane.  Why: an env that
-// finishes costs the in-place reset ~1750 vector instructions of its whole 64-lane wave (cooperative Philox fill + the evaluation
-// by 1-3 owner lanes) -- at 2 % finished envs per step that is 3 of 4 waves, a third of the step kernel's vector work spent at
-// 2-5 % lane utilisation; densely the same resets cost 1/25 of it.
-template <class V>
-struct SplitReset : V {
-  static constexpr bool SPLIT_RESET = true;
 };
 
 struct EnvRegs {
@@ -362,36 +341,18 @@ struct LaunchFlags {
   bool hold;
   bool half_tile;  // per launch: use the 32-row observation tile (variants without observation noise)
 };
-// kLaunchStepStored: the single-step kernel of an observation-noise variant in its StoredOh form (the kept noisy observation read
-// from and written to oh0-2 instead of regenerated) for pds_step with aggregate_phy_steps >= PDS_STORED_OH_FROM_AGG.  Built and
-// measured in round 5, NOT adopted (the macro is 0: the kernels are not instantiated): the regenerating form is the faster one at
-// every sub-step count -- same box, Hover default 2^20: 2 sub-steps 113.5 vs 120.9 us, 4 sub-steps 197.5 vs 205.4
-// (profiles/r05_ab_stored_vs_regen.txt): it runs four blocks per CU (csrc/pds_step.h four_block_variant), the stored form three.
-#ifndef PDS_STORED_OH_FROM_AGG
-#define PDS_STORED_OH_FROM_AGG 0  // A/B builds: 2 = instantiate the stored single-step kernels and use them from 2 sub-steps on
-#endif
-// Which single-step kernels reset finished envs in registers BEHIND their stores (RM_INLINE, csrc/pds_step.h) -- the ones that
-// have a SplitReset form: observation noise or the latency ring (no merged form), not TakeOff (its envs only finish by the
-// 500-step truncation: deferred drain), not Circle with the latency ring or a PID mode (measured 3-7 % slower than its drain).
-#ifndef PDS_INLINE_SINGLE_STEP
-#define PDS_INLINE_SINGLE_STEP 1  // A/B: 0 = deferred drain
-#endif
+// Which single-step kernels reset finished envs in registers BEHIND their stores (RM_INLINE, csrc/pds_step.h): observation
+// noise or the latency ring (no merged form), not TakeOff (its envs only finish by the 500-step truncation: deferred drain),
+// not Circle with the latency ring or a PID mode (measured 3-7 % slower than its drain).
 constexpr bool inline_single_step_rule(int task, bool on, bool lat, int ctrl) {
-  return PDS_INLINE_SINGLE_STEP && (on || lat) && task != PDS_TASK_TAKEOFF && !(task == PDS_TASK_CIRCLE && (lat || ctrl != 0));
+  return (on || lat) && task != PDS_TASK_TAKEOFF && !(task == PDS_TASK_CIRCLE && (lat || ctrl != 0));
 }
-inline bool split_reset_supported(int task, const LaunchFlags &f) { return inline_single_step_rule(task, f.on, f.lat, f.ctrl); }
-// kLaunchStepSplit / kLaunchPostReset: the single-step kernel without its in-place reset (SplitReset<V>) and the dense reset
-// launched behind it.
-enum LaunchKind { kLaunchStep = 0, kLaunchStepK = 1, kLaunchReset = 2, kLaunchStepStored = 3, kLaunchStepSplit = 4, kLaunchPostReset = 5 };
+enum LaunchKind { kLaunchStep = 0, kLaunchStepK = 1, kLaunchReset = 2 };
 // Which variants have a step_k_kernel (csrc/pds_step.h launch_variant instantiates by this rule, pds_step_k_fused states it for
 // the host): every control_mode PWM variant, and the PID modes in the pid family and on the latency ring -- not a PID mode
 // with the ground effect or with the Kalman hold, for which pds_step_k loops over pds_step.
 constexpr bool step_k_rule(int ctrl, bool ge, bool hold) { return ctrl == 0 || (!ge && !hold); }
 inline bool step_k_supported(const LaunchFlags &f) { return step_k_rule(f.ctrl, f.ge, f.hold); }
-#ifndef PDS_POST_RESET_ENVS
-#define PDS_POST_RESET_ENVS 1024  // envs per wave of post_reset_kernel (A/B: 512, 256)
-#endif
-constexpr int kPostResetEnvsPerBlock = PDS_POST_RESET_ENVS;
 // one translation unit per (task, family) keeps the build parallel: pds_task_*.hip
 // Arguments of the fused rollout (csrc/pds_rollout.h).
 struct RolloutArgs {

@@ -1,5 +1,5 @@
-"""Same-box A/B of pds_step timings between library builds / env-var settings for a few env configurations:
-   python profiles/tools/ab_variants.py  (GPU box; PDS_LIB / PDS_STORED_OH_FROM_AGG are set per child process)."""
+"""Same-box A/B of pds_step timings between library builds for a few env configurations:
+   python profiles/tools/ab_variants.py [LIB ...]  (GPU box; PDS_LIB is set per child process)."""
 import json
 import os
 import subprocess
@@ -48,13 +48,7 @@ if os.environ.get("AB_SIGMA"):  # the action recipe: a = -0.1 + sigma * N(0, 1);
 
 def main():
     libs = sys.argv[1:] or ["libpds_hip.so"]
-    settings = []
-    for lib in libs:
-        settings.append((lib, {}))
-    if os.environ.get("AB_SPLIT"):  # round 6: in-place reset (PDS_SPLIT_RESET=0) against SplitReset step kernel + post_reset_kernel
-        settings = [(libs[0] + " in-place-reset", {"PDS_SPLIT_RESET": "0"})] + [(l + " split-reset", {"PDS_SPLIT_RESET": "1"}) for l in libs]
-    if os.environ.get("AB_STORED"):  # (builds with PDS_STORED_OH_FROM_AGG > 0 only)
-        settings.append((libs[-1] + " regen@agg>=2", {"PDS_STORED_OH_FROM_AGG": "0"}))
+    settings = [(lib, {}) for lib in libs]
     N, steps = 1 << 20, 300
     for name, task, kw in CASES:
         for rep in range(2):

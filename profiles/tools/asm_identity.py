@@ -4,7 +4,7 @@
 Both files come from hipcc with the flags of build.py plus --cuda-device-only -S.  A kernel is the text from its label through
 its .end_amdhsa_kernel (instructions and kernel-descriptor directives); comments, trailing blanks, the position-dependent
 number in .LBB<n>_ / .Lfunc_end<n> / .Ltmp<n> labels and the kernel's own mangled name are normalised away, nothing else.
-Kernels are matched by demangled name (c++filt); ppo_split_kernel<K, 1, B> of trees up to fc3622f matches ppo_split_kernel<K, B>.
+Kernels are matched by their plain demangled name (c++filt).
 Prints one row per kernel (identical / gone / APPEARED / DIFFERS, instruction lines) and exits 1 unless every kernel of NEW.s
 is identical to its namesake."""
 import re, subprocess, sys
@@ -36,12 +36,6 @@ def demangle(names):
     return r.stdout.split("\n")[:len(names)]
 
 
-def canon(d):
-    d = d.replace("pds_mlp_detail::", "").replace("void ", "").replace("(Args)", "")
-    m = re.match(r"ppo_split_kernel<(\d), 1, (\w+)>", d)
-    return "ppo_split_kernel<%s, %s>" % m.groups() if m else d
-
-
 def insn_count(body):
     n = 0
     for ln in body:
@@ -55,7 +49,7 @@ def insn_count(body):
 def load(path):
     k = kernels(path)
     names = list(k)
-    return {canon(d): k[nm] for nm, d in zip(names, demangle(names))}
+    return {d: k[nm] for nm, d in zip(names, demangle(names))}
 
 
 a, b = load(sys.argv[1]), load(sys.argv[2])

@@ -22,6 +22,15 @@ VARIANTS = [
     ("hover", dict(observation_frequency=50)),                                  # Kalman-hold variant, noise + DR
     ("takeoff", dict(observation_frequency=25, domain_randomization=-1, use_motor_dynamics=True)),
     ("circle", dict(use_latency=True, latency=0.02)),                           # latency + noise + DR (inline reset)
+    # the single-step kernel's inline reset (observation noise / latency ring: stored after the reset) against the K-step
+    # kernel's (merged back into the loop's registers): two differently compiled forms of the same reset
+    ("hover", dict(domain_randomization=-1, motor_thrust_noise=0.0)),           # observation noise only
+    ("hover", dict(aggregate_phy_steps=2)),
+    ("hover", dict(use_motor_dynamics=True, aggregate_phy_steps=4)),
+    ("circle", dict(use_motor_dynamics=True)),                                  # ref_offset, PT1 + DR
+    ("circle", dict(enable_reset_distribution=False)),                          # ref_offset survives the reset
+    ("hover", dict(DET, use_latency=True, latency=0.035)),                      # latency ring without noise
+    ("hover", dict(use_latency=True, latency=0.02, use_motor_dynamics=True)),
 ]
 
 

@@ -16,6 +16,7 @@ FUSED = [
     ("circle", dict(DET, control_mode="AttitudeRate", use_motor_dynamics=True, domain_randomization=0.1)),  # inline reset
     ("hover", dict(control_mode="AttitudeRate", use_latency=True, latency=0.02)),                    # latency ring, noise + DR
     ("circle", dict(DET, control_mode="Attitude", use_latency=True, latency=0.03, use_motor_dynamics=True)),
+    ("hover", dict(control_mode="AttitudeRate", aggregate_phy_steps=2)),                             # PID state zeroed by the inline reset
 ]
 # what keeps the loop of pds_step: a PID mode with the ground effect or with the Kalman hold
 LOOPED = [
