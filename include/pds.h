@@ -321,6 +321,13 @@ int pds_philox4x32(const uint32_t *d_ctr, const uint32_t *d_key, int rounds, int
  * tests/ hold 2^26 of them against N(0, 1): Kolmogorov-Smirnov distance, moments, tail mass.  Runs on the current device. */
 int pds_noise_normals(uint64_t seed, uint64_t tick, uint32_t block, uint64_t env_id_base, int64_t n, float *d_out, void *stream);
 
+/* The two-word Box-Muller of the Gaussian policy sampler and the ES noise, exposed for verification:
+ * d_out[i][0..1] = (r cos 2 pi u2, r sin 2 pi u2), r = sqrt(-2 ln u1), u1 = ((a >> 8) + 1) 2^-24, u2 = (b >> 8) 2^-24 for the
+ * word pair (a, b) = d_words[i][0..1], i < n -- computed by the device function pds_gaussian_sample, the fused rollouts and
+ * pds_es_* draw their normals with.  tests/ sweep all 2^24 radii and all 2^24 angles against float64.  PDS_EINVAL: a NULL
+ * pointer, n < 1.  Runs on the current device. */
+int pds_box_muller(const uint32_t *d_words, int64_t n, float *d_out, void *stream);
+
 /* observation_history_size = H other than 2 (envs/base.py:44, 303-319, 417-431): advances the [N, H, half]
  * history of every env by the step's new row `d_obs2` [N, 2 * half] (the pds_step output) in one launch.
  * Running envs: hist' = [hist[1:], newest half].  Finished envs (auto_reset != 0): their final history
@@ -450,7 +457,8 @@ int pds_gaussian_sample(const float *d_mu, const float *d_log_std, int64_t n, in
 
 /* The same with the call counter split into a DEVICE word and a by-value offset: call = *d_call_base + call_offset.
  * A rollout captured into a hipGraph passes the step index as the offset and advances the device word once
- * per replay with pds_counter_add (*d_counter += inc, one thread), so every replay draws fresh variates. */
+ * per replay with pds_counter_add (*d_counter += inc, one thread), so every replay draws fresh variates.
+ * The counter packing holds sample ids below 2^56: PDS_EINVAL (both entry points) when id_base + n > 2^56. */
 int pds_gaussian_sample_dev(const float *d_mu, const float *d_log_std, int64_t n, int d_out, uint64_t seed,
                             const uint64_t *d_call_base, uint64_t call_offset, uint64_t id_base, int deterministic,
                             float *d_act, float *d_logp, void *stream);

@@ -1242,6 +1242,22 @@ extern "C" int pds_noise_normals(uint64_t seed, uint64_t tick, uint32_t block, u
   return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
 }
 
+// the two-word Box-Muller of the Gaussian policy sampler and the ES noise (pds_device.h box_muller), one word pair per lane
+__global__ __launch_bounds__(256) void box_muller_kernel(const uint32_t *words, long long n, float *out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float z0, z1;
+  box_muller(words[2 * i], words[2 * i + 1], z0, z1);
+  out[2 * i] = z0; out[2 * i + 1] = z1;
+}
+
+extern "C" int pds_box_muller(const uint32_t *d_words, int64_t n, float *d_out, void *stream) {
+  if (!d_words || !d_out || n < 1) return PDS_EINVAL;
+  hipLaunchKernelGGL(box_muller_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_words,
+                     (long long)n, d_out);
+  return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
+}
+
 extern "C" int pds_philox4x32(const uint32_t *d_ctr, const uint32_t *d_key, int rounds, int64_t n, uint32_t *d_out, void *stream) {
   if (!d_ctr || !d_key || !d_out || n < 0 || (rounds != 7 && rounds != 10)) return PDS_EINVAL;
   if (n == 0) return PDS_OK;

@@ -161,7 +161,9 @@ PDS_DEV float urange_u(float u, float lo, float hi) { return lo + (hi - lo) * u;
 PDS_DEV float urange(uint32_t x, float lo, float hi) { return urange_u(u01(x), lo, hi); }
 // Box-Muller on two Philox words, evaluated with the hardware transcendental units (v_log_f32,
 // v_sqrt_f32, v_sin_f32 / v_cos_f32 take their argument in revolutions): abs error ~1e-6 in z,
-// which is noise on a random variate.  The oracle restates the same formula with libm.
+// which is noise on a random variate -- measured through pds_box_muller over all 2^24 radii and all 2^24 angles against float64:
+// radius 4.88e-7, cos / sin 1.65e-7, so at most 1.44e-6 in z (profiles/gaussian_sample_accuracy.txt).  The oracle restates the
+// same formula with libm.
 PDS_DEV void box_muller(uint32_t a, uint32_t b, float &z0, float &z1) {
   const float u1 = (float)((a >> 8) + 1u) * (1.0f / 16777216.0f);
   const float u2 = u01(b);

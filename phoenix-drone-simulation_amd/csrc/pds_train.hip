@@ -138,6 +138,8 @@ extern "C" int pds_gaussian_sample_dev(const float *d_mu, const float *d_log_std
                                        const uint64_t *d_call_base, uint64_t call_offset, uint64_t id_base,
                                        int deterministic, float *d_act, float *d_logp, void *stream) {
   if (!d_mu || !d_log_std || !d_act || !d_logp || n < 1 || d_out < 1 || d_out > 8) return PDS_EINVAL;
+  // the id packing of PDS_GAUSSIAN_PHILOX holds sample ids below 2^56
+  if ((unsigned __int128)id_base + (unsigned __int128)n > ((unsigned __int128)1 << 56)) return PDS_EINVAL;
   hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_mu, d_log_std,
                      (long long)n, d_out, seed, call_offset, reinterpret_cast<const unsigned long long *>(d_call_base),
                      (unsigned long long)id_base, deterministic, d_act, d_logp);

@@ -34,7 +34,7 @@ EXPORTS = ["pds_version", "pds_default_config", "pds_create", "pds_destroy", "pd
            "pds_field_width",
            "pds_get_state", "pds_set_state", "pds_tick", "pds_set_tick", "pds_sync_tick", "pds_count_nonfinite",
            "pds_bytes_per_env_step", "pds_bytes_per_env_step_k", "pds_last_error", "pds_step_k", "pds_step_k_fused", "pds_set_latency",
-           "pds_latency_steps", "pds_philox4x32", "pds_noise_normals", "pds_gae", "pds_history_advance",
+           "pds_latency_steps", "pds_philox4x32", "pds_noise_normals", "pds_box_muller", "pds_gae", "pds_history_advance",
            "pds_mlp_param_count", "pds_mlp_workspace_floats", "pds_mlp_forward", "pds_ppo_policy_grad",
            "pds_value_grad", "pds_ppo_policy_grad_step", "pds_value_grad_step", "pds_gaussian_sample", "pds_gaussian_sample_dev", "pds_counter_add", "pds_permutation", "pds_rollout_record",
            "pds_adam_step", "pds_rollout", "pds_rollout_history",
@@ -149,6 +149,7 @@ def load():
     later("pds_gaussian_sample_dev", [vp, vp, i64, i32, u64, vp, u64, u64, i32, vp, vp, vp])
     later("pds_counter_add", [vp, u64, vp])
     later("pds_noise_normals", [u64, u64, C.c_uint32, u64, i64, vp, vp])
+    later("pds_box_muller", [vp, i64, vp, vp])
     later("pds_permutation", [vp, i64, u64, u64, vp])
     later("pds_rollout", [vp, i32, mp, mp, vp, vp, C.c_float, vp, u64, vp, u64, i32] + [vp] * 14)
     later("pds_rollout_history", [vp, i32, i32, mp, vp, vp, C.c_float, vp, u64, vp, u64, i32] + [vp] * 9 + [i32] + [vp] * 4)

@@ -1,6 +1,8 @@
 """GPU tests of the evolution strategy: pds_es_perturb / pds_es_gradient (csrc/pds_es.hip) against the noise contract of
-DESIGN.md section 4 -- the noise for every comparison comes from the entry point that is already tested, pds_gaussian_sample
-on zeros -- and ESTrainer (es.py) on a quadratic and end to end on Hover."""
+DESIGN.md section 4 -- the noise for every comparison comes from pds_gaussian_sample on zeros, the entry point that
+tests/test_gpu_sampler.py holds draw for draw against the float64 restatement of that contract (tests/sampler_oracle.py; the
+same file checks the rows of pds_es_perturb against the restatement directly, without the detour through the sampler) -- and
+ESTrainer (es.py) on a quadratic and end to end on Hover."""
 import ctypes as C
 import functools
 import math
