@@ -554,6 +554,44 @@ int pds_es_gradient(const float *d_pair_weights /* [pairs] */, const float *d_mu
                     float scale, float l2, uint64_t seed, uint64_t generation, uint64_t pair_base, float *d_grad /* [n] */,
                     float *d_workspace, void *stream);
 
+/* The deterministic policy gradient of DDPG (algs/ddpg/ddpg.py:316-340, 431-464; ddpg.py DDPGTrainer; csrc/pds_ddpg.hip).  No
+ * handle: the entry points run on the current device, asynchronously on `stream`, allocate nothing and never synchronise
+ * (graph-capturable).  pi is the actor D -> h1 -> h2 -> 4 (its output is act_limit * tanh(MLP)), q the Q network
+ * D + 4 -> h1 -> h2 -> 1 over rows [obs | act]; the hidden activation of each is relu or tanh, chosen independently.
+ * Built for D + 4 <= 64 and h1, h2 <= 64 of both networks: pds_ddpg_supported answers 1 / 0 beforehand.
+ * PDS_EINVAL (before any device call): a NULL pointer (other than d_index and opt), B < 1, a network outside
+ * pds_mlp's range, an actor with d_out != 4, a Q network with d_out != 1 or d_in != D + 4.  PDS_EUNSUPPORTED: D + 4 > 64.
+ *
+ * pds_ddpg_policy_grad: d_grads[pds_mlp_param_count(pi)] = the gradient of -mean_g Q(o_g, act_limit tanh(pi(o_g)))
+ * (compute_loss_pi, algs/ddpg/ddpg.py:336-340) with respect to the ACTOR's parameters, o_g = the first D columns of row
+ * d_index[g] (or g when d_index is NULL) of d_oa [rows, D + 4]: the gradient runs backwards through Q into its action
+ * columns and from there through the actor.  Q's parameters are only read, the stored actions are not read at all.
+ * d_stats[4] = {sum_g Q(o_g, pi(o_g)), 0, 0, B}.  opt != NULL: the partial-sum kernel also takes the torch.optim.Adam step on
+ * pi (the arithmetic of pds_adam_step: both routes give the same bits, as pds_value_grad_step).  d_workspace:
+ * pds_ddpg_workspace_floats(pi, q) floats (host only; PDS_EINVAL / PDS_EUNSUPPORTED as above).  Summed in a fixed order
+ * without atomics: the same inputs give the same bits.
+ *
+ * pds_ddpg_target: for g < B and i = d_index[g] (or g): d_target_rows[i] = d_rew[i] + gamma * (1 - d_done[i]) *
+ * Q_targ(obs2_i, act_limit tanh(pi_targ(obs2_i))), obs2_i = row i of d_obs2 [rows, D]; d_rew, d_done (0 / 1 as float) and
+ * d_target_rows are [rows]; the products and the sum are rounded separately (the Bellman backup of compute_loss_q,
+ * algs/ddpg/ddpg.py:323-326).  Written at the ROW, not at g -- pds_value_grad reads target[index[g]] -- so the Q update is
+ * pds_value_grad_step on d_oa with the same index; rows outside the index are left alone, repeated indices write the same
+ * bits.
+ *
+ * pds_polyak: t = rn(rn(polyak * t) + rn((float)(1 - polyak) * s)) for every parameter t of `targ` and s of `src` (two
+ * networks of one shape; the six tensors in one launch), 1 - polyak formed in double: the bits of the reference's
+ * p_targ.mul_(polyak); p_targ.add_((1 - polyak) * p) (algs/ddpg/ddpg.py:459-464).  PDS_EINVAL: shapes that differ, polyak
+ * outside [0, 1]. */
+int pds_ddpg_supported(const pds_mlp *pi, const pds_mlp *q);
+int64_t pds_ddpg_workspace_floats(const pds_mlp *pi, const pds_mlp *q); /* host only */
+int pds_ddpg_policy_grad(const pds_mlp *pi, const pds_mlp *q, const float *d_oa, const int64_t *d_index, int64_t B,
+                         float act_limit, float *d_grads, float *d_stats, float *d_workspace, const pds_adam *opt,
+                         void *stream);
+int pds_ddpg_target(const pds_mlp *pi_targ, const pds_mlp *q_targ, const float *d_obs2, const int64_t *d_index, int64_t B,
+                    const float *d_rew, const float *d_done, float gamma, float act_limit, float *d_target_rows,
+                    void *stream);
+int pds_polyak(const pds_mlp *targ, const pds_mlp *src, double polyak, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

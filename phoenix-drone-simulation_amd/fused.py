@@ -8,6 +8,9 @@ gradient for the update.  Each call replaces an autograd op chain of the referen
     FusedMLP.fisher_vector_product  NaturalPolicyGradientAlgorithm.Fvp              algs/npg/npg.py:52-77
     conjugate_gradients   conjugate_gradients                                       algs/utils.py:5-38
     FusedMLP.surrogate_kl the candidates of TRPO's line search                      algs/trpo/trpo.py:16-66
+    FusedMLP.ddpg_policy_grad  compute_loss_pi + backward (through Q into the actor) algs/ddpg/ddpg.py:336-340
+    ddpg_target           the Bellman backup of compute_loss_q                      algs/ddpg/ddpg.py:323-326
+    polyak                the target networks' polyak step                          algs/ddpg/ddpg.py:459-464
 
 The gradients are written straight into the `.grad` storage of the torch parameters (one flat
 buffer, torch parameter order), so the optimiser step stays torch.optim.Adam like the reference's."""
@@ -186,6 +189,56 @@ class FusedMLP:
         if rc != native.OK:
             raise RuntimeError(f"pds_npg_surrogate_kl -> {rc}")
         return out
+
+    def ddpg_policy_grad(self, q_fm, oa, index, act_limit, adam_lr=None, betas=(0.9, 0.999), eps=1e-8):
+        """This network as the DDPG actor (output act_limit * tanh): fills .grad with the gradient of
+        -Q(o, pi(o)).mean() over the rows oa[index] = [obs | act] (index None: every row), Q = `q_fm` (read only);
+        stats[0] = sum of Q(o, pi(o)), stats[3] = B (csrc/pds_ddpg.hip).  adam_lr: as in ppo_grad.
+        NotImplementedError for shapes the kernel is not built for (ddpg_supported says so beforehand)."""
+        self._bind(); q_fm._bind()
+        B = oa.shape[0] if index is None else index.shape[0]
+        ws = getattr(self, "ddpg_workspace", None)
+        if ws is None:
+            n = self.lib.pds_ddpg_workspace_floats(C.byref(self.m), C.byref(q_fm.m))
+            if n < 0:
+                raise (NotImplementedError if n == native.EUNSUPPORTED else ValueError)(f"pds_ddpg_workspace_floats -> {n}")
+            self.ddpg_workspace = ws = torch.empty(n, device=self.flat_grad.device)
+        opt = self._adam_arg(adam_lr, betas, eps)
+        with _on(oa):
+            rc = self.lib.pds_ddpg_policy_grad(C.byref(self.m), C.byref(q_fm.m), _ptr(oa), _ptr(index), B, float(act_limit),
+                                               _ptr(self.flat_grad), _ptr(self.stats), _ptr(ws), opt, self._stream(oa))
+        if rc != native.OK:
+            raise (NotImplementedError if rc == native.EUNSUPPORTED else RuntimeError)(f"pds_ddpg_policy_grad -> {rc}")
+        return self.stats
+
+
+def ddpg_supported(pi_fm, q_fm):
+    """True when the fused DDPG kernels cover this actor / Q pair (D + 4 <= 64, hidden <= 64, d_out 4 / 1)."""
+    return native.load().pds_ddpg_supported(C.byref(pi_fm.m), C.byref(q_fm.m)) == 1
+
+
+def ddpg_target(pi_targ_fm, q_targ_fm, obs2, index, rew, done, gamma, act_limit, target_rows):
+    """target_rows[i] = rew[i] + gamma * (1 - done[i]) * Q_targ(obs2[i], act_limit * tanh(pi_targ(obs2[i]))) for the rows
+    i = index[g] (index None: every row); the other rows are left alone (include/pds.h pds_ddpg_target)."""
+    pi_targ_fm._bind(); q_targ_fm._bind()
+    B = obs2.shape[0] if index is None else index.shape[0]
+    with _on(obs2):
+        rc = native.load().pds_ddpg_target(C.byref(pi_targ_fm.m), C.byref(q_targ_fm.m), _ptr(obs2), _ptr(index), B, _ptr(rew),
+                                           _ptr(done), float(gamma), float(act_limit), _ptr(target_rows),
+                                           FusedMLP._stream(obs2))
+    if rc != native.OK:
+        raise (NotImplementedError if rc == native.EUNSUPPORTED else RuntimeError)(f"pds_ddpg_target -> {rc}")
+    return target_rows
+
+
+def polyak(targ_fm, src_fm, rho):
+    """p_targ.mul_(rho); p_targ.add_((1 - rho) * p) over the six tensors of a network pair, one launch, the same bits."""
+    targ_fm._bind(); src_fm._bind()
+    t = targ_fm.params[0]
+    with _on(t):
+        rc = native.load().pds_polyak(C.byref(targ_fm.m), C.byref(src_fm.m), float(rho), FusedMLP._stream(t))
+    if rc != native.OK:
+        raise RuntimeError(f"pds_polyak -> {rc}")
 
 
 def conjugate_gradients(avp, b, iters, residual_tol=1e-10, eps=1e-6):

@@ -40,7 +40,8 @@ EXPORTS = ["pds_version", "pds_default_config", "pds_create", "pds_destroy", "pd
            "pds_adam_step", "pds_rollout", "pds_rollout_history",
            "pds_npg_workspace_floats", "pds_npg_fisher_vector_product", "pds_npg_cg_step", "pds_npg_surrogate_kl",
            "pds_simopt_latency_steps", "pds_simopt_evaluate", "pds_evaluate_supported", "pds_evaluate_policies",
-           "pds_es_workspace_floats", "pds_es_perturb", "pds_es_gradient"]
+           "pds_es_workspace_floats", "pds_es_perturb", "pds_es_gradient",
+           "pds_ddpg_supported", "pds_ddpg_workspace_floats", "pds_ddpg_policy_grad", "pds_ddpg_target", "pds_polyak"]
 
 
 class Mlp(C.Structure):
@@ -169,6 +170,13 @@ def load():
         lib.pds_es_workspace_floats.restype = i64
     later("pds_es_perturb", [vp, i64, i64, C.c_float, u64, u64, u64, vp, vp])
     later("pds_es_gradient", [vp, vp, i64, i64, C.c_float, C.c_float, u64, u64, u64, vp, vp, vp])
+    later("pds_ddpg_supported", [mp, mp])
+    later("pds_ddpg_workspace_floats", [mp, mp])
+    if hasattr(lib, "pds_ddpg_workspace_floats"):
+        lib.pds_ddpg_workspace_floats.restype = i64
+    later("pds_ddpg_policy_grad", [mp, mp, vp, vp, i64, C.c_float, vp, vp, vp, ap, vp])
+    later("pds_ddpg_target", [mp, mp, vp, vp, i64, vp, vp, C.c_float, C.c_float, vp, vp])
+    later("pds_polyak", [mp, mp, C.c_double, vp])
     _lib = lib
     return lib
 
