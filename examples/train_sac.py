@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""Train a Soft Actor-Critic agent (the reference's algs/sac/sac.py) on a batched Simple env and leave a checkpoint behind.
+
+One vector step stores num_envs transitions in the device replay ring; the update reads its mini-batch in place through the
+fused kernels of csrc/pds_sac.hip (the entropy-regularised backup over the twin target Qs, the two Q steps, the squashed-Gaussian
+policy gradient through the smaller Q into both heads of the actor, polyak).  The hyper-parameters carry the reference's names;
+their defaults are starting values, not tuned ones.  The checkpoint has the reference module's keys.
+
+    python examples/train_sac.py --env DroneHoverSimpleEnv-v0 --num-envs 1024 --epochs 2 --log-dir /tmp/sac_run
+"""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import phoenix_drone_simulation_amd as pds  # noqa: E402
+from phoenix_drone_simulation_amd.sac import SACTrainer  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--env", default="DroneHoverSimpleEnv-v0")
+    ap.add_argument("--num-envs", type=int, default=1024)
+    ap.add_argument("--epochs", type=int, default=100)
+    ap.add_argument("--steps-per-epoch", type=int, default=64, help="vector steps per epoch")
+    ap.add_argument("--updates-per-step", type=int, default=1, help="gradient updates after every vector step")
+    ap.add_argument("--mini-batch-size", type=int, default=64)
+    ap.add_argument("--buffer-size", type=int, default=int(1e6))
+    ap.add_argument("--start-steps", type=int, default=10000, help="transitions with uniform random actions")
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--alpha", type=float, default=0.2, help="the entropy temperature (fixed)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--no-fused", action="store_true", help="the torch autograd path")
+    ap.add_argument("--log-dir", default=None, help="default: a fresh temporary directory")
+    args = ap.parse_args()
+    env = pds.make(args.env, num_envs=args.num_envs, seed=args.seed)  # the reference's default config
+    trainer = SACTrainer(env, epochs=args.epochs, steps_per_epoch=args.steps_per_epoch, updates_per_step=args.updates_per_step,
+                         mini_batch_size=args.mini_batch_size, buffer_size=args.buffer_size, start_steps=args.start_steps,
+                         lr=args.lr, alpha=args.alpha, seed=args.seed, fused=not args.no_fused)
+    print(f"{args.env}: {env.num_envs} envs, obs_dim {env.obs_dim}, update path: {'fused HIP kernels' if trainer.fused else 'torch autograd'}")
+    t0 = time.time()
+    for e in range(args.epochs):
+        i = trainer.learn_one_epoch()
+        if e % max(1, args.epochs // 20) == 0 or e == args.epochs - 1:
+            print(f"epoch {i['epoch']:4d}  EpRet {i['ep_ret']:9.2f}  EpLen {i['ep_len']:6.1f}  Q1Vals {i['q1_mean']:9.3f}  Q2Vals {i['q2_mean']:9.3f}  "
+                  f"LogPi {i['log_pi']:8.3f}  LossQ {i['loss_q']:.4e}  LossPi {i['loss_pi']:9.3f}  warm-up {int(i['in_warm_up'])}  "
+                  f"updates {i['updates']}  FPS {i['fps']:.0f}", flush=True)
+    torch.cuda.synchronize()
+    print(f"{trainer.total_steps} env-steps, {trainer.updates} updates in {time.time() - t0:.1f} s")
+    log_dir = args.log_dir or tempfile.mkdtemp(prefix="sac_")
+    path = trainer.save_checkpoint(log_dir)  # torch_save/model.pt, the reference module's keys
+    trainer.write_progress_csv(os.path.join(log_dir, "progress.csv"))
+    print("saved", path)
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -592,6 +592,51 @@ int pds_ddpg_target(const pds_mlp *pi_targ, const pds_mlp *q_targ, const float *
                     void *stream);
 int pds_polyak(const pds_mlp *targ, const pds_mlp *src, double polyak, void *stream);
 
+/* Soft Actor-Critic (algs/sac/sac.py:35-124, 295-337, 439-474; sac.py SACTrainer; csrc/pds_sac.hip).  No handle: the entry
+ * points run on the current device, asynchronously on `stream`, allocate nothing and never synchronise (graph-capturable).
+ * pi is the squashed-Gaussian actor D -> h1 -> h2 -> 8 as ONE pds_mlp: rows 0 .. 3 of w3 / b3 are the reference's mu_layer,
+ * rows 4 .. 7 its log_std_layer.  q1, q2 are the twin Q networks D + 4 -> h1 -> h2 -> 1 over rows [obs | act], of one shape and
+ * activation; the hidden activation is relu or tanh, chosen independently for the actor and the Qs.
+ * Built for D + 4 <= 64 and h1, h2 <= 64 of the three networks: pds_sac_supported answers 1 / 0 beforehand.
+ * PDS_EINVAL (before any device call): a NULL pointer (other than d_index, d_logp and opt), B < 1 (n < 1), a network outside
+ * pds_mlp's range, an actor with d_out != 8, a Q network with d_out != 1 or d_in != D + 4, q1 and q2 of different shape or
+ * activation, sample ids beyond 2^56.  PDS_EUNSUPPORTED: D + 4 > 64.
+ *
+ * The sample.  From a row [mu | log_std] of the actor's output: ls = clamp(log_std, -20, 2), u = fmaf(exp(ls), eps, mu),
+ * a = act_limit * tanh(u), logp = sum_j (-0.5 eps_j^2 - ls_j - 0.5 log 2 pi) - sum_j 2 (log 2 - u_j - softplus(-2 u_j)) with
+ * softplus(x) = max(x, 0) + log1p(exp(-|x|)) (SquashedGaussianMLPActor.forward, algs/sac/sac.py:47-76).
+ * Noise contract: eps of sample g -- its POSITION in the call's batch, not its buffer row, so repeated rows get independent
+ * noise -- is the four variates pds_gaussian_sample draws for sample id id_base + g (id_base = 0 in pds_sac_target and
+ * pds_sac_policy_grad), block 0, in `call` under `seed`: pds_gaussian_sample with mu = 0, log_std = 0 and d_out = 4 returns them.
+ *
+ * pds_sac_sample: d_act[n, 4] and d_logp[n] (or NULL) from d_head [n, 8]; deterministic != 0: eps = 0, a = act_limit tanh(mu).
+ *
+ * pds_sac_target: for g < B and i = d_index[g] (or g): a2, logp2 = the sample of the CURRENT policy pi at obs2_i = row i of
+ * d_obs2 [rows, D]; d_target_rows[i] = d_rew[i] + gamma * (1 - d_done[i]) * (min(Q1_targ, Q2_targ)(obs2_i, a2) - alpha * logp2),
+ * every product and sum rounded separately (the backup of compute_loss_q, algs/sac/sac.py:303-311).  Written at the ROW, as
+ * pds_ddpg_target: the Q update is pds_value_grad_step on d_oa with the same index, once per Q network; rows outside the index
+ * are left alone.  With alpha = 0, q2_targ = q1_targ and sigma too small to move u off mu it gives the bits of pds_ddpg_target.
+ *
+ * pds_sac_policy_grad: d_grads[pds_mlp_param_count(pi)] = the gradient of mean_g (alpha logp_g - min(Q1, Q2)(o_g, a_g))
+ * (compute_loss_pi, algs/sac/sac.py:324-337) with respect to the ACTOR's parameters, o_g = the first D columns of row d_index[g]
+ * (or g) of d_oa [rows, D + 4]: through the smaller Q into its action columns, through tanh and u = mu + exp(ls) eps into both
+ * heads; the log_std head receives no gradient where the clamp binds (torch.clamp: open on [-20, 2] inclusive).  Where
+ * Q1 == Q2 the gradient is Q1's.  Q1 and Q2 are only read, the stored actions are not read at all.
+ * d_stats[4] = {sum_g min Q, sum_g logp_g, 0, B}.  opt != NULL: the partial-sum kernel also takes the torch.optim.Adam step on pi
+ * (the arithmetic of pds_adam_step: both routes give the same bits).  d_workspace: pds_sac_workspace_floats(pi, q1, q2) floats
+ * (host only; PDS_EINVAL / PDS_EUNSUPPORTED as above).  Summed in a fixed order without atomics: the same inputs give the same
+ * bits. */
+int pds_sac_supported(const pds_mlp *pi, const pds_mlp *q1, const pds_mlp *q2);
+int64_t pds_sac_workspace_floats(const pds_mlp *pi, const pds_mlp *q1, const pds_mlp *q2); /* host only */
+int pds_sac_sample(const float *d_head /* [n, 8] actor output */, int64_t n, float act_limit, uint64_t seed, uint64_t call,
+                   uint64_t id_base, int deterministic, float *d_act /* [n, 4] */, float *d_logp /* [n] or NULL */, void *stream);
+int pds_sac_target(const pds_mlp *pi, const pds_mlp *q1_targ, const pds_mlp *q2_targ, const float *d_obs2, const int64_t *d_index,
+                   int64_t B, const float *d_rew, const float *d_done, float gamma, float alpha, float act_limit, uint64_t seed,
+                   uint64_t call, float *d_target_rows, void *stream);
+int pds_sac_policy_grad(const pds_mlp *pi, const pds_mlp *q1, const pds_mlp *q2, const float *d_oa, const int64_t *d_index,
+                        int64_t B, float alpha, float act_limit, uint64_t seed, uint64_t call, float *d_grads, float *d_stats,
+                        float *d_workspace, const pds_adam *opt, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

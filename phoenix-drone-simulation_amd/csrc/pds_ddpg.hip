@@ -51,34 +51,6 @@ struct DdpgArgs {
   float *target;             // target: [rows], written at the ROW
 };
 
-struct NetLds {
-  const float *W1, *W2, *W3, *b1, *b2, *b3;
-};
-
-// wide_forward without images, H1 kept next to H2 (this lane's values: what act' of the backward chain reads)
-template <int ACT>
-__device__ __forceinline__ f32x4 forward_regs(const NetLds &N, const f32x4 (&xin)[kDdpgNin], f32x4 (&h1r)[kNT],
-                                              f32x4 (&h2r)[kNT], int n, int g) {
-  f32x4 cc[kNT];
-#pragma unroll
-  for (int it = 0; it < kNT; it += 2) gemm_wt2s<kDdpgNin, kS>(N.W1, it, xin, n, g, cc[it], cc[it + 1]);
-#pragma unroll
-  for (int it = 0; it < kNT; ++it) {
-    const f32x4 b = lds4(N.b1 + it * kTW + 4 * g);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) h1r[it][q] = act_fn<ACT>(cc[it][q] + b[q]);
-  }
-#pragma unroll
-  for (int it = 0; it < kNT; it += 2) gemm_wt2s<kNT, kS>(N.W2, it, h1r, n, g, cc[it], cc[it + 1]);
-#pragma unroll
-  for (int it = 0; it < kNT; ++it) {
-    const f32x4 b = lds4(N.b2 + it * kTW + 4 * g);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) h2r[it][q] = act_fn<ACT>(cc[it][q] + b[q]);
-  }
-  return gemm_lds<kNT, kS>(N.W3, 0, h2r, n & (kMaxOut - 1), g, (f32x4)(0.f)) + lds4(N.b3 + 4 * g);
-}
-
 // Steps 1-3 for one tile: -> Q(o, act_limit tanh(pi(o))) in register 0 of the lanes (n, 0).  th: tanh(mu) (lanes (n, 0):
 // outputs 0 .. 3), h2p: the actor's H2, h1q / h2q: Q's activations.  GRAD: the actor's H1 / H2 also go to their images.
 template <int AP, int AQ, bool GRAD>
@@ -275,6 +247,21 @@ static int ddpg_check(const pds_mlp *pi, const pds_mlp *q) {
   return q->d_in <= kMaxDim ? PDS_OK : PDS_EUNSUPPORTED;
 }
 
+int launch_ddpg_reduce(const float *partials, int pstride, int nwaves, int total, float denom_scale, float *grads, float *stats,
+                       const pds_mlp &m, const pds_adam *opt, hipStream_t s) {
+  DdpgAdam ad{};
+  if (opt != nullptr) {
+    ad.em = opt->d_exp_avg; ad.ev = opt->d_exp_avg_sq;
+    ad.lr = opt->lr; ad.b1 = opt->beta1; ad.b2 = opt->beta2; ad.eps = opt->eps;
+    ad.bc1 = 1.0f - powf(opt->beta1, (float)opt->step);  // as pds_adam_step
+    ad.bc2s = sqrtf(1.0f - powf(opt->beta2, (float)opt->step));
+  }
+  const int nred = total + kStats;
+  hipLaunchKernelGGL(ddpg_reduce_kernel, dim3((nred + 63) / 64), dim3(1024), 0, s, partials, pstride, nwaves, total,
+                     denom_scale, grads, stats, m, ad);
+  return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
+}
+
 }  // namespace pds_mlp_detail
 using namespace pds_mlp_detail;
 
@@ -314,17 +301,7 @@ extern "C" int pds_ddpg_policy_grad(const pds_mlp *pi, const pds_mlp *q, const f
   const int blocks = wide_grid_blocks(B);
   hipStream_t s = (hipStream_t)stream;
   PDS_DDPG_LAUNCH(ddpg_grad_kernel, dim3(blocks), s, a);
-  DdpgAdam ad{};
-  if (opt != nullptr) {
-    ad.em = opt->d_exp_avg; ad.ev = opt->d_exp_avg_sq;
-    ad.lr = opt->lr; ad.b1 = opt->beta1; ad.b2 = opt->beta2; ad.eps = opt->eps;
-    ad.bc1 = 1.0f - powf(opt->beta1, (float)opt->step);  // as pds_adam_step
-    ad.bc2s = sqrtf(1.0f - powf(opt->beta2, (float)opt->step));
-  }
-  const int nred = o.total + kStats;
-  hipLaunchKernelGGL(ddpg_reduce_kernel, dim3((nred + 63) / 64), dim3(1024), 0, s, (const float *)d_workspace, a.pstride,
-                     blocks * kWideWaves, o.total, 1.0f / (float)B, d_grads, d_stats, *pi, ad);
-  return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
+  return launch_ddpg_reduce(d_workspace, a.pstride, blocks * kWideWaves, o.total, 1.0f / (float)B, d_grads, d_stats, *pi, opt, s);
 }
 
 extern "C" int pds_ddpg_target(const pds_mlp *pi_targ, const pds_mlp *q_targ, const float *d_obs2, const int64_t *d_index,

@@ -126,5 +126,10 @@ int launch_wide(int loss, const Args &a, hipStream_t s);
 // csrc/pds_mlp.hip: PDS_OK for a network every kernel family covers between them (d_in <= kMaxDimIn, h1, h2 <= kMaxDim,
 // d_out <= kMaxOut, relu or tanh, no null tensor), else PDS_EINVAL
 int check(const pds_mlp *m);
+// csrc/pds_ddpg.hip: launches ddpg_reduce_kernel on `s` -- grads[p] = denom_scale * the fixed-order sum of element p over the
+// nwaves partials, stats = the sums of the kStats elements behind them, and the Adam step on `m` when opt != nullptr
+// (csrc/pds_sac.hip sums its partials with the same kernel)
+int launch_ddpg_reduce(const float *partials, int pstride, int nwaves, int total, float denom_scale, float *grads, float *stats,
+                       const pds_mlp &m, const pds_adam *opt, hipStream_t s);
 
 }  // namespace pds_mlp_detail

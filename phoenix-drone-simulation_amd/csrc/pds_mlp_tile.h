@@ -32,16 +32,16 @@ inline int wide_grid_blocks(long long B) {
   return (int)(blocks < kWideMaxBlocks ? blocks : kWideMaxBlocks);  // one persistent block per CU
 }
 
-// weight images [out][in] of the network, zero padded, by the kWideWaves * 64 threads of a block; val(t, i) is what is staged
+// weight images [out][in] of the network, zero padded, by the THREADS threads of a block; val(t, i) is what is staged
 // for the parameter of value t at position i of the flat layout (the identity, or a line-search candidate).
 // W3: the 8 rows d_out <= kMaxOut can fill (the narrow kernels keep 16): rows 8..15 of the 16-row MFMA tile ALIAS rows 0..7
 // (`& 7` / `n & (kMaxOut - 1)` at the reads) -- outputs 8..15 are never read, and their gradient dY is zero, so the aliased
 // rows only ever meet zeros
-template <int S1, class F>
+template <int S1, int THREADS = kWideWaves * 64, class F>
 __device__ __forceinline__ void stage_wide(const pds_mlp &m, float *W1s, float *W2s, float *W3s, float *b1s, float *b2s,
                                            float *b3s, int tid, F val) {
   const Offsets o = offsets(m);
-  constexpr int kThreads = kWideWaves * 64;
+  constexpr int kThreads = THREADS;
   for (int i = tid; i < kMaxDim * S1; i += kThreads) {
     const int r = i / S1, k = i - r * S1;
     W1s[i] = (r < m.h1 && k < m.d_in) ? val(m.w1[r * m.d_in + k], o.w1 + r * m.d_in + k) : 0.f;
@@ -116,6 +116,36 @@ __device__ __forceinline__ f32x4 wide_forward(const float *W1s, const float *W2s
     if (IMG) sts4(H2img + n * kS + it * kTW + 4 * g, h2r[it]);
   }
   return gemm_lds<kNT, kS>(W3s, 0, h2r, n & (kMaxOut - 1), g, (f32x4)(0.f)) + lds4(b3s + 4 * g);
+}
+
+// the staged images of one network (stride kS throughout)
+struct NetLds {
+  const float *W1, *W2, *W3, *b1, *b2, *b3;
+};
+
+// wide_forward without images, H1 kept next to H2 (this lane's values: what act' of a backward chain without weight gradients
+// reads): the Q networks of csrc/pds_ddpg.hip and csrc/pds_sac.hip
+template <int ACT, int NIN>
+__device__ __forceinline__ f32x4 forward_regs(const NetLds &N, const f32x4 (&xin)[NIN], f32x4 (&h1r)[kNT],
+                                              f32x4 (&h2r)[kNT], int n, int g) {
+  f32x4 cc[kNT];
+#pragma unroll
+  for (int it = 0; it < kNT; it += 2) gemm_wt2s<NIN, kS>(N.W1, it, xin, n, g, cc[it], cc[it + 1]);
+#pragma unroll
+  for (int it = 0; it < kNT; ++it) {
+    const f32x4 b = lds4(N.b1 + it * kTW + 4 * g);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) h1r[it][q] = act_fn<ACT>(cc[it][q] + b[q]);
+  }
+#pragma unroll
+  for (int it = 0; it < kNT; it += 2) gemm_wt2s<kNT, kS>(N.W2, it, h1r, n, g, cc[it], cc[it + 1]);
+#pragma unroll
+  for (int it = 0; it < kNT; ++it) {
+    const f32x4 b = lds4(N.b2 + it * kTW + 4 * g);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) h2r[it][q] = act_fn<ACT>(cc[it][q] + b[q]);
+  }
+  return gemm_lds<kNT, kS>(N.W3, 0, h2r, n & (kMaxOut - 1), g, (f32x4)(0.f)) + lds4(N.b3 + 4 * g);
 }
 
 // C[it][jt] += A_it^T B_jt over the 16 samples of a tile, operands as three bf16 pieces of the four values (samples 4 h .. 4 h + 3

@@ -189,7 +189,99 @@ class ReplayBuffer:
                     done=self.done[index])
 
 
-class DDPGTrainer:
+class OffPolicyTrainer:
+    """The vector-step / update / epoch loop the off-policy trainers share (DDPGTrainer here, sac.SACTrainer).  A subclass
+    sets env, N, buffer, warmup_steps, update_after, update_every, steps_per_epoch, updates_per_step and epochs, calls
+    _init_loop(), and provides get_action(obs), update(), _update_info() and _progress_columns()."""
+
+    def _init_loop(self):
+        dev = self.env.device
+        self.obs = None
+        self.ep_ret, self.ep_len = torch.zeros(self.N, device=dev), torch.zeros(self.N, device=dev)
+        self.in_warm_up = True
+        self.total_steps, self.updates, self._since_update = 0, 0, 0
+        self.epoch, self.log, self._t_total = 0, [], 0.0
+
+    # ---- one vector step -------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step_env(self, act=None):
+        """act (default: get_action) -> env.step -> N transitions into the buffer.  next_o is info['final_obs'] where the env
+        finished (the returned observation is already the reset one), the terminal flag is terminated & ~truncated.
+        -> (reward, done)"""
+        if self.obs is None:
+            self.obs, _ = self.env.reset()
+        o = self.obs
+        self.in_warm_up = len(self.buffer) < self.warmup_steps
+        a = self.get_action(o) if act is None else act
+        next_o, r, terminated, truncated, info = self.env.step(a)
+        done = terminated | truncated
+        stored_next = torch.where(done.unsqueeze(-1), info["final_obs"], next_o)
+        self.buffer.store(o, a, r, stored_next, (terminated & ~truncated).to(torch.float32))
+        self.obs = next_o
+        self.total_steps += self.N
+        self._since_update += self.N
+        return r, done
+
+    # ---- epochs ------------------------------------------------------------------------------------------------------------
+    def learn_one_epoch(self):
+        """steps_per_epoch vector steps with their updates -> the log entry: the loop's columns and those of _update_info()."""
+        dev = self.env.device
+        t0 = time.time()
+        inf = float("inf")
+        # finished episodes of the epoch: count, sum, sum of squares, min, max of the return; sum, min, max of the length
+        acc = torch.tensor([0.0, 0.0, 0.0, inf, -inf, 0.0, inf, -inf], device=dev)
+        for _ in range(self.steps_per_epoch):
+            r, done = self.step_env()
+            self.ep_ret += r
+            self.ep_len += 1.0
+            d = done.to(torch.float32)
+            ret, ln = self.ep_ret, self.ep_len
+            acc[0] += d.sum(); acc[1] += (d * ret).sum(); acc[2] += (d * ret * ret).sum()
+            acc[3] = torch.minimum(acc[3], torch.where(done, ret, torch.full_like(ret, inf)).min())
+            acc[4] = torch.maximum(acc[4], torch.where(done, ret, torch.full_like(ret, -inf)).max())
+            acc[5] += (d * ln).sum()
+            acc[6] = torch.minimum(acc[6], torch.where(done, ln, torch.full_like(ln, inf)).min())
+            acc[7] = torch.maximum(acc[7], torch.where(done, ln, torch.full_like(ln, -inf)).max())
+            self.ep_ret = torch.where(done, torch.zeros_like(ret), ret)
+            self.ep_len = torch.where(done, torch.zeros_like(ln), ln)
+            if (not self.in_warm_up and len(self.buffer) >= self.update_after and self._since_update >= self.update_every):
+                for _ in range(self.updates_per_step):
+                    self.update()
+                self._since_update = 0
+        info = dict(epoch=self.epoch + 1, in_warm_up=float(self.in_warm_up), total_env_steps=self.total_steps,
+                    updates=self.updates)
+        info.update(self._update_info())
+        s = acc.tolist()
+        n = max(s[0], 1.0)
+        mean = s[1] / n
+        nan = float("nan")
+        info.update(episodes=s[0], ep_ret=mean if s[0] else nan, ep_ret_min=s[3] if s[0] else nan, ep_ret_max=s[4] if s[0] else nan,
+                    ep_ret_std=math.sqrt(max(s[2] / n - mean * mean, 0.0)) if s[0] else nan, ep_len=s[5] / n if s[0] else nan,
+                    ep_len_min=s[6] if s[0] else nan, ep_len_max=s[7] if s[0] else nan)
+        dt = time.time() - t0
+        self._t_total += dt
+        info.update(time=self._t_total, fps=self.steps_per_epoch * self.N / dt)
+        self.log.append(info)
+        self.epoch += 1
+        return info
+
+    def learn(self, epochs=None, verbose=False):
+        for _ in range(epochs or self.epochs):
+            info = self.learn_one_epoch()
+            if verbose:
+                print({k: (round(v, 4) if isinstance(v, float) else v) for k, v in info.items()})
+        return self.ac, self.env
+
+    def write_progress_csv(self, path):
+        """The per-epoch log, one row per epoch (the form of PPOTrainer.write_progress_csv)."""
+        cols = self._progress_columns()
+        with open(path, "w") as f:
+            f.write(",".join(c for c, _ in cols) + "\n")
+            for row in self.log:
+                f.write(",".join(str(row.get(k, "")) for _, k in cols) + "\n")
+
+
+class DDPGTrainer(OffPolicyTrainer):
     """DDPG on a DroneVecEnv (auto_reset).  Hyper-parameters under the reference's names (ddpg.py:89-114); the defaults are
     starting values, not tuned ones.  steps_per_epoch: vector steps per epoch; updates_per_step: gradient updates after each
     vector step once updating has begun (see the module docstring); buffer_size is rounded DOWN to a multiple of num_envs."""
@@ -238,11 +330,7 @@ class DDPGTrainer:
         self._act = torch.empty(self.N, env.act_dim, device=dev)
         self._logp = torch.empty(self.N, device=dev)
         self._noise_calls = 0
-        self.obs = None
-        self.ep_ret, self.ep_len = torch.zeros(self.N, device=dev), torch.zeros(self.N, device=dev)
-        self.in_warm_up = True
-        self.total_steps, self.updates, self._since_update = 0, 0, 0
-        self.epoch, self.log, self._t_total = 0, [], 0.0
+        self._init_loop()
         self._last = None  # (loss_q, loss_pi, index) of the latest update, device tensors
 
     # ---- acting ------------------------------------------------------------------------------------------------------------
@@ -265,26 +353,6 @@ class DDPGTrainer:
         gaussian_sample(mu, self._log_noise, self._act, self._logp, self.seed, self._noise_calls)
         return torch.clamp(self._act, -self.act_limit, self.act_limit)
 
-    # ---- one vector step -------------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def step_env(self, act=None):
-        """act (default: get_action) -> env.step -> N transitions into the buffer.  next_o is info['final_obs'] where the env
-        finished (the returned observation is already the reset one), the terminal flag is terminated & ~truncated.
-        -> (reward, done)"""
-        if self.obs is None:
-            self.obs, _ = self.env.reset()
-        o = self.obs
-        self.in_warm_up = len(self.buffer) < self.warmup_steps
-        a = self.get_action(o) if act is None else act
-        next_o, r, terminated, truncated, info = self.env.step(a)
-        done = terminated | truncated
-        stored_next = torch.where(done.unsqueeze(-1), info["final_obs"], next_o)
-        self.buffer.store(o, a, r, stored_next, (terminated & ~truncated).to(torch.float32))
-        self.obs = next_o
-        self.total_steps += self.N
-        self._since_update += self.N
-        return r, done
-
     # ---- the update --------------------------------------------------------------------------------------------------------
     def update(self, index=None):
         """One DDPG update (ddpg.py:431-464) on the rows `index` of the buffer (default: sample_indices(mini_batch_size))."""
@@ -306,35 +374,11 @@ class DDPGTrainer:
             self._last = (lq, lp, index)
         self.updates += 1
 
-    # ---- epochs ------------------------------------------------------------------------------------------------------------
-    def learn_one_epoch(self):
-        """steps_per_epoch vector steps with their updates -> the log entry (the reference's columns, ddpg.py:374-383)."""
-        dev = self.env.device
-        t0 = time.time()
-        inf = float("inf")
-        # finished episodes of the epoch: count, sum, sum of squares, min, max of the return; sum, min, max of the length
-        acc = torch.tensor([0.0, 0.0, 0.0, inf, -inf, 0.0, inf, -inf], device=dev)
-        for _ in range(self.steps_per_epoch):
-            r, done = self.step_env()
-            self.ep_ret += r
-            self.ep_len += 1.0
-            d = done.to(torch.float32)
-            ret, ln = self.ep_ret, self.ep_len
-            acc[0] += d.sum(); acc[1] += (d * ret).sum(); acc[2] += (d * ret * ret).sum()
-            acc[3] = torch.minimum(acc[3], torch.where(done, ret, torch.full_like(ret, inf)).min())
-            acc[4] = torch.maximum(acc[4], torch.where(done, ret, torch.full_like(ret, -inf)).max())
-            acc[5] += (d * ln).sum()
-            acc[6] = torch.minimum(acc[6], torch.where(done, ln, torch.full_like(ln, inf)).min())
-            acc[7] = torch.maximum(acc[7], torch.where(done, ln, torch.full_like(ln, -inf)).max())
-            self.ep_ret = torch.where(done, torch.zeros_like(ret), ret)
-            self.ep_len = torch.where(done, torch.zeros_like(ln), ln)
-            if (not self.in_warm_up and len(self.buffer) >= self.update_after and self._since_update >= self.update_every):
-                for _ in range(self.updates_per_step):
-                    self.update()
-                self._since_update = 0
-        info = dict(epoch=self.epoch + 1, in_warm_up=float(self.in_warm_up), total_env_steps=self.total_steps,
-                    updates=self.updates, loss_q=0.0, loss_pi=0.0, q_mean=0.0, q_min=0.0, q_max=0.0)
-        if self._last is not None:  # (zeros during warm-up, as the reference stores them, ddpg.py:427-429)
+    def _update_info(self):
+        """loss_q, loss_pi and the Q values of the latest update (zeros during warm-up, as the reference stores them,
+        ddpg.py:427-429)"""
+        info = dict(loss_q=0.0, loss_pi=0.0, q_mean=0.0, q_min=0.0, q_max=0.0)
+        if self._last is not None:
             lq, lp, index = self._last
             with torch.no_grad():
                 b = self.buffer.batch(index)
@@ -342,26 +386,7 @@ class DDPGTrainer:
             info.update(loss_q=float(lq), loss_pi=float(lp), q_mean=float(qv.mean()), q_min=float(qv.min()), q_max=float(qv.max()))
             if not (math.isfinite(info["loss_q"]) and math.isfinite(info["loss_pi"])):
                 raise FloatingPointError(f"non-finite loss in epoch {self.epoch + 1}")
-        s = acc.tolist()
-        n = max(s[0], 1.0)
-        mean = s[1] / n
-        nan = float("nan")
-        info.update(episodes=s[0], ep_ret=mean if s[0] else nan, ep_ret_min=s[3] if s[0] else nan, ep_ret_max=s[4] if s[0] else nan,
-                    ep_ret_std=math.sqrt(max(s[2] / n - mean * mean, 0.0)) if s[0] else nan, ep_len=s[5] / n if s[0] else nan,
-                    ep_len_min=s[6] if s[0] else nan, ep_len_max=s[7] if s[0] else nan)
-        dt = time.time() - t0
-        self._t_total += dt
-        info.update(time=self._t_total, fps=self.steps_per_epoch * self.N / dt)
-        self.log.append(info)
-        self.epoch += 1
         return info
-
-    def learn(self, epochs=None, verbose=False):
-        for _ in range(epochs or self.epochs):
-            info = self.learn_one_epoch()
-            if verbose:
-                print({k: (round(v, 4) if isinstance(v, float) else v) for k, v in info.items()})
-        return self.ac, self.env
 
     # ---- artefacts ---------------------------------------------------------------------------------------------------------
     def save_checkpoint(self, log_dir):
@@ -378,11 +403,3 @@ class DDPGTrainer:
                 ("QVals/Mean", "q_mean"), ("QVals/Min", "q_min"), ("QVals/Max", "q_max"), ("LossPi", "loss_pi"),
                 ("LossQ", "loss_q"), ("InWarmUp", "in_warm_up"), ("TotalEnvSteps", "total_env_steps"), ("Time", "time"),
                 ("FPS", "fps")]
-
-    def write_progress_csv(self, path):
-        """The per-epoch log, one row per epoch (the form of PPOTrainer.write_progress_csv)."""
-        cols = self._progress_columns()
-        with open(path, "w") as f:
-            f.write(",".join(c for c, _ in cols) + "\n")
-            for row in self.log:
-                f.write(",".join(str(row.get(k, "")) for _, k in cols) + "\n")

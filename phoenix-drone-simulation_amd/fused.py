@@ -11,6 +11,9 @@ gradient for the update.  Each call replaces an autograd op chain of the referen
     FusedMLP.ddpg_policy_grad  compute_loss_pi + backward (through Q into the actor) algs/ddpg/ddpg.py:336-340
     ddpg_target           the Bellman backup of compute_loss_q                      algs/ddpg/ddpg.py:323-326
     polyak                the target networks' polyak step                          algs/ddpg/ddpg.py:459-464
+    sac_sample            SquashedGaussianMLPActor.forward after its two heads      algs/sac/sac.py:47-76
+    sac_target            the entropy-regularised backup of compute_loss_q          algs/sac/sac.py:303-311
+    FusedMLP.sac_policy_grad  compute_loss_pi + backward (through min(Q1, Q2))      algs/sac/sac.py:324-337
 
 The gradients are written straight into the `.grad` storage of the torch parameters (one flat
 buffer, torch parameter order), so the optimiser step stays torch.optim.Adam like the reference's."""
@@ -211,6 +214,29 @@ class FusedMLP:
             raise (NotImplementedError if rc == native.EUNSUPPORTED else RuntimeError)(f"pds_ddpg_policy_grad -> {rc}")
         return self.stats
 
+    def sac_policy_grad(self, q1_fm, q2_fm, oa, index, alpha, act_limit, seed, call, adam_lr=None, betas=(0.9, 0.999), eps=1e-8):
+        """This network as the SAC actor (d_out = 8: [mu | log_std]): fills .grad with the gradient of
+        (alpha logp - min(Q1, Q2)(o, a)).mean() over the rows oa[index] = [obs | act] (index None: every row), a and logp the
+        squashed-Gaussian sample under the noise of (seed, call); Q1, Q2 = `q1_fm`, `q2_fm` (read only).  stats = [sum min Q,
+        sum logp, 0, B] (csrc/pds_sac.hip).  adam_lr: as in ppo_grad.  NotImplementedError for shapes the kernel is not built
+        for (sac_supported says so beforehand)."""
+        self._bind(); q1_fm._bind(); q2_fm._bind()
+        B = oa.shape[0] if index is None else index.shape[0]
+        ws = getattr(self, "sac_workspace", None)
+        if ws is None:
+            n = self.lib.pds_sac_workspace_floats(C.byref(self.m), C.byref(q1_fm.m), C.byref(q2_fm.m))
+            if n < 0:
+                raise (NotImplementedError if n == native.EUNSUPPORTED else ValueError)(f"pds_sac_workspace_floats -> {n}")
+            self.sac_workspace = ws = torch.empty(n, device=self.flat_grad.device)
+        opt = self._adam_arg(adam_lr, betas, eps)
+        with _on(oa):
+            rc = self.lib.pds_sac_policy_grad(C.byref(self.m), C.byref(q1_fm.m), C.byref(q2_fm.m), _ptr(oa), _ptr(index), B,
+                                              float(alpha), float(act_limit), int(seed) & (2 ** 64 - 1), int(call),
+                                              _ptr(self.flat_grad), _ptr(self.stats), _ptr(ws), opt, self._stream(oa))
+        if rc != native.OK:
+            raise (NotImplementedError if rc == native.EUNSUPPORTED else RuntimeError)(f"pds_sac_policy_grad -> {rc}")
+        return self.stats
+
 
 def ddpg_supported(pi_fm, q_fm):
     """True when the fused DDPG kernels cover this actor / Q pair (D + 4 <= 64, hidden <= 64, d_out 4 / 1)."""
@@ -239,6 +265,43 @@ def polyak(targ_fm, src_fm, rho):
         rc = native.load().pds_polyak(C.byref(targ_fm.m), C.byref(src_fm.m), float(rho), FusedMLP._stream(t))
     if rc != native.OK:
         raise RuntimeError(f"pds_polyak -> {rc}")
+
+
+def sac_supported(pi_fm, q1_fm, q2_fm):
+    """True when the fused SAC kernels cover this actor / twin-Q triple (D + 4 <= 64, hidden <= 64, d_out 8 / 1 / 1)."""
+    return native.load().pds_sac_supported(C.byref(pi_fm.m), C.byref(q1_fm.m), C.byref(q2_fm.m)) == 1
+
+
+def sac_sample(head, act_limit, seed, call, id_base=0, deterministic=False, act_out=None, want_logp=True):
+    """(a [n, 4], logp [n] or None) from the actor's output head [n, 8] = [mu | log_std]: the clamped, reparameterised,
+    tanh-squashed sample with its log-probability (include/pds.h pds_sac_sample); eps of row i = the variates of
+    pds_gaussian_sample for sample id id_base + i in `call` under `seed`."""
+    if head.dim() != 2 or head.shape[1] != 8 or not head.is_contiguous() or head.dtype != torch.float32:
+        raise ValueError("head must be a contiguous float32 [n, 8] tensor")
+    n = head.shape[0]
+    act = act_out if act_out is not None else torch.empty(n, 4, device=head.device)
+    logp = torch.empty(n, device=head.device) if want_logp else None
+    with _on(head):
+        rc = native.load().pds_sac_sample(_ptr(head), n, float(act_limit), int(seed) & (2 ** 64 - 1), int(call), int(id_base),
+                                          int(bool(deterministic)), _ptr(act), _ptr(logp), FusedMLP._stream(head))
+    if rc != native.OK:
+        raise RuntimeError(f"pds_sac_sample -> {rc}")
+    return act, logp
+
+
+def sac_target(pi_fm, q1_targ_fm, q2_targ_fm, obs2, index, rew, done, gamma, alpha, act_limit, seed, call, target_rows):
+    """target_rows[i] = rew[i] + gamma * (1 - done[i]) * (min(Q1_targ, Q2_targ)(obs2[i], a2) - alpha * logp2) for the rows
+    i = index[g] (index None: every row), (a2, logp2) the sample of the CURRENT policy `pi_fm` under the noise of (seed, call)
+    at position g; the other rows are left alone (include/pds.h pds_sac_target)."""
+    pi_fm._bind(); q1_targ_fm._bind(); q2_targ_fm._bind()
+    B = obs2.shape[0] if index is None else index.shape[0]
+    with _on(obs2):
+        rc = native.load().pds_sac_target(C.byref(pi_fm.m), C.byref(q1_targ_fm.m), C.byref(q2_targ_fm.m), _ptr(obs2), _ptr(index),
+                                          B, _ptr(rew), _ptr(done), float(gamma), float(alpha), float(act_limit),
+                                          int(seed) & (2 ** 64 - 1), int(call), _ptr(target_rows), FusedMLP._stream(obs2))
+    if rc != native.OK:
+        raise (NotImplementedError if rc == native.EUNSUPPORTED else RuntimeError)(f"pds_sac_target -> {rc}")
+    return target_rows
 
 
 def conjugate_gradients(avp, b, iters, residual_tol=1e-10, eps=1e-6):

@@ -41,7 +41,8 @@ EXPORTS = ["pds_version", "pds_default_config", "pds_create", "pds_destroy", "pd
            "pds_npg_workspace_floats", "pds_npg_fisher_vector_product", "pds_npg_cg_step", "pds_npg_surrogate_kl",
            "pds_simopt_latency_steps", "pds_simopt_evaluate", "pds_evaluate_supported", "pds_evaluate_policies",
            "pds_es_workspace_floats", "pds_es_perturb", "pds_es_gradient",
-           "pds_ddpg_supported", "pds_ddpg_workspace_floats", "pds_ddpg_policy_grad", "pds_ddpg_target", "pds_polyak"]
+           "pds_ddpg_supported", "pds_ddpg_workspace_floats", "pds_ddpg_policy_grad", "pds_ddpg_target", "pds_polyak",
+           "pds_sac_supported", "pds_sac_workspace_floats", "pds_sac_sample", "pds_sac_target", "pds_sac_policy_grad"]
 
 
 class Mlp(C.Structure):
@@ -177,6 +178,13 @@ def load():
     later("pds_ddpg_policy_grad", [mp, mp, vp, vp, i64, C.c_float, vp, vp, vp, ap, vp])
     later("pds_ddpg_target", [mp, mp, vp, vp, i64, vp, vp, C.c_float, C.c_float, vp, vp])
     later("pds_polyak", [mp, mp, C.c_double, vp])
+    later("pds_sac_supported", [mp, mp, mp])
+    later("pds_sac_workspace_floats", [mp, mp, mp])
+    if hasattr(lib, "pds_sac_workspace_floats"):
+        lib.pds_sac_workspace_floats.restype = i64
+    later("pds_sac_sample", [vp, i64, C.c_float, u64, u64, u64, i32, vp, vp, vp])
+    later("pds_sac_target", [mp, mp, mp, vp, vp, i64, vp, vp, C.c_float, C.c_float, C.c_float, u64, u64, vp, vp])
+    later("pds_sac_policy_grad", [mp, mp, mp, vp, vp, i64, C.c_float, C.c_float, u64, u64, vp, vp, vp, ap, vp])
     _lib = lib
     return lib
 
