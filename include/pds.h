@@ -637,6 +637,39 @@ int pds_sac_policy_grad(const pds_mlp *pi, const pds_mlp *q1, const pds_mlp *q2,
                         int64_t B, float alpha, float act_limit, uint64_t seed, uint64_t call, float *d_grads, float *d_stats,
                         float *d_workspace, const pds_adam *opt, void *stream);
 
+/* ---- The fused off-policy collection (csrc/pds_collect.h): K closed-loop vector steps of a DDPG / SAC trainer in ONE launch,
+ * the transitions written into the replay ring the update entry points above read in place.
+ *
+ * pds_collect: for s = 0 .. K - 1, with ring block b(s) = (ptr + s N) mod capacity (N = the handle's envs; ptr and capacity are
+ * multiples of N, so a block never straddles the wrap):
+ *   a     = mode 0 (DDPG, actor d_out 4): clamp(fmaf(exp(d_log_std[q]), z_q, act_limit * tanh(pi(o)_q)), +-act_limit)
+ *           mode 1 (SAC,  actor d_out 8): act_limit * tanh(fmaf(exp(clamp(log_std)), z, mu)) on the head row [mu | log_std]
+ *           with pi(o) the bits of pds_mlp_forward and z the variates pds_gaussian_sample draws for sample id = env row, block 0,
+ *           call = first_call + s under `seed`: the bits of pds_mlp_forward + pds_ddpg_explore / pds_sac_sample
+ *   env.step(a): the bits of pds_step
+ *   d_oa  [b(s) + i] = [o_i(s) | a_i]      d_obs2[b(s) + i] = the final observation where env i finished, else o_i(s + 1)
+ *   d_rew [b(s) + i] = the step reward      d_done[b(s) + i] = 1.f where terminated and not truncated, else 0.f
+ * d_obs [N, D]: in o(0) (what pds_reset / pds_step returned last), out o(K).  d_ep_ret / d_ep_len [N]: running return and length
+ * of every env, in / out (zero where the env finished).  The handle's state and tick advance K steps.
+ * d_tile_stats [ceil(N / 64), 8], written without atomics, every row: over the episodes of that 64-env tile that finished within
+ * the launch { count, sum, sum of squares, min, max of the return, sum, min, max of the length }; neutral values 0, +inf, -inf.
+ * PDS_EINVAL: K < 1, a mode other than 0 / 1, a NULL pointer (d_log_std may be NULL in mode 1), a call before pds_reset, an actor
+ * whose d_out does not match the mode, act_limit <= 0, capacity < N, ptr or capacity not a multiple of N, ptr outside
+ * [0, capacity), d_oa / d_obs2 not 16-byte aligned.  PDS_EUNSUPPORTED: a handle without auto_reset; an env configuration outside
+ * { control_mode PWM, no latency ring, no Kalman hold, no ground effect, noise all off or domain randomisation + thrust noise +
+ * observation noise, TakeOff without motor dynamics }; an actor with d_in != the handle's observation width, more than 64 inputs
+ * or hidden units, or another activation than relu / tanh -- pds_collect_supported answers 1 / 0 beforehand.  A refused call
+ * leaves the handle and every buffer as they were.
+ *
+ * pds_ddpg_explore: DDPG's exploration rule above as an elementwise entry point, d_act[n, 4] from the actor's pre-tanh output
+ * d_net_out [n, 4] (both 16-byte aligned), z of row i = the variates of pds_gaussian_sample for sample id id_base + i. */
+int pds_collect_supported(const pds_handle *h, const pds_mlp *pi, int mode);
+int pds_collect(pds_handle *h, int K, int mode, const pds_mlp *pi, float act_limit, const float *d_log_std /* DDPG: [4]; SAC: NULL */,
+                uint64_t seed, uint64_t first_call, float *d_oa, float *d_obs2, float *d_rew, float *d_done, int64_t capacity,
+                int64_t ptr, float *d_obs, float *d_ep_ret, float *d_ep_len, float *d_tile_stats, void *stream);
+int pds_ddpg_explore(const float *d_net_out /* [n, 4] */, const float *d_log_std, int64_t n, float act_limit, uint64_t seed,
+                     uint64_t call, uint64_t id_base, float *d_act, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

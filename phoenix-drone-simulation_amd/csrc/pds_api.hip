@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "pds_reset.h"  // (pds_types.h + regen_kept_obs for pds_get_state)
+#include "pds_collect_args.h"
 #include "pds_evaluate_args.h"
 #include "pds_simopt.h"
 
@@ -1087,6 +1088,28 @@ extern "C" int pds_rollout_history(pds_handle *h, int T, int history, const pds_
   });
 }
 
+// The per-step streams of a kernel that keeps every step's outcome in registers (pds_evaluate_policies, pds_collect): step_once
+// (csrc/pds_step.h) streams reward / cost / term / trunc out whatever its caller does with them, and those kernels point all four
+// at one [N] sink row of the handle that every step overwrites.  16 N bytes, allocated by the first such call: load_env reads an
+// action quad per env through StepArgs::actions (unused there); the outcome streams take 10 N of them.
+static int point_at_step_sink(pds_handle *h, const char *fn, StepArgs &sa, void *stream) {
+  const long long n = h->cfg.num_envs;
+  if (!h->eval_sink) {
+    if (hipMalloc(&h->eval_sink, (size_t)n * 16) != hipSuccess) {
+      h->eval_sink = nullptr;
+      (void)hipGetLastError();
+      return fail(h, PDS_ENOMEM, "%s: %lld bytes for the per-step sink row", fn, n * 16);
+    }
+    PDS_HIP(h, hipMemsetAsync(h->eval_sink, 0, (size_t)n * 16, (hipStream_t)stream));  // (no uninitialised read in load_env)
+  }
+  sa.actions = reinterpret_cast<const float4 *>(h->eval_sink);  // (load_env's action slot: valid memory, value unused)
+  sa.reward = reinterpret_cast<float *>(h->eval_sink);
+  sa.cost = sa.reward + n;
+  sa.term = reinterpret_cast<uint8_t *>(sa.cost + n);
+  sa.trunc = sa.term + n;
+  return PDS_OK;
+}
+
 // whether pds_evaluate_policies has a kernel for this handle (the two PDS_EUNSUPPORTED conditions of check_rollout_call and below)
 extern "C" int pds_evaluate_supported(const pds_handle *h) {
   if (!h) return PDS_EINVAL;
@@ -1117,23 +1140,10 @@ extern "C" int pds_evaluate_policies(pds_handle *h, int64_t P, int64_t episodes_
                                      "pds_mlp_forward + pds_step give the same bits", fn);
   DeviceGuard guard(h->cfg.device);
   PDS_HIP(h, guard.err);
-  // 16 N bytes: load_env reads an action quad per env through StepArgs::actions (unused here); the outcome streams take 10 N of them
-  if (!h->eval_sink) {
-    if (hipMalloc(&h->eval_sink, (size_t)n * 16) != hipSuccess) {
-      h->eval_sink = nullptr;
-      (void)hipGetLastError();
-      return fail(h, PDS_ENOMEM, "%s: %lld bytes for the per-step sink row", fn, n * 16);
-    }
-    PDS_HIP(h, hipMemsetAsync(h->eval_sink, 0, (size_t)n * 16, (hipStream_t)stream));  // (no uninitialised read in load_env)
-  }
   EvalArgs ea;
   memset(&ea, 0, sizeof(ea));
   base_args(h, ea.s);
-  ea.s.actions = reinterpret_cast<const float4 *>(h->eval_sink);  // (load_env's action slot: valid memory, value unused)
-  ea.s.reward = reinterpret_cast<float *>(h->eval_sink);
-  ea.s.cost = ea.s.reward + n;
-  ea.s.term = reinterpret_cast<uint8_t *>(ea.s.cost + n);
-  ea.s.trunc = ea.s.term + n;
+  if (const int rc = point_at_step_sink(h, fn, ea.s, stream)) return rc;
   ea.s.k_steps = max_steps;
   ea.shape = *shape;
   ea.params = d_params;
@@ -1151,6 +1161,69 @@ extern "C" int pds_evaluate_policies(pds_handle *h, int64_t P, int64_t episodes_
   // tiles stopped at different steps: not a state to continue from -- every stepping entry point asks for pds_reset first
   if (rc == PDS_OK) { h->was_reset = false; h->after_evaluate = true; }
   return rc;
+}
+
+// ---- the fused off-policy collection: csrc/pds_collect.h (OffPolicyTrainer.step_env + the bookkeeping of learn_one_epoch) ----
+// what pds_collect refuses with PDS_EUNSUPPORTED, as a question: the handle (auto_reset, collect_env_supported) and the actor's shape
+static bool collect_shape_ok(const pds_handle *h, const pds_mlp *pi) {
+  return pi->d_in == h->obs_dim && h->obs_dim <= 64 && pi->h1 >= 1 && pi->h1 <= 64 && pi->h2 >= 1 && pi->h2 <= 64 &&
+         (pi->activation == 0 || pi->activation == 1);
+}
+extern "C" int pds_collect_supported(const pds_handle *h, const pds_mlp *pi, int mode) {
+  if (!h || !pi) return PDS_EINVAL;
+  if (mode != kCollectDdpg && mode != kCollectSac) return 0;
+  return h->cfg.auto_reset && collect_env_supported(h->cfg.task, h->flags) && collect_shape_ok(h, pi) &&
+                 pi->d_out == (mode == kCollectSac ? 8 : 4) ? 1 : 0;
+}
+
+extern "C" int pds_collect(pds_handle *h, int K, int mode, const pds_mlp *pi, float act_limit, const float *d_log_std, uint64_t seed,
+                           uint64_t first_call, float *d_oa, float *d_obs2, float *d_rew, float *d_done, int64_t capacity,
+                           int64_t ptr, float *d_obs, float *d_ep_ret, float *d_ep_len, float *d_tile_stats, void *stream) {
+  if (!h) return PDS_EINVAL;
+  const char *fn = "pds_collect";
+  if (K < 1) return fail(h, PDS_EINVAL, "%s: K %d", fn, K);
+  if (mode != kCollectDdpg && mode != kCollectSac) return fail(h, PDS_EINVAL, "%s: mode %d (0 DDPG, 1 SAC)", fn, mode);
+  const bool any_null = !pi || (mode == kCollectDdpg && !d_log_std) || !d_oa || !d_obs2 || !d_rew || !d_done || !d_obs || !d_ep_ret ||
+                        !d_ep_len || !d_tile_stats;
+  if (const int rc = check_rollout_call(h, fn, any_null, nullptr, nullptr)) return rc;
+  if (!collect_env_supported(h->cfg.task, h->flags))
+    return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: control_mode PWM without latency ring, Kalman hold "
+                                     "or ground effect; noise off or the reference's default; TakeOff without motor dynamics) -- the "
+                                     "per-step entry points give the same bits", fn);
+  const int D = h->obs_dim;
+  if (!collect_shape_ok(h, pi))
+    return fail(h, PDS_EUNSUPPORTED, "%s: actor shape (d_in must be the observation width %d <= 64, hidden <= 64, relu or tanh)", fn, D);
+  if (!pi->w1 || !pi->b1 || !pi->w2 || !pi->b2 || !pi->w3 || !pi->b3) return fail(h, PDS_EINVAL, "%s: NULL pointer in the actor", fn);
+  if (pi->d_out != (mode == kCollectSac ? 8 : 4))
+    return fail(h, PDS_EINVAL, "%s: actor d_out %d in mode %d (DDPG 4, SAC 8)", fn, pi->d_out, mode);
+  if (!(act_limit > 0.f) || !std::isfinite(act_limit)) return fail(h, PDS_EINVAL, "%s: act_limit %g", fn, (double)act_limit);
+  const long long n = h->cfg.num_envs;
+  if (capacity < n || capacity % n != 0 || ptr < 0 || ptr >= capacity || ptr % n != 0)
+    return fail(h, PDS_EINVAL, "%s: capacity %lld and ptr %lld must be multiples of the handle's %lld envs, 0 <= ptr < capacity", fn,
+                (long long)capacity, (long long)ptr, n);
+  // the id packing of PDS_GAUSSIAN_PHILOX holds sample ids below 2^56
+  if ((unsigned long long)n > (1ull << 56)) return fail(h, PDS_EINVAL, "%s: sample ids beyond 2^56", fn);
+  if (!rollout_buffers_aligned(d_oa, d_obs) || (((uintptr_t)d_obs2) & 15u) || (((uintptr_t)d_rew | (uintptr_t)d_done |
+      (uintptr_t)d_ep_ret | (uintptr_t)d_ep_len | (uintptr_t)d_tile_stats) & 3u))
+    return fail(h, PDS_EINVAL, "%s: alignment (d_oa, d_obs2: 16 bytes; the others: 4)", fn);
+  DeviceGuard guard(h->cfg.device);
+  PDS_HIP(h, guard.err);
+  CollectArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  base_args(h, ca.s);
+  if (const int rc = point_at_step_sink(h, fn, ca.s, stream)) return rc;
+  ca.s.k_steps = K;
+  ca.pi = *pi;
+  ca.mode = mode; ca.K = K; ca.act_limit = act_limit; ca.log_std = d_log_std;
+  ca.seed = seed; ca.first_call = first_call;
+  ca.oa = d_oa; ca.obs2 = d_obs2; ca.rew = d_rew; ca.done = d_done;
+  ca.capacity = capacity; ca.ptr = ptr;
+  ca.obs = d_obs; ca.ep_ret = d_ep_ret; ca.ep_len = d_ep_len; ca.tile_stats = d_tile_stats;
+  return launch_rollout(h, fn, K, stream, [&](dim3 grid, hipStream_t s) {
+    if (h->cfg.task == PDS_TASK_HOVER) return launch_collect_hover(h->flags, grid, s, ca);
+    if (h->cfg.task == PDS_TASK_CIRCLE) return launch_collect_circle(h->flags, grid, s, ca);
+    return launch_collect_takeoff(h->flags, grid, s, ca);
+  });
 }
 
 // number of envs whose dynamic state holds a NaN or an Inf (diagnostic, see pds_count_nonfinite)

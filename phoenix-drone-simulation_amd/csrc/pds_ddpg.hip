@@ -29,6 +29,7 @@
 // Bound: MFMA f32, as the kernels it is built from.
 #include <math.h>
 
+#include "pds_explore.h"
 #include "pds_mlp_tile.h"
 
 namespace pds_mlp_detail {
@@ -262,6 +263,19 @@ int launch_ddpg_reduce(const float *partials, int pstride, int nwaves, int total
   return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
 }
 
+// one thread per row of the actor's [n, 4] pre-tanh output: DDPG's exploration action (csrc/pds_explore.h ddpg_explore, the device
+// function the network waves of csrc/pds_collect.h call), z = the variates of pds_gaussian_sample for sample id id_base + i
+__global__ __launch_bounds__(256) void ddpg_explore_kernel(const float *net, const float *log_std, long long n, float limit,
+                                                           unsigned long long seed, unsigned long long call,
+                                                           unsigned long long id_base, float *act) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const pds_explore::f32x4 y = *reinterpret_cast<const pds_explore::f32x4 *>(net + i * 4);
+  const pds_explore::f32x4 ls = {log_std[0], log_std[1], log_std[2], log_std[3]};
+  const pds_explore::f32x4 z = pds_explore::gaussian_draw4(id_base + (unsigned long long)i, call, seed);
+  *reinterpret_cast<pds_explore::f32x4 *>(act + i * 4) = pds_explore::ddpg_explore(y, ls, z, limit);
+}
+
 }  // namespace pds_mlp_detail
 using namespace pds_mlp_detail;
 
@@ -325,5 +339,16 @@ extern "C" int pds_polyak(const pds_mlp *targ, const pds_mlp *src, double polyak
   const int total = offsets(*targ).total;
   hipLaunchKernelGGL(polyak_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, *targ, *src, total,
                      (float)polyak, (float)(1.0 - polyak));
+  return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
+}
+
+extern "C" int pds_ddpg_explore(const float *d_net_out, const float *d_log_std, int64_t n, float act_limit, uint64_t seed,
+                                uint64_t call, uint64_t id_base, float *d_act, void *stream) {
+  // the id packing of PDS_GAUSSIAN_PHILOX holds sample ids below 2^56
+  if (!d_net_out || !d_log_std || !d_act || n < 1 || !(act_limit > 0.f) || id_base > (1ull << 56) ||
+      (uint64_t)n > (1ull << 56) - id_base || ((((uintptr_t)d_net_out) | ((uintptr_t)d_act)) & 15u))
+    return PDS_EINVAL;
+  hipLaunchKernelGGL(ddpg_explore_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_net_out, d_log_std,
+                     (long long)n, act_limit, (unsigned long long)seed, (unsigned long long)call, (unsigned long long)id_base, d_act);
   return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
 }

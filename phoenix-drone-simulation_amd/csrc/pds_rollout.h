@@ -116,16 +116,19 @@ PDS_DEV void rollout_post(int *flag, int lane) {  // +1, after every lane's LDS 
   if (dn) { st0 += er; st1 += el; st2 += 1.f; }               \
   ep_ret = dn ? 0.f : er;                                     \
   ep_len = dn ? 0.f : el;
-// Behind the loop: state, running return / length and the tile's clock back to memory, the finished episodes' sums into
-// stats[0..2] (one atomic triple per tile).  RA: the kernel's argument struct, ID: its reload_args tag.
-#define PDS_ENV_WAVE_END(RA, ID)                                                                                              \
+// Behind the loop: state, running return / length and the tile's clock back to memory (PDS_ENV_WAVE_STORE: what every kernel
+// with an env wave ends on, csrc/pds_collect.h too), the finished episodes' sums into stats[0..2] (one atomic triple per
+// tile).  RA: the kernel's argument struct, ID: its reload_args tag.
+#define PDS_ENV_WAVE_STORE(RA, ID)                                                                                            \
   const RA &rl = *reinterpret_cast<const RA *>(&reload_args<ID, true>(ra.s, T));                                              \
   if (active) {                                                                                                               \
     store_state<V>(rl.s, ix, parity, S, true);                                                                                \
     *at(rl.ep_ret, ix) = ep_ret;                                                                                              \
     *at(rl.ep_len, ix) = ep_len;                                                                                              \
   }                                                                                                                           \
-  advance_clock(rl.s.st.clk, t, rk0, parity, (uint32_t)T, lane);                                                              \
+  advance_clock(rl.s.st.clk, t, rk0, parity, (uint32_t)T, lane);
+#define PDS_ENV_WAVE_END(RA, ID)                                                                                              \
+  PDS_ENV_WAVE_STORE(RA, ID)                                                                                                  \
   for (int d = 32; d >= 1; d >>= 1) { st0 += __shfl_xor(st0, d); st1 += __shfl_xor(st1, d); st2 += __shfl_xor(st2, d); }      \
   if (lane == 0 && st2 != 0.f) {                                                                                              \
     atomicAdd(rl.stats + 0, st0);                                                                                             \

@@ -6,7 +6,7 @@
 //
 // The actor is ONE pds_mlp with d_out = 8: w3 / b3 = [mu_layer; log_std_layer] stacked.  In the tile core lane (n, 0) holds
 // outputs 0 .. 3 of sample n (mu), lane (n, 1) outputs 4 .. 7 (log_std); one xor-16 shuffle brings the two together, and both
-// lane groups then evaluate the sample (sac_draw, below) redundantly -- the same instructions on the same values -- so the
+// lane groups then evaluate the sample (sac_draw, csrc/pds_explore.h) redundantly -- the same instructions on the same values -- so the
 // 8-wide output gradient dy = [dmu | dlog_std] is already in the lanes wide_backward wants it in.
 //
 // Per 16-sample tile a wave of sac_grad_kernel runs:
@@ -49,6 +49,7 @@
 
 #include "pds_mlp_tile.h"
 #include "pds_device.h"
+#include "pds_explore.h"
 
 namespace pds_mlp_detail {
 
@@ -56,7 +57,6 @@ constexpr int kSacNin = 4;     // input tiles: D + 4 <= 64
 constexpr int kSacWaves = 3;   // waves per block of the gradient kernel (LDS budget above)
 static_assert(wide_stride<kSacNin>() == kS, "the X image shares the 68-float stride");
 constexpr int kSacImg = 3 * kTS * kS + kTS * kSY;  // X, H1, H2, dY per wave (gradient kernel)
-constexpr float kLogStdMin = -20.f, kLogStdMax = 2.f;  // LOG_STD_MIN / LOG_STD_MAX, algs/sac/sac.py:31-32
 
 struct SacArgs {
   pds_mlp pi, q1, q2;
@@ -73,41 +73,12 @@ struct SacArgs {
   float *target;             // target: [rows], written at the ROW
 };
 
-// softplus(x) = log(1 + e^x) in its stable form
-__device__ __forceinline__ float softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-
-// The squashed-Gaussian sample of one row, stated once for the three kernels (SquashedGaussianMLPActor.forward,
-// algs/sac/sac.py:47-76): ls = clamp(log_std), sig = exp(ls), u = mu + sig eps, th = tanh(u) and
-// logp = sum_j (-0.5 eps_j^2 - ls_j - 0.5 log 2 pi) - sum_j 2 (log 2 - u_j - softplus(-2 u_j)).
-// eps: the noise contract; deterministic: eps = 0 (u = mu).
-struct SacDraw {
-  f32x4 eps, ls, sig, u, th;
-  float logp;
-};
-__device__ __forceinline__ SacDraw sac_draw(const f32x4 mu, const f32x4 log_std, unsigned long long id, unsigned long long call,
-                                            unsigned long long seed, bool deterministic) {
-  SacDraw d;
-  d.eps = (f32x4)(0.f);
-  if (!deterministic) {
-    const pds::U4 r = PDS_GAUSSIAN_PHILOX(id, 0u, call, seed);
-    float z0, z1, z2, z3;
-    pds::box_muller(r.x, r.y, z0, z1);
-    pds::box_muller(r.z, r.w, z2, z3);
-    d.eps = (f32x4){z0, z1, z2, z3};
-  }
-  float gauss = 0.f, corr = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    d.ls[j] = fminf(fmaxf(log_std[j], kLogStdMin), kLogStdMax);
-    d.sig[j] = expf(d.ls[j]);
-    d.u[j] = fmaf(d.sig[j], d.eps[j], mu[j]);
-    d.th[j] = tanhf(d.u[j]);
-    gauss += PDS_GAUSSIAN_LOGP_TERM(d.eps[j], d.ls[j]);
-    corr += 2.f * (0.69314718055994530942f - d.u[j] - softplus(-2.f * d.u[j]));
-  }
-  d.logp = gauss - corr;
-  return d;
-}
+// softplus, SacDraw / sac_draw (the squashed-Gaussian sample of one row, stated once for the three kernels here and for the
+// network waves of csrc/pds_collect.h) and kLogStdMin / kLogStdMax: csrc/pds_explore.h
+using pds_explore::kLogStdMax;
+using pds_explore::kLogStdMin;
+using pds_explore::sac_draw;
+using pds_explore::SacDraw;
 
 // mu and log_std of sample n from the actor's 8 outputs: lane group 0 holds mu, group 1 log_std (groups 2 / 3 hold the aliased
 // rows 8 .. 15 and take part in the shuffle only); afterwards BOTH groups of a pair hold both

@@ -18,7 +18,12 @@ fused=True (csrc/pds_ddpg.hip, fused.py): a mini-batch is read IN PLACE through 
 Bellman backup at the rows, pds_value_grad_step takes the Q step on `oa[index]`, pds_ddpg_policy_grad differentiates
 -Q(o, pi(o)).mean() through Q into the actor and takes its Adam step, pds_polyak moves the targets: six launches, no gather
 copy, no autograd graph.  fused=False is the same recipe in torch autograd (torch.optim.Adam), and is what the kernels are
-tested against.  Shapes the kernels are not built for (D + 4 > 64: observation_history_size >= 4, TakeOff from 3; hidden
+tested against.  fused_collect=True (csrc/pds_collect.h): once warm-up is over, the vector steps up to the next update are ONE
+launch of pds_collect -- actor, exploration noise, env step, the ring rows, the episode statistics -- where step_env issues
+about three dozen; `trainer.collect_fused` reports whether that kernel runs (pds_collect_supported: control_mode PWM, history 2,
+no latency / hold / ground effect).  With the flag on, DDPG acts through pds_ddpg_explore on the per-step path too (tanhf where
+fused_collect=False calls torch.tanh: the one documented difference between the two settings).
+Shapes the kernels are not built for (D + 4 > 64: observation_history_size >= 4, TakeOff from 3; hidden
 sizes above 64, e.g. the reference's (400, 300)) take the autograd path; `trainer.fused` reports which path is in use.
 Single process only."""
 import math
@@ -130,6 +135,13 @@ def autograd_update(ac, ac_targ, pi_optimizer, q_optimizer, data, gamma, polyak)
     return lq.detach(), lp.detach(), qvals
 
 
+def collect_steps(since_update, update_every, N, steps_left_in_epoch):
+    """Vector steps of one pds_collect launch: up to the next point at which an update can happen -- the first step at which
+    `since_update >= update_every` holds, max(1, ceil((update_every - since_update) / N)) steps ahead -- and not past the epoch."""
+    ahead = -((int(since_update) - int(update_every)) // int(N))  # ceil((update_every - since_update) / N)
+    return max(1, min(max(1, ahead), int(steps_left_in_epoch)))
+
+
 class ReplayBuffer:
     """A ring of transitions on one device, filled N rows per vector step: oa [capacity, D + 4] = [obs | act] (the Q network's
     input, read in place by the fused kernels), obs2 [capacity, D], rew, done [capacity] (done as 0. / 1.).  `capacity` must
@@ -176,6 +188,16 @@ class ReplayBuffer:
         self.ptr = (self.ptr + n) % self.capacity
         self.size = min(self.size + n, self.capacity)
 
+    def advance(self, k):
+        """move ptr / size as k store() calls would (the rows were written in place: pds_collect)"""
+        if self.num_envs is None:
+            raise ValueError("advance() before the rows per step are known")
+        rows = int(k) * self.num_envs
+        if k < 0:
+            raise ValueError(f"k = {k}")
+        self.ptr = (self.ptr + rows) % self.capacity
+        self.size = min(self.size + rows, self.capacity)
+
     def sample_indices(self, batch_size):
         """int64 row indices [batch_size], uniform over the filled rows (with repeats), from the buffer's seeded generator"""
         if self.size < 1:
@@ -192,7 +214,11 @@ class ReplayBuffer:
 class OffPolicyTrainer:
     """The vector-step / update / epoch loop the off-policy trainers share (DDPGTrainer here, sac.SACTrainer).  A subclass
     sets env, N, buffer, warmup_steps, update_after, update_every, steps_per_epoch, updates_per_step and epochs, calls
-    _init_loop(), and provides get_action(obs), update(), _update_info() and _progress_columns()."""
+    _init_loop() and _init_collect(), and provides get_action(obs), update(), _update_info() and _progress_columns()."""
+
+    fused_collect = False   # the constructor's keyword
+    collect_fused = False   # ... and whether pds_collect runs after warm-up
+    collect_launches = 0
 
     def _init_loop(self):
         dev = self.env.device
@@ -201,6 +227,41 @@ class OffPolicyTrainer:
         self.in_warm_up = True
         self.total_steps, self.updates, self._since_update = 0, 0, 0
         self.epoch, self.log, self._t_total = 0, [], 0.0
+
+    def _init_collect(self, fused_collect, mode, log_std=None):
+        """fused_collect=True: one pds_collect launch per stretch of vector steps between updates, where the kernel is built for the
+        env and the actor `fm_pi` (mode: fused.COLLECT_DDPG / COLLECT_SAC; log_std: DDPG's [4] log noise scale)."""
+        self.fused_collect = bool(fused_collect)
+        self._collect_mode, self._collect_log_std = mode, log_std
+        self.collect_fused, self.collect_launches, self._cobs = False, 0, None
+        if self.fused_collect and self.fused:
+            from .fused import collect_supported
+            self.collect_fused = collect_supported(self.env, self.fm_pi, mode)
+
+    # ---- K vector steps in one launch ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def collect(self, k):
+        """k vector steps of step_env + the episode bookkeeping of learn_one_epoch as one pds_collect launch (after warm-up only:
+        the actions are the policy's).  -> the launch's [tiles, 8] statistics slab"""
+        from .fused import collect_tiles, fused_collect
+        if self.obs is None:
+            self.obs, _ = self.env.reset()
+        if self._cobs is None:
+            self._cobs = torch.empty_like(self.obs)  # (the env owns the tensors its step() returns)
+        if self.obs is not self._cobs:
+            self._cobs.copy_(self.obs)
+            self.obs = self._cobs
+        self.in_warm_up = False
+        buf = self.buffer
+        slab = torch.empty(collect_tiles(self.env), 8, device=self.env.device)
+        fused_collect(self.env, self.fm_pi, self._collect_mode, k, self.act_limit, self._collect_log_std, self.seed,
+                      self._noise_calls + 1, buf.oa, buf.obs2, buf.rew, buf.done, buf.ptr, self._cobs, self.ep_ret, self.ep_len, slab)
+        self._noise_calls += k
+        buf.advance(k)
+        self.collect_launches += 1
+        self.total_steps += k * self.N
+        self._since_update += k * self.N
+        return slab
 
     # ---- one vector step -------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -230,20 +291,27 @@ class OffPolicyTrainer:
         inf = float("inf")
         # finished episodes of the epoch: count, sum, sum of squares, min, max of the return; sum, min, max of the length
         acc = torch.tensor([0.0, 0.0, 0.0, inf, -inf, 0.0, inf, -inf], device=dev)
-        for _ in range(self.steps_per_epoch):
-            r, done = self.step_env()
-            self.ep_ret += r
-            self.ep_len += 1.0
-            d = done.to(torch.float32)
-            ret, ln = self.ep_ret, self.ep_len
-            acc[0] += d.sum(); acc[1] += (d * ret).sum(); acc[2] += (d * ret * ret).sum()
-            acc[3] = torch.minimum(acc[3], torch.where(done, ret, torch.full_like(ret, inf)).min())
-            acc[4] = torch.maximum(acc[4], torch.where(done, ret, torch.full_like(ret, -inf)).max())
-            acc[5] += (d * ln).sum()
-            acc[6] = torch.minimum(acc[6], torch.where(done, ln, torch.full_like(ln, inf)).min())
-            acc[7] = torch.maximum(acc[7], torch.where(done, ln, torch.full_like(ln, -inf)).max())
-            self.ep_ret = torch.where(done, torch.zeros_like(ret), ret)
-            self.ep_len = torch.where(done, torch.zeros_like(ln), ln)
+        steps_left, slabs = self.steps_per_epoch, []
+        while steps_left > 0:
+            if self.collect_fused and len(self.buffer) >= self.warmup_steps:
+                k = collect_steps(self._since_update, self.update_every, self.N, steps_left)
+                slabs.append(self.collect(k))
+                steps_left -= k
+            else:
+                r, done = self.step_env()
+                steps_left -= 1
+                self.ep_ret += r
+                self.ep_len += 1.0
+                d = done.to(torch.float32)
+                ret, ln = self.ep_ret, self.ep_len
+                acc[0] += d.sum(); acc[1] += (d * ret).sum(); acc[2] += (d * ret * ret).sum()
+                acc[3] = torch.minimum(acc[3], torch.where(done, ret, torch.full_like(ret, inf)).min())
+                acc[4] = torch.maximum(acc[4], torch.where(done, ret, torch.full_like(ret, -inf)).max())
+                acc[5] += (d * ln).sum()
+                acc[6] = torch.minimum(acc[6], torch.where(done, ln, torch.full_like(ln, inf)).min())
+                acc[7] = torch.maximum(acc[7], torch.where(done, ln, torch.full_like(ln, -inf)).max())
+                self.ep_ret = torch.where(done, torch.zeros_like(ret), ret)
+                self.ep_len = torch.where(done, torch.zeros_like(ln), ln)
             if (not self.in_warm_up and len(self.buffer) >= self.update_after and self._since_update >= self.update_every):
                 for _ in range(self.updates_per_step):
                     self.update()
@@ -251,7 +319,14 @@ class OffPolicyTrainer:
         info = dict(epoch=self.epoch + 1, in_warm_up=float(self.in_warm_up), total_env_steps=self.total_steps,
                     updates=self.updates)
         info.update(self._update_info())
-        s = acc.tolist()
+        if slabs:  # the launches' per-tile statistics, once per epoch: three reductions, read back with `acc` in one copy
+            t = torch.cat(slabs)
+            v = torch.cat([acc, t.sum(0), t.min(0).values, t.max(0).values]).tolist()
+            s, su, mn, mx = v[:8], v[8:16], v[16:24], v[24:32]
+            s = [s[0] + su[0], s[1] + su[1], s[2] + su[2], min(s[3], mn[3]), max(s[4], mx[4]), s[5] + su[5], min(s[6], mn[6]),
+                 max(s[7], mx[7])]
+        else:
+            s = acc.tolist()
         n = max(s[0], 1.0)
         mean = s[1] / n
         nan = float("nan")
@@ -288,7 +363,7 @@ class DDPGTrainer(OffPolicyTrainer):
 
     def __init__(self, env, ac_kwargs=None, gamma=0.99, polyak=0.995, pi_lr=1e-4, q_lr=1e-3, mini_batch_size=128,
                  act_noise=0.1, warmup_steps=10000, update_after=1000, update_every=50, buffer_size=int(1e6), epochs=100,
-                 steps_per_epoch=64, updates_per_step=1, seed=0, fused=True):
+                 steps_per_epoch=64, updates_per_step=1, seed=0, fused=True, fused_collect=False):
         if not getattr(env, "_auto_reset", True):
             raise ValueError("DDPGTrainer needs an env with auto_reset=True")
         self.env, self.N, self.D = env, int(env.num_envs), int(env.obs_dim)
@@ -331,6 +406,8 @@ class DDPGTrainer(OffPolicyTrainer):
         self._logp = torch.empty(self.N, device=dev)
         self._noise_calls = 0
         self._init_loop()
+        from .fused import COLLECT_DDPG
+        self._init_collect(fused_collect, COLLECT_DDPG, self._log_noise)
         self._last = None  # (loss_q, loss_pi, index) of the latest update, device tensors
 
     # ---- acting ------------------------------------------------------------------------------------------------------------
@@ -347,6 +424,11 @@ class DDPGTrainer(OffPolicyTrainer):
         section 4: Philox keyed by (seed, env row, call)); uniform in [-1, 1] during warm-up (action_space.sample)."""
         if self.in_warm_up:
             return torch.rand(self.N, self.env.act_dim, device=obs.device, generator=self.gen) * 2.0 - 1.0
+        if self.fused_collect and self.fused:  # the action rule of pds_collect as its elementwise entry point (tanhf)
+            from .fused import ddpg_explore
+            self._noise_calls += 1
+            return ddpg_explore(self.fm_pi.forward(obs), self._log_noise, self.act_limit, self.seed, self._noise_calls,
+                                act_out=self._act)
         from .fused import gaussian_sample
         mu = self.policy_action(obs).contiguous()
         self._noise_calls += 1

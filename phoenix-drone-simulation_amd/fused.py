@@ -14,6 +14,8 @@ gradient for the update.  Each call replaces an autograd op chain of the referen
     sac_sample            SquashedGaussianMLPActor.forward after its two heads      algs/sac/sac.py:47-76
     sac_target            the entropy-regularised backup of compute_loss_q          algs/sac/sac.py:303-311
     FusedMLP.sac_policy_grad  compute_loss_pi + backward (through min(Q1, Q2))      algs/sac/sac.py:324-337
+    ddpg_explore          get_action's clip(pi(o) + noise) behind the actor         algs/ddpg/ddpg.py:342-345
+    fused_collect         roll_out: K vector steps into the replay ring, one launch algs/ddpg/ddpg.py:393-429, algs/sac/sac.py:402-437
 
 The gradients are written straight into the `.grad` storage of the torch parameters (one flat
 buffer, torch parameter order), so the optimiser step stays torch.optim.Adam like the reference's."""
@@ -302,6 +304,52 @@ def sac_target(pi_fm, q1_targ_fm, q2_targ_fm, obs2, index, rew, done, gamma, alp
     if rc != native.OK:
         raise (NotImplementedError if rc == native.EUNSUPPORTED else RuntimeError)(f"pds_sac_target -> {rc}")
     return target_rows
+
+
+COLLECT_DDPG, COLLECT_SAC = 0, 1  # `mode` of pds_collect (include/pds.h)
+
+
+def ddpg_explore(net_out, log_std, act_limit, seed, call, id_base=0, act_out=None):
+    """a [n, 4] = clamp(act_limit * tanh(net_out) + exp(log_std) * z, -act_limit, act_limit) from the actor's pre-tanh output
+    net_out [n, 4] (include/pds.h pds_ddpg_explore); z of row i = the variates of pds_gaussian_sample for sample id
+    id_base + i in `call` under `seed`.  The device function the network waves of pds_collect call."""
+    if net_out.dim() != 2 or net_out.shape[1] != 4 or not net_out.is_contiguous() or net_out.dtype != torch.float32:
+        raise ValueError("net_out must be a contiguous float32 [n, 4] tensor")
+    n = net_out.shape[0]
+    act = act_out if act_out is not None else torch.empty(n, 4, device=net_out.device)
+    with _on(net_out):
+        rc = native.load().pds_ddpg_explore(_ptr(net_out), _ptr(log_std), n, float(act_limit), int(seed) & (2 ** 64 - 1), int(call),
+                                            int(id_base), _ptr(act), FusedMLP._stream(net_out))
+    if rc != native.OK:
+        raise RuntimeError(f"pds_ddpg_explore -> {rc}")
+    return act
+
+
+def collect_supported(env, fm_pi, mode):
+    """True when pds_collect has a kernel for this env and actor in this mode (COLLECT_DDPG: d_out 4, COLLECT_SAC: d_out 8)."""
+    return env.lib.pds_collect_supported(env._handle, C.byref(fm_pi.m), int(mode)) == 1
+
+
+def collect_tiles(env):
+    """rows of the [tiles, 8] statistics slab of one fused_collect launch"""
+    return (int(env.num_envs) + 63) // 64
+
+
+def fused_collect(env, fm_pi, mode, K, act_limit, log_std, seed, first_call, oa, obs2, rew, done, ptr, obs, ep_ret, ep_len,
+                  tile_stats):
+    """ONE launch for K closed-loop vector steps of an off-policy trainer (include/pds.h pds_collect, csrc/pds_collect.h): step s
+    fills the N rows at (ptr + s N) mod capacity of the ring oa / obs2 / rew / done (capacity = oa.shape[0]), obs [N, D] is
+    o(0) on entry and o(K) on return, ep_ret / ep_len run on, tile_stats [collect_tiles(env), 8] receives the finished episodes'
+    statistics.  Raises NotImplementedError / ValueError where the entry point refuses (the env is left as it was)."""
+    fm_pi._bind()
+    with _on(obs):
+        rc = env.lib.pds_collect(env._handle, int(K), int(mode), C.byref(fm_pi.m), float(act_limit), _ptr(log_std),
+                                 int(seed) & (2 ** 64 - 1), int(first_call), _ptr(oa), _ptr(obs2), _ptr(rew), _ptr(done),
+                                 int(oa.shape[0]), int(ptr), _ptr(obs), _ptr(ep_ret), _ptr(ep_len), _ptr(tile_stats),
+                                 FusedMLP._stream(obs))
+    if rc != native.OK:
+        native.check(env._handle, rc, "pds_collect")
+    env._last_obs = obs  # (what a masked reset() copies for the envs outside the mask)
 
 
 def conjugate_gradients(avp, b, iters, residual_tol=1e-10, eps=1e-6):

@@ -42,7 +42,8 @@ EXPORTS = ["pds_version", "pds_default_config", "pds_create", "pds_destroy", "pd
            "pds_simopt_latency_steps", "pds_simopt_evaluate", "pds_evaluate_supported", "pds_evaluate_policies",
            "pds_es_workspace_floats", "pds_es_perturb", "pds_es_gradient",
            "pds_ddpg_supported", "pds_ddpg_workspace_floats", "pds_ddpg_policy_grad", "pds_ddpg_target", "pds_polyak",
-           "pds_sac_supported", "pds_sac_workspace_floats", "pds_sac_sample", "pds_sac_target", "pds_sac_policy_grad"]
+           "pds_sac_supported", "pds_sac_workspace_floats", "pds_sac_sample", "pds_sac_target", "pds_sac_policy_grad",
+           "pds_collect_supported", "pds_collect", "pds_ddpg_explore"]
 
 
 class Mlp(C.Structure):
@@ -185,6 +186,9 @@ def load():
     later("pds_sac_sample", [vp, i64, C.c_float, u64, u64, u64, i32, vp, vp, vp])
     later("pds_sac_target", [mp, mp, mp, vp, vp, i64, vp, vp, C.c_float, C.c_float, C.c_float, u64, u64, vp, vp])
     later("pds_sac_policy_grad", [mp, mp, mp, vp, vp, i64, C.c_float, C.c_float, u64, u64, vp, vp, vp, ap, vp])
+    later("pds_collect_supported", [vp, mp, i32])
+    later("pds_collect", [vp, i32, i32, mp, C.c_float, vp, u64, u64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp])
+    later("pds_ddpg_explore", [vp, vp, i64, C.c_float, u64, u64, u64, vp, vp])
     _lib = lib
     return lib
 

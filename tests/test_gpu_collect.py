@@ -1,0 +1,327 @@
+"""pds_collect (csrc/pds_collect.h): K closed-loop vector steps of an off-policy trainer in one launch, against the composed path
+made only of this library's entry points -- pds_mlp_forward, pds_ddpg_explore / pds_sac_sample, pds_step -- and the torch
+bookkeeping of OffPolicyTrainer.step_env / learn_one_epoch.  Everything the launch writes is compared on its bits."""
+import math
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+HOVER, CIRCLE, TAKEOFF = "DroneHoverSimpleEnv-v0", "DroneCircleSimpleEnv-v0", "DroneTakeOffSimpleEnv-v0"
+LEAN = dict(observation_noise=-1, domain_randomization=-1, motor_thrust_noise=0)
+LIMIT = 12  # max_episode_steps: every case sees the TimeLimit within its 16 steps
+CASES = {
+    "hover_lean": (HOVER, dict(LEAN)),
+    "hover_default": (HOVER, {}),
+    "circle_motor": (CIRCLE, dict(use_motor_dynamics=True)),
+    "takeoff": (TAKEOFF, {}),
+}
+DDPG, SAC = 0, 1
+H1, H2 = 32, 48
+NEUTRAL = [0.0, 0.0, 0.0, math.inf, -math.inf, 0.0, math.inf, -math.inf]
+
+
+def _make(case, N, seed=11, **extra):
+    import phoenix_drone_simulation_amd as pds
+    env_id, kw = CASES[case]
+    return pds.make(env_id, num_envs=N, device=DEV, seed=seed, max_episode_steps=LIMIT, **{**kw, **extra})
+
+
+def _actor(d_in, mode, seed=0, act="tanh"):
+    """a seeded random actor (nn.Linear's initialisation, 32 and 48 hidden units) with spread output biases (-0.15 .. 0.15: the
+    four motors are driven slightly apart), so that under the exploration noise (sigma 0.5-0.6) Hover envs tumble over the
+    300 deg/s bound from the first steps on while about a quarter of them reaches the TimeLimit of 12 -- the float32 CPU oracle
+    on 128 envs: 98 of 128 terminate within 12 steps, 2-16 per step.  With +-0.6 none survived 8 steps.
+    SAC: the log_std rows get a bias of -0.5 (sigma about 0.6)."""
+    from phoenix_drone_simulation_amd.fused import FusedMLP
+    from phoenix_drone_simulation_amd.ppo import _mlp
+    torch.manual_seed(1000 + seed)
+    d_out = 8 if mode == SAC else 4
+    net = _mlp([d_in, H1, H2, d_out], act).to(DEV)
+    with torch.no_grad():
+        net[4].bias[:4] += torch.tensor([-0.15, -0.05, 0.05, 0.15], device=DEV)
+        if mode == SAC:
+            net[4].bias[4:] -= 0.5
+    return FusedMLP(net, act)
+
+
+def _ring(N, D, blocks, fill=None):
+    from phoenix_drone_simulation_amd.ddpg import ReplayBuffer
+    buf = ReplayBuffer(blocks * N, D, DEV, num_envs=N)
+    if fill is not None:
+        for t in (buf.oa, buf.obs2, buf.rew, buf.done):
+            t.fill_(fill)
+    return buf
+
+
+LOG_STD = math.log(0.5)  # DDPG's exploration scale in these tests
+ACT_LIMIT = 1.0
+SEED = 0xC0FFEE
+
+
+def _composed(env, fm, mode, K, buf, first_call=1):
+    """K rounds of the per-step path.  -> (obs, ep_ret, ep_len, per-step [(finished, terminated, truncated, return, length)])"""
+    from phoenix_drone_simulation_amd.fused import ddpg_explore, sac_sample
+    N = env.num_envs
+    log_std = torch.full((4,), LOG_STD, device=DEV)
+    obs = env.reset()[0].clone()
+    ep_ret, ep_len = torch.zeros(N, device=DEV), torch.zeros(N, device=DEV)
+    steps = []
+    for s in range(K):
+        head = fm.forward(obs)
+        if mode == DDPG:
+            a = ddpg_explore(head, log_std, ACT_LIMIT, SEED, first_call + s)
+        else:
+            a = sac_sample(head, ACT_LIMIT, SEED, first_call + s, want_logp=False)[0]
+        o2, r, te, tr, info = env.step(a)
+        done = te | tr
+        nxt = torch.where(done.unsqueeze(-1), info["final_obs"], o2)
+        buf.store(obs, a, r, nxt, (te & ~tr).to(torch.float32))
+        ep_ret += r
+        ep_len += 1.0
+        steps.append((done.clone(), te.clone(), tr.clone(), ep_ret.clone(), ep_len.clone()))
+        ep_ret = torch.where(done, torch.zeros_like(ep_ret), ep_ret)
+        ep_len = torch.where(done, torch.zeros_like(ep_len), ep_len)
+        obs = o2.clone()
+    return obs, ep_ret, ep_len, steps
+
+
+def _fused(env, fm, mode, K, buf, first_call=1):
+    """one pds_collect.  -> (obs, ep_ret, ep_len, slab)"""
+    from phoenix_drone_simulation_amd.fused import collect_supported, collect_tiles, fused_collect
+    N = env.num_envs
+    assert collect_supported(env, fm, mode)
+    log_std = torch.full((4,), LOG_STD, device=DEV) if mode == DDPG else None
+    obs = env.reset()[0].clone()
+    ep_ret, ep_len = torch.zeros(N, device=DEV), torch.zeros(N, device=DEV)
+    slab = torch.full((collect_tiles(env), 8), float("nan"), device=DEV)
+    fused_collect(env, fm, mode, K, ACT_LIMIT, log_std, SEED, first_call, buf.oa, buf.obs2, buf.rew, buf.done, buf.ptr, obs,
+                  ep_ret, ep_len, slab)
+    buf.advance(K)
+    return obs, ep_ret, ep_len, slab
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
+
+
+def _same(a, b):
+    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
+
+
+def _assert_bitwise(env_f, env_c, buf_f, buf_c, out_f, out_c, what):
+    for name in ("oa", "obs2", "rew", "done"):
+        a, b = getattr(buf_f, name), getattr(buf_c, name)
+        assert _same(a, b), (what, name, int((_bits(a) != _bits(b)).sum()))
+    assert (buf_f.ptr, buf_f.size) == (buf_c.ptr, buf_c.size)
+    for name, a, b in zip(("obs", "ep_ret", "ep_len"), out_f, out_c):
+        assert _same(a, b), (what, name, int((_bits(a) != _bits(b)).sum()))
+    assert env_f.tick == env_c.tick and env_f.sync_tick() == env_c.sync_tick()
+    sf, sc = env_f.state_dict(), env_c.state_dict()
+    assert sf.keys() == sc.keys()
+    for f in sf:
+        if f == "tick":
+            assert sf[f] == sc[f]
+        else:
+            assert _same(sf[f], sc[f]), (what, f)
+
+
+def _run_pair(case, mode, N, K, blocks=None, ptr_block=0, fill=None):
+    env_f, env_c = _make(case, N), _make(case, N)
+    fm = _actor(env_f.obs_dim, mode)
+    blocks = blocks or K
+    buf_f, buf_c = _ring(N, env_f.obs_dim, blocks, fill), _ring(N, env_f.obs_dim, blocks, fill)
+    buf_f.ptr = buf_c.ptr = ptr_block * N
+    out_c = _composed(env_c, fm, mode, K, buf_c)
+    out_f = _fused(env_f, fm, mode, K, buf_f)
+    _assert_bitwise(env_f, env_c, buf_f, buf_c, out_f[:3], out_c[:3], (case, mode, N, K))
+    return env_f, env_c, buf_f, out_f, out_c
+
+
+def _counts(steps):
+    n_term = sum(int((te & ~tr).sum()) for _, te, tr, _, _ in steps)
+    n_trunc = sum(int(tr.sum()) for _, te, tr, _, _ in steps)
+    return n_term, n_trunc
+
+
+@pytest.mark.parametrize("K", [1, 3, 16])
+@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("mode", [DDPG, SAC], ids=["ddpg", "sac"])
+def test_one_launch_is_bitwise_the_composed_steps(mode, case, K):
+    """N = 128 (two tiles, one team each).  K = 16 crosses the TimeLimit of 12: the Hover cases hold terminated and truncated
+    transitions, TakeOff truncated ones only (Circle's envs leave their 0.25 m tube later than that: truncated ones at least);
+    `done` is 1 exactly at the terminated-and-not-truncated rows."""
+    N = 128
+    env_f, env_c, buf, out_f, out_c = _run_pair(case, mode, N, K)
+    steps = out_c[3]
+    n_term, n_trunc = _counts(steps)
+    print(f"{case} mode {mode} K {K}: {n_term} terminated, {n_trunc} truncated transitions")
+    want_done = torch.cat([(te & ~tr).to(torch.float32) for _, te, tr, _, _ in steps])
+    assert torch.equal(buf.done[:K * N], want_done) and int(buf.done.sum()) == n_term
+    if K == 16:
+        assert n_trunc >= 1
+        if case == "takeoff":
+            assert n_term == 0
+        elif case.startswith("hover"):
+            assert n_term >= 1
+    env_f.close(); env_c.close()
+
+
+@pytest.mark.parametrize("mode", [DDPG, SAC], ids=["ddpg", "sac"])
+def test_a_partial_last_tile(mode):
+    """N = 100: tile 1 holds 36 envs -- network wave 2 owns 4 rows, wave 3 none; 100 rows of 46 floats start 16-byte aligned,
+    the pieces of the partial tile take the scalar stores."""
+    env_f, env_c, *_ = _run_pair("hover_lean", mode, 100, 16)
+    env_f.close(); env_c.close()
+
+
+@pytest.mark.parametrize("mode", [DDPG, SAC], ids=["ddpg", "sac"])
+def test_the_ring_wraps_between_blocks(mode):
+    """capacity 4 N, ptr 3 N, K = 3: the blocks land at rows 3 N, 0, N; block 2 N keeps its sentinel."""
+    N, S = 128, -7.5
+    env_f, env_c, buf, out_f, out_c = _run_pair("hover_lean", mode, N, 3, blocks=4, ptr_block=3, fill=S)
+    assert buf.ptr == 2 * N and buf.size == 3 * N
+    for t in (buf.oa, buf.obs2, buf.rew, buf.done):
+        assert bool((t[2 * N:3 * N] == S).all())
+        assert not bool((t[3 * N:] == S).all()) and not bool((t[:2 * N] == S).all())
+    env_f.close(); env_c.close()
+
+
+@pytest.mark.parametrize("case", ["hover_lean", "hover_default"])
+def test_257_tiles_take_the_two_team_form(case):
+    """N = 257 x 64: above 256 tiles the launcher puts two teams into a block (where the two-team code object needs no more
+    scratch memory than the one-team one), and the last block is half filled."""
+    env_f, env_c, *_ = _run_pair(case, SAC, 257 * 64, 4)
+    env_f.close(); env_c.close()
+
+
+@pytest.mark.parametrize("mode", [DDPG, SAC], ids=["ddpg", "sac"])
+def test_tile_statistics_are_the_epoch_accumulators(mode):
+    """[tiles, 8] against the composed run's per-step data in float64: count, min / max of return and length and the length sum
+    exactly, return sum and sum of squares at rtol 1e-5 (a fixed-order float32 sum of at most a few hundred terms of like sign)."""
+    N, K = 128, 16
+    env_f, env_c, buf, out_f, out_c = _run_pair("hover_lean", mode, N, K)
+    slab, steps = out_f[3].double().cpu(), out_c[3]
+    assert slab.shape == (2, 8)
+    for tile in range(2):
+        rows = slice(64 * tile, 64 * (tile + 1))
+        rets = torch.cat([ret[rows][dn[rows]].double().cpu() for dn, _, _, ret, _ in steps])
+        lens = torch.cat([ln[rows][dn[rows]].double().cpu() for dn, _, _, _, ln in steps])
+        got = slab[tile]
+        print(f"tile {tile}: {rets.numel()} episodes, fused {got.tolist()}")
+        assert rets.numel() >= 1
+        assert got[0] == rets.numel() and got[3] == rets.min() and got[4] == rets.max()
+        assert got[5] == lens.sum() and got[6] == lens.min() and got[7] == lens.max()
+        assert abs(got[1] - rets.sum()) <= 1e-5 * abs(rets.sum())
+        assert abs(got[2] - (rets * rets).sum()) <= 1e-5 * (rets * rets).sum()
+    env_f.close(); env_c.close()
+
+
+def test_a_launch_without_a_finished_episode_leaves_the_neutral_values():
+    env_f, env_c, buf, out_f, out_c = _run_pair("takeoff", SAC, 128, 3)  # TakeOff only ends at the TimeLimit of 12
+    assert _counts(out_c[3]) == (0, 0)
+    assert torch.equal(out_f[3].cpu(), torch.tensor([NEUTRAL, NEUTRAL]))
+    env_f.close(); env_c.close()
+
+
+def test_ddpg_explore_against_float64():
+    """clamp(limit tanh(x) + exp(ls) z, +-limit) recomputed in float64 with z from pds_gaussian_sample on zeros: 1e-6 absolute at
+    act_limit = 1 (outputs in [-1, 1]: an f32 ulp is at most 6e-8 -- a few ulp of tanhf, one rounding each in the scale and the
+    fma)."""
+    from phoenix_drone_simulation_amd.fused import ddpg_explore, gaussian_sample
+    n = 4096 + 37
+    g = torch.Generator(device=DEV).manual_seed(5)
+    x = 3.0 * torch.randn(n, 4, device=DEV, generator=g)
+    ls = torch.tensor([math.log(0.1), math.log(0.5), 0.0, -20.0], device=DEV)
+    z, logp = torch.empty(n, 4, device=DEV), torch.empty(n, device=DEV)
+    gaussian_sample(torch.zeros(n, 4, device=DEV), torch.zeros(4, device=DEV), z, logp, SEED, 9, id_base=3)
+    got = ddpg_explore(x, ls, 1.0, SEED, 9, id_base=3)
+    want = torch.clamp(torch.tanh(x.double()) + torch.exp(ls.double()) * z.double(), -1.0, 1.0)
+    err = float((got.double() - want).abs().max())
+    print(f"pds_ddpg_explore against float64: largest absolute error {err:.3e}")
+    assert err <= 1e-6
+    assert float(got.abs().max()) <= 1.0 and bool((got.abs() == 1.0).any())  # the clamp binds somewhere
+    assert not torch.equal(got, ddpg_explore(x, ls, 1.0, SEED, 10, id_base=3))  # another call, another noise
+
+
+def _snapshot(env):
+    sd = env.state_dict()  # every get_state field + the tick
+    return {f: v.clone() for f, v in sd.items() if f not in ("tick", "observation_history")}, sd["tick"]
+
+
+def _unchanged(env, snap):
+    before, tick = snap
+    assert env.tick == tick and env.sync_tick() == tick
+    for f, v in before.items():
+        assert torch.equal(env.get_state(f), v), f
+
+
+def _call(env, fm, mode, K=2, ptr=0, blocks=4, rows=None, ran=False, **null):
+    """pds_collect with valid arguments except what the caller breaks (null: buffers passed as NULL); a refused call leaves
+    every buffer's sentinel in place"""
+    from phoenix_drone_simulation_amd.fused import collect_tiles, fused_collect
+    N, D = env.num_envs, env.obs_dim
+    rows = blocks * N if rows is None else rows
+    t = dict(oa=torch.full((rows, D + 4), 3.0, device=DEV), obs2=torch.full((rows, D), 3.0, device=DEV),
+             rew=torch.full((rows,), 3.0, device=DEV), done=torch.full((rows,), 3.0, device=DEV),
+             obs=torch.full((N, D), 3.0, device=DEV), ep_ret=torch.full((N,), 3.0, device=DEV),
+             ep_len=torch.full((N,), 3.0, device=DEV), tile_stats=torch.full((collect_tiles(env), 8), 3.0, device=DEV),
+             log_std=torch.full((4,), LOG_STD, device=DEV))
+    keep = {k: v.clone() for k, v in t.items()}
+    for k in null:
+        t[k] = None
+    try:
+        fused_collect(env, fm, mode, K, ACT_LIMIT, t["log_std"] if mode == DDPG else None, SEED, 1, t["oa"], t["obs2"], t["rew"],
+                      t["done"], ptr, t["obs"], t["ep_ret"], t["ep_len"], t["tile_stats"])
+    finally:
+        for k, v in t.items():
+            if v is not None:
+                assert ran or torch.equal(v, keep[k]), k
+
+
+@pytest.mark.parametrize("kw", [dict(use_latency=True), dict(control_mode="AttitudeRate"), dict(observation_history_size=4),
+                                dict(use_ground_effect=True), dict(auto_reset=False)],
+                         ids=["latency", "attitude_rate", "history4", "ground_effect", "no_auto_reset"])
+def test_unsupported_configurations_are_refused_and_the_env_steps_on(kw):
+    from phoenix_drone_simulation_amd.fused import collect_supported
+    env = _make("hover_default", 128, **kw)
+    env.reset()
+    snap = _snapshot(env)
+    for mode in (DDPG, SAC):
+        fm = _actor(env.obs_dim, mode, act="relu")
+        assert not collect_supported(env, fm, mode)
+        with pytest.raises(NotImplementedError):
+            _call(env, fm, mode)
+        _unchanged(env, snap)
+    env.step(torch.zeros(128, 4, device=DEV))
+    assert env.tick == snap[1] + 1
+    env.close()
+
+
+def test_invalid_calls_are_refused_and_the_env_steps_on():
+    from phoenix_drone_simulation_amd.fused import collect_supported
+    N = 128
+    env = _make("hover_default", N)
+    fm4, fm8 = _actor(env.obs_dim, DDPG), _actor(env.obs_dim, SAC)
+    with pytest.raises(ValueError):
+        _call(env, fm4, DDPG)  # before pds_reset
+    env.reset()
+    snap = _snapshot(env)
+    assert collect_supported(env, fm4, DDPG) and collect_supported(env, fm8, SAC)
+    assert not collect_supported(env, fm4, SAC) and not collect_supported(env, fm8, DDPG)
+    bad = [dict(K=0), dict(ptr=N + 1), dict(rows=N - 64), dict(ptr=4 * N), dict(tile_stats=None), dict(obs2=None), dict(log_std=None)]
+    for b in bad:
+        with pytest.raises(ValueError):
+            _call(env, fm4, DDPG, **b)
+        _unchanged(env, snap)
+    with pytest.raises(ValueError):
+        _call(env, fm4, SAC)  # a d_out = 4 actor in SAC mode
+    with pytest.raises(ValueError):
+        _call(env, fm8, DDPG)
+    _unchanged(env, snap)
+    env.step(torch.zeros(N, 4, device=DEV))
+    assert env.tick == snap[1] + 1
+    _call(env, fm8, SAC, ran=True)  # ... and a valid call goes through afterwards
+    assert env.tick == snap[1] + 3
+    env.close()
