@@ -8,6 +8,7 @@ evaluate_population (the evaluation loop of the reference's utils/evaluation.py,
 
   python examples/evaluate_policies.py runs/*/seed_*              # prints mean return, length and cost per checkpoint
   python examples/evaluate_policies.py runs/ --episodes 256 --env DroneCircleSimpleEnv-v0 --log-dir eval_out
+  python examples/evaluate_policies.py runs/ --metrics            # also the flight-quality table (evaluation.FlightMetrics.table)
 """
 import argparse
 import json
@@ -69,6 +70,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fused", default="auto", choices=["auto", "on", "off"])
     ap.add_argument("--log-dir", default=None, help="write returns.csv / costs.csv per checkpoint under <log-dir>/<group>/<p>/")
+    ap.add_argument("--metrics", action="store_true",
+                    help="also print flight time, mean squared roll / pitch, rate oscillation, action rate, saturation, maximum tilt")
     args = ap.parse_args()
     fused = {"auto": "auto", "on": True, "off": False}[args.fused]
 
@@ -87,13 +90,17 @@ def main():
             print(f"group {gi} {key}: the actors read {d_in} inputs, {env_id} observes {env.obs_dim}: skipped")
             env.close()
             continue
-        ret, length, cost = evaluate_population(env, pop, fused=fused,
-                                                log_dir=os.path.join(args.log_dir, str(gi)) if args.log_dir else None)
+        out = evaluate_population(env, pop, fused=fused, metrics=args.metrics,
+                                  log_dir=os.path.join(args.log_dir, str(gi)) if args.log_dir else None)
+        ret, length, cost = out[:3]
+        table = out[3].table() if args.metrics else {}
         env.close()
         print(f"group {gi}: {d_in} -> {hidden} -> 4, {act}; {pop.P} checkpoint(s)")
         for p, (run_dir, _) in enumerate(members):
             print(f"  {run_dir}: return {float(ret[p].mean()):9.3f} +- {float(ret[p].std()):7.3f}   "
                   f"length {float(length[p].mean()):6.1f}   cost {float(cost[p].mean()):7.2f}")
+            if table:
+                print("    " + "  ".join(f"{k} {float(v[p]):.4g}" for k, v in table.items()))
 
 
 if __name__ == "__main__":

@@ -7,6 +7,9 @@ csrc/pds_es.hip).  The reference has no such trainer: this stands where it sprea
 The checkpoint is PPOTrainer's (`torch_save/model.pt` + `model.json`): examples/evaluate_policies.py reads it.
 
     python examples/train_es.py --env DroneHoverSimpleEnv-v0 --population 4096 --episodes 64 --generations 5 --log-dir /tmp/es_run
+
+--penalise NAME=W (repeatable) trains on return - W x the raw flight metric NAME (es.penalised_return; the names are
+evaluation.METRIC_NAMES), e.g. --penalise action_rate_sq=0.5 against chattering motor commands.
 """
 import argparse
 import os
@@ -17,7 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import phoenix_drone_simulation_amd as pds  # noqa: E402
-from phoenix_drone_simulation_amd.es import ESTrainer  # noqa: E402
+from phoenix_drone_simulation_amd.es import ESTrainer, penalised_return  # noqa: E402
 
 
 def main():
@@ -31,10 +34,19 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log-dir", default=None)
     ap.add_argument("--eval-every", type=int, default=10, help="every that many generations the centre alone flies all envs")
+    ap.add_argument("--penalise", action="append", default=[], metavar="NAME=W",
+                    help="subtract W x the raw flight metric NAME from every episode's return (repeatable)")
     args = ap.parse_args()
+    weights = {}
+    for item in args.penalise:
+        name, sep, w = item.partition("=")
+        if not sep:
+            ap.error(f"--penalise {item!r}: NAME=W")
+        weights[name] = float(w)
+    fitness = penalised_return(weights) if weights else None  # (ValueError names the metrics there are)
     env = pds.make(args.env, num_envs=args.population * args.episodes, seed=args.seed)  # the reference's default config
     trainer = ESTrainer(env, args.population, sigma=args.sigma, lr=args.lr, seed=args.seed, obs_stats="warmup",
-                        eval_every=args.eval_every)
+                        eval_every=args.eval_every, fitness=fitness)
     t0 = time.time()
     steps = 0.0
     for g in range(args.generations):

@@ -423,6 +423,31 @@ int pds_evaluate_policies(pds_handle *h, int64_t P, int64_t episodes_per_policy,
                           const float *d_mean, const float *d_std, float eps, int max_steps, const float *d_obs0, float *d_ret,
                           float *d_len, float *d_cost, void *stream);
 
+/* The same launch, also reporting flight-quality metrics (csrc/pds_evaluate.h, METRICS): what the reference tabulates per real
+ * flight (experiments/02_zero_shot_policy_transfer_hover_task/02_eval_hover_task.py: mean squared roll and pitch, the oscillation
+ * of the rates and of the motor commands, the flight time) as raw sums over the states x(0) .. x(L - 1) the first episode's
+ * policy acted in -- x(0) the state pds_reset left, x(s) the TRUE state before step s (not the noisy observation), L the episode
+ * length; the sums freeze with d_len.  The state after the last step is not counted: the same step resets it away.
+ * a(s): the actor's raw output of step s; u: PDS_F_LAST_ACTION before the step (after a reset, the reset's own action).
+ * Every product and every sum is rounded on its own, steps in order: bitwise what separate elementwise float32 operations give. */
+#define PDS_EVAL_METRICS 8
+enum {
+  PDS_EM_ROLL_SQ = 0,              /* += roll * roll */
+  PDS_EM_PITCH_SQ = 1,             /* += pitch * pitch */
+  PDS_EM_RATE_SQ = 2,              /* += (wx * wx + wy * wy) + wz * wz */
+  PDS_EM_ACTION_RATE_SQ = 3,       /* d = a(s) - u; += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3 */
+  PDS_EM_TILT_MAX = 4,             /* max over the steps of |roll| and |pitch|, from 0; m = (v > m) ? v : m, so a NaN is passed over */
+  PDS_EM_SATURATED_STEPS = 5,      /* += 1 when any |a_j(s)| > 1: the steps whose action control_mode PWM clips */
+  PDS_EM_ROLL_RATE_CROSSINGS = 6,  /* += 1 for s >= 1 when (wx(s - 1) < 0) != (wx(s) < 0) */
+  PDS_EM_PITCH_RATE_CROSSINGS = 7  /* the same for wy */
+};
+/* pds_evaluate_policies with one more output: d_metrics [N, PDS_EVAL_METRICS], 16-byte aligned, row n = the PDS_EM_* values of
+ * env n.  Checks, support (pds_evaluate_supported), d_ret / d_len / d_cost (the same bits) and the state of the handle afterwards
+ * are pds_evaluate_policies'; in addition PDS_EINVAL for a NULL or misaligned d_metrics. */
+int pds_evaluate_policies_metrics(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                                  const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                                  const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics, void *stream);
+
 /* number of parameters; flat gradient layout = [W1, b1, W2, b2, W3, b3] (torch parameter order) */
 int pds_mlp_param_count(const pds_mlp *m);
 /* floats of scratch the *_grad entry points need (per-wave partial sums) */

@@ -17,7 +17,10 @@ _UNITS = ["pds_task_hover.hip", "pds_task_circle.hip", "pds_task_takeoff.hip", "
           "pds_mlp.hip", "pds_mlp_wide.hip", "pds_task_hover_hold.hip", "pds_task_circle_hold.hip", "pds_task_takeoff_hold.hip",
           "pds_task_hover_pid_ge.hip", "pds_task_circle_pid_ge.hip", "pds_rollout_hover_pwm.hip", "pds_rollout_circle_pwm.hip", "pds_rollout_hover_lat.hip", "pds_rollout_circle_lat.hip",
           "pds_evaluate_hover_pwm.hip", "pds_evaluate_circle_pwm.hip", "pds_evaluate_hover_lat.hip", "pds_evaluate_circle_lat.hip",
+          "pds_evaluate_metrics_hover_pwm.hip", "pds_evaluate_metrics_circle_pwm.hip", "pds_evaluate_metrics_hover_lat.hip",
+          "pds_evaluate_metrics_circle_lat.hip",
           "pds_evaluate_hover.hip", "pds_evaluate_circle.hip", "pds_evaluate_takeoff.hip",
+          "pds_evaluate_metrics_hover.hip", "pds_evaluate_metrics_circle.hip", "pds_evaluate_metrics_takeoff.hip",
           "pds_collect_hover.hip", "pds_collect_circle.hip", "pds_collect_takeoff.hip",
           "pds_api.hip", "pds_rollout_hover.hip", "pds_rollout_circle.hip", "pds_rollout_takeoff.hip",
           "pds_rollout_hist_hover.hip", "pds_rollout_hist_circle.hip", "pds_rollout_hist_takeoff.hip",

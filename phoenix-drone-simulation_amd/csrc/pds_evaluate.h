@@ -37,6 +37,23 @@
 // The cost of a step: StepOut carries reward and flags only, and step_once stores the cost through StepArgs::cost like every
 // per-step stream.  The env wave reads its own lane's word back from the sink row BEHIND its post (same lane, same address:
 // program order), so the round trip runs while the network waves compute, and adds it in front of the next step.
+//
+// METRICS (pds_evaluate_policies_metrics; translation units csrc/pds_evaluate_metrics_*.hip): the env wave also sums the eight
+// PDS_EM_* flight metrics (include/pds.h) over the states x(0) .. x(L - 1) its first episode's policy acted in -- the true roll,
+// pitch and body rates, the last action and the action handed over are in its registers anyway.  Every product and every sum is an
+// instruction of its own (__fmul_rn / __fadd_rn / __fsub_rn): the composed path does the same arithmetic with one torch op each.
+// Seven words per lane carry the eight values from step to step: five float sums, the saturated steps above the two sign bits of
+// the previous roll and pitch rate, and the two crossing counters as the halves of one word (an episode has at most 65 535 steps:
+// pds_create).  The counters are integers until the store: exact, like the float sum of ones they stand for.
+// WHERE the seven words live between two steps: in LDS (em_lds, 2 KB per team, touched by the env wave's own lanes only), read
+// and written back BEHIND the act_ready wait, around the update -- two ds_read_b128 and two ds_write_b128 a step.  Kept in
+// registers across step_once they took Hover at its defaults from 149 to 173 VGPRs and its two-team form over the 168-register
+// cap; from LDS the env wave carries nothing through the step (151).  The update is NOT in front of the wait, where the wave
+// idles: with the attitude and rate terms there the compiler gave the env wave 40-50 more VGPRs whichever way the sums were
+// kept (Hover at its defaults 201-215; 88 of the 102 two-team forms and ten one-team forms spilled) --
+// profiles/evaluate_metrics_kernel_resources.txt has both findings.
+// METRICS = false is the kernel as it was: every metrics statement is behind `if constexpr`, the LDS array belongs to a function
+// only the metrics form calls, the argument block is the EvalArgs it was.
 #pragma once
 #include "pds_evaluate_args.h"
 #include "pds_rollout.h"
@@ -57,9 +74,21 @@ PDS_DEV void eval_post(int *flag, int lane, int inc) {  // + inc, after every la
   if (lane == 0) __hip_atomic_fetch_add(flag, inc, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-template <class V_, int TEAMS>
-__global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(const EvalArgs ea) {
+PDS_DEV const EvalArgs &eval_head(const EvalArgs &ka) { return ka; }
+PDS_DEV const EvalArgs &eval_head(const EvalMetricsArgs &ka) { return ka.e; }
+
+// the metrics form's seven words per lane between two steps: [team][0][lane] = roll_sq, pitch_sq, rate_sq, action_rate_sq;
+// [team][1][lane] = tilt_max, saturated steps << 2 | sign bits, pitch crossings << 16 | roll crossings, unused
+template <int TEAMS>
+PDS_DEV float4 *em_lds() {
+  __shared__ float4 em[TEAMS * 2 * kWave];
+  return em;
+}
+
+template <class V_, int TEAMS, bool METRICS = false>
+__global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(const EvalKernelArgs<METRICS> ka) {
   using namespace pds_mlpf;
+  const EvalArgs &ea = eval_head(ka);
   using V = std::conditional_t<regen_obs_variant<V_>(), StoredOh<V_>, V_>;
   constexpr int D = V::D;
   constexpr int TS = tile_stride<D>();
@@ -133,6 +162,14 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
     bool c_counts = false;      // ... and whether it belongs to the first episode
     int qcount = 0;
     bool stopped = false;  // wave-uniform: this tile has posted its stop
+    // METRICS: zero sums; bit 0 / 1 of the second word: wx / wy of the previous state was negative (x(0) has no previous state:
+    // its own signs, no crossing)
+    float4 *em = nullptr;
+    if constexpr (METRICS) {
+      em = em_lds<TEAMS>() + team * 2 * kWave;
+      em[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+      em[kWave + lane] = make_float4(0.f, __int_as_float((S.e.wx < 0.f ? 1 : 0) | (S.e.wy < 0.f ? 2 : 0)), __int_as_float(0), 0.f);
+    }
     for (int s = 0; s < T; ++s) {
       const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<301, true>(ea.s, s));
       // A stopped tile falls through its remaining iterations (a scalar compare and a branch each) instead of leaving the loop:
@@ -153,6 +190,30 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
       long long o1 = 0;
       asm volatile("" : "+s"(o1));
       const float4 act = act_all[team][lane_s];
+      if constexpr (METRICS) {  // x(s), the state the policy acted in, and a(s), raw, against u(k - 1) = the last action before the step
+        const float4 sums = em[lane_s], rest = em[kWave + lane_s];
+        float m_roll = sums.x, m_pitch = sums.y, m_rate = sums.z, m_act = sums.w, m_tilt = rest.x;
+        int m_sat = __float_as_int(rest.y), m_cross = __float_as_int(rest.z);
+        const EnvRegs &e = S.e;
+        m_roll = __fadd_rn(m_roll, alive ? __fmul_rn(e.roll, e.roll) : 0.f);
+        m_pitch = __fadd_rn(m_pitch, alive ? __fmul_rn(e.pitch, e.pitch) : 0.f);
+        const float w2 = __fadd_rn(__fadd_rn(__fmul_rn(e.wx, e.wx), __fmul_rn(e.wy, e.wy)), __fmul_rn(e.wz, e.wz));
+        m_rate = __fadd_rn(m_rate, alive ? w2 : 0.f);
+        const float ar = fabsf(e.roll), ap = fabsf(e.pitch);  // (one compare each: a NaN angle is passed over, whichever it is)
+        m_tilt = (alive && ar > m_tilt) ? ar : m_tilt;
+        m_tilt = (alive && ap > m_tilt) ? ap : m_tilt;
+        const int neg = (e.wx < 0.f ? 1 : 0) | (e.wy < 0.f ? 2 : 0);
+        const int crossed = alive ? ((neg ^ m_sat) & 3) : 0;
+        m_cross += (crossed & 1) | ((crossed & 2) << 15);
+        m_sat = (m_sat & ~3) | neg;
+        const float d0 = __fsub_rn(act.x, S.h1.x), d1 = __fsub_rn(act.y, S.h1.y), d2 = __fsub_rn(act.z, S.h1.z), d3 = __fsub_rn(act.w, S.h1.w);
+        const float dd = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)), __fmul_rn(d3, d3));
+        m_act = __fadd_rn(m_act, alive ? dd : 0.f);
+        const bool sat = fabsf(act.x) > 1.f || fabsf(act.y) > 1.f || fabsf(act.z) > 1.f || fabsf(act.w) > 1.f;
+        m_sat += (alive && sat) ? 4 : 0;
+        em[lane_s] = make_float4(m_roll, m_pitch, m_rate, m_act);
+        em[kWave + lane_s] = make_float4(m_tilt, __int_as_float(m_sat), __int_as_float(m_cross), 0.f);
+      }
       StepOut so;
       step_once<V, kWave, RM, false>(el.s, o1, rks, parity, nullptr, tile, nullptr, queue_all[team], scratch_all[team], lane_s,
                                      wave_base, ix, active, act, S, qcount, nullptr, &so PDS_STAMP_ARG);
@@ -176,6 +237,13 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
     *at(el.ret, ix) = ep_ret;
     *at(el.len, ix) = ep_len;
     *at(el.cost, ix) = ep_cost;
+    if constexpr (METRICS) {  // row `env` of [N, 8] as two 16-byte pieces (every tile is full: env < N)
+      float4 *row = reinterpret_cast<float4 *>(reinterpret_cast<const EvalMetricsArgs *>(&el)->metrics) + 2 * (wave_base + lane);
+      const float4 rest = em[kWave + lane];
+      const int m_sat = __float_as_int(rest.y), m_cross = __float_as_int(rest.z);
+      row[0] = em[lane];
+      row[1] = make_float4(rest.x, (float)(m_sat >> 2), (float)(m_cross & 0xFFFF), (float)((unsigned)m_cross >> 16));
+    }
     return;
   }
 
@@ -201,12 +269,12 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
 // observation-noise variants need 190-250 there (profiles/evaluate_kernel_resources.txt).  The rule is read off the code objects
 // instead of being listed by hand: the two-team form is launched where it needs no more scratch memory per lane than the
 // one-team form.
-template <class RV_>
+template <class RV_, bool METRICS = false>
 inline bool eval_two_teams_fit() {
   static const bool fit = [] {
     hipFuncAttributes one, two;
-    if (hipFuncGetAttributes(&one, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 1>)) != hipSuccess ||
-        hipFuncGetAttributes(&two, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 2>)) != hipSuccess) {
+    if (hipFuncGetAttributes(&one, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 1, METRICS>)) != hipSuccess ||
+        hipFuncGetAttributes(&two, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 2, METRICS>)) != hipSuccess) {
       (void)hipGetLastError();
       return false;
     }
@@ -214,18 +282,21 @@ inline bool eval_two_teams_fit() {
   }();
   return fit;
 }
-struct EvalLaunch {
+template <bool METRICS>
+struct EvalLaunchT {
   dim3 grid;
   hipStream_t s;
-  const EvalArgs &ea;
+  const EvalKernelArgs<METRICS> &ea;
   template <class RV_>
   void run() const {
-    if (grid.x > (unsigned)kRolloutTwoTeamsAbove && eval_two_teams_fit<RV_>())
-      hipLaunchKernelGGL((evaluate_kernel<RV_, 2>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, ea);
+    if (grid.x > (unsigned)kRolloutTwoTeamsAbove && eval_two_teams_fit<RV_, METRICS>())
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 2, METRICS>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, ea);
     else
-      hipLaunchKernelGGL((evaluate_kernel<RV_, 1>), grid, dim3(kRolloutThreads), 0, s, ea);
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 1, METRICS>), grid, dim3(kRolloutThreads), 0, s, ea);
   }
 };
+using EvalLaunch = EvalLaunchT<false>;
+using EvalMetricsLaunch = EvalLaunchT<true>;  // the same rule on the metrics form's own two code objects
 
 // ---- flags -> variant, family by family: the variants launch_rollout_*_family (csrc/pds_rollout.h) instantiates, i.e. the
 // configurations rollout_supported() names.  `l.template run<Variant>()` launches. ----
@@ -259,7 +330,8 @@ inline bool eval_hold(const LaunchFlags &f, const L &l) {
   return true;
 }
 // The families are instantiated in translation units of their own (csrc/pds_evaluate_<task>[_pwm|_lat].hip);
-// launch_evaluate_<task> is the dispatcher in csrc/pds_evaluate_<task>.hip.
+// launch_evaluate_<task> is the dispatcher in csrc/pds_evaluate_<task>.hip.  The metrics form: the same families with an
+// EvalMetricsLaunch, in csrc/pds_evaluate_metrics_<task>[_pwm|_lat].hip.
 template <int TASK, class L>
 inline bool eval_pwm_family(const LaunchFlags &f, const L &l) {
   constexpr bool kMotor = TASK != PDS_TASK_TAKEOFF;  // (TakeOff + motor dynamics: only with the latency ring)

@@ -1,6 +1,8 @@
 // pds_evaluate_args.h -- launch interface of the fused policy evaluation (csrc/pds_evaluate.h; entry point pds_evaluate_policies
 // in csrc/pds_api.hip).
 #pragma once
+#include <type_traits>
+
 #include "pds_types.h"
 
 namespace pds {
@@ -23,6 +25,20 @@ struct EvalArgs {
 };
 static_assert(offsetof(EvalArgs, s) == 0, "reload_args() reads the head of the kernarg segment as a StepArgs");
 
+// Arguments of evaluate_kernel<V, TEAMS, true> (pds_evaluate_policies_metrics): the plain kernel's, and behind them the array of
+// the flight metrics.  The plain kernel's argument block stays the one it was.
+struct EvalMetricsArgs {
+  EvalArgs e;      // FIRST member (the kernel reads the head of its argument block as an EvalArgs, and that as a StepArgs)
+  float *metrics;  // [N, PDS_EVAL_METRICS] the PDS_EM_* sums of every env's first episode (include/pds.h), 16-byte aligned
+};
+static_assert(offsetof(EvalMetricsArgs, e) == 0, "the metrics kernel reads the head of its argument block as an EvalArgs");
+static_assert(PDS_EVAL_METRICS == 8, "a metrics row is stored as two float4");
+// the argument block of evaluate_kernel<V, TEAMS, METRICS> and the EvalArgs at its head
+template <bool METRICS>
+using EvalKernelArgs = std::conditional_t<METRICS, EvalMetricsArgs, EvalArgs>;
+inline EvalArgs &eval_args_head(EvalArgs &ka) { return ka; }
+inline EvalArgs &eval_args_head(EvalMetricsArgs &ka) { return ka.e; }
+
 bool launch_evaluate_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
 bool launch_evaluate_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
 bool launch_evaluate_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
@@ -31,5 +47,13 @@ bool launch_evaluate_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, c
 bool launch_evaluate_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
 bool launch_evaluate_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
 bool launch_evaluate_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
+// the same seven for the metrics form (csrc/pds_evaluate_metrics_<task>[_pwm|_lat].hip)
+bool launch_evaluate_metrics_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
+bool launch_evaluate_metrics_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
+bool launch_evaluate_metrics_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
+bool launch_evaluate_metrics_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
+bool launch_evaluate_metrics_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
+bool launch_evaluate_metrics_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
+bool launch_evaluate_metrics_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
 
 }  // namespace pds

@@ -18,7 +18,7 @@ import time
 import torch
 
 from . import native
-from .evaluation import PolicyPopulation, evaluate_population
+from .evaluation import METRIC_NAMES, PolicyPopulation, evaluate_population
 from .fused import FusedMLP, _on, _ptr, gaussian_sample
 from .ppo import ActorCritic
 
@@ -46,6 +46,25 @@ def pair_weights(u):
     return u[0::2] - u[1::2]
 
 
+def penalised_return(weights):
+    """A ready-made `fitness` for ESTrainer: the mean over the E episodes of return - sum_m weights[m] x raw_m, with raw_m the
+    raw per-episode sum of flight metric m (evaluation.METRIC_NAMES: "action_rate_sq", "rate_sq", ...).  The raw values are sums
+    over the steps of the episode, as the return is, so a weight is a penalty per step.  Unknown names raise ValueError."""
+    weights = {str(k): float(w) for k, w in dict(weights).items()}
+    unknown = sorted(set(weights) - set(METRIC_NAMES))
+    if unknown:
+        raise ValueError(f"unknown flight metrics {unknown}: one of {list(METRIC_NAMES)}")
+
+    def fitness(ret, length, cost, metrics):
+        score = ret.clone()
+        for name, w in weights.items():
+            score = score - w * metrics.raw[..., METRIC_NAMES.index(name)]
+        return score.mean(dim=1)
+
+    fitness.weights = weights
+    return fitness
+
+
 class ESTrainer:
     """OpenAI-ES on a DroneVecEnv of N = population x E envs (E a multiple of 64: evaluate_population's layout).
     The defaults are starting values, not tuned ones.
@@ -53,10 +72,12 @@ class ESTrainer:
     The centre is an ActorCritic (ppo.py) whose `pi.net` parameters are views into ONE flat float32 tensor `mu` in the layout
     of pds_mlp_param_count, so checkpoints are the reference's (`save_checkpoint`).  obs_stats: None (mean 0, std 1), a
     (mean, std) pair, or "warmup" (WARMUP_STEPS random-action steps through OnlineMeanStd); frozen afterwards -- the
-    statistics are not perturbed.  eval_every: every that many generations the centre alone flies all N envs."""
+    statistics are not perturbed.  eval_every: every that many generations the centre alone flies all N envs.
+    fitness: None (the mean return over the E episodes) or a callable fitness(ret, length, cost, metrics) -> [P] on the [P, E]
+    results and the FlightMetrics of evaluate_population(..., metrics=True), e.g. penalised_return({"action_rate_sq": 0.1})."""
 
     def __init__(self, env, population, hidden_sizes=(50, 50), activation="relu", sigma=0.02, lr=0.01, l2=0.005,
-                 betas=(0.9, 0.999), seed=0, obs_stats=None, fused=True, eval_every=10, adam_eps=1e-8):
+                 betas=(0.9, 0.999), seed=0, obs_stats=None, fused=True, eval_every=10, adam_eps=1e-8, fitness=None):
         P, N = int(population), int(env.num_envs)
         if P < 2 or P % 2 != 0:
             raise ValueError(f"population = {P}: antithetic pairs need an even number of policies")
@@ -68,6 +89,9 @@ class ESTrainer:
             raise ValueError(f"activation {activation!r}: relu or tanh")
         if not (math.isfinite(sigma) and sigma > 0):
             raise ValueError(f"sigma = {sigma}")
+        if fitness is not None and not callable(fitness):
+            raise ValueError("fitness: None or a callable fitness(ret, length, cost, metrics) -> [P]")
+        self.fitness = fitness
         self.env, self.P, self.H, self.E, self.N = env, P, P // 2, N // P, N
         self.hidden_sizes, self.activation = tuple(int(h) for h in hidden_sizes), activation
         self.sigma, self.lr, self.l2, self.betas, self.adam_eps = float(sigma), float(lr), float(l2), tuple(betas), float(adam_eps)
@@ -206,8 +230,12 @@ class ESTrainer:
         t0 = self._sync()
         pop = self.ask()
         t1 = self._sync()
-        ret, length, _ = evaluate_population(self.env, pop, fused="auto")
-        fitness = ret.mean(dim=1)
+        if self.fitness is None:
+            ret, length, _ = evaluate_population(self.env, pop, fused="auto")
+            fitness = ret.mean(dim=1)
+        else:
+            ret, length, cost, fm = evaluate_population(self.env, pop, fused="auto", metrics=True)
+            fitness = torch.as_tensor(self.fitness(ret, length, cost, fm), dtype=torch.float32).reshape(-1)
         t2 = self._sync()
         steps, centre = float(length.sum()), float("nan")
         if self.eval_every > 0 and self.generation % self.eval_every == 0:

@@ -8,10 +8,15 @@ episode: the accumulators of an env freeze at its first `terminated | truncated`
 after `max_episode_steps` steps at the latest (TimeLimit).
 
 `evaluate_population` scores a whole POPULATION of policies that way -- a checkpoint sweep, model selection during training,
-an evolution strategy over actor weights -- in one launch: P policies x E episodes (include/pds.h pds_evaluate_policies)."""
+an evolution strategy over actor weights -- in one launch: P policies x E episodes (include/pds.h pds_evaluate_policies).
+With `metrics=True` the same launch also reports the flight-quality sums the reference tabulates per real flight
+(experiments/02_zero_shot_policy_transfer_hover_task/02_eval_hover_task.py): `FlightMetrics`; `metrics_from_arrays` scores a
+logged flight by the same definitions."""
 import ctypes as C
+import math
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -230,10 +235,104 @@ def fused_evaluation_built(env):
     return getattr(env, "observation_history_size", 2) == 2 and bool(env.lib.pds_evaluate_supported(env._handle))
 
 
+# ---- flight-quality metrics (include/pds.h PDS_EM_*) -------------------------------------------------------------------
+METRIC_NAMES = ("roll_sq", "pitch_sq", "rate_sq", "action_rate_sq", "tilt_max", "saturated_steps", "roll_rate_crossings",
+                "pitch_rate_crossings")  # column j of `raw` = PDS_EM_* value j
+
+
+class FlightMetrics:
+    """The eight raw per-episode values of pds_evaluate_policies_metrics: `raw` [P, E, 8] float32 on the CPU (columns:
+    METRIC_NAMES; sums over the states x(0) .. x(L - 1) the policy acted in, x(s) the true state before step s), `length` [P, E]
+    the episode lengths L, `step_seconds` the simulated time of one env step (time_step x aggregate_phy_steps).  Every column
+    is also an attribute, a [P, E] view: `fm.roll_sq`, `fm.tilt_max`, ...  `table()` derives what 02_eval_hover_task.py prints."""
+
+    def __init__(self, raw, length, step_seconds):
+        self.raw = torch.as_tensor(raw, dtype=torch.float32)
+        self.length = torch.as_tensor(length, dtype=torch.float32)
+        self.step_seconds = float(step_seconds)
+        if self.raw.dim() != 3 or self.raw.shape[2] != len(METRIC_NAMES) or tuple(self.raw.shape[:2]) != tuple(self.length.shape):
+            raise ValueError(f"raw must be [P, E, {len(METRIC_NAMES)}] and length [P, E]")
+
+    def __getattr__(self, name):
+        if name in METRIC_NAMES:
+            return self.raw[..., METRIC_NAMES.index(name)]
+        raise AttributeError(name)
+
+    def per_episode(self):
+        """The derived quantities per episode, each [P, E] float64, in the units of 02_eval_hover_task.py: flight_time [s],
+        mse_roll_deg2 / mse_pitch_deg2 [deg^2] (the mean over the episode's steps), freq_roll_rate_hz / freq_pitch_rate_hz
+        (two sign changes of the rate are one oscillation), action_rate (mean squared change of the action per step),
+        saturated_share (of the steps), tilt_max_deg."""
+        raw, L = self.raw.double(), self.length.double()
+        deg2 = (180.0 / math.pi) ** 2
+        t = L * self.step_seconds
+        col = lambda name: raw[..., METRIC_NAMES.index(name)]
+        return dict(flight_time=t, mse_roll_deg2=col("roll_sq") / L * deg2, mse_pitch_deg2=col("pitch_sq") / L * deg2,
+                    freq_roll_rate_hz=col("roll_rate_crossings") / (2.0 * t), freq_pitch_rate_hz=col("pitch_rate_crossings") / (2.0 * t),
+                    action_rate=col("action_rate_sq") / L, saturated_share=col("saturated_steps") / L,
+                    tilt_max_deg=col("tilt_max") * (180.0 / math.pi))
+
+    def table(self):
+        """-> {name: [P] float64}: per policy the mean over its E episodes of every quantity of per_episode()."""
+        return {k: v.mean(dim=1) for k, v in self.per_episode().items()}
+
+
+def metrics_from_arrays(rpy, omega, actions, last_action0):
+    """The eight raw values (METRIC_NAMES order, float64 numpy) of ONE flight from its log: rpy [L, 3] and omega [L, 3] the
+    attitude [rad] and body rates at the L instants a command was issued, actions [L, 4] the commands in the policy's units (1 =
+    full scale), last_action0 [4] the command in force before the first.  Straight from the definitions (include/pds.h), so a real
+    flight and a simulated one are scored alike."""
+    rpy, omega = np.asarray(rpy, dtype=np.float64).reshape(-1, 3), np.asarray(omega, dtype=np.float64).reshape(-1, 3)
+    actions, u = np.asarray(actions, dtype=np.float64).reshape(-1, 4), np.asarray(last_action0, dtype=np.float64).reshape(4)
+    L = rpy.shape[0]
+    if L < 1 or omega.shape[0] != L or actions.shape[0] != L:
+        raise ValueError("rpy, omega and actions hold one row per step, at least one")
+    out = np.zeros(len(METRIC_NAMES))
+    out[0] = np.sum(rpy[:, 0] ** 2)
+    out[1] = np.sum(rpy[:, 1] ** 2)
+    out[2] = np.sum(omega ** 2)
+    before = np.vstack([u[None, :], actions[:-1]])  # the command in force when step s was issued
+    out[3] = np.sum((actions - before) ** 2)
+    for v in np.fmax(np.abs(rpy[:, 0]), np.abs(rpy[:, 1])):  # (fmax and `>`: a NaN angle is passed over)
+        if v > out[4]:
+            out[4] = v
+    out[5] = np.count_nonzero((np.abs(actions) > 1.0).any(axis=1))
+    for j, k in ((0, 6), (1, 7)):
+        neg = omega[:, j] < 0.0
+        out[k] = np.count_nonzero(neg[1:] != neg[:-1])
+    return out
+
+
+def _compose_metrics(acc, prev_neg, alive, rpy, omega, act, last):
+    """One step of the PDS_EM_* sums as separate elementwise float32 ops (what the kernel does with one instruction each), for the
+    envs still `alive`.  acc [8][N]; -> the signs of (wx, wy) for the next step."""
+    zero, one = torch.zeros_like(acc[0]), torch.ones_like(acc[0])
+    roll, pitch = rpy[:, 0], rpy[:, 1]
+    wx, wy, wz = omega[:, 0], omega[:, 1], omega[:, 2]
+    acc[0] += torch.where(alive, roll * roll, zero)
+    acc[1] += torch.where(alive, pitch * pitch, zero)
+    acc[2] += torch.where(alive, (wx * wx + wy * wy) + wz * wz, zero)
+    d = act - last
+    dd = d * d
+    acc[3] += torch.where(alive, ((dd[:, 0] + dd[:, 1]) + dd[:, 2]) + dd[:, 3], zero)
+    for v in (roll.abs(), pitch.abs()):
+        acc[4].copy_(torch.where(alive & (v > acc[4]), v, acc[4]))
+    acc[5] += torch.where(alive & (act.abs() > 1.0).any(dim=1), one, zero)
+    neg = omega[:, :2] < 0
+    if prev_neg is not None:
+        crossed = (neg != prev_neg) & alive.unsqueeze(1)
+        acc[6] += torch.where(crossed[:, 0], one, zero)
+        acc[7] += torch.where(crossed[:, 1], one, zero)
+    return neg
+
+
 @torch.no_grad()
-def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None):
+def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None, metrics=False):
     """-> (returns, ep_lengths, costs), each [P, E] float32 on the CPU: policy p of `population` flies the E = num_envs / P
     envs of block p, one episode per env, deterministically (action = actor mean), as `evaluate` does for one policy.
+    metrics=True: -> (returns, ep_lengths, costs, FlightMetrics) -- the first three are the same bits; the kernel path is
+    pds_evaluate_policies_metrics, the composed path reads rpy, omega and last_action in front of every step and sums with
+    separate torch ops: the same bits again.
 
     fused=True: one launch (pds_evaluate_policies, csrc/pds_evaluate.h); NotImplementedError where no kernel is built --
     observation_history_size != 2 included -- with the env untouched.  fused=False: the composed path, per step one
@@ -264,8 +363,17 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     dev, n, D = env.device, env.num_envs, env.obs_dim
     lib = env.lib
     ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
+    raw = None
     obs, _ = env.reset()
-    if use_kernel:
+    if use_kernel and metrics:
+        shape = population.mlp(0)
+        raw = torch.zeros(n, len(METRIC_NAMES), device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.pds_evaluate_policies_metrics(env._handle, P, E, C.byref(shape), _ptr(population.theta), _ptr(population.mean),
+                                                   _ptr(population.std), population.eps, T, _ptr(obs), _ptr(ret), _ptr(length),
+                                                   _ptr(cost), _ptr(raw), env._stream())
+        native.check(env._handle, rc, "pds_evaluate_policies_metrics")
+    elif use_kernel:
         shape = population.mlp(0)
         with torch.cuda.device(dev):
             rc = lib.pds_evaluate_policies(env._handle, P, E, C.byref(shape), _ptr(population.theta), _ptr(population.mean),
@@ -277,7 +385,11 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
         act = torch.empty(n, 4, device=dev)
         alive = torch.ones(n, dtype=torch.bool, device=dev)
         has = population.mean is not None
+        acc = [torch.zeros(n, device=dev) for _ in METRIC_NAMES] if metrics else None
+        prev_neg = None
         for _ in range(T):
+            if metrics:  # x(s): the state the policy acts in
+                rpy, omega, last = env.get_state("rpy"), env.get_state("omega"), env.get_state("last_action")
             stream = env._stream()
             with torch.cuda.device(dev):
                 for p in range(P):
@@ -287,12 +399,19 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
                                              _ptr(act, 16 * p * E), stream)
                     if rc != native.OK:
                         raise RuntimeError(f"pds_mlp_forward -> {rc}")
+            if metrics:
+                prev_neg = _compose_metrics(acc, prev_neg, alive, rpy, omega, act, last)
             obs, r, term, trunc, info = env.step(act)
             ret += torch.where(alive, r, torch.zeros_like(r))
             cost += torch.where(alive, info["cost"], torch.zeros_like(r))
             length += alive.float()
             alive &= ~(term | trunc)
+        if metrics:
+            raw = torch.stack(acc, dim=1)
     ret, length, cost = ret.cpu().reshape(P, E), length.cpu().reshape(P, E), cost.cpu().reshape(P, E)
+    fm = None
+    if metrics:
+        fm = FlightMetrics(raw.cpu().reshape(P, E, len(METRIC_NAMES)), length, float(env.cfg.time_step) * int(env.cfg.aggregate_phy_steps))
     if log_dir is not None:
         for p in range(P):
             d = os.path.join(log_dir, str(p))
@@ -301,4 +420,9 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
                 f.write("\n".join(str(float(x)) for x in ret[p]) + "\n")
             with open(os.path.join(d, "costs.csv"), "w") as f:
                 f.write("\n".join(str(float(x)) for x in cost[p]) + "\n")
-    return ret, length, cost
+            if metrics:  # one row per episode: the eight raw values and the length
+                with open(os.path.join(d, "metrics.csv"), "w") as f:
+                    f.write(",".join(METRIC_NAMES) + ",length\n")
+                    for e in range(E):
+                        f.write(",".join(repr(float(x)) for x in fm.raw[p, e]) + f",{float(length[p, e])!r}\n")
+    return (ret, length, cost, fm) if metrics else (ret, length, cost)
