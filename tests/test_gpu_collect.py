@@ -28,8 +28,8 @@ def _make(case, N, seed=11, **extra):
     return pds.make(env_id, num_envs=N, device=DEV, seed=seed, max_episode_steps=LIMIT, **{**kw, **extra})
 
 
-def _actor(d_in, mode, seed=0, act="tanh"):
-    """a seeded random actor (nn.Linear's initialisation, 32 and 48 hidden units) with spread output biases (-0.15 .. 0.15: the
+def _actor(d_in, mode, seed=0, act="tanh", hidden=(H1, H2)):
+    """a seeded random actor (nn.Linear's initialisation, 32 and 48 hidden units by default) with spread output biases (-0.15 .. 0.15: the
     four motors are driven slightly apart), so that under the exploration noise (sigma 0.5-0.6) Hover envs tumble over the
     300 deg/s bound from the first steps on while about a quarter of them reaches the TimeLimit of 12 -- the float32 CPU oracle
     on 128 envs: 98 of 128 terminate within 12 steps, 2-16 per step.  With +-0.6 none survived 8 steps.
@@ -38,7 +38,7 @@ def _actor(d_in, mode, seed=0, act="tanh"):
     from phoenix_drone_simulation_amd.ppo import _mlp
     torch.manual_seed(1000 + seed)
     d_out = 8 if mode == SAC else 4
-    net = _mlp([d_in, H1, H2, d_out], act).to(DEV)
+    net = _mlp([d_in, hidden[0], hidden[1], d_out], act).to(DEV)
     with torch.no_grad():
         net[4].bias[:4] += torch.tensor([-0.15, -0.05, 0.05, 0.15], device=DEV)
         if mode == SAC:
@@ -60,20 +60,25 @@ ACT_LIMIT = 1.0
 SEED = 0xC0FFEE
 
 
-def _composed(env, fm, mode, K, buf, first_call=1):
-    """K rounds of the per-step path.  -> (obs, ep_ret, ep_len, per-step [(finished, terminated, truncated, return, length)])"""
+def _composed(env, fm, mode, K, buf, first_call=1, log_std=None, act_limit=ACT_LIMIT, seed=SEED, state=None):
+    """K rounds of the per-step path.  -> (obs, ep_ret, ep_len, per-step [(finished, terminated, truncated, return, length)]).
+    log_std: DDPG's [4] tensor (default: LOG_STD four times); state: (obs, ep_ret, ep_len) of an earlier launch on this env to
+    go on from (default: a fresh reset and zeros)."""
     from phoenix_drone_simulation_amd.fused import ddpg_explore, sac_sample
     N = env.num_envs
-    log_std = torch.full((4,), LOG_STD, device=DEV)
-    obs = env.reset()[0].clone()
-    ep_ret, ep_len = torch.zeros(N, device=DEV), torch.zeros(N, device=DEV)
+    log_std = torch.full((4,), LOG_STD, device=DEV) if log_std is None else log_std
+    if state is None:
+        obs = env.reset()[0].clone()
+        ep_ret, ep_len = torch.zeros(N, device=DEV), torch.zeros(N, device=DEV)
+    else:
+        obs, ep_ret, ep_len = state
     steps = []
     for s in range(K):
         head = fm.forward(obs)
         if mode == DDPG:
-            a = ddpg_explore(head, log_std, ACT_LIMIT, SEED, first_call + s)
+            a = ddpg_explore(head, log_std, act_limit, seed, first_call + s)
         else:
-            a = sac_sample(head, ACT_LIMIT, SEED, first_call + s, want_logp=False)[0]
+            a = sac_sample(head, act_limit, seed, first_call + s, want_logp=False)[0]
         o2, r, te, tr, info = env.step(a)
         done = te | tr
         nxt = torch.where(done.unsqueeze(-1), info["final_obs"], o2)
@@ -87,16 +92,23 @@ def _composed(env, fm, mode, K, buf, first_call=1):
     return obs, ep_ret, ep_len, steps
 
 
-def _fused(env, fm, mode, K, buf, first_call=1):
-    """one pds_collect.  -> (obs, ep_ret, ep_len, slab)"""
+def _fused(env, fm, mode, K, buf, first_call=1, log_std=None, act_limit=ACT_LIMIT, seed=SEED, state=None):
+    """one pds_collect.  -> (obs, ep_ret, ep_len, slab).  log_std, state: as in _composed (the launch works on the state's three
+    tensors in place)"""
     from phoenix_drone_simulation_amd.fused import collect_supported, collect_tiles, fused_collect
     N = env.num_envs
     assert collect_supported(env, fm, mode)
-    log_std = torch.full((4,), LOG_STD, device=DEV) if mode == DDPG else None
-    obs = env.reset()[0].clone()
-    ep_ret, ep_len = torch.zeros(N, device=DEV), torch.zeros(N, device=DEV)
+    if mode == DDPG:
+        log_std = torch.full((4,), LOG_STD, device=DEV) if log_std is None else log_std
+    else:
+        log_std = None
+    if state is None:
+        obs = env.reset()[0].clone()
+        ep_ret, ep_len = torch.zeros(N, device=DEV), torch.zeros(N, device=DEV)
+    else:
+        obs, ep_ret, ep_len = state
     slab = torch.full((collect_tiles(env), 8), float("nan"), device=DEV)
-    fused_collect(env, fm, mode, K, ACT_LIMIT, log_std, SEED, first_call, buf.oa, buf.obs2, buf.rew, buf.done, buf.ptr, obs,
+    fused_collect(env, fm, mode, K, act_limit, log_std, seed, first_call, buf.oa, buf.obs2, buf.rew, buf.done, buf.ptr, obs,
                   ep_ret, ep_len, slab)
     buf.advance(K)
     return obs, ep_ret, ep_len, slab

@@ -1,6 +1,6 @@
 """Every env configuration the constructor accepts, over the axes a kernel variant is chosen by, and for each whether the
-one-launch kernels (pds_rollout, pds_evaluate_policies) are built for it.  TEST INFRASTRUCTURE, shared by
-tests/test_gpu_evaluate_variants.py and the rollout sweep of tests/test_trainer.py.
+one-launch kernels (pds_rollout, pds_evaluate_policies; pds_collect: collect_family) are built for it.  TEST INFRASTRUCTURE,
+shared by tests/test_gpu_evaluate_variants.py, tests/test_gpu_collect_variants.py and the rollout sweep of tests/test_trainer.py.
 
 The axes: task (Hover, Circle, TakeOff) x motor dynamics x domain randomisation x thrust noise x observation noise x ground
 effect x control mode (PWM, AttitudeRate, Attitude) x latency ring x Kalman hold (observation_frequency = 50 < sim_freq = 100; it
@@ -42,6 +42,23 @@ def family(task, motor, dr, tn, on, ge, ctrl, lat, hold):
     if ctrl != "PWM":
         return "pid" if (lean or full) and not takeoff else None
     return None if takeoff and motor else "pwm"
+
+
+COLLECT_COUNT = 10  # literal: Hover and Circle x {lean, full} x {with, without motor dynamics}, TakeOff x {lean, full}
+
+
+def collect_family(task, motor, dr, tn, on, ge, ctrl, lat, hold):
+    """"collect" where the fused off-policy collection (pds_collect) is built for this configuration, else None.  The rule as
+    the comment of csrc/pds_collect_args.h states it, written out here and NOT read from the library: control_mode PWM, no
+    latency ring, no Kalman hold, no ground effect; noise all off or the reference's default (DR + thrust noise + observation
+    noise); with and without motor dynamics, TakeOff without."""
+    if ctrl != "PWM" or lat or hold or ge:
+        return None
+    if not ((dr and tn and on) or not (dr or tn or on)):
+        return None
+    if task == "takeoff" and motor:
+        return None
+    return "collect"
 
 
 def kwargs_of(motor, dr, tn, on, ge, ctrl, lat, hold):
@@ -100,6 +117,20 @@ def variants():
 
 VARIANTS = variants()
 SUPPORTED = [v for v in VARIANTS if v[3] is not None]
+
+
+def collect_variants():
+    """[(id, env id, kwargs)] of the configurations collect_family accepts"""
+    out = []
+    bb = (False, True)
+    for (task, env_id), motor, dr, tn, on, ge, ctrl, lat, hold in itertools.product(TASKS, bb, bb, bb, bb, bb, CTRL, bb, bb):
+        f = (task, motor, dr, tn, on, ge, ctrl, lat, hold)
+        if accepted(*f) and collect_family(*f):
+            out.append((_name(*f), env_id, kwargs_of(*f[1:])))
+    return out
+
+
+COLLECT_SUPPORTED = collect_variants()
 assert len({v[0] for v in VARIANTS}) == len(VARIANTS)
 
 
