@@ -36,6 +36,11 @@ def main():
     ap.add_argument("--eval-every", type=int, default=10, help="every that many generations the centre alone flies all envs")
     ap.add_argument("--penalise", action="append", default=[], metavar="NAME=W",
                     help="subtract W x the raw flight metric NAME from every episode's return (repeatable)")
+    ap.add_argument("--obs-stats", choices=("none", "warmup", "online"), default="warmup",
+                    help="observation standardisation: none, frozen after a random-action warm-up, or kept running from what every "
+                         "generation's policies saw")
+    ap.add_argument("--shaping", choices=("ranks", "ars"), default="ranks", help="centred ranks, or the weights of Augmented Random Search")
+    ap.add_argument("--top-b", type=int, default=None, help="--shaping ars: the best that many pairs enter the update (default: all)")
     args = ap.parse_args()
     weights = {}
     for item in args.penalise:
@@ -45,8 +50,9 @@ def main():
         weights[name] = float(w)
     fitness = penalised_return(weights) if weights else None  # (ValueError names the metrics there are)
     env = pds.make(args.env, num_envs=args.population * args.episodes, seed=args.seed)  # the reference's default config
-    trainer = ESTrainer(env, args.population, sigma=args.sigma, lr=args.lr, seed=args.seed, obs_stats="warmup",
-                        eval_every=args.eval_every, fitness=fitness)
+    trainer = ESTrainer(env, args.population, sigma=args.sigma, lr=args.lr, seed=args.seed,
+                        obs_stats=None if args.obs_stats == "none" else args.obs_stats, eval_every=args.eval_every, fitness=fitness,
+                        shaping=args.shaping, top_b=args.top_b)
     t0 = time.time()
     steps = 0.0
     for g in range(args.generations):

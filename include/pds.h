@@ -448,6 +448,23 @@ int pds_evaluate_policies_metrics(pds_handle *h, int64_t P, int64_t episodes_per
                                   const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
                                   const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics, void *stream);
 
+/* pds_evaluate_policies_metrics with one more output: the sums a running observation standardisation is updated from
+ * (csrc/pds_evaluate.h, STATS), over every observation o(s) a first-episode policy acted on -- o(s) of env n for s < d_len[n], so
+ * their count per policy is the sum of its d_len.  Per feature k < D
+ *     d = o_k - d_mean[p][k]   (d = o_k when d_mean is NULL),   S1 += d,   S2 += d * d,
+ * every difference, product and sum rounded on its own in float32; the shift by the policy's own mean keeps S2 well conditioned.
+ * d_obs_sums [tiles, 4, 2, 64] float32, 16-byte aligned, tiles = N / 64 (tile t = envs 64 t .. 64 t + 63, of policy
+ * t / (episodes_per_policy / 64)): [t][w][0][k] = S1 and [t][w][1][k] = S2 of feature k over the envs 64 t + 16 w .. 64 t + 16 w + 15,
+ * zero for k >= D.  Per env the steps are added in order; the 16 envs of a part are then added as a fixed tree: env j + env j + 8,
+ * then j + (j + 4), then + 2, then + 1.  The four parts of a tile and the tiles of a policy are left to the caller (sum them in
+ * float64).  Every element is written.  Checks, support (pds_evaluate_supported), d_ret / d_len / d_cost / d_metrics (the same
+ * bits) and the state of the handle afterwards are pds_evaluate_policies_metrics'; in addition PDS_EINVAL for a NULL or
+ * misaligned d_obs_sums. */
+int pds_evaluate_policies_stats(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                                const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                                const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
+                                float *d_obs_sums, void *stream);
+
 /* number of parameters; flat gradient layout = [W1, b1, W2, b2, W3, b3] (torch parameter order) */
 int pds_mlp_param_count(const pds_mlp *m);
 /* floats of scratch the *_grad entry points need (per-wave partial sums) */

@@ -1117,17 +1117,20 @@ extern "C" int pds_evaluate_supported(const pds_handle *h) {
 }
 
 // P policies x E episodes in one launch: csrc/pds_evaluate.h (the caller's evaluation loop, utils/evaluation.py:52-107).
-// ONE body for pds_evaluate_policies and pds_evaluate_policies_metrics: the checks, the argument block and the handle's state
-// afterwards are stated once; METRICS adds the d_metrics check and selects the kernels' metrics form.
-template <bool METRICS>
+// ONE body for pds_evaluate_policies, pds_evaluate_policies_metrics and pds_evaluate_policies_stats: the checks, the argument
+// block and the handle's state afterwards are stated once; METRICS adds the d_metrics check and selects the kernels' metrics
+// form, STATS (with METRICS) the d_obs_sums check and the stats form.
+template <bool METRICS, bool STATS = false>
 static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
                                   const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
-                                  const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics, void *stream) {
+                                  const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics, float *d_obs_sums,
+                                  void *stream) {
   if (!h) return PDS_EINVAL;
   if (max_steps < 1) return fail(h, PDS_EINVAL, "%s: max_steps %d", fn, max_steps);
-  const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost || (METRICS && !d_metrics);
+  const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost || (METRICS && !d_metrics) || (STATS && !d_obs_sums);
   if (const int rc = check_rollout_call(h, fn, any_null, d_mean, d_std)) return rc;
   if (METRICS && (((uintptr_t)d_metrics) & 15u)) return fail(h, PDS_EINVAL, "%s: d_metrics must be 16-byte aligned", fn);
+  if (STATS && (((uintptr_t)d_obs_sums) & 15u)) return fail(h, PDS_EINVAL, "%s: d_obs_sums must be 16-byte aligned", fn);
   const long long n = h->cfg.num_envs;
   if (P < 1 || episodes_per_policy < 1 || episodes_per_policy > n || P > n || P * episodes_per_policy != n)
     return fail(h, PDS_EINVAL, "%s: P %lld x episodes_per_policy %lld is not the handle's %lld envs", fn, (long long)P,
@@ -1143,10 +1146,11 @@ static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int6
                                      "pds_mlp_forward + pds_step give the same bits", fn);
   DeviceGuard guard(h->cfg.device);
   PDS_HIP(h, guard.err);
-  EvalKernelArgs<METRICS> ka;
+  EvalKernelArgs<METRICS, STATS> ka;
   memset(&ka, 0, sizeof(ka));
   EvalArgs &ea = eval_args_head(ka);
-  if constexpr (METRICS) ka.metrics = d_metrics;
+  if constexpr (STATS) { ka.m.metrics = d_metrics; ka.obs_sums = d_obs_sums; }
+  else if constexpr (METRICS) ka.metrics = d_metrics;
   base_args(h, ea.s);
   if (const int rc = point_at_step_sink(h, fn, ea.s, stream)) return rc;
   ea.s.k_steps = max_steps;
@@ -1159,7 +1163,11 @@ static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int6
   ea.obs0 = d_obs0;
   ea.ret = d_ret; ea.len = d_len; ea.cost = d_cost;
   const int rc = launch_rollout(h, fn, max_steps, stream, [&](dim3 grid, hipStream_t s) {
-    if constexpr (METRICS) {
+    if constexpr (STATS) {
+      if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_stats_hover(h->flags, grid, s, ka);
+      if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_stats_circle(h->flags, grid, s, ka);
+      return launch_evaluate_stats_takeoff(h->flags, grid, s, ka);
+    } else if constexpr (METRICS) {
       if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_metrics_hover(h->flags, grid, s, ka);
       if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_metrics_circle(h->flags, grid, s, ka);
       return launch_evaluate_metrics_takeoff(h->flags, grid, s, ka);
@@ -1177,7 +1185,7 @@ extern "C" int pds_evaluate_policies(pds_handle *h, int64_t P, int64_t episodes_
                                      const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
                                      const float *d_obs0, float *d_ret, float *d_len, float *d_cost, void *stream) {
   return evaluate_policies_call<false>(h, "pds_evaluate_policies", P, episodes_per_policy, shape, d_params, d_mean, d_std, eps,
-                                       max_steps, d_obs0, d_ret, d_len, d_cost, nullptr, stream);
+                                       max_steps, d_obs0, d_ret, d_len, d_cost, nullptr, nullptr, stream);
 }
 // the same launch with the PDS_EM_* flight metrics of every first episode in d_metrics [N, PDS_EVAL_METRICS]
 extern "C" int pds_evaluate_policies_metrics(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
@@ -1185,7 +1193,15 @@ extern "C" int pds_evaluate_policies_metrics(pds_handle *h, int64_t P, int64_t e
                                              int max_steps, const float *d_obs0, float *d_ret, float *d_len, float *d_cost,
                                              float *d_metrics, void *stream) {
   return evaluate_policies_call<true>(h, "pds_evaluate_policies_metrics", P, episodes_per_policy, shape, d_params, d_mean, d_std,
-                                      eps, max_steps, d_obs0, d_ret, d_len, d_cost, d_metrics, stream);
+                                      eps, max_steps, d_obs0, d_ret, d_len, d_cost, d_metrics, nullptr, stream);
+}
+// the metrics launch with the per-wave observation sums of every tile in d_obs_sums [tiles, 4, 2, 64] (include/pds.h)
+extern "C" int pds_evaluate_policies_stats(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                                           const float *d_params, const float *d_mean, const float *d_std, float eps,
+                                           int max_steps, const float *d_obs0, float *d_ret, float *d_len, float *d_cost,
+                                           float *d_metrics, float *d_obs_sums, void *stream) {
+  return evaluate_policies_call<true, true>(h, "pds_evaluate_policies_stats", P, episodes_per_policy, shape, d_params, d_mean,
+                                            d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost, d_metrics, d_obs_sums, stream);
 }
 
 // ---- the fused off-policy collection: csrc/pds_collect.h (OffPolicyTrainer.step_env + the bookkeeping of learn_one_epoch) ----

@@ -33,6 +33,7 @@
 //   leaves while the other flies on (there is no block barrier behind the prologue).
 //   LDS images: the tile is written by the env wave between its act_ready wait and its obs_ready post, and read by the network
 //   waves between their obs_ready wait and their act_ready post; the action slots the other way round.
+//   (STATS, below: the alive mask of a step is written and read in the tile's windows, by the tile's writer and readers.)
 //
 // The cost of a step: StepOut carries reward and flags only, and step_once stores the cost through StepArgs::cost like every
 // per-step stream.  The env wave reads its own lane's word back from the sink row BEHIND its post (same lane, same address:
@@ -54,6 +55,23 @@
 // profiles/evaluate_metrics_kernel_resources.txt has both findings.
 // METRICS = false is the kernel as it was: every metrics statement is behind `if constexpr`, the LDS array belongs to a function
 // only the metrics form calls, the argument block is the EvalArgs it was.
+//
+// STATS (pds_evaluate_policies_stats; translation units csrc/pds_evaluate_stats_*.hip; built with METRICS only): the NETWORK waves
+// also sum, per feature k < D, d = o_k(s) - mean[p][k] (d = o_k without statistics: mus is 0 there and x - 0 = x on the bits) and
+// d * d over every observation o(s) a first-episode policy acted on -- row r of the tile at step s where env r was `alive` in
+// front of step s, the predicate of ep_len.  gather_input gives lane (n16, g) of wave w the features 16 kt + 4 g + q of row
+// 16 w + n16: every (row, feature) has one owner lane, which carries S1 and S2 of its 4 NIN features in registers through the
+// loop, steps in order, one rounded instruction per difference, product and sum (the composed path: one torch op each).
+//   The alive mask: one 64-bit word per team in LDS (es_lds), bit r = env r is in its first episode.  The mask of step 0, all
+//   ones, is written in the prologue in front of the block barrier.  The env wave writes the mask of step s + 1 in the tile's
+//   window -- between its act_ready wait of step s and its obs_ready post -- and the network waves read it in the tile's window:
+//   between their obs_ready wait and their act_ready post.  It adds no counter and no wait: the hand-over above is the mask's.
+//   A wave that leaves its loop (the stop it saw in obs_ready, whichever step that was) sums its 16 rows per feature in a fixed
+//   tree -- rows j and j + 8, then j and j + 4, then + 2, then + 1: cross-lane moves and __fadd_rn, no atomics -- and stores its
+//   partial to obs_sums[tile][wave][S1 / S2][64] with 16-byte stores, features >= D zero.  The four waves of a tile are summed by
+//   the host: on the device that would take a hand-over.
+// STATS = false is the kernel as it was: every stats statement is behind `if constexpr`, the mask belongs to a function only the
+// stats form calls, the argument blocks are the ones they were.
 #pragma once
 #include "pds_evaluate_args.h"
 #include "pds_rollout.h"
@@ -76,6 +94,7 @@ PDS_DEV void eval_post(int *flag, int lane, int inc) {  // + inc, after every la
 
 PDS_DEV const EvalArgs &eval_head(const EvalArgs &ka) { return ka; }
 PDS_DEV const EvalArgs &eval_head(const EvalMetricsArgs &ka) { return ka.e; }
+PDS_DEV const EvalArgs &eval_head(const EvalStatsArgs &ka) { return ka.m.e; }
 
 // the metrics form's seven words per lane between two steps: [team][0][lane] = roll_sq, pitch_sq, rate_sq, action_rate_sq;
 // [team][1][lane] = tilt_max, saturated steps << 2 | sign bits, pitch crossings << 16 | roll crossings, unused
@@ -85,9 +104,26 @@ PDS_DEV float4 *em_lds() {
   return em;
 }
 
-template <class V_, int TEAMS, bool METRICS = false>
-__global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(const EvalKernelArgs<METRICS> ka) {
+// the stats form's alive mask per team: bit r = env r of the tile is in its first episode (windows: the head of this file)
+template <int TEAMS>
+PDS_DEV unsigned long long *es_lds() {
+  __shared__ unsigned long long alive_mask[TEAMS];
+  return alive_mask;
+}
+// a network lane's accumulators of the stats form: S1 and S2 of its 4 NIN features; the other forms carry none
+template <int NIN, bool STATS>
+struct EsSums {
+  float s1[NIN][4], s2[NIN][4];
+};
+template <int NIN>
+struct EsSums<NIN, false> {};
+// v + (v of the lane whose row differs in bit `bit`): one level of the stats form's row tree (the sum is the same in both lanes)
+PDS_DEV float es_tree_add(float v, int bit) { return __fadd_rn(v, __shfl_xor(v, bit)); }
+
+template <class V_, int TEAMS, bool METRICS = false, bool STATS = false>
+__global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(const EvalKernelArgs<METRICS, STATS> ka) {
   using namespace pds_mlpf;
+  static_assert(METRICS || !STATS, "the stats form is built with the metrics");
   const EvalArgs &ea = eval_head(ka);
   using V = std::conditional_t<regen_obs_variant<V_>(), StoredOh<V_>, V_>;
   constexpr int D = V::D;
@@ -144,6 +180,9 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
     }
   }
   if (tid < TEAMS) { obs_ready[tid] = 0; act_ready[tid] = 0; }
+  if constexpr (STATS) {
+    if (tid < TEAMS) es_lds<TEAMS>()[tid] = ~0ull;  // the mask of step 0
+  }
   __syncthreads();  // (the only block barrier: from here on the roles meet through the counters)
   if (t >= ntiles) return;
 
@@ -223,7 +262,11 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
       ep_len += alive ? 1.f : 0.f;
       c_counts = alive;
       alive = alive && !(so.done || so.trunc);
-      const bool more = __ballot(alive) != 0ull && s + 1 < T;  // wave-uniform
+      const unsigned long long still = __ballot(alive);
+      const bool more = still != 0ull && s + 1 < T;  // wave-uniform
+      if constexpr (STATS) {
+        if (lane == 0) es_lds<TEAMS>()[team] = still;  // the mask of step s + 1, in front of the post
+      }
       eval_post(&obs_ready[team], lane, more ? 1 : kEvalStop);  // o(s + 1) is in the tile / this team's env wave has left
       c_step = *at(el.s.cost, ix);  // (behind the post: see the head of this file)
       stopped = !more;
@@ -249,6 +292,14 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
 
   // ================================ network waves: 16 rows of the tile each ====================================
   const int own = wave * 16 + n16;  // this lane's sample row
+  EsSums<NIN, STATS> es;  // STATS: the sums of this lane's 4 NIN features of row `own` (nothing otherwise)
+  if constexpr (STATS) {
+#pragma unroll
+    for (int kt = 0; kt < NIN; ++kt) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { es.s1[kt][q] = 0.f; es.s2[kt][q] = 0.f; }
+    }
+  }
   for (int s = 0;; ++s) {
     const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<303, true>(ea.s, s));
     if (eval_wait_ge(&obs_ready[team], s) >= kEvalStop) break;  // o(s) is in the tile, or the env wave has left
@@ -257,9 +308,45 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
 #endif
     f32x4 x_own[NIN];
     gather_input<NIN>(tile, TS, own, D, mus, iss, g, x_own);
+    if constexpr (STATS) {  // o(s) of row `own`, where its env was alive in front of step s
+      const bool al = ((es_lds<TEAMS>()[team] >> own) & 1ull) != 0ull;
+#pragma unroll
+      for (int kt = 0; kt < NIN; ++kt) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int k = kt * 16 + 4 * g + q;  // (gather_input's feature; k >= D: d = 0)
+          const float m = mus[k];
+          const float d = __fsub_rn((k < D) ? tile[own * TS + k] : m, m);
+          es.s1[kt][q] = __fadd_rn(es.s1[kt][q], al ? d : 0.f);
+          es.s2[kt][q] = __fadd_rn(es.s2[kt][q], al ? __fmul_rn(d, d) : 0.f);
+        }
+      }
+    }
     const f32x4 mu = (el.shape.activation == 0) ? forward16_shape<0, NIN>(w, el.shape, x_own, n16, g) : forward16_shape<1, NIN>(w, el.shape, x_own, n16, g);
     if (g == 0) act_all[team][own] = make_float4(mu[0], mu[1], mu[2], mu[3]);  // lane n16 owns sample `own`: the actor's four outputs
     rollout_post(&act_ready[team], lane);  // this wave is done with the tile of step s
+  }
+  if constexpr (STATS) {  // this wave's 16 rows per feature, then [t][wave][S1 / S2][64]: lane (0, g) stores the features 16 kt + 4 g ..
+    float4 *out = reinterpret_cast<float4 *>(ka.obs_sums) + (t * kRolloutMlpWaves + wave) * (2 * 16);
+#pragma unroll
+    for (int kt = 0; kt < NIN; ++kt) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int bit = 8; bit >= 1; bit >>= 1) {  // rows j and j + 8, then + 4, + 2, + 1
+          es.s1[kt][q] = es_tree_add(es.s1[kt][q], bit);
+          es.s2[kt][q] = es_tree_add(es.s2[kt][q], bit);
+        }
+      }
+      if (n16 == 0) {
+        out[kt * 4 + g] = make_float4(es.s1[kt][0], es.s1[kt][1], es.s1[kt][2], es.s1[kt][3]);
+        out[16 + kt * 4 + g] = make_float4(es.s2[kt][0], es.s2[kt][1], es.s2[kt][2], es.s2[kt][3]);
+      }
+    }
+#pragma unroll
+    for (int kt = NIN; kt < 4; ++kt) {  // features >= 16 NIN (those in D .. 16 NIN - 1 summed d = 0)
+      if (n16 == 0) { out[kt * 4 + g] = make_float4(0.f, 0.f, 0.f, 0.f); out[16 + kt * 4 + g] = make_float4(0.f, 0.f, 0.f, 0.f); }
+    }
   }
 }
 
@@ -269,12 +356,12 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
 // observation-noise variants need 190-250 there (profiles/evaluate_kernel_resources.txt).  The rule is read off the code objects
 // instead of being listed by hand: the two-team form is launched where it needs no more scratch memory per lane than the
 // one-team form.
-template <class RV_, bool METRICS = false>
+template <class RV_, bool METRICS = false, bool STATS = false>
 inline bool eval_two_teams_fit() {
   static const bool fit = [] {
     hipFuncAttributes one, two;
-    if (hipFuncGetAttributes(&one, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 1, METRICS>)) != hipSuccess ||
-        hipFuncGetAttributes(&two, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 2, METRICS>)) != hipSuccess) {
+    if (hipFuncGetAttributes(&one, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 1, METRICS, STATS>)) != hipSuccess ||
+        hipFuncGetAttributes(&two, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 2, METRICS, STATS>)) != hipSuccess) {
       (void)hipGetLastError();
       return false;
     }
@@ -282,21 +369,22 @@ inline bool eval_two_teams_fit() {
   }();
   return fit;
 }
-template <bool METRICS>
+template <bool METRICS, bool STATS = false>
 struct EvalLaunchT {
   dim3 grid;
   hipStream_t s;
-  const EvalKernelArgs<METRICS> &ea;
+  const EvalKernelArgs<METRICS, STATS> &ea;
   template <class RV_>
   void run() const {
-    if (grid.x > (unsigned)kRolloutTwoTeamsAbove && eval_two_teams_fit<RV_, METRICS>())
-      hipLaunchKernelGGL((evaluate_kernel<RV_, 2, METRICS>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, ea);
+    if (grid.x > (unsigned)kRolloutTwoTeamsAbove && eval_two_teams_fit<RV_, METRICS, STATS>())
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 2, METRICS, STATS>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, ea);
     else
-      hipLaunchKernelGGL((evaluate_kernel<RV_, 1, METRICS>), grid, dim3(kRolloutThreads), 0, s, ea);
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 1, METRICS, STATS>), grid, dim3(kRolloutThreads), 0, s, ea);
   }
 };
 using EvalLaunch = EvalLaunchT<false>;
 using EvalMetricsLaunch = EvalLaunchT<true>;  // the same rule on the metrics form's own two code objects
+using EvalStatsLaunch = EvalLaunchT<true, true>;  // and on the stats form's
 
 // ---- flags -> variant, family by family: the variants launch_rollout_*_family (csrc/pds_rollout.h) instantiates, i.e. the
 // configurations rollout_supported() names.  `l.template run<Variant>()` launches. ----
@@ -331,7 +419,8 @@ inline bool eval_hold(const LaunchFlags &f, const L &l) {
 }
 // The families are instantiated in translation units of their own (csrc/pds_evaluate_<task>[_pwm|_lat].hip);
 // launch_evaluate_<task> is the dispatcher in csrc/pds_evaluate_<task>.hip.  The metrics form: the same families with an
-// EvalMetricsLaunch, in csrc/pds_evaluate_metrics_<task>[_pwm|_lat].hip.
+// EvalMetricsLaunch, in csrc/pds_evaluate_metrics_<task>[_pwm|_lat].hip; the stats form: with an EvalStatsLaunch, in
+// csrc/pds_evaluate_stats_<task>[_pwm|_lat].hip.
 template <int TASK, class L>
 inline bool eval_pwm_family(const LaunchFlags &f, const L &l) {
   constexpr bool kMotor = TASK != PDS_TASK_TAKEOFF;  // (TakeOff + motor dynamics: only with the latency ring)

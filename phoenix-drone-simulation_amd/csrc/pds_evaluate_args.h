@@ -33,11 +33,19 @@ struct EvalMetricsArgs {
 };
 static_assert(offsetof(EvalMetricsArgs, e) == 0, "the metrics kernel reads the head of its argument block as an EvalArgs");
 static_assert(PDS_EVAL_METRICS == 8, "a metrics row is stored as two float4");
-// the argument block of evaluate_kernel<V, TEAMS, METRICS> and the EvalArgs at its head
-template <bool METRICS>
-using EvalKernelArgs = std::conditional_t<METRICS, EvalMetricsArgs, EvalArgs>;
+// Arguments of evaluate_kernel<V, TEAMS, true, true> (pds_evaluate_policies_stats): the metrics kernel's, and behind them the slab
+// of the observation sums.  The argument blocks of the other two forms stay the ones they were.
+struct EvalStatsArgs {
+  EvalMetricsArgs m;  // FIRST member (the kernel reads the head of its argument block as an EvalMetricsArgs)
+  float *obs_sums;    // [tiles, 4, 2, 64]: tile, network wave, S1 / S2, feature (include/pds.h), 16-byte aligned
+};
+static_assert(offsetof(EvalStatsArgs, m) == 0, "the stats kernel reads the head of its argument block as an EvalMetricsArgs");
+// the argument block of evaluate_kernel<V, TEAMS, METRICS, STATS> and the EvalArgs at its head
+template <bool METRICS, bool STATS = false>
+using EvalKernelArgs = std::conditional_t<STATS, EvalStatsArgs, std::conditional_t<METRICS, EvalMetricsArgs, EvalArgs>>;
 inline EvalArgs &eval_args_head(EvalArgs &ka) { return ka; }
 inline EvalArgs &eval_args_head(EvalMetricsArgs &ka) { return ka.e; }
+inline EvalArgs &eval_args_head(EvalStatsArgs &ka) { return ka.m.e; }
 
 bool launch_evaluate_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
 bool launch_evaluate_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
@@ -55,5 +63,13 @@ bool launch_evaluate_metrics_hover_pwm(const LaunchFlags &f, dim3 grid, hipStrea
 bool launch_evaluate_metrics_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
 bool launch_evaluate_metrics_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
 bool launch_evaluate_metrics_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
+// and for the stats form (csrc/pds_evaluate_stats_<task>[_pwm|_lat].hip)
+bool launch_evaluate_stats_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
+bool launch_evaluate_stats_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
+bool launch_evaluate_stats_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
+bool launch_evaluate_stats_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
+bool launch_evaluate_stats_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
+bool launch_evaluate_stats_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
+bool launch_evaluate_stats_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
 
 }  // namespace pds

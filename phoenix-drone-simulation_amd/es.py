@@ -46,6 +46,35 @@ def pair_weights(u):
     return u[0::2] - u[1::2]
 
 
+def ars_pair_weights(fitness, top_b):
+    """The pair weights of Augmented Random Search (Mania et al. 2018, "Simple random search provides a competitive approach to
+    reinforcement learning", algorithm 2, V1-t / V2-t): fitness [2 H], rows 2 i / 2 i + 1 the returns r+ / r- of pair i.  The
+    pairs are ranked by max(r+, r-) (stable: ties go to the lower index); the best `top_b` get (r+ - r-) / sigma_R, sigma_R the
+    standard deviation (as numpy.std: divisor 2 top_b) of their 2 top_b returns; every other pair 0.  A pair with a non-finite
+    return gets 0 and takes no place among the top_b.  sigma_R = 0 (all 2 top_b returns equal: every difference is 0): zeros.
+    -> float32 [H] on fitness's device."""
+    f = torch.as_tensor(fitness, dtype=torch.float32).reshape(-1)
+    if f.numel() < 2 or f.numel() % 2 != 0:
+        raise ValueError(f"fitness must hold the returns of whole pairs, got {f.numel()} values")
+    H, b = f.numel() // 2, int(top_b)
+    if b < 1 or b > H:
+        raise ValueError(f"top_b = {top_b}: between 1 and the number of pairs {H}")
+    plus, minus = f[0::2], f[1::2]
+    ok = torch.isfinite(plus) & torch.isfinite(minus)
+    score = torch.where(ok, torch.maximum(plus, minus), torch.full_like(plus, -math.inf))
+    order = torch.argsort(score, descending=True, stable=True)
+    chosen = order[:b]
+    chosen = chosen[ok[chosen]]
+    w = torch.zeros(H, dtype=torch.float32, device=f.device)
+    if chosen.numel() == 0:
+        return w
+    sigma_r = torch.cat([plus[chosen], minus[chosen]]).std(unbiased=False)
+    if not bool(sigma_r > 0):
+        return w
+    w[chosen] = (plus[chosen] - minus[chosen]) / sigma_r
+    return w
+
+
 def penalised_return(weights):
     """A ready-made `fitness` for ESTrainer: the mean over the E episodes of return - sum_m weights[m] x raw_m, with raw_m the
     raw per-episode sum of flight metric m (evaluation.METRIC_NAMES: "action_rate_sq", "rate_sq", ...).  The raw values are sums
@@ -72,12 +101,20 @@ class ESTrainer:
     The centre is an ActorCritic (ppo.py) whose `pi.net` parameters are views into ONE flat float32 tensor `mu` in the layout
     of pds_mlp_param_count, so checkpoints are the reference's (`save_checkpoint`).  obs_stats: None (mean 0, std 1), a
     (mean, std) pair, or "warmup" (WARMUP_STEPS random-action steps through OnlineMeanStd); frozen afterwards -- the
-    statistics are not perturbed.  eval_every: every that many generations the centre alone flies all N envs.
+    statistics are not perturbed.  obs_stats="online" starts as "warmup" does and then keeps them running: every generation's
+    launch also sums the observations its policies acted on (evaluate_population(..., obs_stats=True)), and their pooled
+    moments are merged into `ac.obs_oms` (OnlineMeanStd.merge_moments) behind the generation, so generation g is standardised
+    with what the generations before it saw -- "V2" of Augmented Random Search.  The centre's evaluation reads the statistics
+    its population flew with and contributes none.
+    shaping: "ranks" (centred ranks, scale -1 / (2 H sigma)) or "ars" (ars_pair_weights on the best `top_b` pairs -- by default
+    all H --, scale -1 / top_b: ARS divides by sigma_R inside the weights and not by the exploration noise).
+    evaluate_fused: the `fused` of the generation's evaluate_population call ("auto": the kernel where it is built).  eval_every: every that many generations the centre alone flies all N envs.
     fitness: None (the mean return over the E episodes) or a callable fitness(ret, length, cost, metrics) -> [P] on the [P, E]
     results and the FlightMetrics of evaluate_population(..., metrics=True), e.g. penalised_return({"action_rate_sq": 0.1})."""
 
     def __init__(self, env, population, hidden_sizes=(50, 50), activation="relu", sigma=0.02, lr=0.01, l2=0.005,
-                 betas=(0.9, 0.999), seed=0, obs_stats=None, fused=True, eval_every=10, adam_eps=1e-8, fitness=None):
+                 betas=(0.9, 0.999), seed=0, obs_stats=None, fused=True, eval_every=10, adam_eps=1e-8, fitness=None, shaping="ranks", top_b=None,
+                 evaluate_fused="auto"):
         P, N = int(population), int(env.num_envs)
         if P < 2 or P % 2 != 0:
             raise ValueError(f"population = {P}: antithetic pairs need an even number of policies")
@@ -91,6 +128,13 @@ class ESTrainer:
             raise ValueError(f"sigma = {sigma}")
         if fitness is not None and not callable(fitness):
             raise ValueError("fitness: None or a callable fitness(ret, length, cost, metrics) -> [P]")
+        if shaping not in ("ranks", "ars"):
+            raise ValueError("shaping: 'ranks' or 'ars'")
+        self.shaping, self.top_b = shaping, int(P // 2 if top_b is None else top_b)
+        if self.top_b < 1 or self.top_b > P // 2:
+            raise ValueError(f"top_b = {top_b}: between 1 and the number of pairs {P // 2}")
+        self.online = isinstance(obs_stats, str) and obs_stats == "online"
+        self.evaluate_fused = evaluate_fused
         self.fitness = fitness
         self.env, self.P, self.H, self.E, self.N = env, P, P // 2, N // P, N
         self.hidden_sizes, self.activation = tuple(int(h) for h in hidden_sizes), activation
@@ -138,8 +182,8 @@ class ESTrainer:
         if obs_stats is None:
             return
         if isinstance(obs_stats, str):
-            if obs_stats != "warmup":
-                raise ValueError("obs_stats: None, (mean, std) or 'warmup'")
+            if obs_stats not in ("warmup", "online"):
+                raise ValueError("obs_stats: None, (mean, std), 'warmup' or 'online'")
             env = self.env
             gen = torch.Generator(device=env.device)
             gen.manual_seed(self.seed & 0x7FFFFFFFFFFFFFFF)
@@ -153,6 +197,16 @@ class ESTrainer:
         mean, std = obs_stats
         oms.mean.data.copy_(torch.as_tensor(mean, dtype=torch.float32).reshape(-1))
         oms.std.data.copy_(torch.as_tensor(std, dtype=torch.float32).reshape(-1))
+
+    @torch.no_grad()
+    def merge_obs_sums(self, sums):
+        """obs_stats="online": the pooled moments of a generation's ObsSums into `ac.obs_oms`, and the new statistics IN PLACE
+        into the [P, D] rows the next ask() hands to the kernel (their addresses stay)."""
+        count, mean, m2 = sums.pooled()
+        oms = self.ac.obs_oms
+        oms.merge_moments(float(count), mean, m2)
+        self._mean_P.copy_(oms.mean.detach().expand(self.P, -1))
+        self._std_P.copy_(oms.std.detach().expand(self.P, -1))
 
     # ---- the two halves of a generation ----------------------------------------------------------------------------------
     def _noise(self):
@@ -193,8 +247,12 @@ class ESTrainer:
             raise ValueError(f"fitness must hold {self.P} values, got {f.numel()}")
         if not bool(torch.isfinite(f).any()):
             raise FloatingPointError(f"every fitness of generation {self.generation} is non-finite")
-        w = pair_weights(centered_ranks(f)).to(self.mu.device).contiguous()
-        scale = -1.0 / (2.0 * self.H * self.sigma)
+        if self.shaping == "ars":
+            w = ars_pair_weights(f, self.top_b).to(self.mu.device).contiguous()
+            scale = -1.0 / self.top_b
+        else:
+            w = pair_weights(centered_ranks(f)).to(self.mu.device).contiguous()
+            scale = -1.0 / (2.0 * self.H * self.sigma)
         if self.fused:
             with _on(w):
                 rc = self.lib.pds_es_gradient(_ptr(w), _ptr(self.mu), self.n, self.H, scale, self.l2, self.seed, self.generation,
@@ -230,11 +288,13 @@ class ESTrainer:
         t0 = self._sync()
         pop = self.ask()
         t1 = self._sync()
+        out = evaluate_population(self.env, pop, fused=self.evaluate_fused, metrics=self.fitness is not None, obs_stats=self.online)
+        sums = out[-1] if self.online else None
         if self.fitness is None:
-            ret, length, _ = evaluate_population(self.env, pop, fused="auto")
+            ret, length = out[0], out[1]
             fitness = ret.mean(dim=1)
         else:
-            ret, length, cost, fm = evaluate_population(self.env, pop, fused="auto", metrics=True)
+            ret, length, cost, fm = out[:4]
             fitness = torch.as_tensor(self.fitness(ret, length, cost, fm), dtype=torch.float32).reshape(-1)
         t2 = self._sync()
         steps, centre = float(length.sum()), float("nan")
@@ -243,6 +303,8 @@ class ESTrainer:
             centre, steps = float(c_ret.mean()), steps + float(c_len.sum())
         t3 = self._sync()
         self.tell(fitness)
+        if self.online:  # behind the centre's evaluation: it flew with its population's statistics
+            self.merge_obs_sums(sums)
         t4 = self._sync()
         finite = fitness[torch.isfinite(fitness)]
         self._t_total += t4 - t0

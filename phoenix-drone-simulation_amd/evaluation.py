@@ -11,7 +11,8 @@ after `max_episode_steps` steps at the latest (TimeLimit).
 an evolution strategy over actor weights -- in one launch: P policies x E episodes (include/pds.h pds_evaluate_policies).
 With `metrics=True` the same launch also reports the flight-quality sums the reference tabulates per real flight
 (experiments/02_zero_shot_policy_transfer_hover_task/02_eval_hover_task.py): `FlightMetrics`; `metrics_from_arrays` scores a
-logged flight by the same definitions."""
+logged flight by the same definitions.  With `obs_stats=True` it also sums the observations the policies acted on, for a running
+standardisation (`ObsSums`; include/pds.h pds_evaluate_policies_stats)."""
 import ctypes as C
 import math
 import os
@@ -326,13 +327,97 @@ def _compose_metrics(acc, prev_neg, alive, rpy, omega, act, last):
     return neg
 
 
+# ---- observation sums (include/pds.h pds_evaluate_policies_stats) ------------------------------------------------------
+SLAB_WAVES, SLAB_FEATURES, SLAB_ROWS = 4, 64, 16  # d_obs_sums [tiles, 4, 2, 64]; a network wave sums 16 rows of its tile
+_OBS_STATS_LOG = None  # a list: the composed path appends (d [N, D] float64, alive [N] bool), on the CPU, per step (the tests' float64 sums)
+
+
+def tree_reduce_rows(acc):
+    """[N, D] per-env float32 sums -> [N / 64, 4, D]: the 16 envs of every quarter tile added in the kernel's fixed tree -- env j
+    + env j + 8, then j + (j + 4), then + 2, then + 1 -- with one float32 add per level (slice adds, never torch.sum, whose order
+    is its own)."""
+    n, d = acc.shape
+    if n % 64 != 0:
+        raise ValueError(f"{n} envs are not whole tiles of 64")
+    x = acc.reshape(n // 64, SLAB_WAVES, SLAB_ROWS, d)
+    for h in (8, 4, 2, 1):
+        x = x[:, :, :h] + x[:, :, h:2 * h]
+    return x[:, :, 0]
+
+
+def _compose_slab(s1, s2):
+    """the per-env sums [N, D] of the composed path -> the kernel's slab [tiles, 4, 2, 64] (features >= D zero)"""
+    n, d = s1.shape
+    slab = torch.zeros(n // 64, SLAB_WAVES, 2, SLAB_FEATURES, device=s1.device)
+    slab[:, :, 0, :d] = tree_reduce_rows(s1)
+    slab[:, :, 1, :d] = tree_reduce_rows(s2)
+    return slab
+
+
+class ObsSums:
+    """What evaluate_population(..., obs_stats=True) sums over every observation o a first-episode policy acted on, per policy p
+    and feature k: with d = o_k - shift[p][k], `sum_d` = sum d and `sum_d2` = sum d^2, each [P, D] float64 on the CPU -- the
+    kernel's float32 partial sums (`slab` [tiles, 4, 2, 64], raw) added over the policy's tiles and the four waves of a tile in
+    float64.  `count` [P] float64: the number of observations, length.sum(1).  `shift` [P, D] float64: the means that were
+    subtracted (the population's own standardisation means; zeros without one).
+    The float64 sums are taken where the slab lives (a population of a million envs writes 33 MB of partial sums: summed on
+    the device, [P, D] comes to the host); `slab` brings the raw float32 array to the CPU when it is first asked for."""
+
+    def __init__(self, slab, count, shift):
+        self._slab = torch.as_tensor(slab, dtype=torch.float32)
+        self._slab_cpu = None
+        self.count = torch.as_tensor(count, dtype=torch.float64).reshape(-1)
+        self.shift = torch.as_tensor(shift, dtype=torch.float64)
+        P, D = self.shift.shape
+        if self._slab.dim() != 4 or tuple(self._slab.shape[1:]) != (SLAB_WAVES, 2, SLAB_FEATURES) or self._slab.shape[0] % P != 0 or D > SLAB_FEATURES:
+            raise ValueError(f"slab must be [tiles, {SLAB_WAVES}, 2, {SLAB_FEATURES}] with tiles a multiple of P = {P}")
+        if self.count.numel() != P:
+            raise ValueError(f"count must hold {P} values")
+        per = self._slab.reshape(P, -1, 2, SLAB_FEATURES).sum(dim=1, dtype=torch.float64).cpu()
+        self.sum_d, self.sum_d2 = per[:, 0, :D].contiguous(), per[:, 1, :D].contiguous()
+
+    @property
+    def slab(self):
+        if self._slab_cpu is None:
+            self._slab_cpu = self._slab.cpu()
+        return self._slab_cpu
+
+    @staticmethod
+    def _moments(n, shift, sd, sd2):
+        n_ = n.unsqueeze(-1) if sd.dim() == 2 else n
+        safe = torch.where(n_ > 0, n_, torch.ones_like(n_))
+        mean = shift + sd / safe
+        m2 = torch.clamp(sd2 - sd * sd / safe, min=0.0)  # (sum (x - mean)^2 >= 0: the rounding of the float32 sums may say otherwise)
+        return n, mean, m2
+
+    def moments(self):
+        """-> (count [P], mean [P, D], M2 [P, D]) float64 per policy: mean = shift + sum_d / count, M2 = sum (o - mean)^2 =
+        sum_d2 - sum_d^2 / count.  A policy without observations (count 0) gets mean = shift and M2 = 0."""
+        return self._moments(self.count, self.shift, self.sum_d, self.sum_d2)
+
+    def pooled(self):
+        """-> (count, mean [D], M2 [D]) float64 over all policies.  Their sums add up as they are where all policies share one
+        shift; otherwise every policy's sums are first re-centred to the shift c of policy 0 in float64: with e = shift_p - c,
+        sum (d + e) = sum_d + n e and sum (d + e)^2 = sum_d2 + 2 e sum_d + n e^2."""
+        c = self.shift[0]
+        e = self.shift - c
+        n = self.count.unsqueeze(-1)
+        sd = (self.sum_d + n * e).sum(dim=0)
+        sd2 = (self.sum_d2 + 2.0 * e * self.sum_d + n * e * e).sum(dim=0)
+        return self._moments(self.count.sum(), c, sd, sd2)
+
+
 @torch.no_grad()
-def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None, metrics=False):
+def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None, metrics=False, obs_stats=False):
     """-> (returns, ep_lengths, costs), each [P, E] float32 on the CPU: policy p of `population` flies the E = num_envs / P
     envs of block p, one episode per env, deterministically (action = actor mean), as `evaluate` does for one policy.
     metrics=True: -> (returns, ep_lengths, costs, FlightMetrics) -- the first three are the same bits; the kernel path is
     pds_evaluate_policies_metrics, the composed path reads rpy, omega and last_action in front of every step and sums with
     separate torch ops: the same bits again.
+    obs_stats=True: the return value gains a LAST element, an `ObsSums`: per policy and feature the sums of d = o - mean[p] and
+    d^2 over every observation the policy acted on in a first episode.  The kernel path is pds_evaluate_policies_stats (it also
+    produces the metrics: metrics=False drops them); the composed path keeps per-env float32 sums with one torch op per
+    difference, product and sum and adds them in the kernel's tree order (`tree_reduce_rows`): the same slab on the bits.
 
     fused=True: one launch (pds_evaluate_policies, csrc/pds_evaluate.h); NotImplementedError where no kernel is built --
     observation_history_size != 2 included -- with the env untouched.  fused=False: the composed path, per step one
@@ -363,9 +448,18 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     dev, n, D = env.device, env.num_envs, env.obs_dim
     lib = env.lib
     ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
-    raw = None
+    raw = slab = None
     obs, _ = env.reset()
-    if use_kernel and metrics:
+    if use_kernel and obs_stats:
+        shape = population.mlp(0)
+        raw = torch.zeros(n, len(METRIC_NAMES), device=dev)
+        slab = torch.zeros(n // 64, SLAB_WAVES, 2, SLAB_FEATURES, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.pds_evaluate_policies_stats(env._handle, P, E, C.byref(shape), _ptr(population.theta), _ptr(population.mean),
+                                                 _ptr(population.std), population.eps, T, _ptr(obs), _ptr(ret), _ptr(length),
+                                                 _ptr(cost), _ptr(raw), _ptr(slab), env._stream())
+        native.check(env._handle, rc, "pds_evaluate_policies_stats")
+    elif use_kernel and metrics:
         shape = population.mlp(0)
         raw = torch.zeros(n, len(METRIC_NAMES), device=dev)
         with torch.cuda.device(dev):
@@ -387,6 +481,10 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
         has = population.mean is not None
         acc = [torch.zeros(n, device=dev) for _ in METRIC_NAMES] if metrics else None
         prev_neg = None
+        if obs_stats:  # per-env sums of d and d * d, d = o - mean of the env's policy
+            s1, s2 = torch.zeros(n, D, device=dev), torch.zeros(n, D, device=dev)
+            shift_rows = population.mean.repeat_interleave(E, dim=0) if has else None
+            zero_nd = torch.zeros(n, D, device=dev)
         for _ in range(T):
             if metrics:  # x(s): the state the policy acts in
                 rpy, omega, last = env.get_state("rpy"), env.get_state("omega"), env.get_state("last_action")
@@ -401,6 +499,13 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
                         raise RuntimeError(f"pds_mlp_forward -> {rc}")
             if metrics:
                 prev_neg = _compose_metrics(acc, prev_neg, alive, rpy, omega, act, last)
+            if obs_stats:  # o(s), for the envs alive in front of step s
+                d = obs - shift_rows if has else obs
+                on = alive.unsqueeze(1)
+                s1 += torch.where(on, d, zero_nd)
+                s2 += torch.where(on, d * d, zero_nd)
+                if _OBS_STATS_LOG is not None:
+                    _OBS_STATS_LOG.append((d.double().cpu(), alive.cpu().clone()))
             obs, r, term, trunc, info = env.step(act)
             ret += torch.where(alive, r, torch.zeros_like(r))
             cost += torch.where(alive, info["cost"], torch.zeros_like(r))
@@ -408,6 +513,8 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
             alive &= ~(term | trunc)
         if metrics:
             raw = torch.stack(acc, dim=1)
+        if obs_stats:
+            slab = _compose_slab(s1, s2)
     ret, length, cost = ret.cpu().reshape(P, E), length.cpu().reshape(P, E), cost.cpu().reshape(P, E)
     fm = None
     if metrics:
@@ -425,4 +532,8 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
                     f.write(",".join(METRIC_NAMES) + ",length\n")
                     for e in range(E):
                         f.write(",".join(repr(float(x)) for x in fm.raw[p, e]) + f",{float(length[p, e])!r}\n")
-    return (ret, length, cost, fm) if metrics else (ret, length, cost)
+    out = (ret, length, cost, fm) if metrics else (ret, length, cost)
+    if obs_stats:
+        shift = population.mean.cpu().double() if population.mean is not None else torch.zeros(P, D, dtype=torch.float64)
+        out = out + (ObsSums(slab, length.double().sum(dim=1), shift),)
+    return out

@@ -88,6 +88,30 @@ class OnlineMeanStd(nn.Module):
         self.count.data.copy_(n_AB)
         self.std.data.copy_(torch.sqrt(M2_AB / n_AB))
 
+    @torch.no_grad()
+    def merge_moments(self, count, mean, m2):
+        """Merge a batch given by its moments -- `count` samples with mean `mean` [D] and M2 = sum (x - mean)^2 `m2` [D] -- into
+        the running statistics: the exact parallel merge of Chan et al. in float64,
+            n = n_A + n_B,  delta = mean_B - mean_A,  mean = mean_A + delta n_B / n,  M2 = M2_A + M2_B + delta^2 n_A n_B / n,
+        with M2_A = n_A std^2, written in place into `mean`, `std`, `count` (the fused kernels hold their addresses).
+        This is NOT the arithmetic of `update(x)`: the reference takes its batch variance around the NEW mean,
+        mean((x - mean_new)^2), and still adds the delta^2 term -- a quirk `update` keeps because the reference has it.  A batch
+        merged here leaves exactly the mean and the (biased) standard deviation of all samples seen.  count = 0: no change."""
+        n_b = float(count)
+        if not n_b > 0.0:
+            return
+        dev = self.mean.device
+        mean_b = torch.as_tensor(mean, dtype=torch.float64).reshape(self.mean.shape).to(dev)
+        m2_b = torch.as_tensor(m2, dtype=torch.float64).reshape(self.mean.shape).to(dev)
+        n_a = float(self.count.double().item())
+        n = n_a + n_b
+        mean_a = self.mean.double()
+        delta = mean_b - mean_a
+        m2_ab = n_a * torch.square(self.std.double()) + m2_b + torch.square(delta) * (n_a * n_b / n)
+        self.mean.data.copy_(mean_a + delta * (n_b / n))
+        self.count.data.fill_(n)
+        self.std.data.copy_(torch.sqrt(m2_ab / n))
+
 
 def _mlp(sizes, activation):
     act = {"relu": nn.ReLU, "tanh": nn.Tanh, "identity": nn.Identity, "sigmoid": nn.Sigmoid,

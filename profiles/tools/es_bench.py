@@ -92,13 +92,13 @@ def time_kernels(pop, n, reps, out):
           file=out, flush=True)
 
 
-def learning(seeds, generations, out):
+def learning(seeds, generations, out, obs_stats="warmup"):
     print(f"# centre return (the centre alone on {P * E} envs, mean over them) per generation; Hover lean, P {P} x E {E}, ESTrainer defaults "
-          "(sigma 0.02, lr 0.01, l2 0.005), obs_stats='warmup'; generation g = the centre before update g + 1", file=out)
+          f"(sigma 0.02, lr 0.01, l2 0.005), obs_stats={obs_stats!r}; generation g = the centre before update g + 1", file=out)
     curves = []
     for seed in seeds:
         env = pds.make("DroneHoverSimpleEnv-v0", num_envs=P * E, seed=seed, **LEAN)
-        tr = ESTrainer(env, P, seed=seed, obs_stats="warmup", eval_every=1)
+        tr = ESTrainer(env, P, seed=seed, obs_stats=obs_stats, eval_every=1)
         logs = [tr.learn_one_generation() for _ in range(generations)]
         curves.append(logs)
         env.close()
@@ -119,18 +119,22 @@ def main():
     ap.add_argument("--generations", type=int, default=30, help="generations per seed of the learning record (0: skip it)")
     ap.add_argument("--timing-out", default=None)
     ap.add_argument("--learning-out", default=None)
+    ap.add_argument("--obs-stats", default="warmup", help="comma-separated obs_stats of the learning record, one block each: warmup,online")
+    ap.add_argument("--no-timing", action="store_true", help="the learning record only")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "es_bench.py needs a HIP device"
     t_out = open(args.timing_out, "w") if args.timing_out else sys.stdout
     print(f"# one generation of ESTrainer on DroneHoverSimpleEnv-v0, {torch.cuda.get_device_name(0)}; device events; one warm-up generation, "
           "then median [min .. max]", file=t_out)
-    time_generation("Hover lean", LEAN, args.reps, t_out)
-    time_generation("Hover defaults", {}, args.reps, t_out)
-    for pop in (4096, 16384):
-        time_kernels(pop, 4504, 4 * args.reps, t_out)
+    if not args.no_timing:
+        time_generation("Hover lean", LEAN, args.reps, t_out)
+        time_generation("Hover defaults", {}, args.reps, t_out)
+        for pop in (4096, 16384):
+            time_kernels(pop, 4504, 4 * args.reps, t_out)
     if args.generations > 0:
         l_out = open(args.learning_out, "w") if args.learning_out else sys.stdout
-        learning((0, 1, 2), args.generations, l_out)
+        for mode in args.obs_stats.split(","):
+            learning((0, 1, 2), args.generations, l_out, mode)
 
 
 if __name__ == "__main__":

@@ -44,9 +44,10 @@ def scratch_of_forms():
     out = {}
     for r in kr.kernel_table():
         if "evaluate_kernel<" in r[0] and HOVER_DEFAULT in r[0]:
-            tail = r[0].split(HOVER_DEFAULT)[1]
-            teams = int(tail.split(",")[1].strip().split(">")[0])
-            out[("true" in tail.split("(")[0], teams)] = r[5]
+            tail = r[0].split(HOVER_DEFAULT)[1].split(">")[0].split(",")[1:]  # TEAMS, METRICS, STATS
+            teams, metrics, stats = int(tail[0]), tail[1].strip() == "true", tail[2].strip() == "true"
+            if not stats:  # (the stats form: profiles/tools/evaluate_stats_bench.py)
+                out[(metrics, teams)] = r[5]
     return out
 
 
