@@ -1,5 +1,5 @@
 // pds_explore.h -- the two exploration rules of the off-policy trainers as device functions, stated once for the elementwise
-// entry points (pds_sac_sample in csrc/pds_sac.hip, pds_ddpg_explore in csrc/pds_api.hip), the SAC update kernels and the
+// entry points (pds_sac_sample in csrc/pds_sac.hip, pds_ddpg_explore in csrc/pds_ddpg.hip), the SAC update kernels and the
 // network waves of the fused collection (csrc/pds_collect.h): same source, same instructions, same bits.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1188,24 +1188,19 @@ __global__ __launch_bounds__(512, 2) void ppo_split_kernel(const Args a) {
       if (4 + q < m.d_out && lane < m.h2) out[o.w3 + (4 + q) * m.h2 + lane] = gW3s2[q];
       if (4 + q < m.d_out && lane == m.h2) out[o.b3 + 4 + q] = gW3s2[q];
     }
-    float s4[kStats] = {st_loss, st_ratio, st_kl, st_cnt};
+    // statistics: lanes of group 0 hold per-sample sums
+  float s4[kStats] = {st_loss, st_ratio, st_kl, st_cnt};
 #pragma unroll
-    for (int q = 0; q < kStats; ++q) {
-      float v = s4[q];
-      for (int d = 8; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-      if (lane == 0) out[o.total + q] = v;
-    }
+  for (int q = 0; q < kStats; ++q) {
+    float v = s4[q];
+    for (int d = 8; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    if (lane == 0) out[o.total + q] = v;
+  }
   }
 }
 
-// The optimiser step that may ride on the partial-sum kernel (pds_*_grad_step): torch.optim.Adam, the arithmetic of
-// pds_adam_step (csrc/pds_train.hip adam_kernel) expression for expression, so both routes give the same bits.
-struct AdamK {
-  float *em, *ev;  // exp_avg, exp_avg_sq [total]; em == nullptr: no step
-  float lr, b1, b2, eps, bc1, bc2s;
-};
-
-// block = 64 outputs x 16 slices of the wave range (sum_partials, pds_mlp_tile.h)
+// block = 64 outputs x 16 slices of the part range (sum_partials, pds_mlp_tile.h); the optimiser step that may ride on it
+// (pds_*_grad_step, pds_ddpg_policy_grad, pds_sac_policy_grad) is adam_apply of pds_mlp_common.h, as in pds_adam_step
 __global__ __launch_bounds__(1024) void reduce_kernel(const float *partials, int pstride, int nwaves, int total,
                                                       float denom_scale, float *grads, float *stats, pds_mlp m, AdamK ad) {
   const int p = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -1214,25 +1209,18 @@ __global__ __launch_bounds__(1024) void reduce_kernel(const float *partials, int
     if (p < total) {
       const float gr = t * denom_scale;
       grads[p] = gr;
-      if (ad.em != nullptr) {
-        const Offsets o = offsets(m);
-        float *dst;
-        if (p < o.b1) dst = const_cast<float *>(m.w1) + p;
-        else if (p < o.w2) dst = const_cast<float *>(m.b1) + (p - o.b1);
-        else if (p < o.b2) dst = const_cast<float *>(m.w2) + (p - o.w2);
-        else if (p < o.w3) dst = const_cast<float *>(m.b2) + (p - o.b2);
-        else if (p < o.b3) dst = const_cast<float *>(m.w3) + (p - o.w3);
-        else dst = const_cast<float *>(m.b3) + (p - o.b3);
-        const float mm = ad.b1 * ad.em[p] + (1.f - ad.b1) * gr;
-        const float vv = ad.b2 * ad.ev[p] + (1.f - ad.b2) * gr * gr;
-        ad.em[p] = mm; ad.ev[p] = vv;
-        const float denom = sqrtf(vv) / ad.bc2s + ad.eps;
-        *dst = *dst - (ad.lr / ad.bc1) * (mm / denom);
-      }
+      if (ad.em != nullptr) adam_apply(ad, p, gr, param_ptr(m, offsets(m), p));
     } else {
       stats[p - total] = t;
     }
   }
+}
+
+int launch_reduce(const float *partials, int pstride, int nparts, int total, float scale, float *grads, float *stats,
+                  const pds_mlp &m, const pds_adam *opt, hipStream_t s) {
+  hipLaunchKernelGGL(reduce_kernel, dim3((total + kStats + 63) / 64), dim3(1024), 0, s, partials, pstride, nparts, total, scale,
+                     grads, stats, m, adam_k(opt));
+  return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
 }
 
 // data-carrying k-steps of a partially filled last k-tile (4: the tile is full enough for the generic code)
@@ -1360,21 +1348,7 @@ static int launch_grad(int loss, Args &a, float *d_grads, float *d_stats, float 
     if (a.m.activation == 0) PDS_MLP_LAUNCH(LOSS_MSE, 0); else PDS_MLP_LAUNCH(LOSS_MSE, 1);
   }
 #undef PDS_MLP_LAUNCH
-  const int n = o.total + kStats;
-  AdamK ad{};
-  if (opt != nullptr) {
-    ad.em = opt->d_exp_avg; ad.ev = opt->d_exp_avg_sq;
-    ad.lr = opt->lr; ad.b1 = opt->beta1; ad.b2 = opt->beta2; ad.eps = opt->eps;
-    ad.bc1 = 1.0f - powf(opt->beta1, (float)opt->step);  // as pds_adam_step
-    ad.bc2s = sqrtf(1.0f - powf(opt->beta2, (float)opt->step));
-  }
-  hipLaunchKernelGGL(reduce_kernel, dim3((n + 63) / 64), dim3(1024), 0, s, (const float *)d_workspace, a.pstride,
-                     blocks, o.total, 1.0f / (float)a.B, d_grads, d_stats, a.m, ad);
-  return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
-}
-
-static bool adam_ok(const pds_adam *opt) {
-  return opt == nullptr || (opt->d_exp_avg && opt->d_exp_avg_sq && opt->step >= 1);
+  return launch_reduce(d_workspace, a.pstride, blocks, o.total, 1.0f / (float)a.B, d_grads, d_stats, a.m, opt, s);
 }
 
 extern "C" int pds_ppo_policy_grad_step(const pds_mlp *m, const float *d_x, const float *d_act, const float *d_adv,

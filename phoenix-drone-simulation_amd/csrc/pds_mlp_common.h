@@ -4,6 +4,7 @@
 // kernels is csrc/pds_mlp_tile.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include "../../include/pds.h"
@@ -70,6 +71,50 @@ __host__ __device__ inline Offsets offsets(const pds_mlp &m) {
   o.total = o.b3 + m.d_out;
   return o;
 }
+// parameter p of the flat layout (o = offsets of the network): f(the tensor it lies in, as a member of pds_mlp; its index there)
+template <class F>
+__device__ __forceinline__ void at_param(const Offsets &o, int p, F f) {
+  if (p < o.b1) f(&pds_mlp::w1, p);
+  else if (p < o.w2) f(&pds_mlp::b1, p - o.b1);
+  else if (p < o.b2) f(&pds_mlp::w2, p - o.w2);
+  else if (p < o.w3) f(&pds_mlp::b2, p - o.b2);
+  else if (p < o.b3) f(&pds_mlp::w3, p - o.w3);
+  else f(&pds_mlp::b3, p - o.b3);
+}
+// ... of network m, as a pointer
+__device__ __forceinline__ float *param_ptr(const pds_mlp &m, const Offsets &o, int p) {
+  float *ptr;
+  at_param(o, p, [&](const float *pds_mlp::*w, int i) { ptr = const_cast<float *>(m.*w) + i; });
+  return ptr;
+}
+
+// torch.optim.Adam (no weight decay, no amsgrad), stated once for pds_adam_step (csrc/pds_train.hip adam_kernel) and for the
+// step that rides on the partial-sum kernel of a gradient call (csrc/pds_mlp.hip reduce_kernel): same source, same bits.
+// The build fuses a * b + c only inside one source expression (-ffp-contract=on), so these expressions stay whole as written.
+struct AdamK {
+  float *em, *ev;  // exp_avg, exp_avg_sq [total]; em == nullptr: no step
+  float lr, b1, b2, eps, bc1, bc2s;
+};
+// the rule every entry point with a `const pds_adam *opt` applies: no step, or a step with its moments and a count from 1
+inline bool adam_ok(const pds_adam *opt) { return opt == nullptr || (opt->d_exp_avg && opt->d_exp_avg_sq && opt->step >= 1); }
+inline AdamK adam_k(const pds_adam *opt) {
+  AdamK ad{};
+  if (opt != nullptr) {
+    ad.em = opt->d_exp_avg; ad.ev = opt->d_exp_avg_sq;
+    ad.lr = opt->lr; ad.b1 = opt->beta1; ad.b2 = opt->beta2; ad.eps = opt->eps;
+    ad.bc1 = 1.0f - powf(opt->beta1, (float)opt->step);
+    ad.bc2s = sqrtf(1.0f - powf(opt->beta2, (float)opt->step));
+  }
+  return ad;
+}
+// m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; *dst -= lr / (1-b1^t) * m / (sqrt(v) / sqrt(1-b2^t) + eps) for parameter p
+__device__ __forceinline__ void adam_apply(const AdamK &ad, int p, float gr, float *dst) {
+  const float mm = ad.b1 * ad.em[p] + (1.f - ad.b1) * gr;
+  const float vv = ad.b2 * ad.ev[p] + (1.f - ad.b2) * gr * gr;
+  ad.em[p] = mm; ad.ev[p] = vv;
+  const float denom = sqrtf(vv) / ad.bc2s + ad.eps;
+  *dst = *dst - (ad.lr / ad.bc1) * (mm / denom);
+}
 
 #define PDS_WAVE_SYNC()                                          \
   do {                                                           \
@@ -126,10 +171,9 @@ int launch_wide(int loss, const Args &a, hipStream_t s);
 // csrc/pds_mlp.hip: PDS_OK for a network every kernel family covers between them (d_in <= kMaxDimIn, h1, h2 <= kMaxDim,
 // d_out <= kMaxOut, relu or tanh, no null tensor), else PDS_EINVAL
 int check(const pds_mlp *m);
-// csrc/pds_ddpg.hip: launches ddpg_reduce_kernel on `s` -- grads[p] = denom_scale * the fixed-order sum of element p over the
-// nwaves partials, stats = the sums of the kStats elements behind them, and the Adam step on `m` when opt != nullptr
-// (csrc/pds_sac.hip sums its partials with the same kernel)
-int launch_ddpg_reduce(const float *partials, int pstride, int nwaves, int total, float denom_scale, float *grads, float *stats,
-                       const pds_mlp &m, const pds_adam *opt, hipStream_t s);
+// csrc/pds_mlp.hip: launches reduce_kernel on `s` -- grads[p] = scale * the fixed-order sum of element p over the nparts
+// partials, stats = the sums of the kStats elements behind them, and the Adam step on `m` when opt != nullptr
+int launch_reduce(const float *partials, int pstride, int nparts, int total, float scale, float *grads, float *stats,
+                  const pds_mlp &m, const pds_adam *opt, hipStream_t s);
 
 }  // namespace pds_mlp_detail

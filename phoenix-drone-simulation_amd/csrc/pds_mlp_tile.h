@@ -1,7 +1,7 @@
 // pds_mlp_tile.h -- the 16-sample-tile core of the K-tiled kernels (csrc/pds_mlp_wide.hip: mlp_wide_kernel; csrc/pds_npg.hip:
 // fvp_kernel, surrogate_kernel), each piece written once: grid size, weight staging, the LDS GEMM, the wave's weight-gradient
-// accumulators with their write-out, the backward chain from the output gradient, and the fixed-order sum of the waves'
-// partials (also reduce_kernel of csrc/pds_mlp.hip).
+// accumulators with their write-out, the backward chain from the output gradient, the statistics behind a wave's partial, and
+// the fixed-order sum of the waves' partials (the last two also in csrc/pds_mlp.hip).
 //
 // The design is mlp_kernel's of csrc/pds_mlp.hip (read that first): a wave owns a 16-sample tile, every GEMM of forward and
 // backward runs on v_mfma_f32_16x16x4_f32 with the transposed chain (activations stay in registers from layer to layer),
@@ -25,10 +25,10 @@ namespace pds_mlp_detail {
 template <int NIN>
 constexpr int wide_stride() { return kTW * NIN + 4; }
 
-// blocks of kWideWaves waves, one 16-sample tile per wave and round
-inline int wide_grid_blocks(long long B) {
+// blocks of `waves` waves, one 16-sample tile per wave and round
+inline int wide_grid_blocks(long long B, int waves = kWideWaves) {
   const long long tiles = (B + kTS - 1) / kTS;
-  const long long blocks = (tiles + kWideWaves - 1) / kWideWaves;
+  const long long blocks = (tiles + waves - 1) / waves;
   return (int)(blocks < kWideMaxBlocks ? blocks : kWideMaxBlocks);  // one persistent block per CU
 }
 
@@ -124,7 +124,7 @@ struct NetLds {
 };
 
 // wide_forward without images, H1 kept next to H2 (this lane's values: what act' of a backward chain without weight gradients
-// reads): the Q networks of csrc/pds_ddpg.hip and csrc/pds_sac.hip
+// reads): the Q networks of csrc/pds_actor_critic.h
 template <int ACT, int NIN>
 __device__ __forceinline__ f32x4 forward_regs(const NetLds &N, const f32x4 (&xin)[NIN], f32x4 (&h1r)[kNT],
                                               f32x4 (&h2r)[kNT], int n, int g) {
@@ -356,6 +356,17 @@ __device__ __forceinline__ void wide_backward(const float *W2s, const float *W3s
     }
   }
   PDS_WAVE_SYNC();  // the images are rewritten by the next tile
+}
+
+// The kStats statistics behind a wave's partial (out[total ..]): the lanes of group 0 hold per-sample sums, lane 0 writes their
+// sum over the 16 samples
+__device__ __forceinline__ void store_stats(float *out, int total, const float (&s4)[kStats], int lane) {
+#pragma unroll
+  for (int q = 0; q < kStats; ++q) {
+    float v = s4[q];
+    for (int d = 8; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    if (lane == 0) out[total + q] = v;
+  }
 }
 
 // Sum of element p over the waves' partials in a fixed order (deterministic, no atomics), by a block of 64 elements x 16

@@ -130,13 +130,7 @@ __global__ __launch_bounds__(kWideWaves * 64, 1) void mlp_wide_kernel(const Args
     float *out = a.partials + wid * a.pstride;
     const Offsets o = offsets(m);
     G.store(m, o, out, n, g);
-    float s4[kStats] = {st_loss, st_ratio, st_kl, st_cnt};  // lanes of group 0 hold per-sample sums
-#pragma unroll
-    for (int q = 0; q < kStats; ++q) {
-      float v = s4[q];
-      for (int d = 8; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-      if (lane == 0) out[o.total + q] = v;
-    }
+    store_stats(out, o.total, {st_loss, st_ratio, st_kl, st_cnt}, lane);
   }
 }
 

@@ -94,14 +94,7 @@ __device__ __forceinline__ f32x4 gemm_glb_x(const float *V, int rows, int cols, 
 }
 
 // parameter i of the flat layout, read from the network's six tensors
-__device__ __forceinline__ float theta_at(const pds_mlp &m, const Offsets &o, int i) {
-  if (i < o.b1) return m.w1[i];
-  if (i < o.w2) return m.b1[i - o.b1];
-  if (i < o.b2) return m.w2[i - o.w2];
-  if (i < o.w3) return m.b2[i - o.b2];
-  if (i < o.b3) return m.w3[i - o.w3];
-  return m.b3[i - o.b3];
-}
+__device__ __forceinline__ float theta_at(const pds_mlp &m, const Offsets &o, int i) { return *param_ptr(m, o, i); }
 // candidate parameter theta + f s: product and sum rounded separately (no FMA contraction)
 __device__ __forceinline__ float cand(float theta, float f, float s) { return __fadd_rn(theta, __fmul_rn(f, s)); }
 

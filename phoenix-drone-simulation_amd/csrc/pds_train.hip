@@ -8,8 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/pds.h"
 #include "pds_device.h"
+#include "pds_mlp_common.h"
 
 namespace pds_train_detail {  // named (not anonymous) so that profiler kernel names are readable
 
@@ -70,27 +70,14 @@ __global__ __launch_bounds__(256) void record_kernel(const float *rew, const uin
   }
 }
 
-// torch.optim.Adam (no weight decay, no amsgrad) on the flat gradient of one MLP:
-// m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr / (1-b1^t) * m / (sqrt(v) / sqrt(1-b2^t) + eps)
+// torch.optim.Adam on the flat gradient of one MLP (adam_apply, csrc/pds_mlp_common.h), one thread per parameter
 __global__ __launch_bounds__(256) void adam_kernel(pds_mlp m, const float *g, float *em, float *ev, int total,
                                                    float lr, float b1, float b2, float eps, float bc1, float bc2s) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= total) return;
-  const int o_b1 = m.h1 * m.d_in, o_w2 = o_b1 + m.h1, o_b2 = o_w2 + m.h2 * m.h1, o_w3 = o_b2 + m.h2,
-            o_b3 = o_w3 + m.d_out * m.h2;
-  float *dst;
-  if (p < o_b1) dst = const_cast<float *>(m.w1) + p;
-  else if (p < o_w2) dst = const_cast<float *>(m.b1) + (p - o_b1);
-  else if (p < o_b2) dst = const_cast<float *>(m.w2) + (p - o_w2);
-  else if (p < o_w3) dst = const_cast<float *>(m.b2) + (p - o_b2);
-  else if (p < o_b3) dst = const_cast<float *>(m.w3) + (p - o_w3);
-  else dst = const_cast<float *>(m.b3) + (p - o_b3);
-  const float gr = g[p];
-  const float mm = b1 * em[p] + (1.f - b1) * gr;
-  const float vv = b2 * ev[p] + (1.f - b2) * gr * gr;
-  em[p] = mm; ev[p] = vv;
-  const float denom = sqrtf(vv) / bc2s + eps;
-  *dst = *dst - (lr / bc1) * (mm / denom);
+  using namespace pds_mlp_detail;
+  float *dst = param_ptr(m, offsets(m), p);
+  adam_apply(AdamK{em, ev, lr, b1, b2, eps, bc1, bc2s}, p, g[p], dst);
 }
 
 // *c += inc by one thread (the device-side call counter of a captured rollout)
@@ -184,11 +171,12 @@ extern "C" int pds_rollout_record(const float *d_rew, const uint8_t *d_term, con
 
 extern "C" int pds_adam_step(const pds_mlp *m, const float *d_grads, float *d_exp_avg, float *d_exp_avg_sq,
                              int64_t step, float lr, float beta1, float beta2, float eps, void *stream) {
-  if (!m || !d_grads || !d_exp_avg || !d_exp_avg_sq || step < 1) return PDS_EINVAL;
+  const pds_adam opt{d_exp_avg, d_exp_avg_sq, step, lr, beta1, beta2, eps};
+  if (!m || !d_grads || !pds_mlp_detail::adam_ok(&opt)) return PDS_EINVAL;
   const int total = pds_mlp_param_count(m);
   if (total < 0) return PDS_EINVAL;
-  const float bc1 = 1.0f - powf(beta1, (float)step), bc2s = sqrtf(1.0f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adam_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, *m, d_grads, d_exp_avg,
-                     d_exp_avg_sq, total, lr, beta1, beta2, eps, bc1, bc2s);
+  const pds_mlp_detail::AdamK ad = pds_mlp_detail::adam_k(&opt);
+  hipLaunchKernelGGL(adam_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, *m, d_grads, ad.em, ad.ev, total,
+                     ad.lr, ad.b1, ad.b2, ad.eps, ad.bc1, ad.bc2s);
   return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
 }
