@@ -9,6 +9,10 @@ evaluate_population (the evaluation loop of the reference's utils/evaluation.py,
   python examples/evaluate_policies.py runs/*/seed_*              # prints mean return, length and cost per checkpoint
   python examples/evaluate_policies.py runs/ --episodes 256 --env DroneCircleSimpleEnv-v0 --log-dir eval_out
   python examples/evaluate_policies.py runs/ --metrics            # also the flight-quality table (evaluation.FlightMetrics.table)
+  python examples/evaluate_policies.py runs_h4/ --history 4       # actors trained with observation_history_size = 4
+
+A group whose actors read H x half inputs (half: one [o, u] half of the env's observation) was trained on an observation history
+of H: its env is built with observation_history_size = H (inferred from the width, or --history) and flies in one launch too.
 """
 import argparse
 import json
@@ -62,6 +66,14 @@ def group_by_shape(runs):
     return groups
 
 
+def infer_history(d_in, half):
+    """observation_history_size of an env whose observation is `d_in` wide: d_in / half, where half is one [o, u] half of the
+    env's row; ValueError where d_in is no multiple of it"""
+    if half < 1 or d_in < half or d_in % half != 0:
+        raise ValueError(f"{d_in} inputs are not a whole number of {half}-wide observation halves")
+    return d_in // half
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("paths", nargs="+", help="run directories, or directories to search for them")
@@ -72,6 +84,8 @@ def main():
     ap.add_argument("--log-dir", default=None, help="write returns.csv / costs.csv per checkpoint under <log-dir>/<group>/<p>/")
     ap.add_argument("--metrics", action="store_true",
                     help="also print flight time, mean squared roll / pitch, rate oscillation, action rate, saturation, maximum tilt")
+    ap.add_argument("--history", type=int, default=None,
+                    help="observation_history_size of the env (default: inferred per group, actor inputs / half the env's observation width)")
     args = ap.parse_args()
     fused = {"auto": "auto", "on": True, "off": False}[args.fused]
 
@@ -85,12 +99,21 @@ def main():
     for gi, (key, members) in enumerate(sorted(groups.items(), key=lambda kv: str(kv[0]))):
         d_in, hidden, act, _ = key
         pop = PolicyPopulation.from_actor_critics([ac for _, ac in members])
-        env = pds.make(env_id, num_envs=pop.P * args.episodes, seed=args.seed)
+        env = pds.make(env_id, num_envs=pop.P * args.episodes, seed=args.seed, observation_history_size=args.history or 2)
+        if env.obs_dim != d_in and args.history is None:  # a history policy: the env again, with the history its width says
+            half = env.obs_dim // 2
+            env.close()
+            try:
+                history = infer_history(d_in, half)
+            except ValueError as e:
+                print(f"group {gi} {key}: {e} of {env_id}: skipped")
+                continue
+            env = pds.make(env_id, num_envs=pop.P * args.episodes, seed=args.seed, observation_history_size=history)
         if env.obs_dim != d_in:
             print(f"group {gi} {key}: the actors read {d_in} inputs, {env_id} observes {env.obs_dim}: skipped")
             env.close()
             continue
-        out = evaluate_population(env, pop, fused=fused, metrics=args.metrics,
+        out = evaluate_population(env, pop, fused=fused, metrics=args.metrics, history_fused=True,
                                   log_dir=os.path.join(args.log_dir, str(gi)) if args.log_dir else None)
         ret, length, cost = out[:3]
         table = out[3].table() if args.metrics else {}

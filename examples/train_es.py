@@ -41,6 +41,10 @@ def main():
                          "generation's policies saw")
     ap.add_argument("--shaping", choices=("ranks", "ars"), default="ranks", help="centred ranks, or the weights of Augmented Random Search")
     ap.add_argument("--top-b", type=int, default=None, help="--shaping ars: the best that many pairs enter the update (default: all)")
+    ap.add_argument("--history", type=int, default=2, help="observation_history_size of the env (the reference's experiment 04: 1, 2, 4, 6, 8)")
+    ap.add_argument("--history-fused", action="store_true",
+                    help="with --history other than 2: evaluate every generation in one launch (pds_evaluate_policies_history) where "
+                         "it is built, instead of the composed path; --obs-stats online stays composed there")
     args = ap.parse_args()
     weights = {}
     for item in args.penalise:
@@ -49,10 +53,11 @@ def main():
             ap.error(f"--penalise {item!r}: NAME=W")
         weights[name] = float(w)
     fitness = penalised_return(weights) if weights else None  # (ValueError names the metrics there are)
-    env = pds.make(args.env, num_envs=args.population * args.episodes, seed=args.seed)  # the reference's default config
+    env = pds.make(args.env, num_envs=args.population * args.episodes, seed=args.seed,
+                   observation_history_size=args.history)  # otherwise the reference's default config
     trainer = ESTrainer(env, args.population, sigma=args.sigma, lr=args.lr, seed=args.seed,
                         obs_stats=None if args.obs_stats == "none" else args.obs_stats, eval_every=args.eval_every, fitness=fitness,
-                        shaping=args.shaping, top_b=args.top_b)
+                        shaping=args.shaping, top_b=args.top_b, history_fused=args.history_fused)
     t0 = time.time()
     steps = 0.0
     for g in range(args.generations):

@@ -465,6 +465,22 @@ int pds_evaluate_policies_stats(pds_handle *h, int64_t P, int64_t episodes_per_p
                                 const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
                                 float *d_obs_sums, void *stream);
 
+/* The population evaluation for policies that read an observation HISTORY (csrc/pds_evaluate_hist.h; observation_history_size =
+ * `history`, envs/base.py:44, 303-319, 417-431): the actors read the last `history` halves [o, u] of their env, history * half
+ * inputs with half = pds_obs_dim / 2.  d_obs0 [N, history * half]: the histories on entry -- after pds_reset, history - 1 copies
+ * of the first half of the row it returned, then its second half.  Behind every step a history is shifted by one half and the
+ * second half of the step's row appended; the history of an env that finished restarts from its reset row in the same way (what
+ * pds_history_advance does under a per-step loop).  shape->d_in = history * half; d_mean, d_std [P, history * half].
+ * d_metrics [N, PDS_EVAL_METRICS], 16-byte aligned, or NULL: the PDS_EM_* values, from the same launch.
+ * Bitwise what max_steps x (pds_mlp_forward per policy + pds_step + pds_history_advance) and the same sums in the same order give.
+ * Checks and the state of the handle afterwards are pds_evaluate_policies'.  PDS_EUNSUPPORTED: a handle without auto_reset, an env
+ * configuration pds_rollout_history is not built for, or history * half > 192 (pds_evaluate_history_supported says so beforehand:
+ * 1 / 0).  history = 2 is accepted: the same bits as pds_evaluate_policies and pds_evaluate_policies_metrics. */
+int pds_evaluate_history_supported(const pds_handle *h, int history);
+int pds_evaluate_policies_history(pds_handle *h, int history, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                                  const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                                  const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics, void *stream);
+
 /* number of parameters; flat gradient layout = [W1, b1, W2, b2, W3, b3] (torch parameter order) */
 int pds_mlp_param_count(const pds_mlp *m);
 /* floats of scratch the *_grad entry points need (per-wave partial sums) */

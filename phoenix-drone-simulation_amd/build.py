@@ -28,8 +28,10 @@ _UNITS = ["pds_task_hover.hip", "pds_task_circle.hip", "pds_task_takeoff.hip", "
           "pds_gae.hip", "pds_train.hip", "pds_history.hip", "pds_npg.hip", "pds_ddpg.hip", "pds_sac.hip", "pds_simopt.hip", "pds_es.hip",
           "pds_evaluate_stats_hover_pwm.hip", "pds_evaluate_stats_circle_pwm.hip", "pds_evaluate_stats_hover_lat.hip",
           "pds_evaluate_stats_circle_lat.hip", "pds_evaluate_stats_hover.hip", "pds_evaluate_stats_circle.hip",
-          "pds_evaluate_stats_takeoff.hip"]  # longest first; the stats form of the evaluation appended
-_HEADERS = ["pds_device.h", "pds_types.h", "pds_reset.h", "pds_step.h", "pds_mlp_fwd.h", "pds_rollout.h", "pds_rollout_hist.h", "pds_mlp_common.h", "pds_mlp_tile.h", "pds_actor_critic.h", "pds_physics.h", "pds_simopt.h", "pds_evaluate.h", "pds_evaluate_args.h", "pds_collect.h", "pds_collect_args.h", "pds_explore.h"]
+          "pds_evaluate_stats_takeoff.hip",
+          "pds_evaluate_hist_hover_pid.hip", "pds_evaluate_hist_circle_pid.hip", "pds_evaluate_hist_hover.hip",
+          "pds_evaluate_hist_circle.hip", "pds_evaluate_hist_takeoff.hip"]  # longest first; the stats form and the history form of the evaluation appended
+_HEADERS = ["pds_device.h", "pds_types.h", "pds_reset.h", "pds_step.h", "pds_mlp_fwd.h", "pds_rollout.h", "pds_rollout_hist.h", "pds_mlp_common.h", "pds_mlp_tile.h", "pds_actor_critic.h", "pds_physics.h", "pds_simopt.h", "pds_evaluate.h", "pds_evaluate_args.h", "pds_evaluate_hist.h", "pds_evaluate_hist_args.h", "pds_collect.h", "pds_collect_args.h", "pds_explore.h"]
 _DEPS = [os.path.join(_CSRC, f) for f in _UNITS + _HEADERS] + [os.path.join(_HERE, "..", "include", "pds.h")]
 _LIB = os.path.join(_HERE, "libpds_hip.so")
 _OBJ = os.path.join(_HERE, "build")

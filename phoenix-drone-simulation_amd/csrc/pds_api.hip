@@ -15,6 +15,7 @@
 #include "pds_reset.h"  // (pds_types.h + regen_kept_obs for pds_get_state)
 #include "pds_collect_args.h"
 #include "pds_evaluate_args.h"
+#include "pds_evaluate_hist_args.h"
 #include "pds_simopt.h"
 
 namespace pds {
@@ -1117,40 +1118,29 @@ extern "C" int pds_evaluate_supported(const pds_handle *h) {
 }
 
 // P policies x E episodes in one launch: csrc/pds_evaluate.h (the caller's evaluation loop, utils/evaluation.py:52-107).
-// ONE body for pds_evaluate_policies, pds_evaluate_policies_metrics and pds_evaluate_policies_stats: the checks, the argument
-// block and the handle's state afterwards are stated once; METRICS adds the d_metrics check and selects the kernels' metrics
-// form, STATS (with METRICS) the d_obs_sums check and the stats form.
-template <bool METRICS, bool STATS = false>
-static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
-                                  const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
-                                  const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics, float *d_obs_sums,
-                                  void *stream) {
-  if (!h) return PDS_EINVAL;
+// What every population evaluation validates about the call, in front of anything that touches the handle (`any_null`: one of the
+// entry point's required pointers is NULL; `d_in`: the inputs the handle's observation gives the actors; d_metrics: checked where
+// given).  The env configuration is the entry point's own question, behind these.
+static int check_evaluate_call(pds_handle *h, const char *fn, bool any_null, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                               int d_in, const float *d_mean, const float *d_std, int max_steps, const float *d_metrics) {
   if (max_steps < 1) return fail(h, PDS_EINVAL, "%s: max_steps %d", fn, max_steps);
-  const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost || (METRICS && !d_metrics) || (STATS && !d_obs_sums);
   if (const int rc = check_rollout_call(h, fn, any_null, d_mean, d_std)) return rc;
-  if (METRICS && (((uintptr_t)d_metrics) & 15u)) return fail(h, PDS_EINVAL, "%s: d_metrics must be 16-byte aligned", fn);
-  if (STATS && (((uintptr_t)d_obs_sums) & 15u)) return fail(h, PDS_EINVAL, "%s: d_obs_sums must be 16-byte aligned", fn);
+  if (((uintptr_t)d_metrics) & 15u) return fail(h, PDS_EINVAL, "%s: d_metrics must be 16-byte aligned", fn);
   const long long n = h->cfg.num_envs;
   if (P < 1 || episodes_per_policy < 1 || episodes_per_policy > n || P > n || P * episodes_per_policy != n)
     return fail(h, PDS_EINVAL, "%s: P %lld x episodes_per_policy %lld is not the handle's %lld envs", fn, (long long)P,
                 (long long)episodes_per_policy, n);
   if (episodes_per_policy % kWave != 0)
     return fail(h, PDS_EINVAL, "%s: episodes_per_policy %lld is not a multiple of %d (one tile)", fn, (long long)episodes_per_policy, kWave);
-  const int D = h->obs_dim;
-  if (shape->d_in != D || shape->h1 < 1 || shape->h1 > 64 || shape->h2 < 1 || shape->h2 > 64 || shape->d_out != 4 ||
+  if (shape->d_in != d_in || shape->h1 < 1 || shape->h1 > 64 || shape->h2 < 1 || shape->h2 > 64 || shape->d_out != 4 ||
       (shape->activation != 0 && shape->activation != 1))
-    return fail(h, PDS_EINVAL, "%s: network shape (d_in must be the observation width %d, hidden <= 64, d_out 4, activation 0 or 1)", fn, D);
-  if (!rollout_supported(h->cfg.task, h->flags))
-    return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: what pds_rollout is built for) -- "
-                                     "pds_mlp_forward + pds_step give the same bits", fn);
-  DeviceGuard guard(h->cfg.device);
-  PDS_HIP(h, guard.err);
-  EvalKernelArgs<METRICS, STATS> ka;
-  memset(&ka, 0, sizeof(ka));
-  EvalArgs &ea = eval_args_head(ka);
-  if constexpr (STATS) { ka.m.metrics = d_metrics; ka.obs_sums = d_obs_sums; }
-  else if constexpr (METRICS) ka.metrics = d_metrics;
+    return fail(h, PDS_EINVAL, "%s: network shape (d_in must be the observation width %d, hidden <= 64, d_out 4, activation 0 or 1)", fn, d_in);
+  return PDS_OK;
+}
+// the EvalArgs every form of the evaluation launches with; the per-step streams point at the handle's sink row
+static int fill_evaluate_args(pds_handle *h, const char *fn, EvalArgs &ea, int64_t episodes_per_policy, const pds_mlp *shape,
+                              const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                              const float *d_obs0, float *d_ret, float *d_len, float *d_cost, void *stream) {
   base_args(h, ea.s);
   if (const int rc = point_at_step_sink(h, fn, ea.s, stream)) return rc;
   ea.s.k_steps = max_steps;
@@ -1162,6 +1152,35 @@ static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int6
   ea.T = max_steps;
   ea.obs0 = d_obs0;
   ea.ret = d_ret; ea.len = d_len; ea.cost = d_cost;
+  return PDS_OK;
+}
+// ONE body for pds_evaluate_policies, pds_evaluate_policies_metrics and pds_evaluate_policies_stats: the checks, the argument
+// block and the handle's state afterwards are stated once; METRICS adds the d_metrics check and selects the kernels' metrics
+// form, STATS (with METRICS) the d_obs_sums check and the stats form.
+template <bool METRICS, bool STATS = false>
+static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                                  const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                                  const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics, float *d_obs_sums,
+                                  void *stream) {
+  if (!h) return PDS_EINVAL;
+  const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost || (METRICS && !d_metrics) || (STATS && !d_obs_sums);
+  if (const int rc = check_evaluate_call(h, fn, any_null, P, episodes_per_policy, shape, h->obs_dim, d_mean, d_std, max_steps,
+                                         METRICS ? d_metrics : nullptr))
+    return rc;
+  if (STATS && (((uintptr_t)d_obs_sums) & 15u)) return fail(h, PDS_EINVAL, "%s: d_obs_sums must be 16-byte aligned", fn);
+  if (!rollout_supported(h->cfg.task, h->flags))
+    return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: what pds_rollout is built for) -- "
+                                     "pds_mlp_forward + pds_step give the same bits", fn);
+  DeviceGuard guard(h->cfg.device);
+  PDS_HIP(h, guard.err);
+  EvalKernelArgs<METRICS, STATS> ka;
+  memset(&ka, 0, sizeof(ka));
+  EvalArgs &ea = eval_args_head(ka);
+  if constexpr (STATS) { ka.m.metrics = d_metrics; ka.obs_sums = d_obs_sums; }
+  else if constexpr (METRICS) ka.metrics = d_metrics;
+  if (const int rc = fill_evaluate_args(h, fn, ea, episodes_per_policy, shape, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret,
+                                        d_len, d_cost, stream))
+    return rc;
   const int rc = launch_rollout(h, fn, max_steps, stream, [&](dim3 grid, hipStream_t s) {
     if constexpr (STATS) {
       if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_stats_hover(h->flags, grid, s, ka);
@@ -1202,6 +1221,53 @@ extern "C" int pds_evaluate_policies_stats(pds_handle *h, int64_t P, int64_t epi
                                            float *d_metrics, float *d_obs_sums, void *stream) {
   return evaluate_policies_call<true, true>(h, "pds_evaluate_policies_stats", P, episodes_per_policy, shape, d_params, d_mean,
                                             d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost, d_metrics, d_obs_sums, stream);
+}
+
+// ---- the population evaluation for observation histories: csrc/pds_evaluate_hist.h ----
+// whether pds_evaluate_policies_history has a kernel for this handle and this observation_history_size
+extern "C" int pds_evaluate_history_supported(const pds_handle *h, int history) {
+  if (!h) return PDS_EINVAL;
+  return h->cfg.auto_reset && rollout_hist_supported(h->cfg.task, h->flags) && history >= 1 && (long long)history * (h->obs_dim / 2) <= 192 ? 1 : 0;
+}
+// P policies x E episodes in one launch, the actors reading the last `history` halves of the handle's row.  The checks and the
+// handle's state afterwards are pds_evaluate_policies'; d_metrics is optional.
+extern "C" int pds_evaluate_policies_history(pds_handle *h, int history, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                                             const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                                             const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
+                                             void *stream) {
+  const char *fn = "pds_evaluate_policies_history";
+  if (!h) return PDS_EINVAL;
+  if (history < 1) return fail(h, PDS_EINVAL, "%s: history %d", fn, history);
+  const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost;
+  const int half = h->obs_dim / 2;
+  const long long HS = (long long)history * half;
+  if (HS > 192) return fail(h, PDS_EUNSUPPORTED, "%s: %d x %d = %lld network inputs (<= 192)", fn, history, half, HS);
+  if (const int rc = check_evaluate_call(h, fn, any_null, P, episodes_per_policy, shape, (int)HS, d_mean, d_std, max_steps, d_metrics))
+    return rc;
+  if (!rollout_hist_supported(h->cfg.task, h->flags))
+    return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: what pds_rollout_history is built for) -- "
+                                     "pds_mlp_forward + pds_step + pds_history_advance give the same bits", fn);
+  DeviceGuard guard(h->cfg.device);
+  PDS_HIP(h, guard.err);
+  EvalHistArgs ka;
+  memset(&ka, 0, sizeof(ka));
+  ka.m.metrics = d_metrics;
+  ka.H = history;
+  if (const int rc = fill_evaluate_args(h, fn, ka.m.e, episodes_per_policy, shape, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret,
+                                        d_len, d_cost, stream))
+    return rc;
+  const int hn = rollout_hist_tiles((int)HS);
+  const int rc = launch_rollout(h, fn, max_steps, stream, [&](dim3 grid, hipStream_t s) {
+    if (h->flags.ctrl != 0) {  // (TakeOff fixes control_mode PWM)
+      if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_hover_pid(h->flags, hn, grid, s, ka);
+      return h->cfg.task == PDS_TASK_CIRCLE && launch_evaluate_hist_circle_pid(h->flags, hn, grid, s, ka);
+    }
+    if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_hover(h->flags, hn, grid, s, ka);
+    if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_hist_circle(h->flags, hn, grid, s, ka);
+    return launch_evaluate_hist_takeoff(h->flags, hn, grid, s, ka);
+  });
+  if (rc == PDS_OK) { h->was_reset = false; h->after_evaluate = true; }  // (tiles stopped at different steps: pds_evaluate_policies)
+  return rc;
 }
 
 // ---- the fused off-policy collection: csrc/pds_collect.h (OffPolicyTrainer.step_env + the bookkeeping of learn_one_epoch) ----

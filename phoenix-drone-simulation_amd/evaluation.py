@@ -236,6 +236,12 @@ def fused_evaluation_built(env):
     return getattr(env, "observation_history_size", 2) == 2 and bool(env.lib.pds_evaluate_supported(env._handle))
 
 
+def fused_history_evaluation_built(env):
+    """Whether pds_evaluate_policies_history has a kernel for this env and its observation_history_size H: a handle with auto_reset
+    whose configuration is one the history rollout is built for, and H x half <= 192 network inputs."""
+    return env.lib.pds_evaluate_history_supported(env._handle, int(getattr(env, "observation_history_size", 2))) == 1
+
+
 # ---- flight-quality metrics (include/pds.h PDS_EM_*) -------------------------------------------------------------------
 METRIC_NAMES = ("roll_sq", "pitch_sq", "rate_sq", "action_rate_sq", "tilt_max", "saturated_steps", "roll_rate_crossings",
                 "pitch_rate_crossings")  # column j of `raw` = PDS_EM_* value j
@@ -408,7 +414,8 @@ class ObsSums:
 
 
 @torch.no_grad()
-def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None, metrics=False, obs_stats=False):
+def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None, metrics=False, obs_stats=False,
+                        history_fused=False):
     """-> (returns, ep_lengths, costs), each [P, E] float32 on the CPU: policy p of `population` flies the E = num_envs / P
     envs of block p, one episode per env, deterministically (action = actor mean), as `evaluate` does for one policy.
     metrics=True: -> (returns, ep_lengths, costs, FlightMetrics) -- the first three are the same bits; the kernel path is
@@ -423,6 +430,10 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     observation_history_size != 2 included -- with the env untouched.  fused=False: the composed path, per step one
     pds_mlp_forward per policy on its block of the observation + env.step + the accumulator updates of `evaluate`: the same
     bits.  fused="auto": the kernel where it is built, the composed path elsewhere.
+    history_fused=True (it changes nothing at observation_history_size == 2): an env with another history size H flies in one
+    launch too (pds_evaluate_policies_history, csrc/pds_evaluate_hist.h: the same bits as its composed path, metrics=True served
+    from the same launch) where `fused_history_evaluation_built(env)` holds; where it does not, and with obs_stats=True (no stats
+    form for histories), fused=True raises NotImplementedError with the env untouched and "auto" runs the composed path.
     The env is reset first and not afterwards: after the fused path it refuses to step until the next reset() of every env
     (a masked reset is refused as well).  `population` is not modified: the call works on device copies of its tensors.
     max_steps: the number of steps flown, by default the env's max_episode_steps (the TimeLimit ends every episode by then)."""
@@ -434,11 +445,21 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
             raise ValueError("fused: True, False or 'auto'")
     else:
         fused = bool(fused)  # (1, 0, numpy.bool_: below `fused is True` must mean what it says)
+    if not isinstance(history_fused, (bool, np.bool_)):
+        raise ValueError("history_fused: True or False")
     T = int(env._max_episode_steps if max_steps is None else max_steps)
     if T < 1:
         raise ValueError(f"max_steps = {T}")
+    H = int(getattr(env, "observation_history_size", 2))
+    use_history = bool(history_fused) and H != 2
     use_kernel = False
-    if fused is not False:
+    if fused is not False and use_history:
+        built = not obs_stats and fused_history_evaluation_built(env)
+        if fused is True and not built:
+            raise NotImplementedError("pds_evaluate_policies_history has no kernel for this call (built: auto_reset, the env configurations "
+                                      "of the history rollout, H x half <= 192 inputs, no obs_stats); fused='auto' runs the composed path")
+        use_kernel = built
+    elif fused is not False:
         built = fused_evaluation_built(env)
         if fused is True and not built:
             raise NotImplementedError("pds_evaluate_policies has no kernel for this env (built: observation_history_size 2, auto_reset, "
@@ -450,7 +471,17 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
     raw = slab = None
     obs, _ = env.reset()
-    if use_kernel and obs_stats:
+    if use_kernel and use_history:
+        shape = population.mlp(0)
+        if metrics:
+            raw = torch.zeros(n, len(METRIC_NAMES), device=dev)
+        obs = obs.contiguous()  # [N, H * half]: the histories env.reset() returns
+        with torch.cuda.device(dev):
+            rc = lib.pds_evaluate_policies_history(env._handle, H, P, E, C.byref(shape), _ptr(population.theta), _ptr(population.mean),
+                                                   _ptr(population.std), population.eps, T, _ptr(obs), _ptr(ret), _ptr(length),
+                                                   _ptr(cost), _ptr(raw), env._stream())
+        native.check(env._handle, rc, "pds_evaluate_policies_history")
+    elif use_kernel and obs_stats:
         shape = population.mlp(0)
         raw = torch.zeros(n, len(METRIC_NAMES), device=dev)
         slab = torch.zeros(n // 64, SLAB_WAVES, 2, SLAB_FEATURES, device=dev)

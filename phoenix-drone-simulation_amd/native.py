@@ -40,6 +40,7 @@ EXPORTS = ["pds_version", "pds_default_config", "pds_create", "pds_destroy", "pd
            "pds_adam_step", "pds_rollout", "pds_rollout_history",
            "pds_npg_workspace_floats", "pds_npg_fisher_vector_product", "pds_npg_cg_step", "pds_npg_surrogate_kl",
            "pds_simopt_latency_steps", "pds_simopt_evaluate", "pds_evaluate_supported", "pds_evaluate_policies", "pds_evaluate_policies_metrics", "pds_evaluate_policies_stats",
+           "pds_evaluate_history_supported", "pds_evaluate_policies_history",
            "pds_es_workspace_floats", "pds_es_perturb", "pds_es_gradient",
            "pds_ddpg_supported", "pds_ddpg_workspace_floats", "pds_ddpg_policy_grad", "pds_ddpg_target", "pds_polyak",
            "pds_sac_supported", "pds_sac_workspace_floats", "pds_sac_sample", "pds_sac_target", "pds_sac_policy_grad",
@@ -169,6 +170,8 @@ def load():
     later("pds_evaluate_policies", [vp, i64, i64, mp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp])
     later("pds_evaluate_policies_metrics", [vp, i64, i64, mp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp])
     later("pds_evaluate_policies_stats", [vp, i64, i64, mp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp])
+    later("pds_evaluate_history_supported", [vp, i32])
+    later("pds_evaluate_policies_history", [vp, i32, i64, i64, mp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp])
     later("pds_es_workspace_floats", [i64, i64])
     if hasattr(lib, "pds_es_workspace_floats"):
         lib.pds_es_workspace_floats.restype = i64
