@@ -1175,26 +1175,16 @@ static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int6
   PDS_HIP(h, guard.err);
   EvalKernelArgs<METRICS, STATS> ka;
   memset(&ka, 0, sizeof(ka));
-  EvalArgs &ea = eval_args_head(ka);
+  EvalArgs &ea = eval_head(ka);
   if constexpr (STATS) { ka.m.metrics = d_metrics; ka.obs_sums = d_obs_sums; }
   else if constexpr (METRICS) ka.metrics = d_metrics;
   if (const int rc = fill_evaluate_args(h, fn, ea, episodes_per_policy, shape, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret,
                                         d_len, d_cost, stream))
     return rc;
   const int rc = launch_rollout(h, fn, max_steps, stream, [&](dim3 grid, hipStream_t s) {
-    if constexpr (STATS) {
-      if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_stats_hover(h->flags, grid, s, ka);
-      if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_stats_circle(h->flags, grid, s, ka);
-      return launch_evaluate_stats_takeoff(h->flags, grid, s, ka);
-    } else if constexpr (METRICS) {
-      if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_metrics_hover(h->flags, grid, s, ka);
-      if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_metrics_circle(h->flags, grid, s, ka);
-      return launch_evaluate_metrics_takeoff(h->flags, grid, s, ka);
-    } else {
-      if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hover(h->flags, grid, s, ea);
-      if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_circle(h->flags, grid, s, ea);
-      return launch_evaluate_takeoff(h->flags, grid, s, ea);
-    }
+    if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hover<METRICS, STATS>(h->flags, grid, s, ka);
+    if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_circle<METRICS, STATS>(h->flags, grid, s, ka);
+    return launch_evaluate_takeoff<METRICS, STATS>(h->flags, grid, s, ka);
   });
   // tiles stopped at different steps: not a state to continue from -- every stepping entry point asks for pds_reset first
   if (rc == PDS_OK) { h->was_reset = false; h->after_evaluate = true; }

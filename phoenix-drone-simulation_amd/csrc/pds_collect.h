@@ -161,13 +161,8 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void collect_kernel(con
     for (int s = 0; s < T; ++s) {
       const CollectArgs &rl = *reinterpret_cast<const CollectArgs *>(&reload_args<401, true>(ra.s, s));
       rollout_wait_ge(&act_ready[team], kRolloutMlpWaves * (s + 1));  // the network waves have read o(s) and written a(s)
-      // (opaque per-iteration copies of the seed and the lane index: see step_k_kernel)
-      RngKey rks = rk;
-      int lane_s = lane;
-      asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
-      // every step's per-step streams go to the SAME sink row: offset 0, but opaque (see evaluate_kernel)
-      long long o1 = 0;
-      asm volatile("" : "+s"(o1));
+      PDS_OPAQUE_STEP_COPIES
+      PDS_SINK_ROW_OFFSET
       const float4 act = act_all[team][lane_s];
       StepOut so;
       step_once<V, kWave, RM, false>(rl.s, o1, rks, parity, nullptr, tile, nullptr, queue_all[team], scratch_all[team], lane_s,
@@ -270,35 +265,24 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void collect_kernel(con
   }
 }
 
-// grid.x = number of 64-env tiles; more tiles than CUs: two teams per block, where the two-team form needs no more scratch
-// memory per lane than the one-team form (EvalLaunch's rule, csrc/pds_evaluate.h: read off the code objects).
-template <class RV_>
-inline bool collect_two_teams_fit() {
-  static const bool fit = [] {
-    hipFuncAttributes one, two;
-    if (hipFuncGetAttributes(&one, reinterpret_cast<const void *>(&collect_kernel<RV_, 1>)) != hipSuccess ||
-        hipFuncGetAttributes(&two, reinterpret_cast<const void *>(&collect_kernel<RV_, 2>)) != hipSuccess) {
-      (void)hipGetLastError();
-      return false;
-    }
-    return two.localSizeBytes <= one.localSizeBytes;
-  }();
-  return fit;
-}
+// grid.x = number of 64-env tiles; more tiles than CUs: two teams per block, where the two-team form of this variant fits
+// (two_teams_fit, csrc/pds_rollout.h: read off the two code objects).
 struct CollectLaunch {
   dim3 grid;
   hipStream_t s;
-  const CollectArgs &ca;
+  const CollectArgs &args;
   template <class RV_>
   void run() const {
-    if (grid.x > (unsigned)kRolloutTwoTeamsAbove && collect_two_teams_fit<RV_>())
-      hipLaunchKernelGGL((collect_kernel<RV_, 2>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, ca);
+    if (grid.x > (unsigned)kRolloutTwoTeamsAbove && two_teams_fit<&collect_kernel<RV_, 1>, &collect_kernel<RV_, 2>>())
+      hipLaunchKernelGGL((collect_kernel<RV_, 2>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, args);
     else
-      hipLaunchKernelGGL((collect_kernel<RV_, 1>), grid, dim3(kRolloutThreads), 0, s, ca);
+      hipLaunchKernelGGL((collect_kernel<RV_, 1>), grid, dim3(kRolloutThreads), 0, s, args);
   }
 };
 
-// flags -> variant: {lean, reference default} x {with, without motor dynamics; TakeOff: without} -- collect_env_supported()
+// flags -> variant: {lean, reference default} x {with, without motor dynamics; TakeOff: without} -- collect_env_supported().
+// (Not fused_lean_or_full<TASK, 0, false> of csrc/pds_rollout.h, whose rows these are: that table decides on f.motor itself, so for
+// TakeOff it would instantiate two motor-dynamics variants in both team forms that collect_env_supported() never admits.)
 template <int TASK, bool MOTOR>
 inline bool collect_lean_or_full(const LaunchFlags &f, const CollectLaunch &l) {
   if (f.dr && f.tn && f.on) l.template run<Variant<TASK, MOTOR, true, false, true, true, 0, false, false>>();

@@ -92,9 +92,18 @@ PDS_DEV void eval_post(int *flag, int lane, int inc) {  // + inc, after every la
   if (lane == 0) __hip_atomic_fetch_add(flag, inc, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-PDS_DEV const EvalArgs &eval_head(const EvalArgs &ka) { return ka; }
-PDS_DEV const EvalArgs &eval_head(const EvalMetricsArgs &ka) { return ka.e; }
-PDS_DEV const EvalArgs &eval_head(const EvalStatsArgs &ka) { return ka.m.e; }
+// policy p's network: the launch's shape with the six tensors of row p of the flat [P, param_count] block
+PDS_DEV pds_mlp eval_policy_row(const EvalArgs &ea, long long p) {
+  pds_mlp m = ea.shape;
+  const float *row = ea.params + p * ea.param_count;  // W1 b1 W2 b2 W3 b3, torch order (pds_mlp_param_count)
+  m.w1 = row;
+  m.b1 = m.w1 + m.h1 * m.d_in;
+  m.w2 = m.b1 + m.h1;
+  m.b2 = m.w2 + m.h2 * m.h1;
+  m.w3 = m.b2 + m.h2;
+  m.b3 = m.w3 + m.d_out * m.h2;
+  return m;
+}
 
 // the metrics form's seven words per lane between two steps: [team][0][lane] = roll_sq, pitch_sq, rate_sq, action_rate_sq;
 // [team][1][lane] = tilt_max, saturated steps << 2 | sign bits, pitch crossings << 16 | roll crossings, unused
@@ -119,6 +128,104 @@ template <int NIN>
 struct EsSums<NIN, false> {};
 // v + (v of the lane whose row differs in bit `bit`): one level of the stats form's row tree (the sum is the same in both lanes)
 PDS_DEV float es_tree_add(float v, int bit) { return __fadd_rn(v, __shfl_xor(v, bit)); }
+
+// ---- the env wave of an evaluation, for evaluate_kernel and evaluate_hist_kernel (csrc/pds_evaluate_hist.h): statement macros
+// over the kernels' own locals, in the style of PDS_ENV_WAVE_BEGIN / PDS_RECORD_STEP of csrc/pds_rollout.h and for the reason
+// given there -- the metrics update as a forced-inline function (the state by reference) moved all 44 kernels of the TakeOff
+// metrics unit and all 8 of the TakeOff history unit: -21 .. +15 instructions, and the scratch of five spilling two-team forms
+// (208 -> 212, 216 -> 212 B, ...), which is what two_teams_fit decides by (profiles/fused_refactor_identity.txt).  Locals of
+// PDS_ENV_WAVE_BEGIN apart, they read lane, T, s, ix, ea, t and wave_base. ----
+// In front of the loop.  Declares the frozen accumulators ep_ret, ep_len, ep_cost and what they hang on:
+#define PDS_EVAL_WAVE_ACCUMULATORS                                                                         \
+  float ep_ret = 0.f, ep_len = 0.f, ep_cost = 0.f;                                                         \
+  bool alive = true;     /* this lane's env is in its first episode */                                     \
+  float c_step = 0.f;    /* the last step's cost, on its way back from the sink row ... */                 \
+  bool c_counts = false; /* ... and whether it belongs to the first episode */                             \
+  int qcount = 0;                                                                                          \
+  bool stopped = false;  /* wave-uniform: this tile has posted its stop */
+// The head of iteration s, down to the action.  A stopped tile falls through its remaining iterations (a scalar compare and a
+// branch each) instead of leaving the loop: the loop stays a counted one.  With a data-dependent exit -- `if (!more) break;` behind
+// the step -- the compiler gave the env wave of the observation-noise variants 40 more VGPRs (Hover at its defaults: 202 against
+// 149), and their two-team form spilled (profiles/evaluate_kernel_resources.txt).  The parity of the state ring goes on toggling
+// there: behind the loop it is parity(entry) ^ (T & 1) in EVERY tile, as after a rollout of T steps -- the library reads tile 0's
+// parity for all envs between launches (csrc/pds_api.hip field_kernel: which hist slot is the last action, which the one before).
+// Then the wait for the four network waves' posts of step s on `act_ready`, the cost of step s - 1 (read back behind its post),
+// and PDS_OPAQUE_STEP_COPIES / PDS_SINK_ROW_OFFSET of csrc/pds_rollout.h.  Declares rks, lane_s, o1 and act = `acts`[lane].
+#define PDS_EVAL_STEP_HEAD(act_ready, acts)                       \
+  if (stopped) { parity ^= 1; continue; }                         \
+  rollout_wait_ge(act_ready, kRolloutMlpWaves * (s + 1));         \
+  ep_cost += c_counts ? c_step : 0.f;                             \
+  PDS_OPAQUE_STEP_COPIES                                          \
+  PDS_SINK_ROW_OFFSET                                             \
+  const float4 act = acts[lane_s];
+// Behind step_once: the accumulator updates of evaluation.evaluate, in its order and its form (x + 0 for an env that has
+// finished).  Declares dn: the env finished in this step, whichever episode it was in.
+#define PDS_EVAL_RECORD_STEP(so)            \
+  ep_ret += alive ? so.reward : 0.f;        \
+  ep_len += alive ? 1.f : 0.f;              \
+  c_counts = alive;                         \
+  const bool dn = so.done || so.trunc;      \
+  alive = alive && !dn;
+// The tail of iteration s in two pieces (the stats form writes its mask between them).  Declares still: the lanes in their first
+// episode, and more (wave-uniform): the env wave will run step s + 1.
+#define PDS_EVAL_STILL                               \
+  const unsigned long long still = __ballot(alive);  \
+  const bool more = still != 0ull && s + 1 < T;
+// ... the ONE post of the iteration on `obs_ready`, +1 or the stop (the protocol at the head of this file); behind it the read-back
+// of this lane's cost of the step from the sink row of `el`.
+#define PDS_EVAL_STEP_TAIL(obs_ready, el)                   \
+  eval_post(obs_ready, lane, more ? 1 : kEvalStop);         \
+  c_step = *at(el.s.cost, ix);                              \
+  stopped = !more;
+// Behind the loop: the last step's cost; the state as the tile left it and the clock T ticks on, whichever step the tile stopped
+// at (the caller resets before it steps again); return, length and cost of the first episode.  RA: the kernel's argument struct,
+// ID: its reload_args tag; declares kl (the reloaded RA) and el (its EvalArgs).
+#define PDS_EVAL_WAVE_END(RA, ID)                                                              \
+  ep_cost += c_counts ? c_step : 0.f;                                                          \
+  const RA &kl = *reinterpret_cast<const RA *>(&reload_args<ID, true>(ea.s, T));               \
+  const EvalArgs &el = eval_head(kl);                                                          \
+  store_state<V>(el.s, ix, parity, S, true);                                                   \
+  advance_clock(el.s.st.clk, t, rk0, parity, (uint32_t)T, lane);                               \
+  *at(el.ret, ix) = ep_ret;                                                                    \
+  *at(el.len, ix) = ep_len;                                                                    \
+  *at(el.cost, ix) = ep_cost;
+// ---- the flight metrics (the head of this file: METRICS), `em` = this team's 2 x 64 float4 of em_lds ----
+// zero sums and the signs of x(0)'s roll and pitch rate
+#define PDS_EM_INIT(em)                                                                                                         \
+  em[lane] = make_float4(0.f, 0.f, 0.f, 0.f);                                                                                   \
+  em[kWave + lane] = make_float4(0.f, __int_as_float((S.e.wx < 0.f ? 1 : 0) | (S.e.wy < 0.f ? 2 : 0)), __int_as_float(0), 0.f);
+// x(s), the state the policy acted in, and a(s), raw, against u(k - 1) = the last action before the step: between the action read
+// and step_once, in a block of its own.  (Tilt: one compare each -- a NaN angle is passed over, whichever it is.)
+#define PDS_EM_STEP(em)                                                                                                                   \
+  const float4 sums = em[lane_s], rest = em[kWave + lane_s];                                                                              \
+  float m_roll = sums.x, m_pitch = sums.y, m_rate = sums.z, m_act = sums.w, m_tilt = rest.x;                                              \
+  int m_sat = __float_as_int(rest.y), m_cross = __float_as_int(rest.z);                                                                   \
+  const EnvRegs &e = S.e;                                                                                                                 \
+  m_roll = __fadd_rn(m_roll, alive ? __fmul_rn(e.roll, e.roll) : 0.f);                                                                    \
+  m_pitch = __fadd_rn(m_pitch, alive ? __fmul_rn(e.pitch, e.pitch) : 0.f);                                                                \
+  const float w2 = __fadd_rn(__fadd_rn(__fmul_rn(e.wx, e.wx), __fmul_rn(e.wy, e.wy)), __fmul_rn(e.wz, e.wz));                             \
+  m_rate = __fadd_rn(m_rate, alive ? w2 : 0.f);                                                                                           \
+  const float ar = fabsf(e.roll), ap = fabsf(e.pitch);                                                                                    \
+  m_tilt = (alive && ar > m_tilt) ? ar : m_tilt;                                                                                          \
+  m_tilt = (alive && ap > m_tilt) ? ap : m_tilt;                                                                                          \
+  const int neg = (e.wx < 0.f ? 1 : 0) | (e.wy < 0.f ? 2 : 0);                                                                            \
+  const int crossed = alive ? ((neg ^ m_sat) & 3) : 0;                                                                                    \
+  m_cross += (crossed & 1) | ((crossed & 2) << 15);                                                                                       \
+  m_sat = (m_sat & ~3) | neg;                                                                                                             \
+  const float d0 = __fsub_rn(act.x, S.h1.x), d1 = __fsub_rn(act.y, S.h1.y), d2 = __fsub_rn(act.z, S.h1.z), d3 = __fsub_rn(act.w, S.h1.w); \
+  const float dd = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)), __fmul_rn(d3, d3));           \
+  m_act = __fadd_rn(m_act, alive ? dd : 0.f);                                                                                             \
+  const bool sat = fabsf(act.x) > 1.f || fabsf(act.y) > 1.f || fabsf(act.z) > 1.f || fabsf(act.w) > 1.f;                                  \
+  m_sat += (alive && sat) ? 4 : 0;                                                                                                        \
+  em[lane_s] = make_float4(m_roll, m_pitch, m_rate, m_act);                                                                               \
+  em[kWave + lane_s] = make_float4(m_tilt, __int_as_float(m_sat), __int_as_float(m_cross), 0.f);
+// row `env` of `metrics` [N, 8] as two 16-byte pieces (every tile is full: env < N), in a block of its own
+#define PDS_EM_STORE(em, metrics)                                                                                 \
+  float4 *row = reinterpret_cast<float4 *>(metrics) + 2 * (wave_base + lane);                                     \
+  const float4 rest = em[kWave + lane];                                                                           \
+  const int m_sat = __float_as_int(rest.y), m_cross = __float_as_int(rest.z);                                     \
+  row[0] = em[lane];                                                                                              \
+  row[1] = make_float4(rest.x, (float)(m_sat >> 2), (float)(m_cross & 0xFFFF), (float)((unsigned)m_cross >> 16));
 
 template <class V_, int TEAMS, bool METRICS = false, bool STATS = false>
 __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(const EvalKernelArgs<METRICS, STATS> ka) {
@@ -160,15 +267,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
   // ---- prologue, per team: policy p's network and statistics and the tile's o(0) into LDS -----------------------------
   if (t < ntiles) {
     const long long p = t / ea.tiles_per_policy;
-    pds_mlp m = ea.shape;
-    const float *row = ea.params + p * ea.param_count;  // W1 b1 W2 b2 W3 b3, torch order (pds_mlp_param_count)
-    m.w1 = row;
-    m.b1 = m.w1 + m.h1 * m.d_in;
-    m.w2 = m.b1 + m.h1;
-    m.b2 = m.w2 + m.h2 * m.h1;
-    m.w3 = m.b2 + m.h2;
-    m.b3 = m.w3 + m.d_out * m.h2;
-    stage_net(m, w, ttid, kRolloutThreads);
+    stage_net(eval_policy_row(ea, p), w, ttid, kRolloutThreads);
     if (ttid < 64) {
       const bool on = ea.mean != nullptr && ttid < D;
       mus[ttid] = on ? ea.mean[p * D + ttid] : 0.f;
@@ -195,97 +294,35 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
     const bool active = true;
     const Idx<V> ix{wave_base, (uint32_t)lane};
     PDS_ENV_WAVE_BEGIN
-    float ep_ret = 0.f, ep_len = 0.f, ep_cost = 0.f;
-    bool alive = true;          // this lane's env is in its first episode
-    float c_step = 0.f;         // the last step's cost, on its way back from the sink row ...
-    bool c_counts = false;      // ... and whether it belongs to the first episode
-    int qcount = 0;
-    bool stopped = false;  // wave-uniform: this tile has posted its stop
+    PDS_EVAL_WAVE_ACCUMULATORS
     // METRICS: zero sums; bit 0 / 1 of the second word: wx / wy of the previous state was negative (x(0) has no previous state:
     // its own signs, no crossing)
     float4 *em = nullptr;
     if constexpr (METRICS) {
       em = em_lds<TEAMS>() + team * 2 * kWave;
-      em[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
-      em[kWave + lane] = make_float4(0.f, __int_as_float((S.e.wx < 0.f ? 1 : 0) | (S.e.wy < 0.f ? 2 : 0)), __int_as_float(0), 0.f);
+      PDS_EM_INIT(em)
     }
     for (int s = 0; s < T; ++s) {
       const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<301, true>(ea.s, s));
-      // A stopped tile falls through its remaining iterations (a scalar compare and a branch each) instead of leaving the loop:
-      // the loop stays a counted one.  With a data-dependent exit -- `if (!more) break;` below -- the compiler gave the env wave
-      // of the observation-noise variants 40 more VGPRs (Hover at its defaults: 202 against 149), and their two-team form
-      // spilled (profiles/evaluate_kernel_resources.txt).  The parity of the state ring goes on toggling there: behind the loop it is
-      // parity(entry) ^ (T & 1) in EVERY tile, as after a rollout of T steps -- the library reads tile 0's parity for all envs
-      // between launches (csrc/pds_api.hip field_kernel: which hist slot is the last action, which the one before).
-      if (stopped) { parity ^= 1; continue; }
-      rollout_wait_ge(&act_ready[team], kRolloutMlpWaves * (s + 1));  // the network waves have read o(s) and written a(s)
-      ep_cost += c_counts ? c_step : 0.f;
-      // (opaque per-iteration copies of the seed and the lane index: see step_k_kernel)
-      RngKey rks = rk;
-      int lane_s = lane;
-      asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
-      // every step's outputs go to the SAME sink row: offset 0, but opaque -- step_once renews its late views of the kernel
-      // arguments per iteration by this offset (reload_args' tag); a constant would hoist them out of the loop, into registers
-      long long o1 = 0;
-      asm volatile("" : "+s"(o1));
-      const float4 act = act_all[team][lane_s];
+      PDS_EVAL_STEP_HEAD(&act_ready[team], act_all[team])  // the network waves have read o(s) and written a(s)
       if constexpr (METRICS) {  // x(s), the state the policy acted in, and a(s), raw, against u(k - 1) = the last action before the step
-        const float4 sums = em[lane_s], rest = em[kWave + lane_s];
-        float m_roll = sums.x, m_pitch = sums.y, m_rate = sums.z, m_act = sums.w, m_tilt = rest.x;
-        int m_sat = __float_as_int(rest.y), m_cross = __float_as_int(rest.z);
-        const EnvRegs &e = S.e;
-        m_roll = __fadd_rn(m_roll, alive ? __fmul_rn(e.roll, e.roll) : 0.f);
-        m_pitch = __fadd_rn(m_pitch, alive ? __fmul_rn(e.pitch, e.pitch) : 0.f);
-        const float w2 = __fadd_rn(__fadd_rn(__fmul_rn(e.wx, e.wx), __fmul_rn(e.wy, e.wy)), __fmul_rn(e.wz, e.wz));
-        m_rate = __fadd_rn(m_rate, alive ? w2 : 0.f);
-        const float ar = fabsf(e.roll), ap = fabsf(e.pitch);  // (one compare each: a NaN angle is passed over, whichever it is)
-        m_tilt = (alive && ar > m_tilt) ? ar : m_tilt;
-        m_tilt = (alive && ap > m_tilt) ? ap : m_tilt;
-        const int neg = (e.wx < 0.f ? 1 : 0) | (e.wy < 0.f ? 2 : 0);
-        const int crossed = alive ? ((neg ^ m_sat) & 3) : 0;
-        m_cross += (crossed & 1) | ((crossed & 2) << 15);
-        m_sat = (m_sat & ~3) | neg;
-        const float d0 = __fsub_rn(act.x, S.h1.x), d1 = __fsub_rn(act.y, S.h1.y), d2 = __fsub_rn(act.z, S.h1.z), d3 = __fsub_rn(act.w, S.h1.w);
-        const float dd = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)), __fmul_rn(d3, d3));
-        m_act = __fadd_rn(m_act, alive ? dd : 0.f);
-        const bool sat = fabsf(act.x) > 1.f || fabsf(act.y) > 1.f || fabsf(act.z) > 1.f || fabsf(act.w) > 1.f;
-        m_sat += (alive && sat) ? 4 : 0;
-        em[lane_s] = make_float4(m_roll, m_pitch, m_rate, m_act);
-        em[kWave + lane_s] = make_float4(m_tilt, __int_as_float(m_sat), __int_as_float(m_cross), 0.f);
+        PDS_EM_STEP(em)
       }
       StepOut so;
       step_once<V, kWave, RM, false>(el.s, o1, rks, parity, nullptr, tile, nullptr, queue_all[team], scratch_all[team], lane_s,
                                      wave_base, ix, active, act, S, qcount, nullptr, &so PDS_STAMP_ARG);
       PDS_NEXT_TICK(rk, parity)
-      // the accumulator updates of evaluation.evaluate, in its order and its form (x + 0 for an env that has finished)
-      ep_ret += alive ? so.reward : 0.f;
-      ep_len += alive ? 1.f : 0.f;
-      c_counts = alive;
-      alive = alive && !(so.done || so.trunc);
-      const unsigned long long still = __ballot(alive);
-      const bool more = still != 0ull && s + 1 < T;  // wave-uniform
+      PDS_EVAL_RECORD_STEP(so)
+      PDS_EVAL_STILL
       if constexpr (STATS) {
         if (lane == 0) es_lds<TEAMS>()[team] = still;  // the mask of step s + 1, in front of the post
       }
-      eval_post(&obs_ready[team], lane, more ? 1 : kEvalStop);  // o(s + 1) is in the tile / this team's env wave has left
-      c_step = *at(el.s.cost, ix);  // (behind the post: see the head of this file)
-      stopped = !more;
+      PDS_EVAL_STEP_TAIL(&obs_ready[team], el)  // o(s + 1) is in the tile / this team's env wave has left
     }
-    ep_cost += c_counts ? c_step : 0.f;
-    // The state as the tile left it and the clock T ticks on, whichever step the tile stopped at: the caller resets before it
-    // steps again (pds_evaluate_policies leaves the handle "not reset").
-    const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<302, true>(ea.s, T));
-    store_state<V>(el.s, ix, parity, S, true);
-    advance_clock(el.s.st.clk, t, rk0, parity, (uint32_t)T, lane);
-    *at(el.ret, ix) = ep_ret;
-    *at(el.len, ix) = ep_len;
-    *at(el.cost, ix) = ep_cost;
-    if constexpr (METRICS) {  // row `env` of [N, 8] as two 16-byte pieces (every tile is full: env < N)
-      float4 *row = reinterpret_cast<float4 *>(reinterpret_cast<const EvalMetricsArgs *>(&el)->metrics) + 2 * (wave_base + lane);
-      const float4 rest = em[kWave + lane];
-      const int m_sat = __float_as_int(rest.y), m_cross = __float_as_int(rest.z);
-      row[0] = em[lane];
-      row[1] = make_float4(rest.x, (float)(m_sat >> 2), (float)(m_cross & 0xFFFF), (float)((unsigned)m_cross >> 16));
+    // (pds_evaluate_policies leaves the handle "not reset")
+    PDS_EVAL_WAVE_END(EvalArgs, 302)
+    if constexpr (METRICS) {
+      PDS_EM_STORE(em, reinterpret_cast<const EvalMetricsArgs *>(&el)->metrics)
     }
     return;
   }
@@ -350,109 +387,40 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
   }
 }
 
-// grid.x = number of 64-env tiles; more tiles than CUs: two teams per block (launch_rollout_variant's rule) -- unless the two-team
-// form of this variant spills where the one-team form does not.  One launch bound covers every wave of a block, so the ten waves
-// of two teams get the env wave's registers cut to 168 (three waves per SIMD) where one team's five leave it 256; the
-// observation-noise variants need 190-250 there (profiles/evaluate_kernel_resources.txt).  The rule is read off the code objects
-// instead of being listed by hand: the two-team form is launched where it needs no more scratch memory per lane than the
-// one-team form.
-template <class RV_, bool METRICS = false, bool STATS = false>
-inline bool eval_two_teams_fit() {
-  static const bool fit = [] {
-    hipFuncAttributes one, two;
-    if (hipFuncGetAttributes(&one, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 1, METRICS, STATS>)) != hipSuccess ||
-        hipFuncGetAttributes(&two, reinterpret_cast<const void *>(&evaluate_kernel<RV_, 2, METRICS, STATS>)) != hipSuccess) {
-      (void)hipGetLastError();
-      return false;
-    }
-    return two.localSizeBytes <= one.localSizeBytes;
-  }();
-  return fit;
-}
+// grid.x = number of 64-env tiles; more tiles than CUs: two teams per block (RolloutLaunch's rule) where the two-team form of
+// this variant and this kernel form fits (two_teams_fit, csrc/pds_rollout.h, on the form's own two code objects).
 template <bool METRICS, bool STATS = false>
 struct EvalLaunchT {
   dim3 grid;
   hipStream_t s;
-  const EvalKernelArgs<METRICS, STATS> &ea;
+  const EvalKernelArgs<METRICS, STATS> &args;
   template <class RV_>
   void run() const {
-    if (grid.x > (unsigned)kRolloutTwoTeamsAbove && eval_two_teams_fit<RV_, METRICS, STATS>())
-      hipLaunchKernelGGL((evaluate_kernel<RV_, 2, METRICS, STATS>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, ea);
+    if (grid.x > (unsigned)kRolloutTwoTeamsAbove && two_teams_fit<&evaluate_kernel<RV_, 1, METRICS, STATS>, &evaluate_kernel<RV_, 2, METRICS, STATS>>())
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 2, METRICS, STATS>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, args);
     else
-      hipLaunchKernelGGL((evaluate_kernel<RV_, 1, METRICS, STATS>), grid, dim3(kRolloutThreads), 0, s, ea);
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 1, METRICS, STATS>), grid, dim3(kRolloutThreads), 0, s, args);
   }
 };
-using EvalLaunch = EvalLaunchT<false>;
-using EvalMetricsLaunch = EvalLaunchT<true>;  // the same rule on the metrics form's own two code objects
-using EvalStatsLaunch = EvalLaunchT<true, true>;  // and on the stats form's
 
-// ---- flags -> variant, family by family: the variants launch_rollout_*_family (csrc/pds_rollout.h) instantiates, i.e. the
-// configurations rollout_supported() names.  `l.template run<Variant>()` launches. ----
-template <int TASK, int CTRL, bool LAT, class L>
-inline bool eval_lean_or_full(const LaunchFlags &f, const L &l) {
-  const bool lean = !f.dr && !f.tn && !f.on, full = f.dr && f.tn && f.on;
-  if (!lean && !full) return false;
-  if (f.motor) {
-    if (full) l.template run<Variant<TASK, true, true, false, true, true, CTRL, LAT, false>>();
-    else l.template run<Variant<TASK, true, false, false, false, false, CTRL, LAT, false>>();
-  } else {
-    if (full) l.template run<Variant<TASK, false, true, false, true, true, CTRL, LAT, false>>();
-    else l.template run<Variant<TASK, false, false, false, false, false, CTRL, LAT, false>>();
-  }
-  return true;
-}
-template <int TASK, bool MOTOR, bool GE, class L>
-inline void eval_pwm(const LaunchFlags &f, const L &l) {
-#define PDS_EVAL_CASE(DR, TN, ON) \
-  if (f.dr == DR && f.tn == TN && f.on == ON) return l.template run<Variant<TASK, MOTOR, DR, GE, TN, ON, 0, false, false>>()
-  PDS_EVAL_CASE(false, false, false); PDS_EVAL_CASE(true, true, true);
-  PDS_EVAL_CASE(true, false, false); PDS_EVAL_CASE(false, true, false); PDS_EVAL_CASE(false, false, true);
-  PDS_EVAL_CASE(true, true, false); PDS_EVAL_CASE(true, false, true); PDS_EVAL_CASE(false, true, true);
-#undef PDS_EVAL_CASE
-}
-template <int TASK, bool MOTOR, class L>
-inline bool eval_hold(const LaunchFlags &f, const L &l) {
-  if (!f.on || f.dr != f.tn) return false;
-  if (f.dr) l.template run<Variant<TASK, MOTOR, true, false, true, true, 0, false, true>>();
-  else l.template run<Variant<TASK, MOTOR, false, false, false, true, 0, false, true>>();
-  return true;
-}
-// The families are instantiated in translation units of their own (csrc/pds_evaluate_<task>[_pwm|_lat].hip);
-// launch_evaluate_<task> is the dispatcher in csrc/pds_evaluate_<task>.hip.  The metrics form: the same families with an
-// EvalMetricsLaunch, in csrc/pds_evaluate_metrics_<task>[_pwm|_lat].hip; the stats form: with an EvalStatsLaunch, in
-// csrc/pds_evaluate_stats_<task>[_pwm|_lat].hip.
-template <int TASK, class L>
-inline bool eval_pwm_family(const LaunchFlags &f, const L &l) {
-  constexpr bool kMotor = TASK != PDS_TASK_TAKEOFF;  // (TakeOff + motor dynamics: only with the latency ring)
-  if (f.ge) {
-    if constexpr (TASK == PDS_TASK_TAKEOFF) { eval_pwm<TASK, false, true>(f, l); return true; }
-    return false;
-  }
-  if constexpr (kMotor) { if (f.motor) { eval_pwm<TASK, true, false>(f, l); return true; } }
-  eval_pwm<TASK, false, false>(f, l);
-  return true;
-}
-template <int TASK, class L>
-inline bool eval_lat_family(const LaunchFlags &f, const L &l) {
-  if (f.ctrl == 0) return eval_lean_or_full<TASK, 0, true>(f, l);
-  if constexpr (TASK != PDS_TASK_TAKEOFF) {  // TakeOff fixes control_mode = 'PWM' (envs/takeoff.py:225)
-    if (f.ctrl == 1) return eval_lean_or_full<TASK, 1, true>(f, l);
-    return eval_lean_or_full<TASK, 2, true>(f, l);
-  }
-  return false;
-}
-template <int TASK, class L>
-inline bool eval_pid_hold_family(const LaunchFlags &f, const L &l) {
-  constexpr bool kMotor = TASK != PDS_TASK_TAKEOFF;
-  if (f.hold) {
-    if constexpr (kMotor) { if (f.motor) return eval_hold<TASK, true>(f, l); }
-    return eval_hold<TASK, false>(f, l);
-  }
-  if constexpr (TASK != PDS_TASK_TAKEOFF) {
-    if (f.ctrl == 1) return eval_lean_or_full<TASK, 1, false>(f, l);
-    if (f.ctrl == 2) return eval_lean_or_full<TASK, 2, false>(f, l);
-  }
-  return false;
-}
+// ---- the seven launch functions of pds_evaluate_args.h.  flags -> variant is the fused family's one table (fused_task and the
+// fused_*_family of csrc/pds_rollout.h) over an EvalLaunchT.  Each function is defined and explicitly instantiated by the
+// translation unit that holds its kernels, csrc/pds_evaluate[_metrics|_stats]_<task>[_pwm|_lat].hip, for that unit's form: a
+// definition every unit could see would instantiate a family's kernels in its task's dispatcher unit as well. ----
+// control_mode PWM (FAMILY = fused_pwm_family) or the latency ring (fused_lat_family) of Hover / Circle
+#define PDS_EVALUATE_FAMILY_UNIT(NAME, FAMILY, TASK, METRICS, STATS)                                                      \
+  template <bool M, bool S>                                                                                               \
+  bool NAME(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<M, S> &ka) {                             \
+    return FAMILY<TASK>(f, EvalLaunchT<M, S>{grid, s, ka});                                                               \
+  }                                                                                                                       \
+  template bool NAME<METRICS, STATS>(const LaunchFlags &, dim3, hipStream_t, const EvalKernelArgs<METRICS, STATS> &);
+// a task's dispatcher + the PID control modes and the Kalman hold; `...`: fused_task's `lat` and `pwm`, the unit's own form of the
+// two family functions (TakeOff, which holds all its families: nullptr, nullptr)
+#define PDS_EVALUATE_TASK_UNIT(NAME, TASK, METRICS, STATS, ...)                                                           \
+  template <bool M, bool S>                                                                                               \
+  bool NAME(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<M, S> &ka) {                             \
+    return fused_task<TASK>(f, EvalLaunchT<M, S>{grid, s, ka}, __VA_ARGS__);                                               \
+  }                                                                                                                       \
+  template bool NAME<METRICS, STATS>(const LaunchFlags &, dim3, hipStream_t, const EvalKernelArgs<METRICS, STATS> &);
 
 }  // namespace pds

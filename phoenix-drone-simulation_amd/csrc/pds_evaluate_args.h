@@ -43,33 +43,33 @@ static_assert(offsetof(EvalStatsArgs, m) == 0, "the stats kernel reads the head 
 // the argument block of evaluate_kernel<V, TEAMS, METRICS, STATS> and the EvalArgs at its head
 template <bool METRICS, bool STATS = false>
 using EvalKernelArgs = std::conditional_t<STATS, EvalStatsArgs, std::conditional_t<METRICS, EvalMetricsArgs, EvalArgs>>;
-inline EvalArgs &eval_args_head(EvalArgs &ka) { return ka; }
-inline EvalArgs &eval_args_head(EvalMetricsArgs &ka) { return ka.e; }
-inline EvalArgs &eval_args_head(EvalStatsArgs &ka) { return ka.m.e; }
+// ... on the host and on the device, for a const or a mutable block (EvalHistArgs of csrc/pds_evaluate_hist_args.h too: its first
+// member is an EvalMetricsArgs `m`, like EvalStatsArgs')
+template <class KA>
+__host__ __device__ inline auto &eval_head(KA &ka) {
+  if constexpr (std::is_same_v<std::remove_const_t<KA>, EvalArgs>) return ka;
+  else if constexpr (std::is_same_v<std::remove_const_t<KA>, EvalMetricsArgs>) return ka.e;
+  else return ka.m.e;
+}
 
-bool launch_evaluate_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
-bool launch_evaluate_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
-bool launch_evaluate_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
-// (their families, one translation unit each, like the rollout's: control_mode PWM with every noise setting / the latency ring)
-bool launch_evaluate_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
-bool launch_evaluate_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
-bool launch_evaluate_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
-bool launch_evaluate_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea);
-// the same seven for the metrics form (csrc/pds_evaluate_metrics_<task>[_pwm|_lat].hip)
-bool launch_evaluate_metrics_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
-bool launch_evaluate_metrics_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
-bool launch_evaluate_metrics_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
-bool launch_evaluate_metrics_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
-bool launch_evaluate_metrics_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
-bool launch_evaluate_metrics_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
-bool launch_evaluate_metrics_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea);
-// and for the stats form (csrc/pds_evaluate_stats_<task>[_pwm|_lat].hip)
-bool launch_evaluate_stats_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
-bool launch_evaluate_stats_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
-bool launch_evaluate_stats_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
-bool launch_evaluate_stats_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
-bool launch_evaluate_stats_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
-bool launch_evaluate_stats_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
-bool launch_evaluate_stats_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea);
+// The launch functions, one set for the three forms (METRICS, STATS = false, false: pds_evaluate_policies; true, false: .._metrics;
+// true, true: .._stats).  Each is defined and explicitly instantiated for one form by the translation unit that holds the form's
+// kernels: csrc/pds_evaluate[_metrics|_stats]_<task>.hip ...
+template <bool METRICS, bool STATS>
+bool launch_evaluate_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
+template <bool METRICS, bool STATS>
+bool launch_evaluate_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
+template <bool METRICS, bool STATS>
+bool launch_evaluate_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
+// ... and their families, csrc/pds_evaluate[_metrics|_stats]_<task>_{pwm,lat}.hip, like the rollout's: control_mode PWM with every
+// noise setting / the latency ring
+template <bool METRICS, bool STATS>
+bool launch_evaluate_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
+template <bool METRICS, bool STATS>
+bool launch_evaluate_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
+template <bool METRICS, bool STATS>
+bool launch_evaluate_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
+template <bool METRICS, bool STATS>
+bool launch_evaluate_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
 
 }  // namespace pds

@@ -4,6 +4,6 @@
 
 namespace pds {
 bool launch_evaluate_hist_circle(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka) {
-  return launch_evaluate_hist_task<PDS_TASK_CIRCLE>(f, hn, grid, s, ka);
+  return hist_task<PDS_TASK_CIRCLE, 0>(f, hn, EvalHistLaunch{grid, s, ka});
 }
 }  // namespace pds

@@ -5,6 +5,6 @@
 
 namespace pds {
 bool launch_evaluate_hist_circle_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka) {
-  return launch_evaluate_hist_pid<PDS_TASK_CIRCLE>(f, hn, grid, s, ka);
+  return hist_pid<PDS_TASK_CIRCLE>(f, hn, EvalHistLaunch{grid, s, ka});
 }
 }  // namespace pds

@@ -5,6 +5,6 @@
 
 namespace pds {
 bool launch_evaluate_hist_hover_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka) {
-  return launch_evaluate_hist_pid<PDS_TASK_HOVER>(f, hn, grid, s, ka);
+  return hist_pid<PDS_TASK_HOVER>(f, hn, EvalHistLaunch{grid, s, ka});
 }
 }  // namespace pds

@@ -1,13 +1,6 @@
-// pds_evaluate_hover.hip -- the fused policy evaluation (pds_evaluate.h) for one task: dispatcher + the PID control modes and the
-// Kalman hold; control_mode PWM with every noise setting: pds_evaluate_hover_pwm.hip, the latency ring: pds_evaluate_hover_lat.hip.
+// pds_evaluate_hover.hip -- evaluate_kernel (pds_evaluate.h), plain form: the task's dispatcher, the PID control modes, the Kalman hold.
 #include "pds_evaluate.h"
 
 namespace pds {
-bool launch_evaluate_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalArgs &ea) {
-  if (!rollout_supported(PDS_TASK_HOVER, f)) return false;
-  if (f.hold) return eval_pid_hold_family<PDS_TASK_HOVER>(f, EvalLaunch{grid, s, ea});
-  if (f.lat) return launch_evaluate_hover_lat(f, grid, s, ea);
-  if (f.ctrl == 0) return launch_evaluate_hover_pwm(f, grid, s, ea);
-  return eval_pid_hold_family<PDS_TASK_HOVER>(f, EvalLaunch{grid, s, ea});
-}
+PDS_EVALUATE_TASK_UNIT(launch_evaluate_hover, PDS_TASK_HOVER, false, false, launch_evaluate_hover_lat<M, S>, launch_evaluate_hover_pwm<M, S>)
 }  // namespace pds

@@ -1,14 +1,6 @@
-// pds_evaluate_metrics_circle.hip -- the fused policy evaluation with flight metrics (pds_evaluate.h, METRICS) for one task:
-// dispatcher + the PID control modes and the Kalman hold; control_mode PWM with every noise setting:
-// pds_evaluate_metrics_circle_pwm.hip, the latency ring: pds_evaluate_metrics_circle_lat.hip.  The variants of pds_evaluate_circle.hip.
+// pds_evaluate_metrics_circle.hip -- evaluate_kernel (pds_evaluate.h), metrics form: the task's dispatcher, the PID control modes, the Kalman hold.
 #include "pds_evaluate.h"
 
 namespace pds {
-bool launch_evaluate_metrics_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea) {
-  if (!rollout_supported(PDS_TASK_CIRCLE, f)) return false;
-  if (f.hold) return eval_pid_hold_family<PDS_TASK_CIRCLE>(f, EvalMetricsLaunch{grid, s, ea});
-  if (f.lat) return launch_evaluate_metrics_circle_lat(f, grid, s, ea);
-  if (f.ctrl == 0) return launch_evaluate_metrics_circle_pwm(f, grid, s, ea);
-  return eval_pid_hold_family<PDS_TASK_CIRCLE>(f, EvalMetricsLaunch{grid, s, ea});
-}
+PDS_EVALUATE_TASK_UNIT(launch_evaluate_circle, PDS_TASK_CIRCLE, true, false, launch_evaluate_circle_lat<M, S>, launch_evaluate_circle_pwm<M, S>)
 }  // namespace pds

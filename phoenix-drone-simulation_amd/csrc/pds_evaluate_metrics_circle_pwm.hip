@@ -1,8 +1,6 @@
-// pds_evaluate_metrics_circle_pwm.hip -- the metrics form of the kernels of pds_evaluate_circle_pwm.hip: control_mode PWM without
-// latency ring / Kalman hold, all eight settings of domain randomisation x thrust noise x observation noise, with and without
-// motor dynamics.
+// pds_evaluate_metrics_circle_pwm.hip -- evaluate_kernel (pds_evaluate.h), metrics form: control_mode PWM, every noise setting x motor dynamics.
 #include "pds_evaluate.h"
 
 namespace pds {
-bool launch_evaluate_metrics_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalMetricsArgs &ea) { return eval_pwm_family<PDS_TASK_CIRCLE>(f, EvalMetricsLaunch{grid, s, ea}); }
+PDS_EVALUATE_FAMILY_UNIT(launch_evaluate_circle_pwm, fused_pwm_family, PDS_TASK_CIRCLE, true, false)
 }  // namespace pds

@@ -1,7 +1,6 @@
-// pds_evaluate_stats_circle_lat.hip -- the stats form (METRICS and STATS) of the kernels of pds_evaluate_circle_lat.hip: the latency ring with
-// control_mode PWM and with the PID modes, {lean, reference default} x {with, without motor dynamics}.
+// pds_evaluate_stats_circle_lat.hip -- evaluate_kernel (pds_evaluate.h), stats form: the latency ring, PWM and PID modes.
 #include "pds_evaluate.h"
 
 namespace pds {
-bool launch_evaluate_stats_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalStatsArgs &ea) { return eval_lat_family<PDS_TASK_CIRCLE>(f, EvalStatsLaunch{grid, s, ea}); }
+PDS_EVALUATE_FAMILY_UNIT(launch_evaluate_circle_lat, fused_lat_family, PDS_TASK_CIRCLE, true, true)
 }  // namespace pds

@@ -136,6 +136,20 @@ PDS_DEV void rollout_post(int *flag, int lane) {  // +1, after every lane's LDS 
     atomicAdd(rl.stats + 2, st2);                                                                                             \
   }
 
+// In front of step_once, every kernel with an env wave (csrc/pds_evaluate.h, pds_collect.h, both rollout kernels): opaque
+// per-iteration copies of the seed and the lane index -- see step_k_kernel: their loop-invariant derivatives would otherwise be
+// formed in the loop header and spilled.  Reads rk and lane; declares rks and lane_s.
+#define PDS_OPAQUE_STEP_COPIES                                                             \
+  RngKey rks = rk;                                                                         \
+  int lane_s = lane;                                                                       \
+  asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
+// The kernels whose per-step streams all go to the SAME sink row (evaluation, collection): offset 0, but opaque -- step_once renews
+// its late views of the kernel arguments per iteration by this offset (reload_args' tag); a constant would hoist them out of the
+// loop, into registers.  Declares o1.
+#define PDS_SINK_ROW_OFFSET \
+  long long o1 = 0;         \
+  asm volatile("" : "+s"(o1));
+
 // ---- the network waves' sampling (both rollout kernels): ActorCritic.step's dist.sample() + log_prob().sum(-1), the
 // values of pds_gaussian_sample (csrc/pds_train.hip sample_kernel; draw and log-probability term: csrc/pds_device.h) ----
 // (Macros again: as forced-inline functions -- arrays by reference or a struct by value, either of the two alone -- they moved the
@@ -273,11 +287,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void rollout_kernel(con
       const unsigned long long q1 = __builtin_amdgcn_s_memtime();
 #endif
       if (!(PDS_ROLLOUT_SKIP & 2)) {
-        // (opaque per-iteration copies of the seed and the lane index: see step_k_kernel -- their loop-invariant
-        //  derivatives would otherwise be formed in the loop header and spilled)
-        RngKey rks = rk;
-        int lane_s = lane;
-        asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
+        PDS_OPAQUE_STEP_COPIES
         const float4 act = act_all[grp][lane_s];
         StepOut so;
 #ifdef PDS_STAMPS_RESET
@@ -433,78 +443,124 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void rollout_kernel(con
 //     {none, both} of DR + thrust noise x {with, without motor dynamics};
 //   the ground effect: TakeOff with control_mode PWM, every noise setting (round 6); nowhere else.
 // `grid.x` = number of 64-env tiles; more tiles than CUs: two teams per block.
-template <class RV_>
-inline void launch_rollout_variant(dim3 grid, hipStream_t s, const RolloutArgs &ra) {
-  if (grid.x > (unsigned)kRolloutTwoTeamsAbove)
-    hipLaunchKernelGGL((rollout_kernel<RV_, 2>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, ra);
-  else
-    hipLaunchKernelGGL((rollout_kernel<RV_, 1>), grid, dim3(kRolloutThreads), 0, s, ra);
+struct RolloutLaunch {
+  dim3 grid;
+  hipStream_t s;
+  const RolloutArgs &args;
+  template <class RV_>
+  void run() const {
+    if (grid.x > (unsigned)kRolloutTwoTeamsAbove)
+      hipLaunchKernelGGL((rollout_kernel<RV_, 2>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, args);
+    else
+      hipLaunchKernelGGL((rollout_kernel<RV_, 1>), grid, dim3(kRolloutThreads), 0, s, args);
+  }
+};
+// The other launchers of the fused family (EvalLaunchT csrc/pds_evaluate.h, CollectLaunch csrc/pds_collect.h) take the two-team
+// form above the same tile count -- unless the two-team form of this variant spills where the one-team form does not.  One launch
+// bound covers every wave of a block, so the ten waves of two teams get the env wave's registers cut to 168 (three waves per SIMD)
+// where one team's five leave it 256; the observation-noise variants of the evaluation need 190-250 there
+// (profiles/evaluate_kernel_resources.txt).  The rule is read off the code objects instead of being listed by hand: the two-team
+// form `Two` is launched where it needs no more scratch memory per lane than the one-team form `One`.
+template <auto One, auto Two>
+inline bool two_teams_fit() {
+  static const bool fit = [] {
+    hipFuncAttributes one, two;
+    if (hipFuncGetAttributes(&one, reinterpret_cast<const void *>(One)) != hipSuccess ||
+        hipFuncGetAttributes(&two, reinterpret_cast<const void *>(Two)) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    return two.localSizeBytes <= one.localSizeBytes;
+  }();
+  return fit;
 }
+
+// ---- flags -> variant, family by family, ONCE for every kernel of the fused family (rollout_kernel, evaluate_kernel in its three
+// forms; collect_kernel takes fused_lean_or_full): the configurations rollout_supported() names.  `l` is the kernel's launcher
+// object (grid, s, args; `l.template run<Variant>()` launches). ----
 // motor dynamics x {lean, full}
-template <int TASK, int CTRL, bool LAT>
-inline bool launch_rollout_lean_or_full(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) {
+template <int TASK, int CTRL, bool LAT, class L>
+inline bool fused_lean_or_full(const LaunchFlags &f, const L &l) {
   const bool lean = !f.dr && !f.tn && !f.on, full = f.dr && f.tn && f.on;
   if (!lean && !full) return false;
   if (f.motor) {
-    if (full) launch_rollout_variant<Variant<TASK, true, true, false, true, true, CTRL, LAT, false>>(grid, s, ra);
-    else launch_rollout_variant<Variant<TASK, true, false, false, false, false, CTRL, LAT, false>>(grid, s, ra);
+    if (full) l.template run<Variant<TASK, true, true, false, true, true, CTRL, LAT, false>>();
+    else l.template run<Variant<TASK, true, false, false, false, false, CTRL, LAT, false>>();
   } else {
-    if (full) launch_rollout_variant<Variant<TASK, false, true, false, true, true, CTRL, LAT, false>>(grid, s, ra);
-    else launch_rollout_variant<Variant<TASK, false, false, false, false, false, CTRL, LAT, false>>(grid, s, ra);
+    if (full) l.template run<Variant<TASK, false, true, false, true, true, CTRL, LAT, false>>();
+    else l.template run<Variant<TASK, false, false, false, false, false, CTRL, LAT, false>>();
   }
   return true;
 }
 // control_mode PWM without latency / hold: all eight noise settings (GE: the ground-effect extension, TakeOff only)
-template <int TASK, bool MOTOR, bool GE = false>
-inline void launch_rollout_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) {
-#define PDS_ROLLOUT_CASE(DR, TN, ON) \
-  if (f.dr == DR && f.tn == TN && f.on == ON) return launch_rollout_variant<Variant<TASK, MOTOR, DR, GE, TN, ON, 0, false, false>>(grid, s, ra)
-  PDS_ROLLOUT_CASE(false, false, false); PDS_ROLLOUT_CASE(true, true, true);
-  PDS_ROLLOUT_CASE(true, false, false); PDS_ROLLOUT_CASE(false, true, false); PDS_ROLLOUT_CASE(false, false, true);
-  PDS_ROLLOUT_CASE(true, true, false); PDS_ROLLOUT_CASE(true, false, true); PDS_ROLLOUT_CASE(false, true, true);
-#undef PDS_ROLLOUT_CASE
+template <int TASK, bool MOTOR, bool GE, class L>
+inline void fused_pwm(const LaunchFlags &f, const L &l) {
+#define PDS_FUSED_CASE(DR, TN, ON) \
+  if (f.dr == DR && f.tn == TN && f.on == ON) return l.template run<Variant<TASK, MOTOR, DR, GE, TN, ON, 0, false, false>>()
+  PDS_FUSED_CASE(false, false, false); PDS_FUSED_CASE(true, true, true);
+  PDS_FUSED_CASE(true, false, false); PDS_FUSED_CASE(false, true, false); PDS_FUSED_CASE(false, false, true);
+  PDS_FUSED_CASE(true, true, false); PDS_FUSED_CASE(true, false, true); PDS_FUSED_CASE(false, true, true);
+#undef PDS_FUSED_CASE
 }
-template <int TASK, bool MOTOR>
-inline bool launch_rollout_hold(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) {
+template <int TASK, bool MOTOR, class L>
+inline bool fused_hold(const LaunchFlags &f, const L &l) {
   if (!f.on || f.dr != f.tn) return false;
-  if (f.dr) launch_rollout_variant<Variant<TASK, MOTOR, true, false, true, true, 0, false, true>>(grid, s, ra);
-  else launch_rollout_variant<Variant<TASK, MOTOR, false, false, false, true, 0, false, true>>(grid, s, ra);
+  if (f.dr) l.template run<Variant<TASK, MOTOR, true, false, true, true, 0, false, true>>();
+  else l.template run<Variant<TASK, MOTOR, false, false, false, true, 0, false, true>>();
   return true;
 }
-// The families are instantiated in translation units of their own (csrc/pds_rollout_<task>[_pwm|_lat].hip: the build compiles
-// them in parallel); launch_rollout_task is the dispatcher in csrc/pds_rollout_<task>.hip.
-template <int TASK>
-inline bool launch_rollout_pwm_family(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) {
+// The families are instantiated in translation units of their own (csrc/pds_{rollout,evaluate,evaluate_metrics,evaluate_stats}_
+// <task>[_pwm|_lat].hip: the build compiles them in parallel).
+template <int TASK, class L>
+inline bool fused_pwm_family(const LaunchFlags &f, const L &l) {
   constexpr bool kMotor = TASK != PDS_TASK_TAKEOFF;  // (TakeOff + motor dynamics: only with the latency ring)
   if (f.ge) {  // round 6: BasePhysics.calculate_ground_effect (envs/physics.py:27-58) on the task it matters for (BASELINE config 4)
-    if constexpr (TASK == PDS_TASK_TAKEOFF) { launch_rollout_pwm<TASK, false, true>(f, grid, s, ra); return true; }
+    if constexpr (TASK == PDS_TASK_TAKEOFF) { fused_pwm<TASK, false, true>(f, l); return true; }
     return false;
   }
-  if constexpr (kMotor) { if (f.motor) { launch_rollout_pwm<TASK, true>(f, grid, s, ra); return true; } }
-  launch_rollout_pwm<TASK, false>(f, grid, s, ra);
+  if constexpr (kMotor) { if (f.motor) { fused_pwm<TASK, true, false>(f, l); return true; } }
+  fused_pwm<TASK, false, false>(f, l);
   return true;
 }
-template <int TASK>
-inline bool launch_rollout_lat_family(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) {
-  if (f.ctrl == 0) return launch_rollout_lean_or_full<TASK, 0, true>(f, grid, s, ra);
+template <int TASK, class L>
+inline bool fused_lat_family(const LaunchFlags &f, const L &l) {
+  if (f.ctrl == 0) return fused_lean_or_full<TASK, 0, true>(f, l);
   if constexpr (TASK != PDS_TASK_TAKEOFF) {  // TakeOff fixes control_mode = 'PWM' (envs/takeoff.py:225)
-    if (f.ctrl == 1) return launch_rollout_lean_or_full<TASK, 1, true>(f, grid, s, ra);
-    return launch_rollout_lean_or_full<TASK, 2, true>(f, grid, s, ra);
+    if (f.ctrl == 1) return fused_lean_or_full<TASK, 1, true>(f, l);
+    return fused_lean_or_full<TASK, 2, true>(f, l);
   }
   return false;
 }
-template <int TASK>
-inline bool launch_rollout_pid_hold_family(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) {
+template <int TASK, class L>
+inline bool fused_pid_hold_family(const LaunchFlags &f, const L &l) {
   constexpr bool kMotor = TASK != PDS_TASK_TAKEOFF;
   if (f.hold) {
-    if constexpr (kMotor) { if (f.motor) return launch_rollout_hold<TASK, true>(f, grid, s, ra); }
-    return launch_rollout_hold<TASK, false>(f, grid, s, ra);
+    if constexpr (kMotor) { if (f.motor) return fused_hold<TASK, true>(f, l); }
+    return fused_hold<TASK, false>(f, l);
   }
   if constexpr (TASK != PDS_TASK_TAKEOFF) {
-    if (f.ctrl == 1) return launch_rollout_lean_or_full<TASK, 1, false>(f, grid, s, ra);
-    if (f.ctrl == 2) return launch_rollout_lean_or_full<TASK, 2, false>(f, grid, s, ra);
+    if (f.ctrl == 1) return fused_lean_or_full<TASK, 1, false>(f, l);
+    if (f.ctrl == 2) return fused_lean_or_full<TASK, 2, false>(f, l);
   }
   return false;
+}
+// The dispatcher of a task's own translation unit (csrc/pds_{rollout,evaluate*}_<task>.hip), which also holds the PID control
+// modes and the Kalman hold.  Hover and Circle: the latency ring and control_mode PWM are the units behind `lat` and `pwm`, the
+// launch functions of that kernel form (same signature: flags, grid, stream, args); TakeOff holds all its families itself and passes nullptr.
+template <class L>
+using FusedFamilyFn = bool(const LaunchFlags &, dim3, hipStream_t, decltype(L::args));
+template <int TASK, class L>
+inline bool fused_task(const LaunchFlags &f, const L &l, FusedFamilyFn<L> *lat, FusedFamilyFn<L> *pwm) {
+  if (!rollout_supported(TASK, f)) return false;
+  if (f.hold) return fused_pid_hold_family<TASK>(f, l);
+  if constexpr (TASK == PDS_TASK_TAKEOFF) {  // (control_mode PWM only, envs/takeoff.py:225)
+    if (f.lat) return fused_lat_family<TASK>(f, l);
+    return fused_pwm_family<TASK>(f, l);
+  } else {
+    if (f.lat) return lat(f, l.grid, l.s, l.args);
+    if (f.ctrl == 0) return pwm(f, l.grid, l.s, l.args);
+    return fused_pid_hold_family<TASK>(f, l);
+  }
 }
 
 }  // namespace pds

@@ -4,10 +4,6 @@
 
 namespace pds {
 bool launch_rollout_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) {
-  if (!rollout_supported(PDS_TASK_CIRCLE, f)) return false;
-  if (f.hold) return launch_rollout_pid_hold_family<PDS_TASK_CIRCLE>(f, grid, s, ra);
-  if (f.lat) return launch_rollout_circle_lat(f, grid, s, ra);
-  if (f.ctrl == 0) return launch_rollout_circle_pwm(f, grid, s, ra);
-  return launch_rollout_pid_hold_family<PDS_TASK_CIRCLE>(f, grid, s, ra);
+  return fused_task<PDS_TASK_CIRCLE>(f, RolloutLaunch{grid, s, ra}, launch_rollout_circle_lat, launch_rollout_circle_pwm);
 }
 }  // namespace pds

@@ -3,5 +3,7 @@
 #include "pds_rollout.h"
 
 namespace pds {
-bool launch_rollout_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) { return launch_rollout_lat_family<PDS_TASK_CIRCLE>(f, grid, s, ra); }
+bool launch_rollout_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) {
+  return fused_lat_family<PDS_TASK_CIRCLE>(f, RolloutLaunch{grid, s, ra});
+}
 }  // namespace pds

@@ -34,6 +34,66 @@ PDS_DEV void gather_hist(const float *row, int d_in, const float *mus, const flo
   }
 }
 
+// ---- pds_history_advance (csrc/pds_history.hip, same values) for the env wave's own row `hrow` of the history tile, for both
+// history kernels.  Statement macros over a constant HALF in scope, like PDS_ENV_WAVE_BEGIN of csrc/pds_rollout.h and for its
+// reason: rollout_hist_kernel expands them in its loop, with its fin_rows copy between the two -- called as forced-inline template
+// functions they change every TakeOff rollout_hist_kernel (16-18 instructions fewer, another schedule).  evaluate_hist_kernel
+// (csrc/pds_evaluate_hist.h) was built on such a function and loses 5-6 instructions per kernel with the statements in its
+// loop, so its function stays, with these two macros as its body
+// (profiles/fused_refactor_identity.txt). ----
+// Shift by one half (`keep` = H HALF - HALF floats stay) and append the HALF floats at `newest`.  Blocks of reads, then the block's
+// writes: a read-then-write loop over one array serialises on the LDS latency of every element -- the compiler must assume the two
+// alias --, ~130 cycles x 51 moves for Hover H = 4: 18.7 -> 13 us per step.  16-byte aligned halves: b128 moves (8 consecutive
+// lanes cover all banks).
+#define PDS_HIST_SHIFT_APPEND(hrow, newest, keep)                                                                                                               \
+  if constexpr (HALF % 4 == 0) {                                                                                                                                \
+    for (int j0 = 0; j0 < keep; j0 += 32) {                                                                                                                     \
+      float4 buf[8];                                                                                                                                            \
+      _Pragma("unroll")                                                                                                                                         \
+      for (int u = 0; u < 8; ++u) buf[u] = (j0 + 4 * u < keep) ? *reinterpret_cast<const float4 *>(hrow + j0 + 4 * u + HALF) : make_float4(0.f, 0.f, 0.f, 0.f); \
+      _Pragma("unroll")                                                                                                                                         \
+      for (int u = 0; u < 8; ++u) if (j0 + 4 * u < keep) *reinterpret_cast<float4 *>(hrow + j0 + 4 * u) = buf[u];                                               \
+    }                                                                                                                                                           \
+    float4 nb[HALF / 4];                                                                                                                                        \
+    _Pragma("unroll")                                                                                                                                           \
+    for (int c = 0; c < HALF / 4; ++c) nb[c] = *reinterpret_cast<const float4 *>(newest + 4 * c);                                                               \
+    _Pragma("unroll")                                                                                                                                           \
+    for (int c = 0; c < HALF / 4; ++c) *reinterpret_cast<float4 *>(hrow + keep + 4 * c) = nb[c];                                                                \
+  } else {                                                                                                                                                      \
+    for (int j0 = 0; j0 < keep; j0 += 16) {                                                                                                                     \
+      float buf[16];                                                                                                                                            \
+      _Pragma("unroll")                                                                                                                                         \
+      for (int u = 0; u < 16; ++u) buf[u] = (j0 + u < keep) ? hrow[j0 + u + HALF] : 0.f;                                                                        \
+      _Pragma("unroll")                                                                                                                                         \
+      for (int u = 0; u < 16; ++u) if (j0 + u < keep) hrow[j0 + u] = buf[u];                                                                                    \
+    }                                                                                                                                                           \
+    float nb[HALF];                                                                                                                                             \
+    _Pragma("unroll")                                                                                                                                           \
+    for (int c = 0; c < HALF; ++c) nb[c] = newest[c];                                                                                                           \
+    _Pragma("unroll")                                                                                                                                           \
+    for (int c = 0; c < HALF; ++c) hrow[keep + c] = nb[c];                                                                                                      \
+  }
+// The restart of a finished env from its reset row `krow` (the step's row of the kernel's own tile): H - 1 copies of its first
+// half, then its second half (envs/base.py:417-431).
+#define PDS_HIST_RESTART(hrow, krow, H, keep)                                 \
+  float k0[HALF], k1[HALF];                                                   \
+  _Pragma("unroll")                                                           \
+  for (int c = 0; c < HALF; ++c) { k0[c] = krow[c]; k1[c] = krow[HALF + c]; } \
+  for (int j = 0; j < H - 1; ++j)                                             \
+    _Pragma("unroll")                                                         \
+    for (int c = 0; c < HALF; ++c) hrow[j * HALF + c] = k0[c];                \
+  _Pragma("unroll")                                                           \
+  for (int c = 0; c < HALF; ++c) hrow[keep + c] = k1[c];
+
+// The actor's pass for this lane's 16 rows, both history kernels: forward16_wide (csrc/pds_mlp_fwd.h) with the tile steps of
+// pds_mlp_forward's dispatch.  `m`: the actor's shape; reads wpi, x_own, n16, g; declares kh2 and the output `mu`.  (As a
+// forced-inline function it left every rollout_hist_kernel alone and moved the HN = 12 forms of evaluate_hist_kernel.)
+#define PDS_FORWARD16_WIDE(m, mu)                                                                                                         \
+  const bool kh2 = m.h1 == m.h2 && last_tile_steps(m.h1, kNT) == 2;                                                                       \
+  f32x4 mu;                                                                                                                               \
+  if (m.activation == 0) mu = kh2 ? forward16_wide<0, HN, S1, 2>(wpi, x_own, n16, g) : forward16_wide<0, HN, S1, 4>(wpi, x_own, n16, g);  \
+  else mu = kh2 ? forward16_wide<1, HN, S1, 2>(wpi, x_own, n16, g) : forward16_wide<1, HN, S1, 4>(wpi, x_own, n16, g);
+
 template <class V_, int HN>
 __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const RolloutHistArgs ra) {
   using namespace pds_mlpf;
@@ -103,9 +163,7 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
       const RolloutHistArgs &rl = *reinterpret_cast<const RolloutHistArgs *>(&reload_args<211, true>(ra.s, s));
       const long long o1 = (long long)s * rl.s.n;
       rollout_wait_ge(&act_ready, kRolloutMlpWaves * (s + 1));  // the network waves have read the histories and written a(s)
-      RngKey rks = rk;  // (opaque per-iteration copies: see step_k_kernel)
-      int lane_s = lane;
-      asm volatile("" : "+s"(rks.seed_lo), "+s"(rks.seed_hi), "+v"(lane_s));
+      PDS_OPAQUE_STEP_COPIES
       const float4 act = act_all[lane_s];
       StepOut so;
       step_once<V, kWave, RM, false>(rl.s, o1, rks, parity, nullptr, tile, nullptr, queue, scratch, lane_s, wave_base, ix, active, act, S,
@@ -120,35 +178,7 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
       const float *krow = tile + lane * TS;
       const float *newest = dn ? fin + lane * D + HALF : krow + HALF;
       const int keep = HS - HALF;
-      // (blocks of reads, then the block's writes: a read-then-write loop over one array serialises on the LDS latency of every
-      //  element -- the compiler must assume the two alias --, ~130 cycles x 51 moves for Hover H = 4: 18.7 -> 13 us per step)
-      if constexpr (HALF % 4 == 0) {  // 16-byte aligned halves: b128 moves (8 consecutive lanes cover all banks)
-        for (int j0 = 0; j0 < keep; j0 += 32) {
-          float4 buf[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) buf[u] = (j0 + 4 * u < keep) ? *reinterpret_cast<const float4 *>(hrow + j0 + 4 * u + HALF) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-          for (int u = 0; u < 8; ++u) if (j0 + 4 * u < keep) *reinterpret_cast<float4 *>(hrow + j0 + 4 * u) = buf[u];
-        }
-        float4 nb[HALF / 4];
-#pragma unroll
-        for (int c = 0; c < HALF / 4; ++c) nb[c] = *reinterpret_cast<const float4 *>(newest + 4 * c);
-#pragma unroll
-        for (int c = 0; c < HALF / 4; ++c) *reinterpret_cast<float4 *>(hrow + keep + 4 * c) = nb[c];
-      } else {
-        for (int j0 = 0; j0 < keep; j0 += 16) {
-          float buf[16];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) buf[u] = (j0 + u < keep) ? hrow[j0 + u + HALF] : 0.f;
-#pragma unroll
-          for (int u = 0; u < 16; ++u) if (j0 + u < keep) hrow[j0 + u] = buf[u];
-        }
-        float nb[HALF];
-#pragma unroll
-        for (int c = 0; c < HALF; ++c) nb[c] = newest[c];
-#pragma unroll
-        for (int c = 0; c < HALF; ++c) hrow[keep + c] = nb[c];
-      }
+      PDS_HIST_SHIFT_APPEND(hrow, newest, keep)
       // the final history of an env the TimeLimit cut bootstraps its path with V (also when it terminated on that step, and
       // for every env that finished on the rollout's last step: algs/iwpg/iwpg.py:374-379; the rule behind done_all[] of
       // rollout_kernel, where the reason for the two wordings is) -> the caller's slot list
@@ -172,15 +202,8 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();  // (the rows are overwritten below)
       }
-      if (dn) {  // restart: H - 1 copies of the reset row's first half, then its second half (envs/base.py:417-431)
-        float k0[HALF], k1[HALF];
-#pragma unroll
-        for (int c = 0; c < HALF; ++c) { k0[c] = krow[c]; k1[c] = krow[HALF + c]; }
-        for (int j = 0; j < H - 1; ++j)
-#pragma unroll
-          for (int c = 0; c < HALF; ++c) hrow[j * HALF + c] = k0[c];
-#pragma unroll
-        for (int c = 0; c < HALF; ++c) hrow[keep + c] = k1[c];
+      if (dn) {
+        PDS_HIST_RESTART(hrow, krow, H, keep)
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -240,44 +263,52 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
     PDS_DRAW_ACTION_NOISE(rl, g == 0, call0 + (unsigned long long)s + 1ull, env_own, d_out)
     rollout_wait_ge(&obs_ready, s);  // the histories of step s are in LDS
     gather_hist<HN>(hist + own * S1, HS, mus, iss, g, x_own);
-    const bool kh2 = rl.pi.h1 == rl.pi.h2 && last_tile_steps(rl.pi.h1, kNT) == 2;
-    f32x4 mu;
-    if (rl.pi.activation == 0) mu = kh2 ? forward16_wide<0, HN, S1, 2>(wpi, x_own, n16, g) : forward16_wide<0, HN, S1, 4>(wpi, x_own, n16, g);
-    else mu = kh2 ? forward16_wide<1, HN, S1, 2>(wpi, x_own, n16, g) : forward16_wide<1, HN, S1, 4>(wpi, x_own, n16, g);
+    PDS_FORWARD16_WIDE(rl.pi, mu)
     if (g == 0) PDS_EMIT_ACTION(rl, mu, d_out, act_all[own], o1 + env_own, own_ok);  // lane n16 owns sample `own`: outputs 0..3 of the actor
     rollout_post(&act_ready, lane);  // this wave is done with the histories of step s
   }
 }
 
-template <class RV_>
-inline void launch_rollout_hist_variant(int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra) {
-  if (hn == 4) hipLaunchKernelGGL((rollout_hist_kernel<RV_, 4>), grid, dim3(kRolloutThreads), 0, s, ra);
-  else if (hn == 6) hipLaunchKernelGGL((rollout_hist_kernel<RV_, 6>), grid, dim3(kRolloutThreads), 0, s, ra);
-  else if (hn == 8) hipLaunchKernelGGL((rollout_hist_kernel<RV_, 8>), grid, dim3(kRolloutThreads), 0, s, ra);
-  else hipLaunchKernelGGL((rollout_hist_kernel<RV_, 12>), grid, dim3(kRolloutThreads), 0, s, ra);
+// ---- flags -> variant and input width, ONCE for both history kernels.  `l` is the kernel's launcher object (grid, s, args);
+// `l.template run<Variant, HN>()` launches. ----
+// hn = rollout_hist_tiles(H half): the input widths the kernels are instantiated for
+template <class RV_, class L>
+inline void hist_width(int hn, const L &l) {
+  if (hn == 4) l.template run<RV_, 4>();
+  else if (hn == 6) l.template run<RV_, 6>();
+  else if (hn == 8) l.template run<RV_, 8>();
+  else l.template run<RV_, 12>();
 }
-// CTRL 0: control_mode PWM (csrc/pds_rollout_hist_<task>.hip); 1 / 2: AttitudeRate / Attitude, the PID state in the env wave's
-// registers like the rest of the env (csrc/pds_rollout_hist_<task>_pid.hip, translation units of their own)
-template <int TASK, int CTRL = 0>
-inline bool launch_rollout_hist_task(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra) {
+// {lean, reference-default noise} x {with, without motor dynamics; TakeOff: without}.  CTRL 0: control_mode PWM
+// (csrc/pds_{rollout,evaluate}_hist_<task>.hip); 1 / 2: AttitudeRate / Attitude, the PID state in the env wave's registers like the
+// rest of the env (csrc/pds_{rollout,evaluate}_hist_<task>_pid.hip, translation units of their own)
+template <int TASK, int CTRL, class L>
+inline bool hist_task(const LaunchFlags &f, int hn, const L &l) {
   static_assert(CTRL == 0 || TASK != PDS_TASK_TAKEOFF, "TakeOff fixes control_mode PWM (envs/takeoff.py:225)");
   if (!rollout_hist_supported(TASK, f) || f.ctrl != CTRL) return false;
   const bool full = f.on;
   if constexpr (TASK != PDS_TASK_TAKEOFF) {
     if (f.motor) {
-      if (full) launch_rollout_hist_variant<Variant<TASK, true, true, false, true, true, CTRL, false, false>>(hn, grid, s, ra);
-      else launch_rollout_hist_variant<Variant<TASK, true, false, false, false, false, CTRL, false, false>>(hn, grid, s, ra);
+      if (full) hist_width<Variant<TASK, true, true, false, true, true, CTRL, false, false>>(hn, l);
+      else hist_width<Variant<TASK, true, false, false, false, false, CTRL, false, false>>(hn, l);
       return true;
     }
   }
-  if (full) launch_rollout_hist_variant<Variant<TASK, false, true, false, true, true, CTRL, false, false>>(hn, grid, s, ra);
-  else launch_rollout_hist_variant<Variant<TASK, false, false, false, false, false, CTRL, false, false>>(hn, grid, s, ra);
+  if (full) hist_width<Variant<TASK, false, true, false, true, true, CTRL, false, false>>(hn, l);
+  else hist_width<Variant<TASK, false, false, false, false, false, CTRL, false, false>>(hn, l);
   return true;
 }
-template <int TASK>
-inline bool launch_rollout_hist_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra) {
-  if (f.ctrl == 1) return launch_rollout_hist_task<TASK, 1>(f, hn, grid, s, ra);
-  return launch_rollout_hist_task<TASK, 2>(f, hn, grid, s, ra);
+template <int TASK, class L>
+inline bool hist_pid(const LaunchFlags &f, int hn, const L &l) {
+  if (f.ctrl == 1) return hist_task<TASK, 1>(f, hn, l);
+  return hist_task<TASK, 2>(f, hn, l);
 }
+struct RolloutHistLaunch {
+  dim3 grid;  // one block per 64-env tile
+  hipStream_t s;
+  const RolloutHistArgs &args;
+  template <class RV_, int HN>
+  void run() const { hipLaunchKernelGGL((rollout_hist_kernel<RV_, HN>), grid, dim3(kRolloutThreads), 0, s, args); }
+};
 
 }  // namespace pds

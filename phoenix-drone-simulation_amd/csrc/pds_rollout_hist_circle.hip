@@ -4,6 +4,6 @@
 
 namespace pds {
 bool launch_rollout_hist_circle(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra) {
-  return launch_rollout_hist_task<PDS_TASK_CIRCLE>(f, hn, grid, s, ra);
+  return hist_task<PDS_TASK_CIRCLE, 0>(f, hn, RolloutHistLaunch{grid, s, ra});
 }
 }  // namespace pds

@@ -5,6 +5,6 @@
 
 namespace pds {
 bool launch_rollout_hist_circle_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra) {
-  return launch_rollout_hist_pid<PDS_TASK_CIRCLE>(f, hn, grid, s, ra);
+  return hist_pid<PDS_TASK_CIRCLE>(f, hn, RolloutHistLaunch{grid, s, ra});
 }
 }  // namespace pds

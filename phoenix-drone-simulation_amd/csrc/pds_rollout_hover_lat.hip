@@ -3,5 +3,7 @@
 #include "pds_rollout.h"
 
 namespace pds {
-bool launch_rollout_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) { return launch_rollout_lat_family<PDS_TASK_HOVER>(f, grid, s, ra); }
+bool launch_rollout_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) {
+  return fused_lat_family<PDS_TASK_HOVER>(f, RolloutLaunch{grid, s, ra});
+}
 }  // namespace pds

@@ -4,9 +4,6 @@
 
 namespace pds {
 bool launch_rollout_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra) {
-  if (!rollout_supported(PDS_TASK_TAKEOFF, f)) return false;
-  if (f.hold) return launch_rollout_pid_hold_family<PDS_TASK_TAKEOFF>(f, grid, s, ra);
-  if (f.lat) return launch_rollout_lat_family<PDS_TASK_TAKEOFF>(f, grid, s, ra);
-  return launch_rollout_pwm_family<PDS_TASK_TAKEOFF>(f, grid, s, ra);
+  return fused_task<PDS_TASK_TAKEOFF>(f, RolloutLaunch{grid, s, ra}, nullptr, nullptr);
 }
 }  // namespace pds

@@ -373,8 +373,8 @@ struct RolloutArgs {
 
 static_assert(offsetof(RolloutArgs, s) == 0, "reload_args() reads the head of the kernarg segment as a StepArgs");
 
-// The env configurations the fused rollout has a kernel for (csrc/pds_rollout.h launch_rollout_task / _family decide by the same
-// rule; pds_rollout asks BEFORE it touches the handle).
+// The env configurations the fused rollout has a kernel for (csrc/pds_rollout.h fused_task and the fused_*_family tables decide by the
+// same rule; pds_rollout asks BEFORE it touches the handle).
 inline bool rollout_supported(int task, const LaunchFlags &f) {
   if (f.ge) return task == PDS_TASK_TAKEOFF && f.ctrl == 0 && !f.lat && !f.hold && !f.motor;
   const bool lean = !f.dr && !f.tn && !f.on, full = f.dr && f.tn && f.on;

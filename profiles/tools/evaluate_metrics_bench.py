@@ -7,7 +7,7 @@ alternating within one process, the host clock around a call that ends in a devi
 
 Pass condition (exit status 1 otherwise): at every size the median of "fused with metrics" is not above the median of "composed
 with metrics".  Recorded, not a bar: the ratio with / without metrics next to the plain path's own min-max spread, and the team
-count of each launch, read off the library's code objects by the launcher's rule (csrc/pds_evaluate.h eval_two_teams_fit).
+count of each launch, read off the library's code objects by the launcher's rule (csrc/pds_rollout.h two_teams_fit).
 
   python profiles/tools/evaluate_metrics_bench.py > profiles/evaluate_metrics_timing.txt
 """

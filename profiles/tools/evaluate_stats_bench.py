@@ -8,7 +8,7 @@ ends in a device synchronise:
 
 Nothing here is a bar: the tool records the ratio stats / metrics next to the metrics path's own min-max spread, says where the
 stats form is slower than the composed path (exit status 0 either way), and names the team count of each launch, read off the
-library's code objects by the launcher's rule (csrc/pds_evaluate.h eval_two_teams_fit).
+library's code objects by the launcher's rule (csrc/pds_rollout.h two_teams_fit).
 
   python profiles/tools/evaluate_stats_bench.py > profiles/evaluate_stats_timing.txt
 """

@@ -1,7 +1,8 @@
-"""The dispatch table of pds_evaluate_policies, swept: csrc/pds_evaluate.h restates rollout_supported() (csrc/pds_types.h) by hand
-as template-flag lists (eval_pwm, eval_lean_or_full, eval_hold and the three families), in seven translation units, with a one-team
+"""The dispatch table of pds_evaluate_policies, swept: csrc/pds_rollout.h states rollout_supported() (csrc/pds_types.h) a second
+time, as the template-flag lists every kernel of the fused family is launched through (fused_pwm, fused_lean_or_full, fused_hold and
+the three families; the evaluation instantiates them over its EvalLaunchT), in seven translation units, with a one-team
 and a two-team form per variant (256 against 168 registers for the env wave: different generated code).  A swapped flag in one
-PDS_EVAL_CASE flies another env than the handle's; a family whose launcher says `false` for what pds_evaluate_supported promised
+PDS_FUSED_CASE flies another env than the handle's; a family whose launcher says `false` for what pds_evaluate_supported promised
 is an error code.  tests/variant_cases.py enumerates every configuration the constructor accepts and states the rule in its own
 words; here the library must agree with it, and EVERY supported configuration is flown in both forms, bit for bit against the
 composed path (whose env steps are pds_step's: the per-step kernels of that configuration)."""
@@ -56,7 +57,7 @@ def _population(env, P, seed):
 @pytest.mark.parametrize("vid,env_id,kw,fam", vc.SUPPORTED, ids=[v[0] for v in vc.SUPPORTED])
 def test_every_supported_configuration_fused_equals_composed(vid, env_id, kw, fam, P):
     """P = 3: three tiles, one team per block.  P = 257: 257 tiles -- above 256 the launcher puts two teams in a block where the
-    two-team form of the variant fits (eval_two_teams_fit), and the last block is half filled."""
+    two-team form of the variant fits (two_teams_fit), and the last block is half filled."""
     import phoenix_drone_simulation_amd as pds
     from phoenix_drone_simulation_amd.evaluation import evaluate_population, fused_evaluation_built
     from test_gpu_evaluate import _equal
