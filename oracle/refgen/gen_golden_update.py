@@ -14,7 +14,9 @@ restatement needs to repeat the two updates WITHOUT any randomness of its own:
   * per epoch the buffer's own outputs (adv, target_v, discounted_ret), the policy learning rate, Loss/Pi and Loss/Value.
 
 tests/test_trainer.py feeds the recorded rollouts and shuffles to `ppo.PPOTrainer.update()` (PyTorch-op path on CPU tensors,
-fused MFMA path on the GPU) and compares the parameters after each update.  Only data is written: tests/golden/update.npz.
+fused MFMA path on the GPU) and compares the parameters after each update.  Only data is written: tests/golden/update.npz,
+and tests/golden/update_options.npz -- the reference's update() on the epoch-0 batch with use_kl_early_stopping=True
+(early_stopping_pin below; outputs only: the KL sequence, the iteration it stopped at, the state_dict afterwards).
 Stand-ins (absent modules): pybullet*, gymnasium, mpi4py (one rank), torch.utils.tensorboard -- as for the other generators."""
 import copy
 import os
@@ -95,6 +97,8 @@ def main():
         out[f"e{e}_path_last_val"] = np.array([v for _, v in rec["paths"]], dtype=np.float32)
         out[f"e{e}_terminated"] = np.array(rec["term"], dtype=np.uint8)
         assert len(rec["term"]) == STEPS and rec["paths"][-1][0] == STEPS
+        if e == 0:
+            early_stopping_pin(alg, rec)
         alg.update()
         out[f"e{e}_shuffles"] = np.stack(rec["shuffles"])                                  # [train_v_iterations, STEPS]
         out[f"e{e}_loss_pi"] = np.float64(alg.loss_pi_before)
@@ -107,6 +111,63 @@ def main():
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path) // 1024, "kB;", len(out), "arrays; paths per epoch",
           [len(out[f"e{e}_path_end"]) for e in range(2)], "lr", [float(out[f"e{e}_lr"]) for e in range(2)])
+
+
+def early_stopping_pin(alg, rec):
+    """The reference's own update() on the epoch-0 batch with use_kl_early_stopping=True, between the rollout and the recorded
+    update: networks, optimisers, buffer pointers and both random generators are restored afterwards, so update.npz comes
+    out as before.  Pass 1 (target_kl = inf) reads the KL the stopping rule sees after each iteration (the argument of
+    mpi_tools.mpi_avg, iwpg.py:440); pass 2 runs at target_kl = sqrt(kl[4] kl[5]) and records the iteration of its `Reached ES
+    criterion` log line and the state_dict after the update.  Outputs only -> tests/golden/update_options.npz."""
+    import re
+    import phoenix_drone_simulation.utils.mpi_tools as mpi_tools
+
+    def snapshot():
+        return dict(ac=copy.deepcopy(alg.ac.state_dict()), pi=copy.deepcopy(alg.pi_optimizer.state_dict()),
+                    vf=copy.deepcopy(alg.vf_optimizer.state_dict()), np=np.random.get_state(), torch=torch.get_rng_state(),
+                    ptr=(alg.buf.ptr, alg.buf.path_start_idx), flags=(alg.use_kl_early_stopping, alg.target_kl),
+                    shuffles=len(rec["shuffles"]))
+
+    def restore(s):
+        alg.ac.load_state_dict(s["ac"]); alg.pi_optimizer.load_state_dict(s["pi"]); alg.vf_optimizer.load_state_dict(s["vf"])
+        np.random.set_state(s["np"]); torch.set_rng_state(s["torch"])
+        alg.buf.ptr, alg.buf.path_start_idx = s["ptr"]
+        alg.use_kl_early_stopping, alg.target_kl = s["flags"]
+        del rec["shuffles"][s["shuffles"]:]
+
+    snap = snapshot()
+    kls, lines = [], []
+    mpi_avg, log = mpi_tools.mpi_avg, alg.logger.log
+
+    def rec_avg(x):
+        kls.append(float(x))
+        return mpi_avg(x)
+
+    def rec_log(msg, *a, **k):
+        lines.append(str(msg))
+    mpi_tools.mpi_avg, alg.logger.log = rec_avg, rec_log
+    try:
+        alg.use_kl_early_stopping, alg.target_kl = True, float("inf")
+        alg.update()
+        kl_free = list(kls)
+        assert len(kl_free) == PI_ITERS and not lines
+        restore(snap)
+        target = float(np.sqrt(kl_free[4] * kl_free[5]))
+        del kls[:]
+        alg.use_kl_early_stopping, alg.target_kl = True, target
+        alg.update()
+        hits = [int(m.group(1)) for m in (re.search(r"Reached ES criterion after (\d+) steps", ln) for ln in lines) if m]
+        assert len(hits) == 1 and hits[0] == len(kls), (hits, kls)
+        out = dict(target_kl=np.float64(target), stop_iter=np.int64(hits[0]), kl_free=np.array(kl_free, dtype=np.float64),
+                   kl_stopped=np.array(kls, dtype=np.float64))
+        for k, v in alg.ac.state_dict().items():
+            out["sd_after__" + k] = v.numpy().copy()
+    finally:
+        mpi_tools.mpi_avg, alg.logger.log = mpi_avg, log
+        restore(snap)
+    path = os.path.join(HERE, "..", "..", "tests", "golden", "update_options.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, "target_kl %.6e" % target, "stop_iter", hits[0], "kl", ["%.3e" % x for x in kl_free])
 
 
 if __name__ == "__main__":

@@ -224,11 +224,14 @@ def value_loss(ac, obs, ret):
 def gae(rew, val, terminated, truncated, final_val, last_val, gamma, lam, rew_scale=0.0, rew_clip=10.0):
     """pds_gae on [T, N] device tensors -> (adv, target_v, discounted_ret)."""
     T, N = rew.shape
-    out = [torch.empty_like(rew) for _ in range(3)]
+    # the kernel reads and writes dense [T, N]: every input contiguous (final_val may be None), the outputs allocated dense
+    # (empty_like would keep the strides of a transposed `rew`)
+    out = [torch.empty((T, N), dtype=torch.float32, device=rew.device) for _ in range(3)]
     p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    rew, val, terminated, truncated, last_val = (t.contiguous() for t in (rew, val, terminated, truncated, last_val))
+    final_val = final_val.contiguous() if final_val is not None else None
     with torch.cuda.device(rew.device):  # pds_gae launches on the current device
-        rc = native.load().pds_gae(p(rew.contiguous()), p(val.contiguous()), p(terminated.contiguous()),
-                                   p(truncated.contiguous()), p(final_val), p(last_val.contiguous()),
+        rc = native.load().pds_gae(p(rew), p(val), p(terminated), p(truncated), p(final_val), p(last_val),
                                    C.c_float(gamma), C.c_float(lam), C.c_float(rew_scale), C.c_float(rew_clip),
                                    T, N, p(out[0]), p(out[1]), p(out[2]),
                                    C.c_void_p(torch.cuda.current_stream(rew.device).cuda_stream))
@@ -618,7 +621,7 @@ class PPOTrainer:
         with torch.no_grad():
             loss_pi_before, _ = ppo_loss(ac, data, self.clip_ratio, self.entropy_coef)
             p_dist = ac.pi.dist(data["obs"])
-        stop_iter = self.train_pi_iterations
+        stop_iter, last_kl = self.train_pi_iterations, None
         for i in range(self.train_pi_iterations):
             self.pi_opt.zero_grad()
             loss_pi, pi_info = ppo_loss(ac, data, self.clip_ratio, self.entropy_coef)
@@ -630,12 +633,17 @@ class PPOTrainer:
             if self.use_kl_early_stopping:
                 with torch.no_grad():
                     kl = _avg(torch.distributions.kl.kl_divergence(p_dist, ac.pi.dist(data["obs"])).mean())
-                if kl.item() > self.target_kl:
+                last_kl = kl.item()
+                if last_kl > self.target_kl:
                     stop_iter = i + 1
                     break
         self._update_running_statistics(raw_obs, disc_ret)
-        return dict(loss_pi=float(loss_pi_before), loss_v=loss_v_before, stop_iter=stop_iter,
+        # Entropy and PolicyRatio as the reference logs them: pi_info of the LAST iteration's loss (algs/iwpg/iwpg.py:426, 445-453)
+        info = dict(loss_pi=float(loss_pi_before), loss_v=loss_v_before, stop_iter=stop_iter,
                     entropy=float(pi_info["ent"].detach()), ratio=float(pi_info["ratio"].detach()))
+        if last_kl is not None:  # the last KL the early-stopping rule evaluated
+            info["kl"] = last_kl
+        return info
 
     def _fused_update(self, data, raw_obs, disc_ret, B, mbs):
         """The same update with the loss gradients from csrc/pds_mlp.hip: one fused pass over the batch
@@ -654,13 +662,14 @@ class PPOTrainer:
                     pass
             act, adv, logp_old = data["act"].contiguous(), data["adv"].contiguous(), data["log_p"].contiguous()
             log_std = ac.pi.log_std
-            # entropy of Normal(., sigma): sum(0.5 + 0.5 log 2 pi + log sigma), independent of the network
-            ent = float((0.5 + 0.5 * math.log(2 * math.pi) + log_std).sum())
+            # entropy of Normal(., sigma) per action dimension: 0.5 + 0.5 log 2 pi + log sigma, independent of the network; the
+            # loss and the log take dist.entropy().mean(), the mean over batch and action dimensions (algs/ppo/ppo.py:32, 37)
+            ent = float((0.5 + 0.5 * math.log(2 * math.pi) + log_std).mean())
             if self.use_kl_early_stopping:
                 with torch.no_grad():
                     mu_old = self.fm_pi.forward(obs)
             first = None
-            stop_iter = self.train_pi_iterations
+            stop_iter, last_kl = self.train_pi_iterations, None
             for i in range(self.train_pi_iterations):
                 # the value steps due by now: spread evenly over the policy iterations (one value step per policy step)
                 feed((i + 1) * v_total // self.train_pi_iterations - i * v_total // self.train_pi_iterations)
@@ -675,16 +684,24 @@ class PPOTrainer:
                     _avg(self.fm_pi.flat_grad)
                     self.fm_pi.adam_step(self.pi_opt.param_groups[0]["lr"])  # lr follows the LambdaLR schedule
                 if self.use_kl_early_stopping:
-                    with torch.no_grad():  # KL(N(mu_old, s) || N(mu_new, s)) = sum (mu_old - mu_new)^2 / (2 s^2)
-                        kl = _avg((((mu_old - self.fm_pi.forward(obs)) ** 2) / (2 * torch.exp(2 * log_std))).sum(-1).mean())
-                    if kl.item() > self.target_kl:
+                    # KL(N(mu_old, s) || N(mu_new, s)) per action dimension = (mu_old - mu_new)^2 / (2 s^2); the reference's stopping
+                    # rule takes kl_divergence(p, q).mean(), the mean over batch AND action dimensions (algs/iwpg/iwpg.py:436-440)
+                    with torch.no_grad():
+                        kl = _avg((((mu_old - self.fm_pi.forward(obs)) ** 2) / (2 * torch.exp(2 * log_std))).mean())
+                    last_kl = kl.item()
+                    if last_kl > self.target_kl:
                         stop_iter = i + 1
                         break
             feed(v_total)  # (whatever an early stop of the policy loop has left; not on an exception)
         self._update_running_statistics(raw_obs, disc_ret)
-        f = first.tolist()
-        return dict(loss_pi=f[0] / f[3] - self.entropy_coef * ent, loss_v=float(loss_v_before), stop_iter=stop_iter,
-                    entropy=ent, ratio=f[1] / f[3])
+        # Loss/Pi from the first iteration's sums (the loss before the update); PolicyRatio from the last iteration's, as the
+        # reference logs it (pi_info of the last loss it evaluated, algs/iwpg/iwpg.py:426, 445-453) -- `stats` still holds them
+        f, last = torch.stack([first, stats]).tolist()
+        info = dict(loss_pi=f[0] / f[3] - self.entropy_coef * ent, loss_v=float(loss_v_before), stop_iter=stop_iter,
+                    entropy=ent, ratio=last[1] / last[3])
+        if last_kl is not None:  # the last KL the early-stopping rule evaluated
+            info["kl"] = last_kl
+        return info
 
     def save_checkpoint(self, log_dir, activation=None):
         """The artefacts the reference's logger leaves per run (utils/loggers.py:382-407,

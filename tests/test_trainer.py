@@ -9,7 +9,9 @@ import pytest
 import torch
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "trainer.npz")
+import gae_oracle as go  # noqa: E402
 import golden_util as gu  # noqa: E402
+import ppo_update_cases as uo  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -74,32 +76,6 @@ def test_exploration_noise_schedule(g):
         assert float(torch.exp(ac.pi.log_std[0])) == pytest.approx(float(s), rel=1e-6)
 
 
-def _gae_numpy(rew, val, term, trunc, fval, last_val, gamma, lam, scale, clip):
-    """Host restatement of Buffer.finish_path per path (algs/core.py:461-533) for [T, N] arrays."""
-    T, N = rew.shape
-    adv, tv, dr = np.zeros_like(rew), np.zeros_like(rew), np.zeros_like(rew)
-    for n in range(N):
-        start = 0
-        for t in range(T):
-            end = term[t, n] or trunc[t, n] or t == T - 1
-            if not end:
-                continue
-            b = fval[t, n] if trunc[t, n] else (0.0 if term[t, n] else last_val[n])  # (cut wins: iwpg.py:374-379)
-            r = np.append(rew[start:t + 1, n], b).astype(np.float64)
-            v = np.append(val[start:t + 1, n], b).astype(np.float64)
-            disc = np.zeros(len(r)); acc = 0.0
-            for k in range(len(r) - 1, -1, -1):
-                acc = r[k] + gamma * acc; disc[k] = acc
-            rs = np.clip(r * scale, -clip, clip) if scale > 0 else r
-            deltas = rs[:-1] + gamma * v[1:] - v[:-1]
-            a = np.zeros(len(deltas)); acc = 0.0
-            for k in range(len(deltas) - 1, -1, -1):
-                acc = deltas[k] + gamma * lam * acc; a[k] = acc
-            adv[start:t + 1, n], tv[start:t + 1, n], dr[start:t + 1, n] = a, a + v[:-1], disc[:-1]
-            start = t + 1
-    return adv, tv, dr
-
-
 @pytest.mark.gpu
 def test_gae_kernel_matches_reference_buffer(g):
     """pds_gae on the exact trajectories the reference Buffer processed (4 paths: terminated,
@@ -125,6 +101,12 @@ def test_gae_kernel_matches_reference_buffer(g):
         np.testing.assert_allclose(adv.cpu().numpy()[:, 0], g[f"buf_{tag}_adv"], rtol=2e-5, atol=2e-5)
         np.testing.assert_allclose(tv.cpu().numpy()[:, 0], g[f"buf_{tag}_target_v"], rtol=2e-5, atol=2e-5)
         np.testing.assert_allclose(dr.cpu().numpy()[:, 0], g[f"buf_{tag}_discounted_ret"], rtol=2e-5, atol=2e-5)
+        # ... and to the float64 oracle within the kernel's own bar, 6 x 2^-24 x S element by element (tests/gae_oracle.py; the
+        # oracle reproduces these fixtures to 1e-6 S: tests/test_gae_oracle_cpu.py)
+        c = lambda x: np.asarray(x).reshape(T, 1)  # noqa: E731
+        want, S = go.gae_oracle(c(rew), c(val), c(term), c(trunc), c(fval), np.zeros(1), 0.99, 0.95, scale, 10.0)
+        m = go.margins([x.cpu().numpy() for x in (adv, tv, dr)], want, S)
+        assert max(m) <= 1.0, (tag, m)
 
 
 @pytest.mark.gpu
@@ -138,9 +120,16 @@ def test_gae_kernel_random_rollout():
     dev = torch.device("cuda")
     for scale in (0.0, 0.37):
         out = gae(*(torch.tensor(x, device=dev) for x in (rew, val, term, trunc, fval, last)), 0.99, 0.95, scale, 10.0)
-        ref = _gae_numpy(rew, val, term, trunc, fval, last, 0.99, 0.95, scale, 10.0)
-        for a, b in zip(out, ref):
-            np.testing.assert_allclose(a.cpu().numpy(), b, rtol=1e-4, atol=1e-4)
+        # the per-path form of the reference Buffer (float64) and the recursion that also yields S agree to float64 rounding;
+        # the kernel is within 6 x 2^-24 x S of them, element by element (tests/gae_oracle.py)
+        f32 = lambda x: float(np.float32(x))  # noqa: E731
+        ref = go.gae_numpy(rew.astype(np.float64), val.astype(np.float64), term, trunc, fval.astype(np.float64),
+                           last.astype(np.float64), f32(0.99), f32(0.95), f32(scale), 10.0)
+        want, S = go.gae_oracle(rew, val, term, trunc, fval, last, 0.99, 0.95, scale, 10.0)
+        for b, w, s in zip(ref, want, S):
+            assert np.all(np.abs(b - w) <= 1e-13 * s)
+        m = go.margins([a.cpu().numpy() for a in out], want, S)
+        assert max(m) <= 1.0, (scale, m)
 
 
 @pytest.mark.gpu
@@ -391,6 +380,10 @@ _ROLLOUT_BITWISE_CASES = [
     ("DroneHoverSimpleEnv-v0", dict(observation_history_size=6, use_motor_dynamics=True, observation_noise=-1,
                                     domain_randomization=-1, motor_thrust_noise=0), 64 * 300),                      # 102, > 256 tiles
     ("DroneCircleSimpleEnv-v0", dict(observation_history_size=6), 70),                                              # 120
+    # use_standardized_obs=False: NULL d_mean / d_std into pds_rollout and pds_rollout_history (`trainer`: PPOTrainer's kwargs)
+    ("DroneHoverSimpleEnv-v0", dict(trainer=dict(use_standardized_obs=False)), 200),
+    ("DroneHoverSimpleEnv-v0", dict(observation_history_size=4, trainer=dict(use_standardized_obs=False)), 200),
+    ("DroneCircleSimpleEnv-v0", dict(observation_history_size=8, trainer=dict(use_standardized_obs=False)), 130),
 ]
 
 
@@ -401,21 +394,46 @@ def test_fused_rollout_equals_per_step_rollout_bitwise(task, kw, n):
     step with the state in registers, V(final_obs), episode bookkeeping; csrc/pds_rollout.h) against the per-step
     kernels of round 2 (7 launches per step): every rollout buffer bit for bit, over two consecutive rollouts with an
     update of the running statistics in between, short episodes so that resets and TimeLimit truncations occur."""
-    _fused_rollout_against_per_step_rollout(task, kw, n, rollouts=2)
+    kw = dict(kw)
+    _fused_rollout_against_per_step_rollout(task, kw, n, rollouts=2, trainer_kw=kw.pop("trainer", None))
 
 
-def _fused_rollout_against_per_step_rollout(task, kw, n, rollouts, T=12):
+@pytest.mark.gpu
+def test_fused_rollout_equals_per_step_rollout_bitwise_with_a_reset_before_each_rollout():
+    """reset_each_rollout=True (the reference's epoch-end cut) on the history kernel over three rollouts, the epoch counter
+    advanced between them so that the second and third start with env.reset() and a re-initialised history on both paths:
+    trunc_buf[T - 1] covers every env that terminated on the last step (at least one does), and V(final_obs) agrees there
+    between the one-launch and the per-step path."""
+    _fused_rollout_against_per_step_rollout("DroneHoverSimpleEnv-v0", dict(observation_history_size=4), 200, rollouts=3,
+                                            trainer_kw=dict(reset_each_rollout=True))
+
+
+def _fused_rollout_against_per_step_rollout(task, kw, n, rollouts, T=12, trainer_kw=None):
     import phoenix_drone_simulation_amd as pds
     from phoenix_drone_simulation_amd.ppo import PPOTrainer
+    trainer_kw = dict(trainer_kw or {})
     tr = []
     for fused_rollout in (True, False):
         env = pds.make(task, num_envs=n, seed=3, max_episode_steps=9, **kw)
-        tr.append(PPOTrainer(env, rollout_len=T, epochs=4, seed=5, fused=True, graph_rollout=False, fused_rollout=fused_rollout))
+        tr.append(PPOTrainer(env, rollout_len=T, epochs=4, seed=5, fused=True, graph_rollout=False, fused_rollout=fused_rollout,
+                             **trainer_kw))
     a, b = tr
+    ended_on_last = 0
+    if trainer_kw.get("use_standardized_obs") is False:
+        assert a.ac.obs_oms is None and a._oms()[:2] == (None, None)
     for rnd in range(rollouts):
         sa, sb = a.roll_out(), b.roll_out()
         torch.cuda.synchronize()
         assert a.fused_rollout is True and b.fused_rollout is False
+        if trainer_kw.get("reset_each_rollout"):  # the cut wins over a termination on the last step, on both paths
+            for t_ in tr:
+                assert bool((t_.trunc_buf[T - 1] >= t_.term_buf[T - 1]).all())
+            at_cut = a.trunc_buf[T - 1].bool()
+            assert torch.equal(at_cut, b.trunc_buf[T - 1].bool())
+            assert torch.equal(a.fval_buf[T - 1][at_cut], b.fval_buf[T - 1][at_cut])
+            ended_on_last += int(a.term_buf[T - 1].sum())
+            print("reset_each_rollout: rollout", rnd, "terminated on the last step:", int(a.term_buf[T - 1].sum()), "cut there:",
+                  int(at_cut.sum()))
         for name in ("obs_buf", "act_buf", "logp_buf", "val_buf", "rew_buf", "term_buf", "trunc_buf", "ep_ret", "ep_len", "last_val"):
             x, y = getattr(a, name), getattr(b, name)
             assert torch.equal(x, y), (rnd, name, (x != y).nonzero()[:4])
@@ -445,6 +463,10 @@ def _fused_rollout_against_per_step_rollout(task, kw, n, rollouts, T=12):
             with torch.no_grad():
                 for p_ in t_.ac.parameters():
                     p_.mul_(1.01)
+            if trainer_kw.get("reset_each_rollout"):
+                t_.epoch += 1  # learn_one_epoch: roll_out resets the envs (and their histories) from the second epoch on
+    if trainer_kw.get("reset_each_rollout"):
+        assert a.epoch == rollouts > 1 and ended_on_last >= 1  # (the rows the cut is there for occurred)
     for t_ in tr:
         t_.env.close()
 
@@ -726,15 +748,7 @@ def test_trainer_stays_fused_up_to_192_inputs():
 
 
 # ---- one full update() of the reference's trainer, replayed (tests/golden/update.npz) ------------------------------------------
-class _ReplayEnv:
-    """Stands in for a DroneVecEnv where only the trainer's update is exercised (CPU test): one env, no stepping."""
-
-    def __init__(self, obs_dim, device):
-        self.num_envs, self.obs_dim, self.act_dim, self.device = 1, int(obs_dim), 4, torch.device(device)
-        self.env_id_base = 0
-
-    def reset(self):
-        return torch.zeros(1, self.obs_dim, device=self.device), {}
+_ReplayEnv = uo.ReplayEnv  # (one env, no stepping: only the trainer's update is exercised)
 
 
 def _replay_reference_updates(env, fused, rtol, atol):
@@ -745,31 +759,18 @@ def _replay_reference_updates(env, fused, rtol, atol):
     carry over from the first update into the second (algs/iwpg/iwpg.py:282-485, algs/ppo/ppo.py:22-40)."""
     import phoenix_drone_simulation_amd.ppo as ppo
     g = np.load(os.path.join(os.path.dirname(GOLD), "update.npz"))
-    T, D = int(g["steps"]), int(g["obs_dim"])
-    tr = ppo.PPOTrainer(env, rollout_len=T, epochs=int(g["epochs_total"]), gamma=float(g["gamma"]), lam=float(g["lam"]),
-                        clip_ratio=float(g["clip_ratio"]), pi_lr=float(g["pi_lr"]), vf_lr=float(g["vf_lr"]),
-                        train_pi_iterations=int(g["train_pi_iterations"]), train_v_iterations=int(g["train_v_iterations"]),
-                        num_mini_batches=int(g["num_mini_batches"]), seed=0, fused=fused, graph_rollout=False)
+    tr = uo.make_replay_trainer(g, env, fused)  # the recorded hyper-parameters and initial state_dict
     dev = env.device
-    with torch.no_grad():
-        for k, p_ in tr.ac.state_dict().items():
-            p_.copy_(torch.as_tensor(g["sd_init__" + k], device=dev))
     for e in range(2):
         d = gu.load_update_epoch(g, e, dev)
         assert abs(tr.pi_opt.param_groups[0]["lr"] - float(g[f"e{e}_lr"])) < 1e-12
-        tr.ac.update(frac=e / tr.epochs)
-        assert torch.allclose(tr.ac.pi.log_std.cpu(), torch.as_tensor(g[f"e{e}_log_std"], dtype=torch.float32), rtol=0, atol=1e-7)
-        tr.obs_buf.copy_(d["obs"]); tr.act_buf.copy_(d["act"]); tr.rew_buf.copy_(d["rew"]); tr.val_buf.copy_(d["val"])
-        tr.logp_buf.copy_(d["logp"]); tr.term_buf.copy_(d["term"]); tr.trunc_buf.copy_(d["trunc"]); tr.fval_buf.copy_(d["fval"])
-        tr.last_val = d["last_val"]
+        shuffles = uo.load_replay_epoch(tr, g, e, d)  # anneal (log_std asserted), rollout buffers, the recorded shuffles
         # the Buffer's own outputs (algs/core.py:461-533): reward scaling by the running return std of the epoch before
         scale = float(1.0 / (tr.ac.ret_oms.std.item() + tr.ac.ret_oms.eps))
         adv, tv, dr = ppo.gae(tr.rew_buf, tr.val_buf, tr.term_buf, tr.trunc_buf, tr.fval_buf, tr.last_val, tr.gamma, tr.lam,
                               scale, float(tr.ac.ret_oms.bound))
         for got, want, what in ((adv, d["adv"], "adv"), (tv, d["target_v"], "target_v"), (dr, d["disc_ret"], "discounted_ret")):
             gu.assert_close(got.reshape(-1).cpu().numpy(), want.cpu().numpy(), 2e-5, 2e-5, f"epoch {e} {what}")
-        shuffles = iter(d["shuffles"])
-        tr.perm_fn = lambda B: next(shuffles)
         info = tr.update()
         assert next(shuffles, None) is None  # every recorded shuffle was consumed: train_v_iterations of them
         assert abs(info["loss_pi"] - float(g[f"e{e}_loss_pi"])) < 1e-4 * max(1.0, abs(float(g[f"e{e}_loss_pi"]))), (e, info)
