@@ -158,9 +158,8 @@ class DroneVecEnv:
         self.render_mode = render_mode
         self.debug = debug
         self._handle = C.c_void_p()
-        with torch.cuda.device(self.device):
-            rc = self.lib.pds_create(C.byref(cfg), C.byref(self._handle))
-        native.check(None, rc, "pds_create")
+        with torch.cuda.device(self.device):  # (the handle is still NULL where pds_create refuses: the error text is the library's own)
+            native.call("pds_create", C.byref(cfg), C.byref(self._handle), handle=self._handle)
         self.obs_dim = self.lib.pds_obs_dim(self._handle)
         # The kernel produces the reference's default history of 2: [o(k-1), u(k-2), o(k), u(k-1)].  Other
         # sizes H (experiments/04_*: 1, 2, 4, 6, 8; envs/base.py:303-319) are composed on the device from
@@ -245,9 +244,7 @@ class DroneVecEnv:
             m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
             b["obs"].copy_(self._last_obs)  # envs outside the mask keep their last observation
         self._last_obs = b["obs"]
-        rc = self.lib.pds_reset(self._handle, C.c_void_p(m.data_ptr()) if m is not None else None,
-                                C.c_void_p(b["obs"].data_ptr()), self._stream())
-        native.check(self._handle, rc, "pds_reset")
+        native.call("pds_reset", self._handle, m, b["obs"], on=self.device, handle=self._handle)
         if self._hist is not None:
             return self._refill_history(b["obs"], m), {}
         return b["obs"], {}
@@ -262,10 +259,7 @@ class DroneVecEnv:
             m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
             b["obs"].copy_(self._last_obs)  # envs outside the mask keep their last observation
         self._last_obs = b["obs"]
-        rc = self.lib.pds_reset_from_samples(
-            self._handle, C.c_void_p(m.data_ptr()) if m is not None else None,
-            C.c_void_p(s.data_ptr()), C.c_void_p(b["obs"].data_ptr()), self._stream())
-        native.check(self._handle, rc, "pds_reset_from_samples")
+        native.call("pds_reset_from_samples", self._handle, m, s, b["obs"], on=self.device, handle=self._handle)
         if self._hist is not None:
             return self._refill_history(b["obs"], m), {}
         return b["obs"], {}
@@ -443,8 +437,7 @@ class DroneVecEnv:
             # the aliased action-history entries of the first two steps after a reset (agents.py:386, base.py:425-426)
             # are resolved in-kernel for observation_history_size == 2 only -- same refusal as the constructor's
             raise NotImplementedError("set_latency >= one time step with observation_history_size != 2 is not built")
-        rc = self.lib.pds_set_latency(self._handle, float(new_latency))
-        native.check(self._handle, rc, "pds_set_latency")
+        native.call("pds_set_latency", self._handle, float(new_latency), handle=self._handle)
 
     @property
     def latency_steps(self):
@@ -480,8 +473,7 @@ class DroneVecEnv:
         w = self.lib.pds_field_width(fid)
         dt = torch.int32 if name in native.INT_FIELDS else torch.float32
         out = torch.zeros(self.num_envs, w, dtype=dt, device=self.device)
-        rc = self.lib.pds_get_state(self._handle, fid, C.c_void_p(out.data_ptr()), self._stream())
-        native.check(self._handle, rc, f"pds_get_state({name})")
+        native.call("pds_get_state", self._handle, fid, out, on=self.device, handle=self._handle)
         return out
 
     def set_state(self, name, value):
@@ -489,15 +481,13 @@ class DroneVecEnv:
         w = self.lib.pds_field_width(fid)
         dt = torch.int32 if name in native.INT_FIELDS else torch.float32
         v = torch.as_tensor(value).to(device=self.device, dtype=dt).reshape(self.num_envs, w).contiguous()
-        rc = self.lib.pds_set_state(self._handle, fid, C.c_void_p(v.data_ptr()), self._stream())
-        native.check(self._handle, rc, f"pds_set_state({name})")
+        native.call("pds_set_state", self._handle, fid, v, on=self.device, handle=self._handle)
         torch.cuda.current_stream(self.device).synchronize()  # `v` may be a temporary
 
     def count_nonfinite(self):
         """Number of envs whose dynamic state holds a NaN / Inf (diagnostic; synchronises)."""
         out = C.c_int64(0)
-        rc = self.lib.pds_count_nonfinite(self._handle, C.byref(out), self._stream())
-        native.check(self._handle, rc, "pds_count_nonfinite")
+        native.call("pds_count_nonfinite", self._handle, C.byref(out), on=self.device, handle=self._handle)
         return int(out.value)
 
     def state_dict(self):
@@ -515,8 +505,7 @@ class DroneVecEnv:
                 self._hist = v.to(self.device).clone()
             elif name != "tick":
                 self.set_state(name, v)
-        rc = self.lib.pds_set_tick(self._handle, int(sd["tick"]))
-        native.check(self._handle, rc, "pds_set_tick")
+        native.call("pds_set_tick", self._handle, int(sd["tick"]), handle=self._handle)
 
     @property
     def bytes_per_env_step(self):

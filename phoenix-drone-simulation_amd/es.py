@@ -19,10 +19,9 @@ import torch
 
 from . import native
 from .evaluation import METRIC_NAMES, PolicyPopulation, evaluate_population
-from .fused import FusedMLP, _on, _ptr, gaussian_sample
+from .fused import gaussian_sample
 from .ppo import ActorCritic
 
-_ACT_ID = {"relu": 0, "tanh": 1}
 WARMUP_STEPS = 32  # obs_stats="warmup": random-action env steps that feed the observation statistics before they are frozen
 
 
@@ -123,7 +122,7 @@ class ESTrainer:
             raise ValueError(f"env.num_envs = {N} is not population x E for population = {P}")
         if (N // P) % 64 != 0:
             raise ValueError(f"episodes per policy E = {N} / {P} = {N // P} is not a multiple of 64 (one tile)")
-        if activation not in _ACT_ID:
+        if activation not in native.ACTIVATIONS:
             raise ValueError(f"activation {activation!r}: relu or tanh")
         if not (math.isfinite(sigma) and sigma > 0):
             raise ValueError(f"sigma = {sigma}")
@@ -154,13 +153,11 @@ class ESTrainer:
         params = [p for l in lin for p in (l.weight, l.bias)]
         self.n = sum(p.numel() for p in params)
         self.mu = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
-        m, off, ptrs = native.Mlp(), 0, []
+        off = 0
         for p in params:
             p.data = self.mu[off:off + p.numel()].view_as(p)
-            ptrs.append(p.data_ptr())
             off += p.numel()
-        m.d_in, (m.h1, m.h2), m.d_out, m.activation = env.obs_dim, self.hidden_sizes, env.act_dim, _ACT_ID[activation]
-        m.w1, m.b1, m.w2, m.b2, m.w3, m.b3 = ptrs
+        m = native.mlp(env.obs_dim, *self.hidden_sizes, env.act_dim, activation, tensors=params)
         if self.lib.pds_mlp_param_count(C.byref(m)) != self.n:
             raise ValueError("layer sizes outside the fused kernels' range (d_in <= 192, h1, h2 <= 64, d_out <= 8)")
         self._mlp = m
@@ -229,11 +226,7 @@ class ESTrainer:
         the kernel wrote (the trainer's own buffer, overwritten by the next ask)."""
         theta = self._theta
         if self.fused:
-            with _on(theta):
-                rc = self.lib.pds_es_perturb(_ptr(self.mu), self.n, self.H, self.sigma, self.seed, self.generation, self.pair_base,
-                                             _ptr(theta), FusedMLP._stream(theta))
-            if rc != native.OK:
-                raise RuntimeError(f"pds_es_perturb -> {rc}")
+            native.call("pds_es_perturb", self.mu, self.n, self.H, self.sigma, self.seed, self.generation, self.pair_base, theta, on=theta)
         else:
             step = self.sigma * self._noise()
             theta[0::2] = self.mu + step
@@ -256,19 +249,12 @@ class ESTrainer:
             w = pair_weights(centered_ranks(f)).to(self.mu.device).contiguous()
             scale = -1.0 / (2.0 * self.H * self.sigma)
         if self.fused:
-            with _on(w):
-                rc = self.lib.pds_es_gradient(_ptr(w), _ptr(self.mu), self.n, self.H, scale, self.l2, self.seed, self.generation,
-                                              self.pair_base, _ptr(self.grad), _ptr(self._workspace), FusedMLP._stream(w))
-            if rc != native.OK:
-                raise RuntimeError(f"pds_es_gradient -> {rc}")
+            native.call("pds_es_gradient", w, self.mu, self.n, self.H, scale, self.l2, self.seed, self.generation, self.pair_base,
+                        self.grad, self._workspace, on=w)
         else:
             self.grad.copy_(scale * (w @ self._noise()) + self.l2 * self.mu)
-        with _on(self.mu):
-            rc = self.lib.pds_adam_step(C.byref(self._mlp), _ptr(self.grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
-                                        self.generation + 1, self.lr, self.betas[0], self.betas[1], self.adam_eps,
-                                        FusedMLP._stream(self.mu))
-        if rc != native.OK:
-            raise RuntimeError(f"pds_adam_step -> {rc}")
+        native.call("pds_adam_step", self._mlp, self.grad, self.exp_avg, self.exp_avg_sq, self.generation + 1, self.lr, self.betas[0],
+                    self.betas[1], self.adam_eps, on=self.mu)
         self.generation += 1
 
     @torch.no_grad()

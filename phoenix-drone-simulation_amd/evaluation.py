@@ -13,7 +13,6 @@ With `metrics=True` the same launch also reports the flight-quality sums the ref
 (experiments/02_zero_shot_policy_transfer_hover_task/02_eval_hover_task.py): `FlightMetrics`; `metrics_from_arrays` scores a
 logged flight by the same definitions.  With `obs_stats=True` it also sums the observations the policies acted on, for a running
 standardisation (`ObsSums`; include/pds.h pds_evaluate_policies_stats)."""
-import ctypes as C
 import math
 import os
 
@@ -22,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import native
+from .native import _ptr
 
 
 def _as_policy(policy):
@@ -85,12 +85,7 @@ def get_batch(env, policy, steps):
 
 
 # ---- a population of policies in one launch ----------------------------------------------------------------------------
-_ACT_ID = {"relu": 0, "tanh": 1}
 _ACT_MODULE = {"relu": nn.ReLU, "tanh": nn.Tanh}
-
-
-def _ptr(t, byte_offset=0):
-    return C.c_void_p(t.data_ptr() + byte_offset) if t is not None else None
 
 
 def _actor_shape(net):
@@ -120,7 +115,7 @@ class PolicyPopulation:
         hidden_sizes = tuple(int(h) for h in hidden_sizes)
         if len(hidden_sizes) != 2:
             raise ValueError("two hidden layers")
-        if activation not in _ACT_ID:
+        if activation not in native.ACTIVATIONS:
             raise ValueError(f"activation {activation!r}: relu or tanh")
         self.d_in, self.hidden_sizes, self.d_out, self.activation = int(d_in), hidden_sizes, int(d_out), activation
         h1, h2 = hidden_sizes
@@ -210,14 +205,8 @@ class PolicyPopulation:
 
     def mlp(self, p=0):
         """struct pds_mlp of policy p: pointers into row p of theta."""
-        m = native.Mlp()
-        m.d_in, (m.h1, m.h2), m.d_out, m.activation = self.d_in, self.hidden_sizes, self.d_out, _ACT_ID[self.activation]
-        h1, h2 = self.hidden_sizes
-        base = self.theta.data_ptr() + 4 * p * self.param_count
-        for name, n in (("w1", h1 * self.d_in), ("b1", h1), ("w2", h2 * h1), ("b2", h2), ("w3", self.d_out * h2), ("b3", self.d_out)):
-            setattr(m, name, base)
-            base += 4 * n
-        return m
+        return native.mlp(self.d_in, *self.hidden_sizes, self.d_out, self.activation,
+                          base=self.theta.data_ptr() + 4 * p * self.param_count)
 
 
 def _check_population_call(env, population):
@@ -467,44 +456,26 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
         use_kernel = built
     population = population.to(env.device)
     dev, n, D = env.device, env.num_envs, env.obs_dim
-    lib = env.lib
     ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
     raw = slab = None
     obs, _ = env.reset()
-    if use_kernel and use_history:
-        shape = population.mlp(0)
-        if metrics:
+    if use_kernel:
+        if metrics or obs_stats:
             raw = torch.zeros(n, len(METRIC_NAMES), device=dev)
-        obs = obs.contiguous()  # [N, H * half]: the histories env.reset() returns
-        with torch.cuda.device(dev):
-            rc = lib.pds_evaluate_policies_history(env._handle, H, P, E, C.byref(shape), _ptr(population.theta), _ptr(population.mean),
-                                                   _ptr(population.std), population.eps, T, _ptr(obs), _ptr(ret), _ptr(length),
-                                                   _ptr(cost), _ptr(raw), env._stream())
-        native.check(env._handle, rc, "pds_evaluate_policies_history")
-    elif use_kernel and obs_stats:
-        shape = population.mlp(0)
-        raw = torch.zeros(n, len(METRIC_NAMES), device=dev)
-        slab = torch.zeros(n // 64, SLAB_WAVES, 2, SLAB_FEATURES, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.pds_evaluate_policies_stats(env._handle, P, E, C.byref(shape), _ptr(population.theta), _ptr(population.mean),
-                                                 _ptr(population.std), population.eps, T, _ptr(obs), _ptr(ret), _ptr(length),
-                                                 _ptr(cost), _ptr(raw), _ptr(slab), env._stream())
-        native.check(env._handle, rc, "pds_evaluate_policies_stats")
-    elif use_kernel and metrics:
-        shape = population.mlp(0)
-        raw = torch.zeros(n, len(METRIC_NAMES), device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.pds_evaluate_policies_metrics(env._handle, P, E, C.byref(shape), _ptr(population.theta), _ptr(population.mean),
-                                                   _ptr(population.std), population.eps, T, _ptr(obs), _ptr(ret), _ptr(length),
-                                                   _ptr(cost), _ptr(raw), env._stream())
-        native.check(env._handle, rc, "pds_evaluate_policies_metrics")
-    elif use_kernel:
-        shape = population.mlp(0)
-        with torch.cuda.device(dev):
-            rc = lib.pds_evaluate_policies(env._handle, P, E, C.byref(shape), _ptr(population.theta), _ptr(population.mean),
-                                           _ptr(population.std), population.eps, T, _ptr(obs), _ptr(ret), _ptr(length), _ptr(cost),
-                                           env._stream())
-        native.check(env._handle, rc, "pds_evaluate_policies")
+        if obs_stats:
+            slab = torch.zeros(n // 64, SLAB_WAVES, 2, SLAB_FEATURES, device=dev)
+        # four entry points, one argument list: the history form leads with H, the others trail d_metrics / d_obs_sums
+        if use_history:  # (never with obs_stats)
+            obs = obs.contiguous()  # [N, H * half]: the histories env.reset() returns
+            name, lead, trail = "pds_evaluate_policies_history", (H,), (raw,)
+        elif obs_stats:
+            name, lead, trail = "pds_evaluate_policies_stats", (), (raw, slab)
+        elif metrics:
+            name, lead, trail = "pds_evaluate_policies_metrics", (), (raw,)
+        else:
+            name, lead, trail = "pds_evaluate_policies", (), ()
+        native.call(name, env._handle, *lead, P, E, population.mlp(0), population.theta, population.mean, population.std,
+                    population.eps, T, obs, ret, length, cost, *trail, on=dev, handle=env._handle)
     else:
         mlps = [population.mlp(p) for p in range(P)]
         act = torch.empty(n, 4, device=dev)
@@ -519,15 +490,9 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
         for _ in range(T):
             if metrics:  # x(s): the state the policy acts in
                 rpy, omega, last = env.get_state("rpy"), env.get_state("omega"), env.get_state("last_action")
-            stream = env._stream()
-            with torch.cuda.device(dev):
-                for p in range(P):
-                    rc = lib.pds_mlp_forward(C.byref(mlps[p]), _ptr(obs, 4 * p * E * D), None, E,
-                                             _ptr(population.mean, 4 * p * D) if has else None,
-                                             _ptr(population.std, 4 * p * D) if has else None, population.eps,
-                                             _ptr(act, 16 * p * E), stream)
-                    if rc != native.OK:
-                        raise RuntimeError(f"pds_mlp_forward -> {rc}")
+            for p in range(P):
+                native.call("pds_mlp_forward", mlps[p], _ptr(obs, 4 * p * E * D), None, E, _ptr(population.mean, 4 * p * D) if has else None,
+                            _ptr(population.std, 4 * p * D) if has else None, population.eps, _ptr(act, 16 * p * E), on=dev)
             if metrics:
                 prev_neg = _compose_metrics(acc, prev_neg, alive, rpy, omega, act, last)
             if obs_stats:  # o(s), for the envs alive in front of step s

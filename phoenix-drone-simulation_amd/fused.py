@@ -26,36 +26,16 @@ import torch.nn as nn
 
 from . import native
 
-_ACT = {"relu": 0, "tanh": 1}
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
-_NULL = _NullCtx()
-
-
-def _on(t):
-    """Context that makes t's device current if it is not (a process that holds envs / networks on several
-    GPUs must not launch on, or take the stream of, whichever device happens to be current)."""
-    return _NULL if t.device.index == torch.cuda.current_device() else torch.cuda.device(t.device)
+_ptr, _on = native._ptr, native.on_device  # (for direct calls; every launch below enters the library through native.call)
 
 
 class FusedMLP:
-    """View of `nn.Sequential(Linear, act, Linear, act, Linear[, Identity])` as a struct pds_mlp."""
+    """View of `nn.Sequential(Linear, act, Linear, act, Linear[, Identity])` as a struct pds_mlp (`m`; native.call re-binds its
+    pointers wherever a FusedMLP is an argument)."""
 
     def __init__(self, net, activation):
         lin = [l for l in net if isinstance(l, nn.Linear)]
-        if len(lin) != 3 or activation not in _ACT:
+        if len(lin) != 3 or activation not in native.ACTIVATIONS:
             raise NotImplementedError("fused kernels cover 2 hidden layers with relu or tanh")
         self.lin = lin
         self.params = [p for l in lin for p in (l.weight, l.bias)]
@@ -63,11 +43,8 @@ class FusedMLP:
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                 raise ValueError("fused kernels need contiguous float32 parameters on the HIP device")
         self.lib = native.load()
-        m = native.Mlp()
-        m.d_in, m.h1, m.h2, m.d_out = lin[0].in_features, lin[0].out_features, lin[1].out_features, lin[2].out_features
-        m.activation = _ACT[activation]
-        self.m = m
-        self._bind()
+        self.m = m = native.mlp(lin[0].in_features, lin[0].out_features, lin[1].out_features, lin[2].out_features, activation,
+                                tensors=self.params)
         n = self.lib.pds_mlp_param_count(C.byref(m))
         if n < 0:
             raise ValueError("layer sizes outside the fused kernels' range (d_in <= 192, h1, h2 <= 64, d_out <= 8)")
@@ -81,26 +58,19 @@ class FusedMLP:
         self.workspace = torch.empty(self.lib.pds_mlp_workspace_floats(C.byref(m)), device=dev)
 
     def _bind(self):
-        m, l = self.m, self.lin
-        m.w1, m.b1, m.w2, m.b2, m.w3, m.b3 = (p.data_ptr() for p in (l[0].weight, l[0].bias, l[1].weight, l[1].bias,
-                                                                       l[2].weight, l[2].bias))
+        l = self.lin
+        native.bind_mlp(self.m, (l[0].weight, l[0].bias, l[1].weight, l[1].bias, l[2].weight, l[2].bias))
 
     @staticmethod
     def _stream(t=None):
-        """The caller's current stream ON THE TENSOR'S DEVICE (the kernels of pds_mlp / pds_train / pds_gae run
-        on the current device: `_on(t)` makes that the tensor's one for the duration of the call)."""
+        """The caller's current stream ON THE TENSOR'S DEVICE, for a direct call (native.call appends it by itself)."""
         return C.c_void_p(torch.cuda.current_stream(t.device if t is not None else None).cuda_stream)
 
     def forward(self, x, index=None, mean=None, std=None, eps=1e-5, out=None):
         """y[B, d_out] = net(standardise(x[index]))."""
-        self._bind()
         B = x.shape[0] if index is None else index.shape[0]
         y = out if out is not None else torch.empty(B, self.m.d_out, device=x.device)
-        with _on(x):
-            rc = self.lib.pds_mlp_forward(C.byref(self.m), _ptr(x), _ptr(index), B, _ptr(mean), _ptr(std), float(eps),
-                                          _ptr(y), self._stream(x))
-        if rc != native.OK:
-            raise RuntimeError(f"pds_mlp_forward -> {rc}")
+        native.call("pds_mlp_forward", self, x, index, B, mean, std, float(eps), y, on=x)
         return y
 
     def _adam_state(self):
@@ -122,41 +92,25 @@ class FusedMLP:
         """Fills the parameters' .grad with d loss_pi / d theta; returns the stats tensor
         [sum(-min(..)), sum(ratio), sum(0.5 z^2), B] (device, no sync).  adam_lr: also take the torch.optim.Adam step
         with this learning rate, in the same two launches (same bits as ppo_grad + adam_step)."""
-        self._bind()
         opt = self._adam_arg(adam_lr, betas, eps)
-        with _on(x):
-            rc = self.lib.pds_ppo_policy_grad_step(C.byref(self.m), _ptr(x), _ptr(act), _ptr(adv), _ptr(logp_old),
-                                                   _ptr(log_std), x.shape[0], float(clip_ratio), _ptr(self.flat_grad),
-                                                   _ptr(self.stats), _ptr(self.workspace), opt, self._stream(x))
-        if rc != native.OK:
-            raise RuntimeError(f"pds_ppo_policy_grad -> {rc}")
+        native.call("pds_ppo_policy_grad_step", self, x, act, adv, logp_old, log_std, x.shape[0], float(clip_ratio), self.flat_grad,
+                    self.stats, self.workspace, opt, on=x)
         return self.stats
 
     def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8):
         """torch.optim.Adam.step for this network's parameters from the flat gradient, in one launch."""
         self._adam_state()
         self.adam_steps += 1
-        self._bind()
-        with _on(self.flat_grad):
-            rc = self.lib.pds_adam_step(C.byref(self.m), _ptr(self.flat_grad), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
-                                        self.adam_steps, float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                        self._stream(self.flat_grad))
-        if rc != native.OK:
-            raise RuntimeError(f"pds_adam_step -> {rc}")
+        native.call("pds_adam_step", self, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.adam_steps, float(lr), float(betas[0]),
+                    float(betas[1]), float(eps), on=self.flat_grad)
 
     def value_grad(self, x, target, index=None, adam_lr=None, betas=(0.9, 0.999), eps=1e-8):
         """Fills .grad with d mse(net(x[index]), target[index]) / d theta; stats[0] = sum of squared errors.
         adam_lr: as in ppo_grad."""
-        self._bind()
         B = x.shape[0] if index is None else index.shape[0]
         opt = self._adam_arg(adam_lr, betas, eps)
-        with _on(x):
-            rc = self.lib.pds_value_grad_step(C.byref(self.m), _ptr(x), _ptr(index), _ptr(target), B, _ptr(self.flat_grad),
-                                              _ptr(self.stats), _ptr(self.workspace), opt, self._stream(x))
-        if rc != native.OK:
-            raise RuntimeError(f"pds_value_grad -> {rc}")
+        native.call("pds_value_grad_step", self, x, index, target, B, self.flat_grad, self.stats, self.workspace, opt, on=x)
         return self.stats
-
 
     def _npg_workspace(self, candidates):
         n = self.lib.pds_npg_workspace_floats(C.byref(self.m), int(candidates))
@@ -168,31 +122,19 @@ class FusedMLP:
     def fisher_vector_product(self, x, v, log_std, damping, index=None, out=None):
         """F v + damping v (flat, param_count) over the standardised rows x[index] (csrc/pds_npg.hip): the Fisher matrix of
         the Gaussian policy with the fixed log_std at the current parameters, mean over samples x action dims."""
-        self._bind()
         B = x.shape[0] if index is None else index.shape[0]
         out = out if out is not None else torch.empty_like(self.flat_grad)
-        ws = self._npg_workspace(0)
-        with _on(x):
-            rc = self.lib.pds_npg_fisher_vector_product(C.byref(self.m), _ptr(x), _ptr(index), B, _ptr(log_std), _ptr(v),
-                                                        float(damping), _ptr(out), _ptr(ws), self._stream(x))
-        if rc != native.OK:
-            raise RuntimeError(f"pds_npg_fisher_vector_product -> {rc}")
+        native.call("pds_npg_fisher_vector_product", self, x, index, B, log_std, v, float(damping), out, self._npg_workspace(0), on=x)
         return out
 
     def surrogate_kl(self, step, fracs, x, act, adv, logp_old, mu_old, log_std, theta_out=None):
         """[J, 4] device tensor: per candidate theta + fracs[j] * step (fracs: float32 device tensor [J]) the sum of ratio * adv
         over the batch, the sum of KL(Normal(mu_old, sigma) || Normal(mu_j, sigma)) over samples x action dims, a non-finite
         flag and the sum of ratio (csrc/pds_npg.hip).  theta_out [J, param_count]: also the candidates' parameters."""
-        self._bind()
         J = int(fracs.shape[0])
         out = torch.empty(J, 4, device=x.device)
-        ws = self._npg_workspace(J)
-        with _on(x):
-            rc = self.lib.pds_npg_surrogate_kl(C.byref(self.m), _ptr(step), _ptr(fracs), J, _ptr(x), _ptr(act), _ptr(adv),
-                                               _ptr(logp_old), _ptr(mu_old), _ptr(log_std), x.shape[0], _ptr(out),
-                                               _ptr(theta_out), _ptr(ws), self._stream(x))
-        if rc != native.OK:
-            raise RuntimeError(f"pds_npg_surrogate_kl -> {rc}")
+        native.call("pds_npg_surrogate_kl", self, step, fracs, J, x, act, adv, logp_old, mu_old, log_std, x.shape[0], out, theta_out,
+                    self._npg_workspace(J), on=x)
         return out
 
     def ddpg_policy_grad(self, q_fm, oa, index, act_limit, adam_lr=None, betas=(0.9, 0.999), eps=1e-8):
@@ -200,7 +142,6 @@ class FusedMLP:
         -Q(o, pi(o)).mean() over the rows oa[index] = [obs | act] (index None: every row), Q = `q_fm` (read only);
         stats[0] = sum of Q(o, pi(o)), stats[3] = B (csrc/pds_ddpg.hip).  adam_lr: as in ppo_grad.
         NotImplementedError for shapes the kernel is not built for (ddpg_supported says so beforehand)."""
-        self._bind(); q_fm._bind()
         B = oa.shape[0] if index is None else index.shape[0]
         ws = getattr(self, "ddpg_workspace", None)
         if ws is None:
@@ -209,11 +150,7 @@ class FusedMLP:
                 raise (NotImplementedError if n == native.EUNSUPPORTED else ValueError)(f"pds_ddpg_workspace_floats -> {n}")
             self.ddpg_workspace = ws = torch.empty(n, device=self.flat_grad.device)
         opt = self._adam_arg(adam_lr, betas, eps)
-        with _on(oa):
-            rc = self.lib.pds_ddpg_policy_grad(C.byref(self.m), C.byref(q_fm.m), _ptr(oa), _ptr(index), B, float(act_limit),
-                                               _ptr(self.flat_grad), _ptr(self.stats), _ptr(ws), opt, self._stream(oa))
-        if rc != native.OK:
-            raise (NotImplementedError if rc == native.EUNSUPPORTED else RuntimeError)(f"pds_ddpg_policy_grad -> {rc}")
+        native.call("pds_ddpg_policy_grad", self, q_fm, oa, index, B, float(act_limit), self.flat_grad, self.stats, ws, opt, on=oa)
         return self.stats
 
     def sac_policy_grad(self, q1_fm, q2_fm, oa, index, alpha, act_limit, seed, call, adam_lr=None, betas=(0.9, 0.999), eps=1e-8):
@@ -222,7 +159,6 @@ class FusedMLP:
         squashed-Gaussian sample under the noise of (seed, call); Q1, Q2 = `q1_fm`, `q2_fm` (read only).  stats = [sum min Q,
         sum logp, 0, B] (csrc/pds_sac.hip).  adam_lr: as in ppo_grad.  NotImplementedError for shapes the kernel is not built
         for (sac_supported says so beforehand)."""
-        self._bind(); q1_fm._bind(); q2_fm._bind()
         B = oa.shape[0] if index is None else index.shape[0]
         ws = getattr(self, "sac_workspace", None)
         if ws is None:
@@ -231,12 +167,8 @@ class FusedMLP:
                 raise (NotImplementedError if n == native.EUNSUPPORTED else ValueError)(f"pds_sac_workspace_floats -> {n}")
             self.sac_workspace = ws = torch.empty(n, device=self.flat_grad.device)
         opt = self._adam_arg(adam_lr, betas, eps)
-        with _on(oa):
-            rc = self.lib.pds_sac_policy_grad(C.byref(self.m), C.byref(q1_fm.m), C.byref(q2_fm.m), _ptr(oa), _ptr(index), B,
-                                              float(alpha), float(act_limit), int(seed) & (2 ** 64 - 1), int(call),
-                                              _ptr(self.flat_grad), _ptr(self.stats), _ptr(ws), opt, self._stream(oa))
-        if rc != native.OK:
-            raise (NotImplementedError if rc == native.EUNSUPPORTED else RuntimeError)(f"pds_sac_policy_grad -> {rc}")
+        native.call("pds_sac_policy_grad", self, q1_fm, q2_fm, oa, index, B, float(alpha), float(act_limit),
+                    int(seed) & (2 ** 64 - 1), int(call), self.flat_grad, self.stats, ws, opt, on=oa)
         return self.stats
 
 
@@ -248,25 +180,15 @@ def ddpg_supported(pi_fm, q_fm):
 def ddpg_target(pi_targ_fm, q_targ_fm, obs2, index, rew, done, gamma, act_limit, target_rows):
     """target_rows[i] = rew[i] + gamma * (1 - done[i]) * Q_targ(obs2[i], act_limit * tanh(pi_targ(obs2[i]))) for the rows
     i = index[g] (index None: every row); the other rows are left alone (include/pds.h pds_ddpg_target)."""
-    pi_targ_fm._bind(); q_targ_fm._bind()
     B = obs2.shape[0] if index is None else index.shape[0]
-    with _on(obs2):
-        rc = native.load().pds_ddpg_target(C.byref(pi_targ_fm.m), C.byref(q_targ_fm.m), _ptr(obs2), _ptr(index), B, _ptr(rew),
-                                           _ptr(done), float(gamma), float(act_limit), _ptr(target_rows),
-                                           FusedMLP._stream(obs2))
-    if rc != native.OK:
-        raise (NotImplementedError if rc == native.EUNSUPPORTED else RuntimeError)(f"pds_ddpg_target -> {rc}")
+    native.call("pds_ddpg_target", pi_targ_fm, q_targ_fm, obs2, index, B, rew, done, float(gamma), float(act_limit), target_rows,
+                on=obs2)
     return target_rows
 
 
 def polyak(targ_fm, src_fm, rho):
     """p_targ.mul_(rho); p_targ.add_((1 - rho) * p) over the six tensors of a network pair, one launch, the same bits."""
-    targ_fm._bind(); src_fm._bind()
-    t = targ_fm.params[0]
-    with _on(t):
-        rc = native.load().pds_polyak(C.byref(targ_fm.m), C.byref(src_fm.m), float(rho), FusedMLP._stream(t))
-    if rc != native.OK:
-        raise RuntimeError(f"pds_polyak -> {rc}")
+    native.call("pds_polyak", targ_fm, src_fm, float(rho), on=targ_fm.params[0])
 
 
 def sac_supported(pi_fm, q1_fm, q2_fm):
@@ -283,11 +205,8 @@ def sac_sample(head, act_limit, seed, call, id_base=0, deterministic=False, act_
     n = head.shape[0]
     act = act_out if act_out is not None else torch.empty(n, 4, device=head.device)
     logp = torch.empty(n, device=head.device) if want_logp else None
-    with _on(head):
-        rc = native.load().pds_sac_sample(_ptr(head), n, float(act_limit), int(seed) & (2 ** 64 - 1), int(call), int(id_base),
-                                          int(bool(deterministic)), _ptr(act), _ptr(logp), FusedMLP._stream(head))
-    if rc != native.OK:
-        raise RuntimeError(f"pds_sac_sample -> {rc}")
+    native.call("pds_sac_sample", head, n, float(act_limit), int(seed) & (2 ** 64 - 1), int(call), int(id_base),
+                int(bool(deterministic)), act, logp, on=head)
     return act, logp
 
 
@@ -295,14 +214,9 @@ def sac_target(pi_fm, q1_targ_fm, q2_targ_fm, obs2, index, rew, done, gamma, alp
     """target_rows[i] = rew[i] + gamma * (1 - done[i]) * (min(Q1_targ, Q2_targ)(obs2[i], a2) - alpha * logp2) for the rows
     i = index[g] (index None: every row), (a2, logp2) the sample of the CURRENT policy `pi_fm` under the noise of (seed, call)
     at position g; the other rows are left alone (include/pds.h pds_sac_target)."""
-    pi_fm._bind(); q1_targ_fm._bind(); q2_targ_fm._bind()
     B = obs2.shape[0] if index is None else index.shape[0]
-    with _on(obs2):
-        rc = native.load().pds_sac_target(C.byref(pi_fm.m), C.byref(q1_targ_fm.m), C.byref(q2_targ_fm.m), _ptr(obs2), _ptr(index),
-                                          B, _ptr(rew), _ptr(done), float(gamma), float(alpha), float(act_limit),
-                                          int(seed) & (2 ** 64 - 1), int(call), _ptr(target_rows), FusedMLP._stream(obs2))
-    if rc != native.OK:
-        raise (NotImplementedError if rc == native.EUNSUPPORTED else RuntimeError)(f"pds_sac_target -> {rc}")
+    native.call("pds_sac_target", pi_fm, q1_targ_fm, q2_targ_fm, obs2, index, B, rew, done, float(gamma), float(alpha),
+                float(act_limit), int(seed) & (2 ** 64 - 1), int(call), target_rows, on=obs2)
     return target_rows
 
 
@@ -317,11 +231,8 @@ def ddpg_explore(net_out, log_std, act_limit, seed, call, id_base=0, act_out=Non
         raise ValueError("net_out must be a contiguous float32 [n, 4] tensor")
     n = net_out.shape[0]
     act = act_out if act_out is not None else torch.empty(n, 4, device=net_out.device)
-    with _on(net_out):
-        rc = native.load().pds_ddpg_explore(_ptr(net_out), _ptr(log_std), n, float(act_limit), int(seed) & (2 ** 64 - 1), int(call),
-                                            int(id_base), _ptr(act), FusedMLP._stream(net_out))
-    if rc != native.OK:
-        raise RuntimeError(f"pds_ddpg_explore -> {rc}")
+    native.call("pds_ddpg_explore", net_out, log_std, n, float(act_limit), int(seed) & (2 ** 64 - 1), int(call), int(id_base), act,
+                on=net_out)
     return act
 
 
@@ -341,14 +252,9 @@ def fused_collect(env, fm_pi, mode, K, act_limit, log_std, seed, first_call, oa,
     fills the N rows at (ptr + s N) mod capacity of the ring oa / obs2 / rew / done (capacity = oa.shape[0]), obs [N, D] is
     o(0) on entry and o(K) on return, ep_ret / ep_len run on, tile_stats [collect_tiles(env), 8] receives the finished episodes'
     statistics.  Raises NotImplementedError / ValueError where the entry point refuses (the env is left as it was)."""
-    fm_pi._bind()
-    with _on(obs):
-        rc = env.lib.pds_collect(env._handle, int(K), int(mode), C.byref(fm_pi.m), float(act_limit), _ptr(log_std),
-                                 int(seed) & (2 ** 64 - 1), int(first_call), _ptr(oa), _ptr(obs2), _ptr(rew), _ptr(done),
-                                 int(oa.shape[0]), int(ptr), _ptr(obs), _ptr(ep_ret), _ptr(ep_len), _ptr(tile_stats),
-                                 FusedMLP._stream(obs))
-    if rc != native.OK:
-        native.check(env._handle, rc, "pds_collect")
+    native.call("pds_collect", env._handle, int(K), int(mode), fm_pi, float(act_limit), log_std, int(seed) & (2 ** 64 - 1),
+                int(first_call), oa, obs2, rew, done, int(oa.shape[0]), int(ptr), obs, ep_ret, ep_len, tile_stats,
+                on=obs, handle=env._handle)
     env._last_obs = obs  # (what a masked reset() copies for the envs outside the mask)
 
 
@@ -356,18 +262,12 @@ def conjugate_gradients(avp, b, iters, residual_tol=1e-10, eps=1e-6):
     """conjugate_gradients (algs/utils.py:5-38) with one pds_npg_cg_step launch per iteration: `avp(p, out)` writes A p into
     out.  The reference's early break is a device flag that freezes x, r and p (no host sync).  -> (x, state) with state =
     {r.r, stopped} on the device."""
-    lib = native.load()
     n = b.numel()
     x, r, p, z = (torch.empty_like(b) for _ in range(4))
     st = torch.zeros(2, device=b.device)
-    stream = FusedMLP._stream(b)
 
     def step(zz, init):
-        with _on(b):
-            rc = lib.pds_npg_cg_step(n, _ptr(x), _ptr(r), _ptr(p), _ptr(zz), _ptr(st), float(eps), float(residual_tol),
-                                     int(init), stream)
-        if rc != native.OK:
-            raise RuntimeError(f"pds_npg_cg_step -> {rc}")
+        native.call("pds_npg_cg_step", n, x, r, p, zz, st, float(eps), float(residual_tol), int(init), on=b)
 
     step(b, True)
     for _ in range(int(iters)):
@@ -380,19 +280,13 @@ def random_permutation(n, seed, call, device):
     """int64 tensor p with p[i] = a pseudo-random permutation of range(n) keyed by (seed, call): one launch
     (include/pds.h pds_permutation) where torch.randperm sorts."""
     out = torch.empty(int(n), dtype=torch.int64, device=device)
-    with _on(out):
-        rc = native.load().pds_permutation(_ptr(out), int(n), int(seed) & (2 ** 64 - 1), int(call), FusedMLP._stream(out))
-    if rc != native.OK:
-        raise RuntimeError(f"pds_permutation -> {rc}")
+    native.call("pds_permutation", out, int(n), int(seed) & (2 ** 64 - 1), int(call), on=out)
     return out
 
 
 def counter_add(counter, inc):
     """counter (int64 device tensor of one element) += inc, stream-ordered (captured-rollout call counter)."""
-    with _on(counter):
-        rc = native.load().pds_counter_add(_ptr(counter), int(inc), FusedMLP._stream(counter))
-    if rc != native.OK:
-        raise RuntimeError(f"pds_counter_add -> {rc}")
+    native.call("pds_counter_add", counter, int(inc), on=counter)
 
 
 def fused_rollout(env, fm_pi, fm_v, T, mean, std, eps, log_std, seed, call_offset, deterministic, obs_buf, act_buf, logp_buf,
@@ -400,15 +294,9 @@ def fused_rollout(env, fm_pi, fm_v, T, mean, std, eps, log_std, seed, call_offse
     """ONE launch for the T closed-loop steps of a rollout (include/pds.h pds_rollout, csrc/pds_rollout.h): obs_buf is
     [T + 1, N, D] with o(0) in row 0.  Raises NotImplementedError for env configurations the kernel is not built
     for (the per-step path gives the same bits)."""
-    fm_pi._bind(); fm_v._bind()
-    with _on(obs_buf):
-        rc = env.lib.pds_rollout(env._handle, int(T), C.byref(fm_pi.m), C.byref(fm_v.m), _ptr(mean), _ptr(std), float(eps),
-                                 _ptr(log_std), int(seed), _ptr(call_base), int(call_offset), int(bool(deterministic)),
-                                 _ptr(obs_buf), _ptr(act_buf), _ptr(logp_buf), _ptr(val_buf), _ptr(rew_buf), _ptr(term_buf),
-                                 _ptr(trunc_buf), _ptr(cost_buf), _ptr(fval_buf), _ptr(last_val), _ptr(ep_ret), _ptr(ep_len),
-                                 _ptr(stats), FusedMLP._stream(obs_buf))
-    if rc != native.OK:
-        native.check(env._handle, rc, "pds_rollout")
+    native.call("pds_rollout", env._handle, int(T), fm_pi, fm_v, mean, std, float(eps), log_std, int(seed), call_base,
+                int(call_offset), int(bool(deterministic)), obs_buf, act_buf, logp_buf, val_buf, rew_buf, term_buf, trunc_buf,
+                cost_buf, fval_buf, last_val, ep_ret, ep_len, stats, on=obs_buf, handle=env._handle)
 
 
 def fused_rollout_history(env, fm_pi, T, H, mean, std, eps, log_std, seed, call_offset, deterministic, obs_buf, act_buf, logp_buf,
@@ -418,33 +306,18 @@ def fused_rollout_history(env, fm_pi, T, H, mean, std, eps, log_std, seed, call_
     is NOT in the kernel (the caller evaluates V over obs_buf and over the final histories in fin_rows [slots, N, H * half],
     whose fin_step [slots, N] (int32, preset to -1) names the step each belongs to).  Raises NotImplementedError for env
     configurations the kernel is not built for (the per-step path gives the same bits)."""
-    fm_pi._bind()
-    with _on(obs_buf):
-        rc = env.lib.pds_rollout_history(env._handle, int(T), int(H), C.byref(fm_pi.m), _ptr(mean), _ptr(std), float(eps),
-                                         _ptr(log_std), int(seed), _ptr(call_base), int(call_offset), int(bool(deterministic)),
-                                         _ptr(obs_buf), _ptr(act_buf), _ptr(logp_buf), _ptr(rew_buf), _ptr(term_buf),
-                                         _ptr(trunc_buf), _ptr(cost_buf), _ptr(fin_rows), _ptr(fin_step), int(fin_rows.shape[0]),
-                                         _ptr(ep_ret), _ptr(ep_len), _ptr(stats), FusedMLP._stream(obs_buf))
-    if rc != native.OK:
-        native.check(env._handle, rc, "pds_rollout_history")
+    native.call("pds_rollout_history", env._handle, int(T), int(H), fm_pi, mean, std, float(eps), log_std, int(seed), call_base,
+                int(call_offset), int(bool(deterministic)), obs_buf, act_buf, logp_buf, rew_buf, term_buf, trunc_buf, cost_buf,
+                fin_rows, fin_step, int(fin_rows.shape[0]), ep_ret, ep_len, stats, on=obs_buf, handle=env._handle)
 
 
 def gaussian_sample(mu, log_std, act_out, logp_out, seed, call, id_base=0, deterministic=False, call_base=None):
     """act_out[n, d] = mu + exp(log_std) * z, logp_out[n] = log N(act | mu, sigma) summed over d.  The Philox
     call counter is `call` (+ the int64 device word `call_base` when given: hipGraph-capturable form)."""
-    with _on(mu):
-        rc = native.load().pds_gaussian_sample_dev(_ptr(mu), _ptr(log_std), mu.shape[0], mu.shape[1], int(seed),
-                                                   _ptr(call_base), int(call), int(id_base), int(bool(deterministic)),
-                                                   _ptr(act_out), _ptr(logp_out), FusedMLP._stream(mu))
-    if rc != native.OK:
-        raise RuntimeError(f"pds_gaussian_sample -> {rc}")
+    native.call("pds_gaussian_sample_dev", mu, log_std, mu.shape[0], mu.shape[1], int(seed), call_base, int(call), int(id_base),
+                int(bool(deterministic)), act_out, logp_out, on=mu)
 
 
 def rollout_record(rew, term, trunc, rew_buf_t, term_buf_t, trunc_buf_t, ep_ret, ep_len, stats):
     """One step of the rollout bookkeeping (see include/pds.h pds_rollout_record)."""
-    with _on(rew):
-        rc = native.load().pds_rollout_record(_ptr(rew), _ptr(term), _ptr(trunc), rew.shape[0], _ptr(rew_buf_t),
-                                              _ptr(term_buf_t), _ptr(trunc_buf_t), _ptr(ep_ret), _ptr(ep_len), _ptr(stats),
-                                              FusedMLP._stream(rew))
-    if rc != native.OK:
-        raise RuntimeError(f"pds_rollout_record -> {rc}")
+    native.call("pds_rollout_record", rew, term, trunc, rew.shape[0], rew_buf_t, term_buf_t, trunc_buf_t, ep_ret, ep_len, stats, on=rew)

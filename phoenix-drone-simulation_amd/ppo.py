@@ -17,7 +17,6 @@ finish are auto-reset inside pds_step and bootstrap from `final_obs`.
 PyTorch is used for what it is good at here: the two tiny MLPs and Adam.
 """
 import contextlib
-import ctypes as C
 import math
 
 import time
@@ -227,16 +226,10 @@ def gae(rew, val, terminated, truncated, final_val, last_val, gamma, lam, rew_sc
     # the kernel reads and writes dense [T, N]: every input contiguous (final_val may be None), the outputs allocated dense
     # (empty_like would keep the strides of a transposed `rew`)
     out = [torch.empty((T, N), dtype=torch.float32, device=rew.device) for _ in range(3)]
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     rew, val, terminated, truncated, last_val = (t.contiguous() for t in (rew, val, terminated, truncated, last_val))
     final_val = final_val.contiguous() if final_val is not None else None
-    with torch.cuda.device(rew.device):  # pds_gae launches on the current device
-        rc = native.load().pds_gae(p(rew), p(val), p(terminated), p(truncated), p(final_val), p(last_val),
-                                   C.c_float(gamma), C.c_float(lam), C.c_float(rew_scale), C.c_float(rew_clip),
-                                   T, N, p(out[0]), p(out[1]), p(out[2]),
-                                   C.c_void_p(torch.cuda.current_stream(rew.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"pds_gae failed ({rc})")
+    native.call("pds_gae", rew, val, terminated, truncated, final_val, last_val, float(gamma), float(lam), float(rew_scale),
+                float(rew_clip), T, N, *out, on=rew)
     return out
 
 
