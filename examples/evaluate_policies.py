@@ -10,6 +10,7 @@ evaluate_population (the evaluation loop of the reference's utils/evaluation.py,
   python examples/evaluate_policies.py runs/ --episodes 256 --env DroneCircleSimpleEnv-v0 --log-dir eval_out
   python examples/evaluate_policies.py runs/ --metrics            # also the flight-quality table (evaluation.FlightMetrics.table)
   python examples/evaluate_policies.py runs_h4/ --history 4       # actors trained with observation_history_size = 4
+  python examples/evaluate_policies.py runs/ --record 64 --record-dir flights   # the first 64 flights per checkpoint as CSV logs
 
 A group whose actors read H x half inputs (half: one [o, u] half of the env's observation) was trained on an observation history
 of H: its env is built with observation_history_size = H (inferred from the width, or --history) and flies in one launch too.
@@ -86,7 +87,15 @@ def main():
                     help="also print flight time, mean squared roll / pitch, rate oscillation, action rate, saturation, maximum tilt")
     ap.add_argument("--history", type=int, default=None,
                     help="observation_history_size of the env (default: inferred per group, actor inputs / half the env's observation width)")
+    ap.add_argument("--record", type=int, default=None, metavar="R",
+                    help="record the first R episodes per checkpoint (a multiple of 64, at most --episodes): state, action and "
+                         "observation of every step, from the same launch (evaluation.Flights)")
+    ap.add_argument("--record-dir", default=None, metavar="DIR",
+                    help="with --record: one CSV log per recorded episode under <DIR>/<group>/<p>/ in the layout of the "
+                         "simulation-optimisation logs (Flights.to_csv_dir; control_mode PWM)")
     args = ap.parse_args()
+    if args.record_dir and not args.record:
+        ap.error("--record-dir needs --record R")
     fused = {"auto": "auto", "on": True, "off": False}[args.fused]
 
     loaded = [(d, *load_run(d)) for d in find_run_dirs(args.paths)]
@@ -113,11 +122,19 @@ def main():
             print(f"group {gi} {key}: the actors read {d_in} inputs, {env_id} observes {env.obs_dim}: skipped")
             env.close()
             continue
-        out = evaluate_population(env, pop, fused=fused, metrics=args.metrics, history_fused=True,
+        out = evaluate_population(env, pop, fused=fused, metrics=args.metrics, history_fused=True, record=args.record,
                                   log_dir=os.path.join(args.log_dir, str(gi)) if args.log_dir else None)
         ret, length, cost = out[:3]
         table = out[3].table() if args.metrics else {}
         env.close()
+        if args.record:
+            flights = out[-1]
+            print(f"group {gi}: recorded {flights.R} flights per checkpoint, {int(flights.length.sum())} steps in all")
+            if args.record_dir:
+                for p in range(pop.P):
+                    one = type(flights)(flights.state[p:p + 1], flights.action[p:p + 1], None, flights.length[p:p + 1], flights.step_seconds,
+                                        flights.last_action0[p:p + 1], control_mode=flights.control_mode)
+                    one.to_csv_dir(os.path.join(args.record_dir, str(gi), str(p)))
         print(f"group {gi}: {d_in} -> {hidden} -> 4, {act}; {pop.P} checkpoint(s)")
         for p, (run_dir, _) in enumerate(members):
             print(f"  {run_dir}: return {float(ret[p].mean()):9.3f} +- {float(ret[p].std()):7.3f}   "

@@ -71,7 +71,25 @@
 //   partial to obs_sums[tile][wave][S1 / S2][64] with 16-byte stores, features >= D zero.  The four waves of a tile are summed by
 //   the host: on the device that would take a hand-over.
 // STATS = false is the kernel as it was: every stats statement is behind `if constexpr`, the mask belongs to a function only the
-// stats form calls, the argument blocks are the ones they were.
+// stats and the record form call, the argument blocks are the ones they were.
+//
+// RECORD (pds_evaluate_policies_record; translation units csrc/pds_evaluate_record_*.hip; built with METRICS, never with STATS):
+// the flights leave the kernel.  Of a policy's E / 64 tiles the first rec_tiles record (wave-uniform; EvalRecordArgs,
+// csrc/pds_evaluate_args.h, has the column of a lane); the metrics are summed as in the metrics form and stored where an array is given.
+//   The ENV wave stores x(s) = S.e -- the reference log's twelve columns, in the log's order -- and the raw a(s) of every lane
+//   `alive` in front of step s (the predicate of ep_len) as four 16-byte pieces to flight[s][piece][column]: per piece a wave
+//   writes one contiguous 1 KiB line.  Where PDS_EM_STEP is: behind the act_ready wait, which is where the action exists, and
+//   for the reason given under METRICS not in front of it.  Plain vector stores of registers the wave holds there anyway;
+//   nothing is carried across step_once but the column, two scalar registers.
+//   The NETWORK waves, where obs_rec is given, copy the rows of the tile whose env is alive in front of step s, raw, to
+//   obs_rec[s][column][D]: each wave its 16 rows, 16 D contiguous floats, one dword per lane and pass -- in the tile's read window,
+//   between their obs_ready wait and their act_ready post.  The alive mask is the stats form's (es_lds): same windows, no new
+//   counter, no new wait.
+//   Nothing else is written: a stopped tile writes nothing more, the rows s >= length of an env and every row of a tile that does
+//   not record keep what the caller put there.  NOT recorded: the terminal state x(L) and the terminal observation -- a finished
+//   env is reset in place inside step_once, and final_obs is NULL in this kernel.
+// RECORD = false is the kernel as it was: every record statement is behind `if constexpr`, the argument blocks are the ones
+// they were (profiles/evaluate_record_kernel_resources.txt: the other forms' code objects keep their figures).
 #pragma once
 #include "pds_evaluate_args.h"
 #include "pds_rollout.h"
@@ -227,10 +245,31 @@ PDS_DEV float es_tree_add(float v, int bit) { return __fadd_rn(v, __shfl_xor(v, 
   row[0] = em[lane];                                                                                              \
   row[1] = make_float4(rest.x, (float)(m_sat >> 2), (float)(m_cross & 0xFFFF), (float)((unsigned)m_cross >> 16));
 
-template <class V_, int TEAMS, bool METRICS = false, bool STATS = false>
-__global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(const EvalKernelArgs<METRICS, STATS> ka) {
+// ---- the record of the flights (the head of this file: RECORD) ----
+// the column of lane 0 of tile t in the record (csrc/pds_evaluate_args.h EvalRecordArgs), or -1 where the tile does not record
+PDS_DEV long long eval_record_column(const EvalArgs &ea, int rec_tiles, long long t) {
+  const long long p = t / ea.tiles_per_policy;
+  const int k = (int)(t - p * ea.tiles_per_policy);
+  return k < rec_tiles ? (p * rec_tiles + k) * kWave : -1;
+}
+// x(s) = S.e and a(s) = act of the lanes in their first episode, behind the act_ready wait and in front of step_once: four plain
+// 16-byte stores of registers the wave holds there anyway.  `rl`: the reloaded EvalRecordArgs
+#define PDS_ER_STEP(rl)                                                                                   \
+  const long long nrec = (ntiles / (rl)->m.e.tiles_per_policy) * (rl)->rec_tiles * kWave;                 \
+  float4 *line = (rl)->flight + (long long)s * 4 * nrec + rec_col + lane_s;                               \
+  if (alive) {                                                                                            \
+    line[0] = make_float4(S.e.px, S.e.py, S.e.pz, S.e.vx);                                                \
+    line[nrec] = make_float4(S.e.vy, S.e.vz, S.e.roll, S.e.pitch);                                        \
+    line[2 * nrec] = make_float4(S.e.yaw, S.e.wx, S.e.wy, S.e.wz);                                        \
+    line[3 * nrec] = act;                                                                                 \
+  }
+
+template <class V_, int TEAMS, bool METRICS = false, bool STATS = false, bool RECORD = false>
+__global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(const EvalKernelArgs<METRICS, STATS, RECORD> ka) {
   using namespace pds_mlpf;
   static_assert(METRICS || !STATS, "the stats form is built with the metrics");
+  static_assert(METRICS || !RECORD, "the record form is built with the metrics");
+  static_assert(!STATS || !RECORD, "no form records and gathers statistics");
   const EvalArgs &ea = eval_head(ka);
   using V = std::conditional_t<regen_obs_variant<V_>(), StoredOh<V_>, V_>;
   constexpr int D = V::D;
@@ -279,7 +318,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
     }
   }
   if (tid < TEAMS) { obs_ready[tid] = 0; act_ready[tid] = 0; }
-  if constexpr (STATS) {
+  if constexpr (STATS || RECORD) {
     if (tid < TEAMS) es_lds<TEAMS>()[tid] = ~0ull;  // the mask of step 0
   }
   __syncthreads();  // (the only block barrier: from here on the roles meet through the counters)
@@ -302,11 +341,18 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
       em = em_lds<TEAMS>() + team * 2 * kWave;
       PDS_EM_INIT(em)
     }
+    long long rec_col = -1;  // RECORD: column of lane 0 in the record, wave-uniform; < 0: this tile does not record
+    if constexpr (RECORD) rec_col = eval_record_column(ea, ka.rec_tiles, t);
     for (int s = 0; s < T; ++s) {
       const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<301, true>(ea.s, s));
       PDS_EVAL_STEP_HEAD(&act_ready[team], act_all[team])  // the network waves have read o(s) and written a(s)
       if constexpr (METRICS) {  // x(s), the state the policy acted in, and a(s), raw, against u(k - 1) = the last action before the step
         PDS_EM_STEP(em)
+      }
+      if constexpr (RECORD) {  // x(s) and a(s) where the env is in its first episode: four lines of the record, nothing carried
+        if (rec_col >= 0) {
+          PDS_ER_STEP(reinterpret_cast<const EvalRecordArgs *>(&el))
+        }
       }
       StepOut so;
       step_once<V, kWave, RM, false>(el.s, o1, rks, parity, nullptr, tile, nullptr, queue_all[team], scratch_all[team], lane_s,
@@ -314,14 +360,18 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
       PDS_NEXT_TICK(rk, parity)
       PDS_EVAL_RECORD_STEP(so)
       PDS_EVAL_STILL
-      if constexpr (STATS) {
+      if constexpr (STATS || RECORD) {
         if (lane == 0) es_lds<TEAMS>()[team] = still;  // the mask of step s + 1, in front of the post
       }
       PDS_EVAL_STEP_TAIL(&obs_ready[team], el)  // o(s + 1) is in the tile / this team's env wave has left
     }
     // (pds_evaluate_policies leaves the handle "not reset")
     PDS_EVAL_WAVE_END(EvalArgs, 302)
-    if constexpr (METRICS) {
+    if constexpr (RECORD) {  // (the metrics are summed whether or not the caller takes them)
+      if (reinterpret_cast<const EvalMetricsArgs *>(&el)->metrics != nullptr) {
+        PDS_EM_STORE(em, reinterpret_cast<const EvalMetricsArgs *>(&el)->metrics)
+      }
+    } else if constexpr (METRICS) {
       PDS_EM_STORE(em, reinterpret_cast<const EvalMetricsArgs *>(&el)->metrics)
     }
     return;
@@ -336,6 +386,10 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
 #pragma unroll
       for (int q = 0; q < 4; ++q) { es.s1[kt][q] = 0.f; es.s2[kt][q] = 0.f; }
     }
+  }
+  long long rec_col = -1;  // RECORD: as in the env wave; here < 0 also where no observations are asked for
+  if constexpr (RECORD) {
+    if (ka.obs_rec != nullptr) rec_col = eval_record_column(ea, ka.rec_tiles, t);
   }
   for (int s = 0;; ++s) {
     const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<303, true>(ea.s, s));
@@ -356,6 +410,18 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
           const float d = __fsub_rn((k < D) ? tile[own * TS + k] : m, m);
           es.s1[kt][q] = __fadd_rn(es.s1[kt][q], al ? d : 0.f);
           es.s2[kt][q] = __fadd_rn(es.s2[kt][q], al ? __fmul_rn(d, d) : 0.f);
+        }
+      }
+    }
+    if constexpr (RECORD) {  // o(s), raw, of this wave's 16 rows whose env was alive in front of step s: 16 D contiguous floats
+      if (rec_col >= 0) {
+        const EvalRecordArgs &rl = *reinterpret_cast<const EvalRecordArgs *>(&el);
+        const long long nrec = (ntiles / rl.m.e.tiles_per_policy) * rl.rec_tiles * kWave;
+        float *out = rl.obs_rec + ((long long)s * nrec + rec_col + wave * 16) * D;
+        const unsigned rows = (unsigned)(es_lds<TEAMS>()[team] >> (wave * 16)) & 0xFFFFu;
+        for (int idx = lane; idx < 16 * D; idx += kWave) {
+          const int r = idx / D, c = idx - r * D;
+          if ((rows >> r) & 1u) out[idx] = tile[(wave * 16 + r) * TS + c];
         }
       }
     }
@@ -389,38 +455,43 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
 
 // grid.x = number of 64-env tiles; more tiles than CUs: two teams per block (RolloutLaunch's rule) where the two-team form of
 // this variant and this kernel form fits (two_teams_fit, csrc/pds_rollout.h, on the form's own two code objects).
-template <bool METRICS, bool STATS = false>
+template <bool METRICS, bool STATS = false, bool RECORD = false>
 struct EvalLaunchT {
   dim3 grid;
   hipStream_t s;
-  const EvalKernelArgs<METRICS, STATS> &args;
+  const EvalKernelArgs<METRICS, STATS, RECORD> &args;
   template <class RV_>
   void run() const {
-    if (grid.x > (unsigned)kRolloutTwoTeamsAbove && two_teams_fit<&evaluate_kernel<RV_, 1, METRICS, STATS>, &evaluate_kernel<RV_, 2, METRICS, STATS>>())
-      hipLaunchKernelGGL((evaluate_kernel<RV_, 2, METRICS, STATS>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, args);
+    if (grid.x > (unsigned)kRolloutTwoTeamsAbove &&
+        two_teams_fit<&evaluate_kernel<RV_, 1, METRICS, STATS, RECORD>, &evaluate_kernel<RV_, 2, METRICS, STATS, RECORD>>())
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 2, METRICS, STATS, RECORD>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, args);
     else
-      hipLaunchKernelGGL((evaluate_kernel<RV_, 1, METRICS, STATS>), grid, dim3(kRolloutThreads), 0, s, args);
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 1, METRICS, STATS, RECORD>), grid, dim3(kRolloutThreads), 0, s, args);
   }
 };
 
 // ---- the seven launch functions of pds_evaluate_args.h.  flags -> variant is the fused family's one table (fused_task and the
 // fused_*_family of csrc/pds_rollout.h) over an EvalLaunchT.  Each function is defined and explicitly instantiated by the
-// translation unit that holds its kernels, csrc/pds_evaluate[_metrics|_stats]_<task>[_pwm|_lat].hip, for that unit's form: a
+// translation unit that holds its kernels, csrc/pds_evaluate[_metrics|_stats|_record]_<task>[_pwm|_lat].hip, for that unit's form (the _FORM
+// macros name RECORD; the two older ones are the forms without it): a
 // definition every unit could see would instantiate a family's kernels in its task's dispatcher unit as well. ----
 // control_mode PWM (FAMILY = fused_pwm_family) or the latency ring (fused_lat_family) of Hover / Circle
-#define PDS_EVALUATE_FAMILY_UNIT(NAME, FAMILY, TASK, METRICS, STATS)                                                      \
-  template <bool M, bool S>                                                                                               \
-  bool NAME(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<M, S> &ka) {                             \
-    return FAMILY<TASK>(f, EvalLaunchT<M, S>{grid, s, ka});                                                               \
+#define PDS_EVALUATE_FAMILY_UNIT(NAME, FAMILY, TASK, METRICS, STATS) PDS_EVALUATE_FAMILY_UNIT_FORM(NAME, FAMILY, TASK, METRICS, STATS, false)
+#define PDS_EVALUATE_FAMILY_UNIT_FORM(NAME, FAMILY, TASK, METRICS, STATS, RECORD)                                         \
+  template <bool M, bool S, bool R>                                                                                       \
+  bool NAME(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<M, S, R> &ka) {                          \
+    return FAMILY<TASK>(f, EvalLaunchT<M, S, R>{grid, s, ka});                                                            \
   }                                                                                                                       \
-  template bool NAME<METRICS, STATS>(const LaunchFlags &, dim3, hipStream_t, const EvalKernelArgs<METRICS, STATS> &);
+  template bool NAME<METRICS, STATS, RECORD>(const LaunchFlags &, dim3, hipStream_t, const EvalKernelArgs<METRICS, STATS, RECORD> &);
 // a task's dispatcher + the PID control modes and the Kalman hold; `...`: fused_task's `lat` and `pwm`, the unit's own form of the
-// two family functions (TakeOff, which holds all its families: nullptr, nullptr)
-#define PDS_EVALUATE_TASK_UNIT(NAME, TASK, METRICS, STATS, ...)                                                           \
-  template <bool M, bool S>                                                                                               \
-  bool NAME(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<M, S> &ka) {                             \
-    return fused_task<TASK>(f, EvalLaunchT<M, S>{grid, s, ka}, __VA_ARGS__);                                               \
+// two family functions (TakeOff, which holds all its families: nullptr, nullptr).  <M, S> names the family functions of the three
+// forms without a record (R = false, the default); the record form's units say <M, S, R>
+#define PDS_EVALUATE_TASK_UNIT(NAME, TASK, METRICS, STATS, ...) PDS_EVALUATE_TASK_UNIT_FORM(NAME, TASK, METRICS, STATS, false, __VA_ARGS__)
+#define PDS_EVALUATE_TASK_UNIT_FORM(NAME, TASK, METRICS, STATS, RECORD, ...)                                              \
+  template <bool M, bool S, bool R>                                                                                       \
+  bool NAME(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<M, S, R> &ka) {                          \
+    return fused_task<TASK>(f, EvalLaunchT<M, S, R>{grid, s, ka}, __VA_ARGS__);                                           \
   }                                                                                                                       \
-  template bool NAME<METRICS, STATS>(const LaunchFlags &, dim3, hipStream_t, const EvalKernelArgs<METRICS, STATS> &);
+  template bool NAME<METRICS, STATS, RECORD>(const LaunchFlags &, dim3, hipStream_t, const EvalKernelArgs<METRICS, STATS, RECORD> &);
 
 }  // namespace pds

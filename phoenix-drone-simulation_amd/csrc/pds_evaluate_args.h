@@ -40,11 +40,13 @@ struct EvalStatsArgs {
   float *obs_sums;    // [tiles, 4, 2, 64]: tile, network wave, S1 / S2, feature (include/pds.h), 16-byte aligned
 };
 static_assert(offsetof(EvalStatsArgs, m) == 0, "the stats kernel reads the head of its argument block as an EvalMetricsArgs");
-// the argument block of evaluate_kernel<V, TEAMS, METRICS, STATS> and the EvalArgs at its head
-template <bool METRICS, bool STATS = false>
-using EvalKernelArgs = std::conditional_t<STATS, EvalStatsArgs, std::conditional_t<METRICS, EvalMetricsArgs, EvalArgs>>;
+struct EvalRecordArgs;  // (last in this file)
+// the argument block of evaluate_kernel<V, TEAMS, METRICS, STATS[, RECORD]> and the EvalArgs at its head
+template <bool METRICS, bool STATS = false, bool RECORD = false>
+using EvalKernelArgs =
+    std::conditional_t<RECORD, EvalRecordArgs, std::conditional_t<STATS, EvalStatsArgs, std::conditional_t<METRICS, EvalMetricsArgs, EvalArgs>>>;
 // ... on the host and on the device, for a const or a mutable block (EvalHistArgs of csrc/pds_evaluate_hist_args.h too: its first
-// member is an EvalMetricsArgs `m`, like EvalStatsArgs')
+// member is an EvalMetricsArgs `m`, like EvalStatsArgs' and EvalRecordArgs')
 template <class KA>
 __host__ __device__ inline auto &eval_head(KA &ka) {
   if constexpr (std::is_same_v<std::remove_const_t<KA>, EvalArgs>) return ka;
@@ -52,24 +54,38 @@ __host__ __device__ inline auto &eval_head(KA &ka) {
   else return ka.m.e;
 }
 
-// The launch functions, one set for the three forms (METRICS, STATS = false, false: pds_evaluate_policies; true, false: .._metrics;
-// true, true: .._stats).  Each is defined and explicitly instantiated for one form by the translation unit that holds the form's
-// kernels: csrc/pds_evaluate[_metrics|_stats]_<task>.hip ...
-template <bool METRICS, bool STATS>
-bool launch_evaluate_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
-template <bool METRICS, bool STATS>
-bool launch_evaluate_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
-template <bool METRICS, bool STATS>
-bool launch_evaluate_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
-// ... and their families, csrc/pds_evaluate[_metrics|_stats]_<task>_{pwm,lat}.hip, like the rollout's: control_mode PWM with every
+// The launch functions, one set for the four forms (METRICS, STATS = false, false: pds_evaluate_policies; true, false: .._metrics;
+// true, true: .._stats; RECORD is named by the record form only -- true, false, true: .._record).  Each is defined and explicitly
+// instantiated for one form by the translation unit that holds the form's kernels: csrc/pds_evaluate[_metrics|_stats|_record]_<task>.hip ...
+template <bool METRICS, bool STATS, bool RECORD = false>
+bool launch_evaluate_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
+template <bool METRICS, bool STATS, bool RECORD = false>
+bool launch_evaluate_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
+template <bool METRICS, bool STATS, bool RECORD = false>
+bool launch_evaluate_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
+// ... and their families, csrc/pds_evaluate[_metrics|_stats|_record]_<task>_{pwm,lat}.hip, like the rollout's: control_mode PWM with every
 // noise setting / the latency ring
-template <bool METRICS, bool STATS>
-bool launch_evaluate_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
-template <bool METRICS, bool STATS>
-bool launch_evaluate_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
-template <bool METRICS, bool STATS>
-bool launch_evaluate_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
-template <bool METRICS, bool STATS>
-bool launch_evaluate_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS> &ka);
+template <bool METRICS, bool STATS, bool RECORD = false>
+bool launch_evaluate_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
+template <bool METRICS, bool STATS, bool RECORD = false>
+bool launch_evaluate_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
+template <bool METRICS, bool STATS, bool RECORD = false>
+bool launch_evaluate_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
+template <bool METRICS, bool STATS, bool RECORD = false>
+bool launch_evaluate_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
+
+// Arguments of evaluate_kernel<V, TEAMS, true, false, true> (pds_evaluate_policies_record): the metrics kernel's (`metrics` may be
+// NULL here: summed, not stored) and behind them the record of the flights.  Of the E / 64 tiles of a policy the first rec_tiles
+// record: tile t iff t % tiles_per_policy < rec_tiles (wave-uniform), its lane's column of the record
+//   j = (t / tiles_per_policy) * 64 * rec_tiles + (t % tiles_per_policy) * 64 + lane,       N_rec = P * 64 * rec_tiles.
+// The argument blocks of the other forms stay the ones they were.
+struct EvalRecordArgs {
+  EvalMetricsArgs m;  // FIRST member (the kernel reads the head of its argument block as an EvalMetricsArgs)
+  float4 *flight;     // [T, 4, N_rec, 4] floats, 16-byte aligned: step s, piece q, column j -- piece 0 = (px, py, pz, vx), 1 = (vy, vz,
+                      // roll, pitch), 2 = (yaw, wx, wy, wz) of x(s), 3 = a(s) raw; a wave stores a piece as one 1 KiB line
+  float *obs_rec;     // [T, N_rec, D] the raw observation o(s) the policy acted on, or NULL
+  int rec_tiles;      // 1 <= rec_tiles <= tiles_per_policy
+};
+static_assert(offsetof(EvalRecordArgs, m) == 0, "the record kernel reads the head of its argument block as an EvalMetricsArgs");
 
 }  // namespace pds

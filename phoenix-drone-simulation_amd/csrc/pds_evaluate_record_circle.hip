@@ -1,0 +1,6 @@
+// pds_evaluate_record_circle.hip -- evaluate_kernel (pds_evaluate.h), record form: the task's dispatcher, the PID control modes, the Kalman hold.
+#include "pds_evaluate.h"
+
+namespace pds {
+PDS_EVALUATE_TASK_UNIT_FORM(launch_evaluate_circle, PDS_TASK_CIRCLE, true, false, true, launch_evaluate_circle_lat<M, S, R>, launch_evaluate_circle_pwm<M, S, R>)
+}  // namespace pds

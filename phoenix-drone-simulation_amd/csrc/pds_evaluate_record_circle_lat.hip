@@ -1,0 +1,6 @@
+// pds_evaluate_record_circle_lat.hip -- evaluate_kernel (pds_evaluate.h), record form: the latency ring, PWM and PID modes.
+#include "pds_evaluate.h"
+
+namespace pds {
+PDS_EVALUATE_FAMILY_UNIT_FORM(launch_evaluate_circle_lat, fused_lat_family, PDS_TASK_CIRCLE, true, false, true)
+}  // namespace pds

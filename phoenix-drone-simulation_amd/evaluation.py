@@ -12,7 +12,9 @@ an evolution strategy over actor weights -- in one launch: P policies x E episod
 With `metrics=True` the same launch also reports the flight-quality sums the reference tabulates per real flight
 (experiments/02_zero_shot_policy_transfer_hover_task/02_eval_hover_task.py): `FlightMetrics`; `metrics_from_arrays` scores a
 logged flight by the same definitions.  With `obs_stats=True` it also sums the observations the policies acted on, for a running
-standardisation (`ObsSums`; include/pds.h pds_evaluate_policies_stats)."""
+standardisation (`ObsSums`; include/pds.h pds_evaluate_policies_stats).  With `record=R` the launch also writes the flights
+themselves out -- state, action and observation of every step of the first R episodes per policy -- as a `Flights`
+(include/pds_record.h pds_evaluate_policies_record)."""
 import math
 import os
 
@@ -402,9 +404,117 @@ class ObsSums:
         return self._moments(self.count.sum(), c, sd, sd2)
 
 
+# ---- the recorded flights (include/pds_record.h pds_evaluate_policies_record) ---------------------------------------------------
+class Flights:
+    """What evaluate_population(..., record=R) records of the first R episodes of each of P policies, float32 on the CPU:
+    `state` [P, R, T, 12] the true state x(s) the policy acted in, in the column order of a flight log (simopt.OBS_COLUMNS: x y z,
+    x_dot y_dot z_dot, roll pitch yaw, roll_dot pitch_dot yaw_dot), `action` [P, R, T, 4] the raw action a(s) handed to step s,
+    `observation` [P, R, T, D] the raw (unstandardised) observation o(s) the policy acted on, or None, `length` [P, R] the
+    episode lengths L and `step_seconds` the simulated time of one env step.  Rows s >= L are zero.  The terminal state x(L) and
+    the terminal observation are not part of the record.  `last_action0` [P, R, 4]: the command in force before the first step
+    (the env's last_action after its reset), `control_mode` the env's."""
+
+    def __init__(self, state, action, observation, length, step_seconds, last_action0=None, control_mode="PWM"):
+        self.state = torch.as_tensor(state, dtype=torch.float32)
+        self.action = torch.as_tensor(action, dtype=torch.float32)
+        self.observation = None if observation is None else torch.as_tensor(observation, dtype=torch.float32)
+        self.length = torch.as_tensor(length, dtype=torch.float32)
+        self.step_seconds = float(step_seconds)
+        self.control_mode = control_mode
+        if self.state.dim() != 4 or self.state.shape[3] != 12:
+            raise ValueError(f"state must be [P, R, T, 12], got {tuple(self.state.shape)}")
+        P, R, T = self.state.shape[:3]
+        if tuple(self.action.shape) != (P, R, T, 4) or tuple(self.length.shape) != (P, R):
+            raise ValueError(f"action must be [{P}, {R}, {T}, 4] and length [{P}, {R}]")
+        if self.observation is not None and (self.observation.dim() != 4 or tuple(self.observation.shape[:3]) != (P, R, T)):
+            raise ValueError(f"observation must be [{P}, {R}, {T}, D]")
+        if bool((self.length < 0).any()) or bool((self.length > T).any()):
+            raise ValueError(f"lengths outside 0 .. {T}")
+        self.last_action0 = torch.zeros(P, R, 4) if last_action0 is None else torch.as_tensor(last_action0, dtype=torch.float32).reshape(P, R, 4)
+
+    @property
+    def P(self):
+        return int(self.state.shape[0])
+
+    @property
+    def R(self):
+        return int(self.state.shape[1])
+
+    def episode(self, p, e):
+        """-> dict(state [L, 12], action [L, 4], observation [L, D] or None): episode e of policy p, cut to its length L."""
+        L = int(self.length[p, e])
+        return dict(state=self.state[p, e, :L], action=self.action[p, e, :L],
+                    observation=None if self.observation is None else self.observation[p, e, :L])
+
+    def metrics(self):
+        """-> [P, R, 8] float64 numpy: metrics_from_arrays of every recorded episode (METRIC_NAMES order) -- the definitions in
+        float64 over the recorded float32 states, next to the float32 sums of the launch (FlightMetrics.raw)."""
+        out = np.zeros((self.P, self.R, len(METRIC_NAMES)))
+        for p in range(self.P):
+            for e in range(self.R):
+                ep = self.episode(p, e)
+                x = ep["state"].numpy()
+                out[p, e] = metrics_from_arrays(x[:, 6:9], x[:, 9:12], ep["action"].numpy(), self.last_action0[p, e].numpy())
+        return out
+
+    def pairs(self):
+        """-> (X, Y), each [sum over the episodes of (L - 1), D] float32: X = o(s), Y = o(s + 1) for s + 1 < L within an episode,
+        the episodes in order (policy, then episode).  These are get_batch's pairs WITHOUT the terminal row of each episode -- the
+        pair (o(L - 1), terminal observation) is not there, the terminal observation not being recorded -- and unstandardised."""
+        if self.observation is None:
+            raise ValueError("recorded without observations (record_observations=False)")
+        xs, ys = [], []
+        for p in range(self.P):
+            for e in range(self.R):
+                o = self.episode(p, e)["observation"]
+                xs.append(o[:-1]); ys.append(o[1:])
+        return torch.cat(xs), torch.cat(ys)
+
+    def _logs(self):
+        """per recorded episode ((p, e), the 12 log columns [L, 12] float64, the PWMs [L, 4] a fully charged battery takes)"""
+        if self.control_mode != "PWM":
+            raise ValueError(f"control mode {self.control_mode}: the actions are motor PWMs under control_mode PWM only")
+        for p in range(self.P):
+            for e in range(self.R):
+                ep = self.episode(p, e)
+                yield (p, e), ep["state"].double().numpy(), (np.clip(ep["action"].double().numpy(), -1.0, 1.0) + 1.0) * 30000.0
+
+    def to_csv_dir(self, path, voltage=3.9):
+        """One CSV per recorded episode, `path`/policy_<p>_episode_<e>.csv, in the layout MiniTrajectories.from_csv_dir reads:
+        simopt.OBS_COLUMNS, simopt.PWM_COLUMNS and `bat`.  PWM = (clip(a, -1, 1) + 1) * 30000 is what the motors took; the file
+        holds the PWM that gives the same thrust at the constant battery `voltage` (the battery model of the logs inverted, as
+        examples/run_simulation_optimization.py synthetic_logs does), so that from_csv_dir recovers the actions.  control_mode PWM
+        only: ValueError otherwise.  -> the list of files."""
+        from . import simopt
+        mt = simopt.MiniTrajectories
+        logs = list(self._logs())
+        os.makedirs(path, exist_ok=True)
+        files = []
+        for (p, e), log, pwm in logs:
+            grams = pwm / 65535 * 60
+            raw = (mt.BATTERY_QUAD * grams ** 2 + mt.BATTERY_LIN * grams) / voltage * 65535
+            name = os.path.join(path, f"policy_{p:04d}_episode_{e:05d}.csv")
+            with open(name, "w") as f:
+                f.write(",".join(simopt.OBS_COLUMNS + simopt.PWM_COLUMNS + ["bat"]) + "\n")
+                for s in range(log.shape[0]):
+                    f.write(",".join(repr(float(v)) for v in list(log[s]) + list(raw[s]) + [voltage]) + "\n")
+            files.append(name)
+        return files
+
+    def mini_trajectories(self, T=35, pre_steps=5, skip=10):
+        """-> simopt.MiniTrajectories: create_trajectory_slices of every recorded episode that is long enough for one slice
+        (L > T + pre_steps), concatenated in order; the actions are the clipped ones the motors took.  control_mode PWM only."""
+        from . import simopt
+        parts = [simopt.MiniTrajectories.create_trajectory_slices(log, pwm, T, pre_steps, skip)
+                 for _, log, pwm in self._logs() if log.shape[0] > T + pre_steps]
+        if not parts:
+            raise ValueError(f"no recorded episode is longer than T + pre_steps = {T + pre_steps} steps")
+        return simopt.MiniTrajectories(*[np.concatenate([part[k] for part in parts]) for k in range(3)])
+
+
 @torch.no_grad()
 def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None, metrics=False, obs_stats=False,
-                        history_fused=False):
+                        history_fused=False, record=None, record_observations=True, record_limit_bytes=1 << 30):
     """-> (returns, ep_lengths, costs), each [P, E] float32 on the CPU: policy p of `population` flies the E = num_envs / P
     envs of block p, one episode per env, deterministically (action = actor mean), as `evaluate` does for one policy.
     metrics=True: -> (returns, ep_lengths, costs, FlightMetrics) -- the first three are the same bits; the kernel path is
@@ -414,6 +524,14 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     d^2 over every observation the policy acted on in a first episode.  The kernel path is pds_evaluate_policies_stats (it also
     produces the metrics: metrics=False drops them); the composed path keeps per-env float32 sums with one torch op per
     difference, product and sum and adds them in the kernel's tree order (`tree_reduce_rows`): the same slab on the bits.
+    record=R (a positive multiple of 64, at most E; not together with obs_stats): the return value gains a LAST element, a
+    `Flights`: of every policy's first R episodes the true state x(s) the policy acted in, the raw action a(s) and -- unless
+    record_observations=False -- the raw observation o(s) it acted on, for every step s < length; rows past an episode's end
+    are zero.  Not recorded: the terminal state x(L) and the terminal observation (a finished env is reset in place inside the
+    step).  The kernel path is pds_evaluate_policies_record (it also produces the metrics: metrics=False drops them); the
+    composed path -- every env without a fused kernel, observation histories included, where o(s) is the history the actor read
+    -- reads pos, vel, rpy and omega in front of every step: the same bits.  The record takes max_steps x P x R x (64 + 4 D)
+    bytes on the device and again on the host; above record_limit_bytes the call raises ValueError before it allocates.
 
     fused=True: one launch (pds_evaluate_policies, csrc/pds_evaluate.h); NotImplementedError where no kernel is built --
     observation_history_size != 2 included -- with the env untouched.  fused=False: the composed path, per step one
@@ -439,8 +557,23 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     T = int(env._max_episode_steps if max_steps is None else max_steps)
     if T < 1:
         raise ValueError(f"max_steps = {T}")
+    R = None
+    if record is not None:  # (what pds_evaluate_policies_record refuses, before the library is asked anything)
+        if isinstance(record, (bool, np.bool_)) or int(record) != record:
+            raise ValueError(f"record = {record!r}: a number of episodes per policy")
+        R = int(record)
+        if R < 64 or R % 64 != 0 or R > E:
+            raise ValueError(f"record = {R} is not a positive multiple of 64 (one tile) up to E = {E}")
+        if obs_stats:
+            raise ValueError("record and obs_stats do not come together: no kernel form gathers both")
+        need = T * P * R * (64 + 4 * int(env.obs_dim))
+        if need > int(record_limit_bytes):
+            raise ValueError(f"the record of {T} steps x {P} x {R} episodes takes {need} bytes, above record_limit_bytes = "
+                             f"{int(record_limit_bytes)}: record fewer episodes or fewer steps, or raise the limit")
     H = int(getattr(env, "observation_history_size", 2))
     use_history = bool(history_fused) and H != 2
+    if R is not None:
+        use_history = False  # (no record kernel for histories: they record through the composed path)
     use_kernel = False
     if fused is not False and use_history:
         built = not obs_stats and fused_history_evaluation_built(env)
@@ -457,10 +590,15 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     population = population.to(env.device)
     dev, n, D = env.device, env.num_envs, env.obs_dim
     ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
-    raw = slab = None
+    raw = slab = flight = obs_rec = u0 = None
     obs, _ = env.reset()
+    if R is not None:  # zero-filled: the rows past an episode's end stay zero on both paths
+        rec_env = (torch.arange(P, device=dev).unsqueeze(1) * E + torch.arange(R, device=dev).unsqueeze(0)).reshape(-1)  # [P R] env of column j
+        u0 = env.get_state("last_action")[rec_env].cpu()  # the command in force before the first (Flights.metrics)
+        flight = torch.zeros(T, 4, P * R, 4, device=dev)
+        obs_rec = torch.zeros(T, P * R, D, device=dev) if record_observations else None
     if use_kernel:
-        if metrics or obs_stats:
+        if metrics or obs_stats or R is not None:
             raw = torch.zeros(n, len(METRIC_NAMES), device=dev)
         if obs_stats:
             slab = torch.zeros(n // 64, SLAB_WAVES, 2, SLAB_FEATURES, device=dev)
@@ -468,6 +606,8 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
         if use_history:  # (never with obs_stats)
             obs = obs.contiguous()  # [N, H * half]: the histories env.reset() returns
             name, lead, trail = "pds_evaluate_policies_history", (H,), (raw,)
+        elif R is not None:
+            name, lead, trail = "pds_evaluate_policies_record", (), (raw, R, flight, obs_rec)
         elif obs_stats:
             name, lead, trail = "pds_evaluate_policies_stats", (), (raw, slab)
         elif metrics:
@@ -487,7 +627,7 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
             s1, s2 = torch.zeros(n, D, device=dev), torch.zeros(n, D, device=dev)
             shift_rows = population.mean.repeat_interleave(E, dim=0) if has else None
             zero_nd = torch.zeros(n, D, device=dev)
-        for _ in range(T):
+        for s in range(T):
             if metrics:  # x(s): the state the policy acts in
                 rpy, omega, last = env.get_state("rpy"), env.get_state("omega"), env.get_state("last_action")
             for p in range(P):
@@ -495,6 +635,13 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
                             _ptr(population.std, 4 * p * D) if has else None, population.eps, _ptr(act, 16 * p * E), on=dev)
             if metrics:
                 prev_neg = _compose_metrics(acc, prev_neg, alive, rpy, omega, act, last)
+            if R is not None:  # x(s), a(s) and o(s) of the recorded envs alive in front of step s
+                x = torch.cat([env.get_state(f) for f in ("pos", "vel", "rpy", "omega")] + [act], dim=1)[rec_env]  # [P R, 16]
+                on = alive[rec_env].unsqueeze(1)
+                flight[s] = torch.where(on, x, torch.zeros_like(x)).reshape(P * R, 4, 4).transpose(0, 1)
+                if obs_rec is not None:
+                    o = obs[rec_env]
+                    obs_rec[s] = torch.where(on, o, torch.zeros_like(o))
             if obs_stats:  # o(s), for the envs alive in front of step s
                 d = obs - shift_rows if has else obs
                 on = alive.unsqueeze(1)
@@ -532,4 +679,9 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     if obs_stats:
         shift = population.mean.cpu().double() if population.mean is not None else torch.zeros(P, D, dtype=torch.float64)
         out = out + (ObsSums(slab, length.double().sum(dim=1), shift),)
+    if R is not None:
+        fl = flight.permute(2, 0, 1, 3).contiguous().cpu().reshape(P, R, T, 16)  # [column, step, piece, 4]: the 12 log columns, then the action
+        out = out + (Flights(fl[..., :12], fl[..., 12:], None if obs_rec is None else obs_rec.permute(1, 0, 2).contiguous().cpu().reshape(P, R, T, D),
+                             length[:, :R], float(env.cfg.time_step) * int(env.cfg.aggregate_phy_steps), u0.reshape(P, R, 4),
+                             control_mode={v: k for k, v in native.CONTROL_MODES.items()}[int(env.cfg.control_mode)]),)
     return out

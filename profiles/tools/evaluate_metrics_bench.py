@@ -44,9 +44,9 @@ def scratch_of_forms():
     out = {}
     for r in kr.kernel_table():
         if "evaluate_kernel<" in r[0] and HOVER_DEFAULT in r[0]:
-            tail = r[0].split(HOVER_DEFAULT)[1].split(">")[0].split(",")[1:]  # TEAMS, METRICS, STATS
+            tail = r[0].split(HOVER_DEFAULT)[1].split(">")[0].split(",")[1:]  # TEAMS, METRICS, STATS, RECORD
             teams, metrics, stats = int(tail[0]), tail[1].strip() == "true", tail[2].strip() == "true"
-            if not stats:  # (the stats form: profiles/tools/evaluate_stats_bench.py)
+            if not stats and tail[3].strip() != "true":  # (the stats and record forms: profiles/tools/evaluate_{stats,record}_bench.py)
                 out[(metrics, teams)] = r[5]
     return out
 

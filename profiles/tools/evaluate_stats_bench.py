@@ -32,8 +32,8 @@ def scratch_of_forms():
     out = {}
     for r in kr.kernel_table():
         if "evaluate_kernel<" in r[0] and mb.HOVER_DEFAULT in r[0]:
-            tail = r[0].split(mb.HOVER_DEFAULT)[1].split(">")[0].split(",")[1:]  # TEAMS, METRICS, STATS
-            if tail[1].strip() == "true":
+            tail = r[0].split(mb.HOVER_DEFAULT)[1].split(">")[0].split(",")[1:]  # TEAMS, METRICS, STATS, RECORD
+            if tail[1].strip() == "true" and tail[3].strip() != "true":
                 out[(tail[2].strip() == "true", int(tail[0]))] = r[5]
     return out
 

@@ -13,7 +13,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kernel_resources as kr  # noqa: E402
 
-NAME = re.compile(r"evaluate_kernel<pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>, (\d), (\w+), (\w+)>")
+NAME = re.compile(r"evaluate_kernel<pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>, (\d), (\w+), (\w+), false>")  # (the last argument: RECORD, profiles/tools/evaluate_record_resources.py)
 TASK = ("Hover", "Circle", "TakeOff")
 CTRL = ("PWM", "Rate", "Att")
 RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "evaluate_metrics_kernel_resources.txt")
