@@ -423,7 +423,7 @@ int pds_evaluate_policies(pds_handle *h, int64_t P, int64_t episodes_per_policy,
                           const float *d_mean, const float *d_std, float eps, int max_steps, const float *d_obs0, float *d_ret,
                           float *d_len, float *d_cost, void *stream);
 
-/* The same launch, also reporting flight-quality metrics (csrc/pds_evaluate.h, METRICS): what the reference tabulates per real
+/* The same launch, also reporting flight-quality metrics (csrc/pds_evaluate.h, the flight metrics): what the reference tabulates per real
  * flight (experiments/02_zero_shot_policy_transfer_hover_task/02_eval_hover_task.py: mean squared roll and pitch, the oscillation
  * of the rates and of the motor commands, the flight time) as raw sums over the states x(0) .. x(L - 1) the first episode's
  * policy acted in -- x(0) the state pds_reset left, x(s) the TRUE state before step s (not the noisy observation), L the episode
@@ -449,7 +449,7 @@ int pds_evaluate_policies_metrics(pds_handle *h, int64_t P, int64_t episodes_per
                                   const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics, void *stream);
 
 /* pds_evaluate_policies_metrics with one more output: the sums a running observation standardisation is updated from
- * (csrc/pds_evaluate.h, STATS), over every observation o(s) a first-episode policy acted on -- o(s) of env n for s < d_len[n], so
+ * (csrc/pds_evaluate.h, the observation sums), over every observation o(s) a first-episode policy acted on -- o(s) of env n for s < d_len[n], so
  * their count per policy is the sum of its d_len.  Per feature k < D
  *     d = o_k - d_mean[p][k]   (d = o_k when d_mean is NULL),   S1 += d,   S2 += d * d,
  * every difference, product and sum rounded on its own in float32; the shift by the policy's own mean keeps S2 well conditioned.
@@ -464,6 +464,26 @@ int pds_evaluate_policies_stats(pds_handle *h, int64_t P, int64_t episodes_per_p
                                 const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
                                 const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
                                 float *d_obs_sums, void *stream);
+
+/* pds_evaluate_policies_metrics (d_metrics may be NULL here) that also RECORDS the flights it scores (csrc/pds_evaluate.h, the
+ * record): of every policy's episodes_per_policy envs the first record_per_policy -- a positive multiple of 64, at most
+ * episodes_per_policy -- are recorded, N_rec = P * record_per_policy columns, column j = p * record_per_policy + e for env e of
+ * policy p.
+ * d_flight [max_steps, 4, N_rec, 4] float32, 16-byte aligned: for step s and column j four pieces of four floats,
+ *     piece 0 = (px, py, pz, vx), 1 = (vy, vz, roll, pitch), 2 = (yaw, wx, wy, wz) of x(s), 3 = a(s),
+ * x(s) the true state the policy acted in (what the PDS_EM_* sums are taken over) and a(s) the raw action handed to step s:
+ * together the twelve columns of a flight log and the four commands.
+ * d_obs_rec [max_steps, N_rec, D] float32 or NULL: the raw (unstandardised) observation o(s) the policy acted on.
+ * Only the rows s < d_len of a recorded env are written; every other element keeps what the caller put there (zero-fill the
+ * buffers).  Not recorded: the terminal state x(L) and the terminal observation -- a finished env is reset in place inside the step.
+ * d_ret / d_len / d_cost / d_metrics are the bits of pds_evaluate_policies_metrics.  Checks, support (pds_evaluate_supported) and
+ * the state of the handle afterwards are pds_evaluate_policies'; in front of them PDS_EINVAL for a record_per_policy that is not
+ * a positive multiple of 64 or exceeds episodes_per_policy, a NULL or misaligned d_flight, or a d_obs_rec that is not 4-byte
+ * aligned. */
+int pds_evaluate_policies_record(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                                 const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                                 const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
+                                 int64_t record_per_policy, float *d_flight, float *d_obs_rec, void *stream);
 
 /* The population evaluation for policies that read an observation HISTORY (csrc/pds_evaluate_hist.h; observation_history_size =
  * `history`, envs/base.py:44, 303-319, 417-431): the actors read the last `history` halves [o, u] of their env, history * half

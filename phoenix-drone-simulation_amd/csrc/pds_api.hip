@@ -14,7 +14,6 @@
 
 #include "pds_reset.h"  // (pds_types.h + regen_kept_obs for pds_get_state)
 #include "pds_collect_args.h"
-#include "../../include/pds_record.h"
 #include "pds_evaluate_args.h"
 #include "pds_evaluate_hist_args.h"
 #include "pds_simopt.h"
@@ -1155,61 +1154,55 @@ static int fill_evaluate_args(pds_handle *h, const char *fn, EvalArgs &ea, int64
   ea.ret = d_ret; ea.len = d_len; ea.cost = d_cost;
   return PDS_OK;
 }
-// ONE body for pds_evaluate_policies, pds_evaluate_policies_metrics and pds_evaluate_policies_stats: the checks, the argument
-// block and the handle's state afterwards are stated once; METRICS adds the d_metrics check and selects the kernels' metrics
-// form, STATS (with METRICS) the d_obs_sums check and the stats form.  RECORD (pds_evaluate_policies_record, with METRICS): `rec`
-// holds what that entry point adds; its checks come first, d_metrics is optional and the record form's kernels are launched.
-struct EvalRecordCall {
+// ONE body for the four forms of pds_evaluate_policies (EvalForm, csrc/pds_evaluate_args.h): the checks, the argument block and the
+// handle's state afterwards are stated once.  EvalFormCall holds what the forms add to the plain call; a form leaves what it does
+// not take NULL / 0.  Metrics and Stats ask for d_metrics, Stats for d_obs_sums; the Record form's checks come first and its
+// d_metrics is optional.
+struct EvalFormCall {
+  float *d_metrics, *d_obs_sums;
   int64_t record_per_policy;
   float *d_flight, *d_obs_rec;
 };
-template <bool METRICS, bool STATS = false, bool RECORD = false>
+template <EvalForm F>
 static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
                                   const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
-                                  const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics, float *d_obs_sums,
-                                  void *stream, const EvalRecordCall *rec = nullptr) {
+                                  const float *d_obs0, float *d_ret, float *d_len, float *d_cost, const EvalFormCall &x, void *stream) {
+  constexpr bool STATS = F == EvalForm::Stats, RECORD = F == EvalForm::Record;
   if (!h) return PDS_EINVAL;
   if constexpr (RECORD) {  // (decided before the handle is looked at)
-    if (rec->record_per_policy < kWave || rec->record_per_policy % kWave != 0 || rec->record_per_policy > episodes_per_policy)
+    if (x.record_per_policy < kWave || x.record_per_policy % kWave != 0 || x.record_per_policy > episodes_per_policy)
       return fail(h, PDS_EINVAL, "%s: record_per_policy %lld is not a positive multiple of %d up to episodes_per_policy %lld", fn,
-                  (long long)rec->record_per_policy, kWave, (long long)episodes_per_policy);
-    if (!rec->d_flight || (((uintptr_t)rec->d_flight) & 15u)) return fail(h, PDS_EINVAL, "%s: d_flight must be given and 16-byte aligned", fn);
-    if (((uintptr_t)rec->d_obs_rec) & 3u) return fail(h, PDS_EINVAL, "%s: d_obs_rec must be 4-byte aligned", fn);
+                  (long long)x.record_per_policy, kWave, (long long)episodes_per_policy);
+    if (!x.d_flight || (((uintptr_t)x.d_flight) & 15u)) return fail(h, PDS_EINVAL, "%s: d_flight must be given and 16-byte aligned", fn);
+    if (((uintptr_t)x.d_obs_rec) & 3u) return fail(h, PDS_EINVAL, "%s: d_obs_rec must be 4-byte aligned", fn);
   }
-  const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost || (METRICS && !RECORD && !d_metrics) || (STATS && !d_obs_sums);
-  if (const int rc = check_evaluate_call(h, fn, any_null, P, episodes_per_policy, shape, h->obs_dim, d_mean, d_std, max_steps,
-                                         METRICS ? d_metrics : nullptr))
+  const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost ||
+                        (eval_sums_metrics(F) && !RECORD && !x.d_metrics) || (STATS && !x.d_obs_sums);
+  if (const int rc = check_evaluate_call(h, fn, any_null, P, episodes_per_policy, shape, h->obs_dim, d_mean, d_std, max_steps, x.d_metrics))
     return rc;
-  if (STATS && (((uintptr_t)d_obs_sums) & 15u)) return fail(h, PDS_EINVAL, "%s: d_obs_sums must be 16-byte aligned", fn);
+  if (STATS && (((uintptr_t)x.d_obs_sums) & 15u)) return fail(h, PDS_EINVAL, "%s: d_obs_sums must be 16-byte aligned", fn);
   if (!rollout_supported(h->cfg.task, h->flags))
     return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: what pds_rollout is built for) -- "
                                      "pds_mlp_forward + pds_step give the same bits", fn);
   DeviceGuard guard(h->cfg.device);
   PDS_HIP(h, guard.err);
-  EvalKernelArgs<METRICS, STATS, RECORD> ka;
+  EvalKernelArgs<F> ka;
   memset(&ka, 0, sizeof(ka));
-  EvalArgs &ea = eval_head(ka);
+  if constexpr (F == EvalForm::Metrics) ka.metrics = x.d_metrics;
+  else if constexpr (eval_sums_metrics(F)) ka.m.metrics = x.d_metrics;
+  if constexpr (STATS) ka.obs_sums = x.d_obs_sums;
   if constexpr (RECORD) {
-    ka.m.metrics = d_metrics;
-    ka.flight = reinterpret_cast<float4 *>(rec->d_flight);
-    ka.obs_rec = rec->d_obs_rec;
-    ka.rec_tiles = (int)(rec->record_per_policy / kWave);
+    ka.flight = reinterpret_cast<float4 *>(x.d_flight);
+    ka.obs_rec = x.d_obs_rec;
+    ka.rec_tiles = (int)(x.record_per_policy / kWave);
   }
-  else if constexpr (STATS) { ka.m.metrics = d_metrics; ka.obs_sums = d_obs_sums; }
-  else if constexpr (METRICS) ka.metrics = d_metrics;
-  if (const int rc = fill_evaluate_args(h, fn, ea, episodes_per_policy, shape, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret,
-                                        d_len, d_cost, stream))
+  if (const int rc = fill_evaluate_args(h, fn, eval_head(ka), episodes_per_policy, shape, d_params, d_mean, d_std, eps, max_steps, d_obs0,
+                                        d_ret, d_len, d_cost, stream))
     return rc;
   const int rc = launch_rollout(h, fn, max_steps, stream, [&](dim3 grid, hipStream_t s) {
-    if constexpr (RECORD) {
-      if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hover<METRICS, STATS, RECORD>(h->flags, grid, s, ka);
-      if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_circle<METRICS, STATS, RECORD>(h->flags, grid, s, ka);
-      return launch_evaluate_takeoff<METRICS, STATS, RECORD>(h->flags, grid, s, ka);
-    } else {
-    if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hover<METRICS, STATS>(h->flags, grid, s, ka);
-    if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_circle<METRICS, STATS>(h->flags, grid, s, ka);
-    return launch_evaluate_takeoff<METRICS, STATS>(h->flags, grid, s, ka);
-    }
+    if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hover<F>(h->flags, grid, s, ka);
+    if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_circle<F>(h->flags, grid, s, ka);
+    return launch_evaluate_takeoff<F>(h->flags, grid, s, ka);
   });
   // tiles stopped at different steps: not a state to continue from -- every stepping entry point asks for pds_reset first
   if (rc == PDS_OK) { h->was_reset = false; h->after_evaluate = true; }
@@ -1218,35 +1211,35 @@ static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int6
 extern "C" int pds_evaluate_policies(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
                                      const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
                                      const float *d_obs0, float *d_ret, float *d_len, float *d_cost, void *stream) {
-  return evaluate_policies_call<false>(h, "pds_evaluate_policies", P, episodes_per_policy, shape, d_params, d_mean, d_std, eps,
-                                       max_steps, d_obs0, d_ret, d_len, d_cost, nullptr, nullptr, stream);
+  return evaluate_policies_call<EvalForm::Plain>(h, "pds_evaluate_policies", P, episodes_per_policy, shape, d_params, d_mean, d_std, eps,
+                                                 max_steps, d_obs0, d_ret, d_len, d_cost, {}, stream);
 }
 // the same launch with the PDS_EM_* flight metrics of every first episode in d_metrics [N, PDS_EVAL_METRICS]
 extern "C" int pds_evaluate_policies_metrics(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
                                              const float *d_params, const float *d_mean, const float *d_std, float eps,
                                              int max_steps, const float *d_obs0, float *d_ret, float *d_len, float *d_cost,
                                              float *d_metrics, void *stream) {
-  return evaluate_policies_call<true>(h, "pds_evaluate_policies_metrics", P, episodes_per_policy, shape, d_params, d_mean, d_std,
-                                      eps, max_steps, d_obs0, d_ret, d_len, d_cost, d_metrics, nullptr, stream);
+  return evaluate_policies_call<EvalForm::Metrics>(h, "pds_evaluate_policies_metrics", P, episodes_per_policy, shape, d_params, d_mean,
+                                                   d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost, {d_metrics}, stream);
 }
 // the metrics launch with the per-wave observation sums of every tile in d_obs_sums [tiles, 4, 2, 64] (include/pds.h)
 extern "C" int pds_evaluate_policies_stats(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
                                            const float *d_params, const float *d_mean, const float *d_std, float eps,
                                            int max_steps, const float *d_obs0, float *d_ret, float *d_len, float *d_cost,
                                            float *d_metrics, float *d_obs_sums, void *stream) {
-  return evaluate_policies_call<true, true>(h, "pds_evaluate_policies_stats", P, episodes_per_policy, shape, d_params, d_mean,
-                                            d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost, d_metrics, d_obs_sums, stream);
+  return evaluate_policies_call<EvalForm::Stats>(h, "pds_evaluate_policies_stats", P, episodes_per_policy, shape, d_params, d_mean,
+                                                 d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost, {d_metrics, d_obs_sums}, stream);
 }
 // the metrics launch (d_metrics optional) that also records the flights of the first record_per_policy envs of every policy:
-// d_flight [T, 4, N_rec, 4] and, where given, d_obs_rec [T, N_rec, D] (include/pds_record.h; csrc/pds_evaluate.h RECORD)
+// d_flight [T, 4, N_rec, 4] and, where given, d_obs_rec [T, N_rec, D] (include/pds.h; csrc/pds_evaluate.h, the record)
 extern "C" int pds_evaluate_policies_record(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
                                             const float *d_params, const float *d_mean, const float *d_std, float eps,
                                             int max_steps, const float *d_obs0, float *d_ret, float *d_len, float *d_cost,
                                             float *d_metrics, int64_t record_per_policy, float *d_flight, float *d_obs_rec,
                                             void *stream) {
-  const EvalRecordCall rec{record_per_policy, d_flight, d_obs_rec};
-  return evaluate_policies_call<true, false, true>(h, "pds_evaluate_policies_record", P, episodes_per_policy, shape, d_params, d_mean,
-                                                   d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost, d_metrics, nullptr, stream, &rec);
+  return evaluate_policies_call<EvalForm::Record>(h, "pds_evaluate_policies_record", P, episodes_per_policy, shape, d_params, d_mean, d_std,
+                                                  eps, max_steps, d_obs0, d_ret, d_len, d_cost,
+                                                  {d_metrics, nullptr, record_per_policy, d_flight, d_obs_rec}, stream);
 }
 
 // ---- the population evaluation for observation histories: csrc/pds_evaluate_hist.h ----

@@ -33,13 +33,21 @@
 //   leaves while the other flies on (there is no block barrier behind the prologue).
 //   LDS images: the tile is written by the env wave between its act_ready wait and its obs_ready post, and read by the network
 //   waves between their obs_ready wait and their act_ready post; the action slots the other way round.
-//   (STATS, below: the alive mask of a step is written and read in the tile's windows, by the tile's writer and readers.)
+//   (EvalForm::Stats and Record, below: the alive mask of a step is written and read in the tile's windows, by the tile's writer and readers.)
 //
 // The cost of a step: StepOut carries reward and flags only, and step_once stores the cost through StepArgs::cost like every
 // per-step stream.  The env wave reads its own lane's word back from the sink row BEHIND its post (same lane, same address:
 // program order), so the round trip runs while the network waves compute, and adds it in front of the next step.
 //
-// METRICS (pds_evaluate_policies_metrics; translation units csrc/pds_evaluate_metrics_*.hip): the env wave also sums the eight
+// The kernel has four forms, EvalForm F of csrc/pds_evaluate_args.h, one entry point and one set of translation units each;
+// every statement a form adds is behind an `if constexpr` on F, and its LDS belongs to a function only the forms that use it call.
+//   Plain   (pds_evaluate_policies,         csrc/pds_evaluate_<task>*.hip):          return, length and cost, as above
+//   Metrics (pds_evaluate_policies_metrics, csrc/pds_evaluate_metrics_<task>*.hip):  + the flight metrics
+//   Stats   (pds_evaluate_policies_stats,   csrc/pds_evaluate_stats_<task>*.hip):    + the flight metrics and the observation sums
+//   Record  (pds_evaluate_policies_record,  csrc/pds_evaluate_record_<task>*.hip):   + the flight metrics and the recorded flights
+// eval_sums_metrics(F): every form but Plain.  eval_keeps_alive_mask(F): Stats and Record.  No form gathers sums and records.
+//
+// THE FLIGHT METRICS (eval_sums_metrics(F)): the env wave also sums the eight
 // PDS_EM_* flight metrics (include/pds.h) over the states x(0) .. x(L - 1) its first episode's policy acted in -- the true roll,
 // pitch and body rates, the last action and the action handed over are in its registers anyway.  Every product and every sum is an
 // instruction of its own (__fmul_rn / __fadd_rn / __fsub_rn): the composed path does the same arithmetic with one torch op each.
@@ -53,10 +61,8 @@
 // idles: with the attitude and rate terms there the compiler gave the env wave 40-50 more VGPRs whichever way the sums were
 // kept (Hover at its defaults 201-215; 88 of the 102 two-team forms and ten one-team forms spilled) --
 // profiles/evaluate_metrics_kernel_resources.txt has both findings.
-// METRICS = false is the kernel as it was: every metrics statement is behind `if constexpr`, the LDS array belongs to a function
-// only the metrics form calls, the argument block is the EvalArgs it was.
 //
-// STATS (pds_evaluate_policies_stats; translation units csrc/pds_evaluate_stats_*.hip; built with METRICS only): the NETWORK waves
+// THE OBSERVATION SUMS (F == EvalForm::Stats): the NETWORK waves
 // also sum, per feature k < D, d = o_k(s) - mean[p][k] (d = o_k without statistics: mus is 0 there and x - 0 = x on the bits) and
 // d * d over every observation o(s) a first-episode policy acted on -- row r of the tile at step s where env r was `alive` in
 // front of step s, the predicate of ep_len.  gather_input gives lane (n16, g) of wave w the features 16 kt + 4 g + q of row
@@ -70,16 +76,13 @@
 //   tree -- rows j and j + 8, then j and j + 4, then + 2, then + 1: cross-lane moves and __fadd_rn, no atomics -- and stores its
 //   partial to obs_sums[tile][wave][S1 / S2][64] with 16-byte stores, features >= D zero.  The four waves of a tile are summed by
 //   the host: on the device that would take a hand-over.
-// STATS = false is the kernel as it was: every stats statement is behind `if constexpr`, the mask belongs to a function only the
-// stats and the record form call, the argument blocks are the ones they were.
 //
-// RECORD (pds_evaluate_policies_record; translation units csrc/pds_evaluate_record_*.hip; built with METRICS, never with STATS):
-// the flights leave the kernel.  Of a policy's E / 64 tiles the first rec_tiles record (wave-uniform; EvalRecordArgs,
+// THE RECORD (F == EvalForm::Record): the flights leave the kernel.  Of a policy's E / 64 tiles the first rec_tiles record (wave-uniform; EvalRecordArgs,
 // csrc/pds_evaluate_args.h, has the column of a lane); the metrics are summed as in the metrics form and stored where an array is given.
 //   The ENV wave stores x(s) = S.e -- the reference log's twelve columns, in the log's order -- and the raw a(s) of every lane
 //   `alive` in front of step s (the predicate of ep_len) as four 16-byte pieces to flight[s][piece][column]: per piece a wave
 //   writes one contiguous 1 KiB line.  Where PDS_EM_STEP is: behind the act_ready wait, which is where the action exists, and
-//   for the reason given under METRICS not in front of it.  Plain vector stores of registers the wave holds there anyway;
+//   for the reason given under the flight metrics not in front of it.  Plain vector stores of registers the wave holds there anyway;
 //   nothing is carried across step_once but the column, two scalar registers.
 //   The NETWORK waves, where obs_rec is given, copy the rows of the tile whose env is alive in front of step s, raw, to
 //   obs_rec[s][column][D]: each wave its 16 rows, 16 D contiguous floats, one dword per lane and pass -- in the tile's read window,
@@ -88,8 +91,7 @@
 //   Nothing else is written: a stopped tile writes nothing more, the rows s >= length of an env and every row of a tile that does
 //   not record keep what the caller put there.  NOT recorded: the terminal state x(L) and the terminal observation -- a finished
 //   env is reset in place inside step_once, and final_obs is NULL in this kernel.
-// RECORD = false is the kernel as it was: every record statement is behind `if constexpr`, the argument blocks are the ones
-// they were (profiles/evaluate_record_kernel_resources.txt: the other forms' code objects keep their figures).
+// (profiles/evaluate_{metrics,stats,record}_kernel_resources.txt: the compiler's figures of every form's code objects.)
 #pragma once
 #include "pds_evaluate_args.h"
 #include "pds_rollout.h"
@@ -138,7 +140,7 @@ PDS_DEV unsigned long long *es_lds() {
   return alive_mask;
 }
 // a network lane's accumulators of the stats form: S1 and S2 of its 4 NIN features; the other forms carry none
-template <int NIN, bool STATS>
+template <int NIN, bool SUMS>
 struct EsSums {
   float s1[NIN][4], s2[NIN][4];
 };
@@ -207,7 +209,7 @@ PDS_DEV float es_tree_add(float v, int bit) { return __fadd_rn(v, __shfl_xor(v, 
   *at(el.ret, ix) = ep_ret;                                                                    \
   *at(el.len, ix) = ep_len;                                                                    \
   *at(el.cost, ix) = ep_cost;
-// ---- the flight metrics (the head of this file: METRICS), `em` = this team's 2 x 64 float4 of em_lds ----
+// ---- the flight metrics (the head of this file), `em` = this team's 2 x 64 float4 of em_lds ----
 // zero sums and the signs of x(0)'s roll and pitch rate
 #define PDS_EM_INIT(em)                                                                                                         \
   em[lane] = make_float4(0.f, 0.f, 0.f, 0.f);                                                                                   \
@@ -245,7 +247,7 @@ PDS_DEV float es_tree_add(float v, int bit) { return __fadd_rn(v, __shfl_xor(v, 
   row[0] = em[lane];                                                                                              \
   row[1] = make_float4(rest.x, (float)(m_sat >> 2), (float)(m_cross & 0xFFFF), (float)((unsigned)m_cross >> 16));
 
-// ---- the record of the flights (the head of this file: RECORD) ----
+// ---- the record of the flights (the head of this file) ----
 // the column of lane 0 of tile t in the record (csrc/pds_evaluate_args.h EvalRecordArgs), or -1 where the tile does not record
 PDS_DEV long long eval_record_column(const EvalArgs &ea, int rec_tiles, long long t) {
   const long long p = t / ea.tiles_per_policy;
@@ -264,12 +266,9 @@ PDS_DEV long long eval_record_column(const EvalArgs &ea, int rec_tiles, long lon
     line[3 * nrec] = act;                                                                                 \
   }
 
-template <class V_, int TEAMS, bool METRICS = false, bool STATS = false, bool RECORD = false>
-__global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(const EvalKernelArgs<METRICS, STATS, RECORD> ka) {
+template <class V_, int TEAMS, EvalForm F>
+__global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(const EvalKernelArgs<F> ka) {
   using namespace pds_mlpf;
-  static_assert(METRICS || !STATS, "the stats form is built with the metrics");
-  static_assert(METRICS || !RECORD, "the record form is built with the metrics");
-  static_assert(!STATS || !RECORD, "no form records and gathers statistics");
   const EvalArgs &ea = eval_head(ka);
   using V = std::conditional_t<regen_obs_variant<V_>(), StoredOh<V_>, V_>;
   constexpr int D = V::D;
@@ -318,7 +317,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
     }
   }
   if (tid < TEAMS) { obs_ready[tid] = 0; act_ready[tid] = 0; }
-  if constexpr (STATS || RECORD) {
+  if constexpr (eval_keeps_alive_mask(F)) {
     if (tid < TEAMS) es_lds<TEAMS>()[tid] = ~0ull;  // the mask of step 0
   }
   __syncthreads();  // (the only block barrier: from here on the roles meet through the counters)
@@ -334,22 +333,22 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
     const Idx<V> ix{wave_base, (uint32_t)lane};
     PDS_ENV_WAVE_BEGIN
     PDS_EVAL_WAVE_ACCUMULATORS
-    // METRICS: zero sums; bit 0 / 1 of the second word: wx / wy of the previous state was negative (x(0) has no previous state:
+    // the flight metrics: zero sums; bit 0 / 1 of the second word: wx / wy of the previous state was negative (x(0) has no previous state:
     // its own signs, no crossing)
     float4 *em = nullptr;
-    if constexpr (METRICS) {
+    if constexpr (eval_sums_metrics(F)) {
       em = em_lds<TEAMS>() + team * 2 * kWave;
       PDS_EM_INIT(em)
     }
-    long long rec_col = -1;  // RECORD: column of lane 0 in the record, wave-uniform; < 0: this tile does not record
-    if constexpr (RECORD) rec_col = eval_record_column(ea, ka.rec_tiles, t);
+    long long rec_col = -1;  // Record: column of lane 0 in the record, wave-uniform; < 0: this tile does not record
+    if constexpr (F == EvalForm::Record) rec_col = eval_record_column(ea, ka.rec_tiles, t);
     for (int s = 0; s < T; ++s) {
       const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<301, true>(ea.s, s));
       PDS_EVAL_STEP_HEAD(&act_ready[team], act_all[team])  // the network waves have read o(s) and written a(s)
-      if constexpr (METRICS) {  // x(s), the state the policy acted in, and a(s), raw, against u(k - 1) = the last action before the step
+      if constexpr (eval_sums_metrics(F)) {  // x(s), the state the policy acted in, and a(s), raw, against u(k - 1) = the last action before the step
         PDS_EM_STEP(em)
       }
-      if constexpr (RECORD) {  // x(s) and a(s) where the env is in its first episode: four lines of the record, nothing carried
+      if constexpr (F == EvalForm::Record) {  // x(s) and a(s) where the env is in its first episode: four lines of the record, nothing carried
         if (rec_col >= 0) {
           PDS_ER_STEP(reinterpret_cast<const EvalRecordArgs *>(&el))
         }
@@ -360,18 +359,18 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
       PDS_NEXT_TICK(rk, parity)
       PDS_EVAL_RECORD_STEP(so)
       PDS_EVAL_STILL
-      if constexpr (STATS || RECORD) {
+      if constexpr (eval_keeps_alive_mask(F)) {
         if (lane == 0) es_lds<TEAMS>()[team] = still;  // the mask of step s + 1, in front of the post
       }
       PDS_EVAL_STEP_TAIL(&obs_ready[team], el)  // o(s + 1) is in the tile / this team's env wave has left
     }
     // (pds_evaluate_policies leaves the handle "not reset")
     PDS_EVAL_WAVE_END(EvalArgs, 302)
-    if constexpr (RECORD) {  // (the metrics are summed whether or not the caller takes them)
+    if constexpr (F == EvalForm::Record) {  // (the metrics are summed whether or not the caller takes them)
       if (reinterpret_cast<const EvalMetricsArgs *>(&el)->metrics != nullptr) {
         PDS_EM_STORE(em, reinterpret_cast<const EvalMetricsArgs *>(&el)->metrics)
       }
-    } else if constexpr (METRICS) {
+    } else if constexpr (eval_sums_metrics(F)) {
       PDS_EM_STORE(em, reinterpret_cast<const EvalMetricsArgs *>(&el)->metrics)
     }
     return;
@@ -379,16 +378,16 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
 
   // ================================ network waves: 16 rows of the tile each ====================================
   const int own = wave * 16 + n16;  // this lane's sample row
-  EsSums<NIN, STATS> es;  // STATS: the sums of this lane's 4 NIN features of row `own` (nothing otherwise)
-  if constexpr (STATS) {
+  EsSums<NIN, F == EvalForm::Stats> es;  // Stats: the sums of this lane's 4 NIN features of row `own` (nothing otherwise)
+  if constexpr (F == EvalForm::Stats) {
 #pragma unroll
     for (int kt = 0; kt < NIN; ++kt) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) { es.s1[kt][q] = 0.f; es.s2[kt][q] = 0.f; }
     }
   }
-  long long rec_col = -1;  // RECORD: as in the env wave; here < 0 also where no observations are asked for
-  if constexpr (RECORD) {
+  long long rec_col = -1;  // Record: as in the env wave; here < 0 also where no observations are asked for
+  if constexpr (F == EvalForm::Record) {
     if (ka.obs_rec != nullptr) rec_col = eval_record_column(ea, ka.rec_tiles, t);
   }
   for (int s = 0;; ++s) {
@@ -399,7 +398,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
 #endif
     f32x4 x_own[NIN];
     gather_input<NIN>(tile, TS, own, D, mus, iss, g, x_own);
-    if constexpr (STATS) {  // o(s) of row `own`, where its env was alive in front of step s
+    if constexpr (F == EvalForm::Stats) {  // o(s) of row `own`, where its env was alive in front of step s
       const bool al = ((es_lds<TEAMS>()[team] >> own) & 1ull) != 0ull;
 #pragma unroll
       for (int kt = 0; kt < NIN; ++kt) {
@@ -413,7 +412,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
         }
       }
     }
-    if constexpr (RECORD) {  // o(s), raw, of this wave's 16 rows whose env was alive in front of step s: 16 D contiguous floats
+    if constexpr (F == EvalForm::Record) {  // o(s), raw, of this wave's 16 rows whose env was alive in front of step s: 16 D contiguous floats
       if (rec_col >= 0) {
         const EvalRecordArgs &rl = *reinterpret_cast<const EvalRecordArgs *>(&el);
         const long long nrec = (ntiles / rl.m.e.tiles_per_policy) * rl.rec_tiles * kWave;
@@ -429,7 +428,7 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
     if (g == 0) act_all[team][own] = make_float4(mu[0], mu[1], mu[2], mu[3]);  // lane n16 owns sample `own`: the actor's four outputs
     rollout_post(&act_ready[team], lane);  // this wave is done with the tile of step s
   }
-  if constexpr (STATS) {  // this wave's 16 rows per feature, then [t][wave][S1 / S2][64]: lane (0, g) stores the features 16 kt + 4 g ..
+  if constexpr (F == EvalForm::Stats) {  // this wave's 16 rows per feature, then [t][wave][S1 / S2][64]: lane (0, g) stores the features 16 kt + 4 g ..
     float4 *out = reinterpret_cast<float4 *>(ka.obs_sums) + (t * kRolloutMlpWaves + wave) * (2 * 16);
 #pragma unroll
     for (int kt = 0; kt < NIN; ++kt) {
@@ -455,43 +454,38 @@ __global__ __launch_bounds__(kRolloutThreads * TEAMS, 1) void evaluate_kernel(co
 
 // grid.x = number of 64-env tiles; more tiles than CUs: two teams per block (RolloutLaunch's rule) where the two-team form of
 // this variant and this kernel form fits (two_teams_fit, csrc/pds_rollout.h, on the form's own two code objects).
-template <bool METRICS, bool STATS = false, bool RECORD = false>
+template <EvalForm F>
 struct EvalLaunchT {
   dim3 grid;
   hipStream_t s;
-  const EvalKernelArgs<METRICS, STATS, RECORD> &args;
+  const EvalKernelArgs<F> &args;
   template <class RV_>
   void run() const {
-    if (grid.x > (unsigned)kRolloutTwoTeamsAbove &&
-        two_teams_fit<&evaluate_kernel<RV_, 1, METRICS, STATS, RECORD>, &evaluate_kernel<RV_, 2, METRICS, STATS, RECORD>>())
-      hipLaunchKernelGGL((evaluate_kernel<RV_, 2, METRICS, STATS, RECORD>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, args);
+    if (grid.x > (unsigned)kRolloutTwoTeamsAbove && two_teams_fit<&evaluate_kernel<RV_, 1, F>, &evaluate_kernel<RV_, 2, F>>())
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 2, F>), dim3((grid.x + 1) / 2), dim3(2 * kRolloutThreads), 0, s, args);
     else
-      hipLaunchKernelGGL((evaluate_kernel<RV_, 1, METRICS, STATS, RECORD>), grid, dim3(kRolloutThreads), 0, s, args);
+      hipLaunchKernelGGL((evaluate_kernel<RV_, 1, F>), grid, dim3(kRolloutThreads), 0, s, args);
   }
 };
 
 // ---- the seven launch functions of pds_evaluate_args.h.  flags -> variant is the fused family's one table (fused_task and the
 // fused_*_family of csrc/pds_rollout.h) over an EvalLaunchT.  Each function is defined and explicitly instantiated by the
-// translation unit that holds its kernels, csrc/pds_evaluate[_metrics|_stats|_record]_<task>[_pwm|_lat].hip, for that unit's form (the _FORM
-// macros name RECORD; the two older ones are the forms without it): a
-// definition every unit could see would instantiate a family's kernels in its task's dispatcher unit as well. ----
+// translation unit that holds its kernels, csrc/pds_evaluate[_metrics|_stats|_record]_<task>[_pwm|_lat].hip, for that unit's
+// FORM: a definition every unit could see would instantiate a family's kernels in its task's dispatcher unit as well. ----
 // control_mode PWM (FAMILY = fused_pwm_family) or the latency ring (fused_lat_family) of Hover / Circle
-#define PDS_EVALUATE_FAMILY_UNIT(NAME, FAMILY, TASK, METRICS, STATS) PDS_EVALUATE_FAMILY_UNIT_FORM(NAME, FAMILY, TASK, METRICS, STATS, false)
-#define PDS_EVALUATE_FAMILY_UNIT_FORM(NAME, FAMILY, TASK, METRICS, STATS, RECORD)                                         \
-  template <bool M, bool S, bool R>                                                                                       \
-  bool NAME(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<M, S, R> &ka) {                          \
-    return FAMILY<TASK>(f, EvalLaunchT<M, S, R>{grid, s, ka});                                                            \
-  }                                                                                                                       \
-  template bool NAME<METRICS, STATS, RECORD>(const LaunchFlags &, dim3, hipStream_t, const EvalKernelArgs<METRICS, STATS, RECORD> &);
-// a task's dispatcher + the PID control modes and the Kalman hold; `...`: fused_task's `lat` and `pwm`, the unit's own form of the
-// two family functions (TakeOff, which holds all its families: nullptr, nullptr).  <M, S> names the family functions of the three
-// forms without a record (R = false, the default); the record form's units say <M, S, R>
-#define PDS_EVALUATE_TASK_UNIT(NAME, TASK, METRICS, STATS, ...) PDS_EVALUATE_TASK_UNIT_FORM(NAME, TASK, METRICS, STATS, false, __VA_ARGS__)
-#define PDS_EVALUATE_TASK_UNIT_FORM(NAME, TASK, METRICS, STATS, RECORD, ...)                                              \
-  template <bool M, bool S, bool R>                                                                                       \
-  bool NAME(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<M, S, R> &ka) {                          \
-    return fused_task<TASK>(f, EvalLaunchT<M, S, R>{grid, s, ka}, __VA_ARGS__);                                           \
-  }                                                                                                                       \
-  template bool NAME<METRICS, STATS, RECORD>(const LaunchFlags &, dim3, hipStream_t, const EvalKernelArgs<METRICS, STATS, RECORD> &);
+#define PDS_EVALUATE_FAMILY_UNIT(NAME, FAMILY, TASK, FORM)                                     \
+  template <EvalForm F>                                                                        \
+  bool NAME(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<F> &ka) {     \
+    return FAMILY<TASK>(f, EvalLaunchT<F>{grid, s, ka});                                       \
+  }                                                                                            \
+  template bool NAME<FORM>(const LaunchFlags &, dim3, hipStream_t, const EvalKernelArgs<FORM> &);
+// a task's dispatcher + the PID control modes and the Kalman hold; lat, pwm: fused_task's, the unit's own form <F> of the two
+// family functions (TakeOff, which holds all its families: nullptr, nullptr)
+#define PDS_EVALUATE_TASK_UNIT(NAME, TASK, FORM, lat, pwm)                                     \
+  template <EvalForm F>                                                                        \
+  bool NAME(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<F> &ka) {     \
+    return fused_task<TASK>(f, EvalLaunchT<F>{grid, s, ka}, lat, pwm);                         \
+  }                                                                                            \
+  template bool NAME<FORM>(const LaunchFlags &, dim3, hipStream_t, const EvalKernelArgs<FORM> &);
 
 }  // namespace pds

@@ -25,60 +25,32 @@ struct EvalArgs {
 };
 static_assert(offsetof(EvalArgs, s) == 0, "reload_args() reads the head of the kernarg segment as a StepArgs");
 
-// Arguments of evaluate_kernel<V, TEAMS, true> (pds_evaluate_policies_metrics): the plain kernel's, and behind them the array of
-// the flight metrics.  The plain kernel's argument block stays the one it was.
+// The four forms of evaluate_kernel (csrc/pds_evaluate.h has what each does) and of everything that launches it.  Plain:
+// pds_evaluate_policies; Metrics: pds_evaluate_policies_metrics; Stats: pds_evaluate_policies_stats; Record:
+// pds_evaluate_policies_record.
+enum class EvalForm : int { Plain, Metrics, Stats, Record };
+// the env wave sums the PDS_EM_* flight metrics
+constexpr bool eval_sums_metrics(EvalForm f) { return f != EvalForm::Plain; }
+// the env wave keeps the alive mask of the tile for the network waves
+constexpr bool eval_keeps_alive_mask(EvalForm f) { return f == EvalForm::Stats || f == EvalForm::Record; }
+
+// Arguments of the Metrics form: the plain kernel's, and behind them the array of the flight metrics.
 struct EvalMetricsArgs {
   EvalArgs e;      // FIRST member (the kernel reads the head of its argument block as an EvalArgs, and that as a StepArgs)
   float *metrics;  // [N, PDS_EVAL_METRICS] the PDS_EM_* sums of every env's first episode (include/pds.h), 16-byte aligned
 };
 static_assert(offsetof(EvalMetricsArgs, e) == 0, "the metrics kernel reads the head of its argument block as an EvalArgs");
 static_assert(PDS_EVAL_METRICS == 8, "a metrics row is stored as two float4");
-// Arguments of evaluate_kernel<V, TEAMS, true, true> (pds_evaluate_policies_stats): the metrics kernel's, and behind them the slab
-// of the observation sums.  The argument blocks of the other two forms stay the ones they were.
+// Arguments of the Stats form: the metrics kernel's, and behind them the slab of the observation sums.
 struct EvalStatsArgs {
   EvalMetricsArgs m;  // FIRST member (the kernel reads the head of its argument block as an EvalMetricsArgs)
   float *obs_sums;    // [tiles, 4, 2, 64]: tile, network wave, S1 / S2, feature (include/pds.h), 16-byte aligned
 };
 static_assert(offsetof(EvalStatsArgs, m) == 0, "the stats kernel reads the head of its argument block as an EvalMetricsArgs");
-struct EvalRecordArgs;  // (last in this file)
-// the argument block of evaluate_kernel<V, TEAMS, METRICS, STATS[, RECORD]> and the EvalArgs at its head
-template <bool METRICS, bool STATS = false, bool RECORD = false>
-using EvalKernelArgs =
-    std::conditional_t<RECORD, EvalRecordArgs, std::conditional_t<STATS, EvalStatsArgs, std::conditional_t<METRICS, EvalMetricsArgs, EvalArgs>>>;
-// ... on the host and on the device, for a const or a mutable block (EvalHistArgs of csrc/pds_evaluate_hist_args.h too: its first
-// member is an EvalMetricsArgs `m`, like EvalStatsArgs' and EvalRecordArgs')
-template <class KA>
-__host__ __device__ inline auto &eval_head(KA &ka) {
-  if constexpr (std::is_same_v<std::remove_const_t<KA>, EvalArgs>) return ka;
-  else if constexpr (std::is_same_v<std::remove_const_t<KA>, EvalMetricsArgs>) return ka.e;
-  else return ka.m.e;
-}
-
-// The launch functions, one set for the four forms (METRICS, STATS = false, false: pds_evaluate_policies; true, false: .._metrics;
-// true, true: .._stats; RECORD is named by the record form only -- true, false, true: .._record).  Each is defined and explicitly
-// instantiated for one form by the translation unit that holds the form's kernels: csrc/pds_evaluate[_metrics|_stats|_record]_<task>.hip ...
-template <bool METRICS, bool STATS, bool RECORD = false>
-bool launch_evaluate_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
-template <bool METRICS, bool STATS, bool RECORD = false>
-bool launch_evaluate_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
-template <bool METRICS, bool STATS, bool RECORD = false>
-bool launch_evaluate_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
-// ... and their families, csrc/pds_evaluate[_metrics|_stats|_record]_<task>_{pwm,lat}.hip, like the rollout's: control_mode PWM with every
-// noise setting / the latency ring
-template <bool METRICS, bool STATS, bool RECORD = false>
-bool launch_evaluate_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
-template <bool METRICS, bool STATS, bool RECORD = false>
-bool launch_evaluate_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
-template <bool METRICS, bool STATS, bool RECORD = false>
-bool launch_evaluate_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
-template <bool METRICS, bool STATS, bool RECORD = false>
-bool launch_evaluate_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<METRICS, STATS, RECORD> &ka);
-
-// Arguments of evaluate_kernel<V, TEAMS, true, false, true> (pds_evaluate_policies_record): the metrics kernel's (`metrics` may be
-// NULL here: summed, not stored) and behind them the record of the flights.  Of the E / 64 tiles of a policy the first rec_tiles
-// record: tile t iff t % tiles_per_policy < rec_tiles (wave-uniform), its lane's column of the record
+// Arguments of the Record form: the metrics kernel's (`metrics` may be NULL here: summed, not stored) and behind them the record
+// of the flights.  Of the E / 64 tiles of a policy the first rec_tiles record: tile t iff t % tiles_per_policy < rec_tiles
+// (wave-uniform), its lane's column of the record
 //   j = (t / tiles_per_policy) * 64 * rec_tiles + (t % tiles_per_policy) * 64 + lane,       N_rec = P * 64 * rec_tiles.
-// The argument blocks of the other forms stay the ones they were.
 struct EvalRecordArgs {
   EvalMetricsArgs m;  // FIRST member (the kernel reads the head of its argument block as an EvalMetricsArgs)
   float4 *flight;     // [T, 4, N_rec, 4] floats, 16-byte aligned: step s, piece q, column j -- piece 0 = (px, py, pz, vx), 1 = (vy, vz,
@@ -87,5 +59,38 @@ struct EvalRecordArgs {
   int rec_tiles;      // 1 <= rec_tiles <= tiles_per_policy
 };
 static_assert(offsetof(EvalRecordArgs, m) == 0, "the record kernel reads the head of its argument block as an EvalMetricsArgs");
+// The four blocks are the kernels' argument segments: size and the place of the last member, as the compiler laid them out.
+static_assert(sizeof(EvalArgs) == 720 && offsetof(EvalArgs, cost) == 712, "the kernarg layout of the Plain form");
+static_assert(sizeof(EvalMetricsArgs) == 728 && offsetof(EvalMetricsArgs, metrics) == 720, "the kernarg layout of the Metrics form");
+static_assert(sizeof(EvalStatsArgs) == 736 && offsetof(EvalStatsArgs, obs_sums) == 728, "the kernarg layout of the Stats form");
+static_assert(sizeof(EvalRecordArgs) == 752 && offsetof(EvalRecordArgs, rec_tiles) == 744, "the kernarg layout of the Record form");
+
+// form -> the argument block of evaluate_kernel<V, TEAMS, F>
+template <EvalForm F> struct EvalKernelArgsOf;
+template <> struct EvalKernelArgsOf<EvalForm::Plain> { using type = EvalArgs; };
+template <> struct EvalKernelArgsOf<EvalForm::Metrics> { using type = EvalMetricsArgs; };
+template <> struct EvalKernelArgsOf<EvalForm::Stats> { using type = EvalStatsArgs; };
+template <> struct EvalKernelArgsOf<EvalForm::Record> { using type = EvalRecordArgs; };
+template <EvalForm F> using EvalKernelArgs = typename EvalKernelArgsOf<F>::type;
+// ... and the EvalArgs at its head, on the host and on the device, for a const or a mutable block (EvalHistArgs of
+// csrc/pds_evaluate_hist_args.h too: its first member is an EvalMetricsArgs `m`, like EvalStatsArgs' and EvalRecordArgs')
+template <class KA>
+__host__ __device__ inline auto &eval_head(KA &ka) {
+  if constexpr (std::is_same_v<std::remove_const_t<KA>, EvalArgs>) return ka;
+  else if constexpr (std::is_same_v<std::remove_const_t<KA>, EvalMetricsArgs>) return ka.e;
+  else return ka.m.e;
+}
+
+// The launch functions, one set for the four forms.  Each is defined and explicitly instantiated for one form by the translation
+// unit that holds the form's kernels: csrc/pds_evaluate[_metrics|_stats|_record]_<task>.hip ...
+template <EvalForm F> bool launch_evaluate_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<F> &ka);
+template <EvalForm F> bool launch_evaluate_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<F> &ka);
+template <EvalForm F> bool launch_evaluate_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<F> &ka);
+// ... and their families, csrc/pds_evaluate[_metrics|_stats|_record]_<task>_{pwm,lat}.hip, like the rollout's: control_mode PWM with every
+// noise setting / the latency ring
+template <EvalForm F> bool launch_evaluate_hover_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<F> &ka);
+template <EvalForm F> bool launch_evaluate_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<F> &ka);
+template <EvalForm F> bool launch_evaluate_circle_pwm(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<F> &ka);
+template <EvalForm F> bool launch_evaluate_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const EvalKernelArgs<F> &ka);
 
 }  // namespace pds

@@ -2,5 +2,5 @@
 #include "pds_evaluate.h"
 
 namespace pds {
-PDS_EVALUATE_FAMILY_UNIT(launch_evaluate_circle_lat, fused_lat_family, PDS_TASK_CIRCLE, false, false)
+PDS_EVALUATE_FAMILY_UNIT(launch_evaluate_circle_lat, fused_lat_family, PDS_TASK_CIRCLE, EvalForm::Plain)
 }  // namespace pds

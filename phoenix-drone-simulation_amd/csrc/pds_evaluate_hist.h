@@ -22,7 +22,7 @@
 // slots go the other way round, and em_lds belongs to the env wave.  "o(s + 1) is in the tile" reads "the histories of step
 // s + 1 are in LDS".
 //
-// METRICS: the env wave always sums the eight PDS_EM_* values, exactly as evaluate_kernel<.., METRICS = true> does -- seven words
+// METRICS: the env wave always sums the eight PDS_EM_* values, exactly as evaluate_kernel<.., EvalForm::Metrics> does -- seven words
 // per lane in LDS, read and written back behind the act_ready wait, one rounded instruction per product and sum -- and stores the
 // [N, 8] row where d_metrics is non-NULL: one code object per variant instead of a plain and a metrics form.
 #pragma once

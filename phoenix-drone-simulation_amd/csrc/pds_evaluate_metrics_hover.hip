@@ -2,5 +2,5 @@
 #include "pds_evaluate.h"
 
 namespace pds {
-PDS_EVALUATE_TASK_UNIT(launch_evaluate_hover, PDS_TASK_HOVER, true, false, launch_evaluate_hover_lat<M, S>, launch_evaluate_hover_pwm<M, S>)
+PDS_EVALUATE_TASK_UNIT(launch_evaluate_hover, PDS_TASK_HOVER, EvalForm::Metrics, launch_evaluate_hover_lat<F>, launch_evaluate_hover_pwm<F>)
 }  // namespace pds

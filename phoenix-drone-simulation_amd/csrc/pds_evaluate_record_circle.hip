@@ -2,5 +2,5 @@
 #include "pds_evaluate.h"
 
 namespace pds {
-PDS_EVALUATE_TASK_UNIT_FORM(launch_evaluate_circle, PDS_TASK_CIRCLE, true, false, true, launch_evaluate_circle_lat<M, S, R>, launch_evaluate_circle_pwm<M, S, R>)
+PDS_EVALUATE_TASK_UNIT(launch_evaluate_circle, PDS_TASK_CIRCLE, EvalForm::Record, launch_evaluate_circle_lat<F>, launch_evaluate_circle_pwm<F>)
 }  // namespace pds

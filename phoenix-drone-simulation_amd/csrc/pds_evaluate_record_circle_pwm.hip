@@ -2,5 +2,5 @@
 #include "pds_evaluate.h"
 
 namespace pds {
-PDS_EVALUATE_FAMILY_UNIT_FORM(launch_evaluate_circle_pwm, fused_pwm_family, PDS_TASK_CIRCLE, true, false, true)
+PDS_EVALUATE_FAMILY_UNIT(launch_evaluate_circle_pwm, fused_pwm_family, PDS_TASK_CIRCLE, EvalForm::Record)
 }  // namespace pds

@@ -2,5 +2,5 @@
 #include "pds_evaluate.h"
 
 namespace pds {
-PDS_EVALUATE_TASK_UNIT_FORM(launch_evaluate_hover, PDS_TASK_HOVER, true, false, true, launch_evaluate_hover_lat<M, S, R>, launch_evaluate_hover_pwm<M, S, R>)
+PDS_EVALUATE_TASK_UNIT(launch_evaluate_hover, PDS_TASK_HOVER, EvalForm::Record, launch_evaluate_hover_lat<F>, launch_evaluate_hover_pwm<F>)
 }  // namespace pds

@@ -2,5 +2,5 @@
 #include "pds_evaluate.h"
 
 namespace pds {
-PDS_EVALUATE_TASK_UNIT(launch_evaluate_circle, PDS_TASK_CIRCLE, true, true, launch_evaluate_circle_lat<M, S>, launch_evaluate_circle_pwm<M, S>)
+PDS_EVALUATE_TASK_UNIT(launch_evaluate_circle, PDS_TASK_CIRCLE, EvalForm::Stats, launch_evaluate_circle_lat<F>, launch_evaluate_circle_pwm<F>)
 }  // namespace pds

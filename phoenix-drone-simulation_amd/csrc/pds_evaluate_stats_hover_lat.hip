@@ -2,5 +2,5 @@
 #include "pds_evaluate.h"
 
 namespace pds {
-PDS_EVALUATE_FAMILY_UNIT(launch_evaluate_hover_lat, fused_lat_family, PDS_TASK_HOVER, true, true)
+PDS_EVALUATE_FAMILY_UNIT(launch_evaluate_hover_lat, fused_lat_family, PDS_TASK_HOVER, EvalForm::Stats)
 }  // namespace pds

@@ -2,5 +2,5 @@
 #include "pds_evaluate.h"
 
 namespace pds {
-PDS_EVALUATE_TASK_UNIT(launch_evaluate_takeoff, PDS_TASK_TAKEOFF, true, true, nullptr, nullptr)
+PDS_EVALUATE_TASK_UNIT(launch_evaluate_takeoff, PDS_TASK_TAKEOFF, EvalForm::Stats, nullptr, nullptr)
 }  // namespace pds

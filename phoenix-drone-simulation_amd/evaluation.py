@@ -14,7 +14,7 @@ With `metrics=True` the same launch also reports the flight-quality sums the ref
 logged flight by the same definitions.  With `obs_stats=True` it also sums the observations the policies acted on, for a running
 standardisation (`ObsSums`; include/pds.h pds_evaluate_policies_stats).  With `record=R` the launch also writes the flights
 themselves out -- state, action and observation of every step of the first R episodes per policy -- as a `Flights`
-(include/pds_record.h pds_evaluate_policies_record)."""
+(include/pds.h pds_evaluate_policies_record)."""
 import math
 import os
 
@@ -24,6 +24,15 @@ import torch.nn as nn
 
 from . import native
 from .native import _ptr
+
+
+def _write_episode_csvs(log_dir, ret, cost):
+    """returns.csv and, where `cost` is given, costs.csv in `log_dir`: one value per line"""
+    os.makedirs(log_dir, exist_ok=True)
+    for name, values in (("returns.csv", ret), ("costs.csv", cost)):
+        if values is not None:
+            with open(os.path.join(log_dir, name), "w") as f:
+                f.write("\n".join(str(float(x)) for x in values) + "\n")
 
 
 def _as_policy(policy):
@@ -55,12 +64,7 @@ def evaluate(env, policy, log_dir=None, log_costs=True):
         policy.train()  # back to train mode (evaluation.py:91)
     ret, length, cost = ret.cpu(), length.cpu(), cost.cpu()
     if log_dir is not None:
-        os.makedirs(log_dir, exist_ok=True)
-        with open(os.path.join(log_dir, "returns.csv"), "w") as f:
-            f.write("\n".join(str(float(x)) for x in ret) + "\n")
-        if log_costs:
-            with open(os.path.join(log_dir, "costs.csv"), "w") as f:
-                f.write("\n".join(str(float(x)) for x in cost) + "\n")
+        _write_episode_csvs(log_dir, ret, cost if log_costs else None)
     return ret, length, cost
 
 
@@ -404,7 +408,7 @@ class ObsSums:
         return self._moments(self.count.sum(), c, sd, sd2)
 
 
-# ---- the recorded flights (include/pds_record.h pds_evaluate_policies_record) ---------------------------------------------------
+# ---- the recorded flights (include/pds.h pds_evaluate_policies_record) ----------------------------------------------------------
 class Flights:
     """What evaluate_population(..., record=R) records of the first R episodes of each of P policies, float32 on the CPU:
     `state` [P, R, T, 12] the true state x(s) the policy acted in, in the column order of a flight log (simopt.OBS_COLUMNS: x y z,
@@ -512,6 +516,156 @@ class Flights:
         return simopt.MiniTrajectories(*[np.concatenate([part[k] for part in parts]) for k in range(3)])
 
 
+def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats, history_fused, record, record_limit_bytes):
+    """The argument checks of evaluate_population and its choice of path, with the env untouched -> (P, E, T, R or None, the
+    form "plain" / "metrics" / "stats" / "record", whether the kernel path flies, and H where that is the history kernel, else None)"""
+    P, E = _check_population_call(env, population)
+    if population.d_in != env.obs_dim:
+        raise ValueError(f"the population's actors read {population.d_in} inputs, the env observes {env.obs_dim}")
+    if isinstance(fused, str):
+        if fused != "auto":
+            raise ValueError("fused: True, False or 'auto'")
+    else:
+        fused = bool(fused)  # (1, 0, numpy.bool_: below `fused is True` must mean what it says)
+    if not isinstance(history_fused, (bool, np.bool_)):
+        raise ValueError("history_fused: True or False")
+    T = int(env._max_episode_steps if max_steps is None else max_steps)
+    if T < 1:
+        raise ValueError(f"max_steps = {T}")
+    R = None
+    if record is not None:  # (what pds_evaluate_policies_record refuses, before the library is asked anything)
+        if isinstance(record, (bool, np.bool_)) or int(record) != record:
+            raise ValueError(f"record = {record!r}: a number of episodes per policy")
+        R = int(record)
+        if R < 64 or R % 64 != 0 or R > E:
+            raise ValueError(f"record = {R} is not a positive multiple of 64 (one tile) up to E = {E}")
+        if obs_stats:
+            raise ValueError("record and obs_stats do not come together: no kernel form gathers both")
+        need = T * P * R * (64 + 4 * int(env.obs_dim))
+        if need > int(record_limit_bytes):
+            raise ValueError(f"the record of {T} steps x {P} x {R} episodes takes {need} bytes, above record_limit_bytes = "
+                             f"{int(record_limit_bytes)}: record fewer episodes or fewer steps, or raise the limit")
+    form = "record" if R is not None else "stats" if obs_stats else "metrics" if metrics else "plain"
+    H = int(getattr(env, "observation_history_size", 2))
+    # (no record kernel for histories: they record through the composed path)
+    use_history = bool(history_fused) and H != 2 and R is None
+    use_kernel = False
+    if fused is not False and use_history:
+        built = not obs_stats and fused_history_evaluation_built(env)
+        if fused is True and not built:
+            raise NotImplementedError("pds_evaluate_policies_history has no kernel for this call (built: auto_reset, the env configurations "
+                                      "of the history rollout, H x half <= 192 inputs, no obs_stats); fused='auto' runs the composed path")
+        use_kernel = built
+    elif fused is not False:
+        built = fused_evaluation_built(env)
+        if fused is True and not built:
+            raise NotImplementedError("pds_evaluate_policies has no kernel for this env (built: observation_history_size 2, auto_reset, "
+                                      "the env configurations of the fused rollout); fused='auto' runs the composed path")
+        use_kernel = built
+    return P, E, T, R, form, use_kernel, (H if use_history else None)
+
+
+def _fly_kernel(env, population, obs, P, E, T, form, H, rec):
+    """One launch -> (ret, length, cost, raw, slab) on the device, raw / slab None where the form has none; the record is written
+    into `rec`'s arrays.  Per form the entry point and what trails d_cost in its argument list; the history kernel leads with H
+    and takes d_metrics or NULL."""
+    dev, n = env.device, env.num_envs
+    ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
+    raw = torch.zeros(n, len(METRIC_NAMES), device=dev) if form != "plain" else None
+    slab = torch.zeros(n // 64, SLAB_WAVES, 2, SLAB_FEATURES, device=dev) if form == "stats" else None
+    _, R, flight, obs_rec = rec if rec is not None else (None,) * 4
+    name, trail = {"plain": ("pds_evaluate_policies", ()),
+                   "metrics": ("pds_evaluate_policies_metrics", (raw,)),
+                   "stats": ("pds_evaluate_policies_stats", (raw, slab)),
+                   "record": ("pds_evaluate_policies_record", (raw, R, flight, obs_rec))}[form]
+    lead = ()
+    if H is not None:  # (plain or metrics; [N, H * half]: the histories env.reset() returns)
+        obs, name, lead, trail = obs.contiguous(), "pds_evaluate_policies_history", (H,), (raw,)
+    native.call(name, env._handle, *lead, P, E, population.mlp(0), population.theta, population.mean, population.std,
+                population.eps, T, obs, ret, length, cost, *trail, on=dev, handle=env._handle)
+    return ret, length, cost, raw, slab
+
+
+def _fly_composed(env, population, obs, P, E, T, metrics, obs_stats, rec):
+    """The same flight step by step -> _fly_kernel's tuple, the same bits: per step one pds_mlp_forward per policy on its block of
+    the observation, env.step and the accumulator updates of `evaluate`, every sum a torch op of its own."""
+    dev, n, D = env.device, env.num_envs, env.obs_dim
+    ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
+    raw = slab = None
+    mlps = [population.mlp(p) for p in range(P)]
+    act = torch.empty(n, 4, device=dev)
+    alive = torch.ones(n, dtype=torch.bool, device=dev)
+    has = population.mean is not None
+    acc = [torch.zeros(n, device=dev) for _ in METRIC_NAMES] if metrics else None
+    prev_neg = None
+    if obs_stats:  # per-env sums of d and d * d, d = o - mean of the env's policy
+        s1, s2 = torch.zeros(n, D, device=dev), torch.zeros(n, D, device=dev)
+        shift_rows = population.mean.repeat_interleave(E, dim=0) if has else None
+        zero_nd = torch.zeros(n, D, device=dev)
+    if rec is not None:
+        rec_env, R, flight, obs_rec = rec
+    for s in range(T):
+        if metrics:  # x(s): the state the policy acts in
+            rpy, omega, last = env.get_state("rpy"), env.get_state("omega"), env.get_state("last_action")
+        for p in range(P):
+            native.call("pds_mlp_forward", mlps[p], _ptr(obs, 4 * p * E * D), None, E, _ptr(population.mean, 4 * p * D) if has else None,
+                        _ptr(population.std, 4 * p * D) if has else None, population.eps, _ptr(act, 16 * p * E), on=dev)
+        if metrics:
+            prev_neg = _compose_metrics(acc, prev_neg, alive, rpy, omega, act, last)
+        if rec is not None:  # x(s), a(s) and o(s) of the recorded envs alive in front of step s
+            x = torch.cat([env.get_state(f) for f in ("pos", "vel", "rpy", "omega")] + [act], dim=1)[rec_env]  # [P R, 16]
+            on = alive[rec_env].unsqueeze(1)
+            flight[s] = torch.where(on, x, torch.zeros_like(x)).reshape(P * R, 4, 4).transpose(0, 1)
+            if obs_rec is not None:
+                o = obs[rec_env]
+                obs_rec[s] = torch.where(on, o, torch.zeros_like(o))
+        if obs_stats:  # o(s), for the envs alive in front of step s
+            d = obs - shift_rows if has else obs
+            on = alive.unsqueeze(1)
+            s1 += torch.where(on, d, zero_nd)
+            s2 += torch.where(on, d * d, zero_nd)
+            if _OBS_STATS_LOG is not None:
+                _OBS_STATS_LOG.append((d.double().cpu(), alive.cpu().clone()))
+        obs, r, term, trunc, info = env.step(act)
+        ret += torch.where(alive, r, torch.zeros_like(r))
+        cost += torch.where(alive, info["cost"], torch.zeros_like(r))
+        length += alive.float()
+        alive &= ~(term | trunc)
+    if metrics:
+        raw = torch.stack(acc, dim=1)
+    if obs_stats:
+        slab = _compose_slab(s1, s2)
+    return ret, length, cost, raw, slab
+
+
+def _population_result(env, population, P, E, T, flown, metrics, obs_stats, rec, u0, log_dir):
+    """What evaluate_population returns, from a flight's device tensors; the CSVs of log_dir"""
+    ret, length, cost, raw, slab = flown
+    D, step_seconds = env.obs_dim, float(env.cfg.time_step) * int(env.cfg.aggregate_phy_steps)
+    ret, length, cost = ret.cpu().reshape(P, E), length.cpu().reshape(P, E), cost.cpu().reshape(P, E)
+    fm = FlightMetrics(raw.cpu().reshape(P, E, len(METRIC_NAMES)), length, step_seconds) if metrics else None
+    if log_dir is not None:
+        for p in range(P):
+            d = os.path.join(log_dir, str(p))
+            _write_episode_csvs(d, ret[p], cost[p])
+            if metrics:  # one row per episode: the eight raw values and the length
+                with open(os.path.join(d, "metrics.csv"), "w") as f:
+                    f.write(",".join(METRIC_NAMES) + ",length\n")
+                    for e in range(E):
+                        f.write(",".join(repr(float(x)) for x in fm.raw[p, e]) + f",{float(length[p, e])!r}\n")
+    out = (ret, length, cost, fm) if metrics else (ret, length, cost)
+    if obs_stats:
+        shift = population.mean.cpu().double() if population.mean is not None else torch.zeros(P, D, dtype=torch.float64)
+        out = out + (ObsSums(slab, length.double().sum(dim=1), shift),)
+    if rec is not None:
+        _, R, flight, obs_rec = rec
+        fl = flight.permute(2, 0, 1, 3).contiguous().cpu().reshape(P, R, T, 16)  # [column, step, piece, 4]: the 12 log columns, then the action
+        out = out + (Flights(fl[..., :12], fl[..., 12:], None if obs_rec is None else obs_rec.permute(1, 0, 2).contiguous().cpu().reshape(P, R, T, D),
+                             length[:, :R], step_seconds, u0.reshape(P, R, 4),
+                             control_mode={v: k for k, v in native.CONTROL_MODES.items()}[int(env.cfg.control_mode)]),)
+    return out
+
+
 @torch.no_grad()
 def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None, metrics=False, obs_stats=False,
                         history_fused=False, record=None, record_observations=True, record_limit_bytes=1 << 30):
@@ -544,144 +698,18 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     The env is reset first and not afterwards: after the fused path it refuses to step until the next reset() of every env
     (a masked reset is refused as well).  `population` is not modified: the call works on device copies of its tensors.
     max_steps: the number of steps flown, by default the env's max_episode_steps (the TimeLimit ends every episode by then)."""
-    P, E = _check_population_call(env, population)
-    if population.d_in != env.obs_dim:
-        raise ValueError(f"the population's actors read {population.d_in} inputs, the env observes {env.obs_dim}")
-    if isinstance(fused, str):
-        if fused != "auto":
-            raise ValueError("fused: True, False or 'auto'")
-    else:
-        fused = bool(fused)  # (1, 0, numpy.bool_: below `fused is True` must mean what it says)
-    if not isinstance(history_fused, (bool, np.bool_)):
-        raise ValueError("history_fused: True or False")
-    T = int(env._max_episode_steps if max_steps is None else max_steps)
-    if T < 1:
-        raise ValueError(f"max_steps = {T}")
-    R = None
-    if record is not None:  # (what pds_evaluate_policies_record refuses, before the library is asked anything)
-        if isinstance(record, (bool, np.bool_)) or int(record) != record:
-            raise ValueError(f"record = {record!r}: a number of episodes per policy")
-        R = int(record)
-        if R < 64 or R % 64 != 0 or R > E:
-            raise ValueError(f"record = {R} is not a positive multiple of 64 (one tile) up to E = {E}")
-        if obs_stats:
-            raise ValueError("record and obs_stats do not come together: no kernel form gathers both")
-        need = T * P * R * (64 + 4 * int(env.obs_dim))
-        if need > int(record_limit_bytes):
-            raise ValueError(f"the record of {T} steps x {P} x {R} episodes takes {need} bytes, above record_limit_bytes = "
-                             f"{int(record_limit_bytes)}: record fewer episodes or fewer steps, or raise the limit")
-    H = int(getattr(env, "observation_history_size", 2))
-    use_history = bool(history_fused) and H != 2
-    if R is not None:
-        use_history = False  # (no record kernel for histories: they record through the composed path)
-    use_kernel = False
-    if fused is not False and use_history:
-        built = not obs_stats and fused_history_evaluation_built(env)
-        if fused is True and not built:
-            raise NotImplementedError("pds_evaluate_policies_history has no kernel for this call (built: auto_reset, the env configurations "
-                                      "of the history rollout, H x half <= 192 inputs, no obs_stats); fused='auto' runs the composed path")
-        use_kernel = built
-    elif fused is not False:
-        built = fused_evaluation_built(env)
-        if fused is True and not built:
-            raise NotImplementedError("pds_evaluate_policies has no kernel for this env (built: observation_history_size 2, auto_reset, "
-                                      "the env configurations of the fused rollout); fused='auto' runs the composed path")
-        use_kernel = built
+    P, E, T, R, form, use_kernel, H = _plan_population_call(env, population, fused, max_steps, metrics, obs_stats, history_fused, record,
+                                                            record_limit_bytes)
     population = population.to(env.device)
-    dev, n, D = env.device, env.num_envs, env.obs_dim
-    ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
-    raw = slab = flight = obs_rec = u0 = None
+    dev, D = env.device, env.obs_dim
+    rec = u0 = None
     obs, _ = env.reset()
     if R is not None:  # zero-filled: the rows past an episode's end stay zero on both paths
         rec_env = (torch.arange(P, device=dev).unsqueeze(1) * E + torch.arange(R, device=dev).unsqueeze(0)).reshape(-1)  # [P R] env of column j
         u0 = env.get_state("last_action")[rec_env].cpu()  # the command in force before the first (Flights.metrics)
-        flight = torch.zeros(T, 4, P * R, 4, device=dev)
-        obs_rec = torch.zeros(T, P * R, D, device=dev) if record_observations else None
+        rec = (rec_env, R, torch.zeros(T, 4, P * R, 4, device=dev), torch.zeros(T, P * R, D, device=dev) if record_observations else None)
     if use_kernel:
-        if metrics or obs_stats or R is not None:
-            raw = torch.zeros(n, len(METRIC_NAMES), device=dev)
-        if obs_stats:
-            slab = torch.zeros(n // 64, SLAB_WAVES, 2, SLAB_FEATURES, device=dev)
-        # four entry points, one argument list: the history form leads with H, the others trail d_metrics / d_obs_sums
-        if use_history:  # (never with obs_stats)
-            obs = obs.contiguous()  # [N, H * half]: the histories env.reset() returns
-            name, lead, trail = "pds_evaluate_policies_history", (H,), (raw,)
-        elif R is not None:
-            name, lead, trail = "pds_evaluate_policies_record", (), (raw, R, flight, obs_rec)
-        elif obs_stats:
-            name, lead, trail = "pds_evaluate_policies_stats", (), (raw, slab)
-        elif metrics:
-            name, lead, trail = "pds_evaluate_policies_metrics", (), (raw,)
-        else:
-            name, lead, trail = "pds_evaluate_policies", (), ()
-        native.call(name, env._handle, *lead, P, E, population.mlp(0), population.theta, population.mean, population.std,
-                    population.eps, T, obs, ret, length, cost, *trail, on=dev, handle=env._handle)
+        flown = _fly_kernel(env, population, obs, P, E, T, form, H, rec)
     else:
-        mlps = [population.mlp(p) for p in range(P)]
-        act = torch.empty(n, 4, device=dev)
-        alive = torch.ones(n, dtype=torch.bool, device=dev)
-        has = population.mean is not None
-        acc = [torch.zeros(n, device=dev) for _ in METRIC_NAMES] if metrics else None
-        prev_neg = None
-        if obs_stats:  # per-env sums of d and d * d, d = o - mean of the env's policy
-            s1, s2 = torch.zeros(n, D, device=dev), torch.zeros(n, D, device=dev)
-            shift_rows = population.mean.repeat_interleave(E, dim=0) if has else None
-            zero_nd = torch.zeros(n, D, device=dev)
-        for s in range(T):
-            if metrics:  # x(s): the state the policy acts in
-                rpy, omega, last = env.get_state("rpy"), env.get_state("omega"), env.get_state("last_action")
-            for p in range(P):
-                native.call("pds_mlp_forward", mlps[p], _ptr(obs, 4 * p * E * D), None, E, _ptr(population.mean, 4 * p * D) if has else None,
-                            _ptr(population.std, 4 * p * D) if has else None, population.eps, _ptr(act, 16 * p * E), on=dev)
-            if metrics:
-                prev_neg = _compose_metrics(acc, prev_neg, alive, rpy, omega, act, last)
-            if R is not None:  # x(s), a(s) and o(s) of the recorded envs alive in front of step s
-                x = torch.cat([env.get_state(f) for f in ("pos", "vel", "rpy", "omega")] + [act], dim=1)[rec_env]  # [P R, 16]
-                on = alive[rec_env].unsqueeze(1)
-                flight[s] = torch.where(on, x, torch.zeros_like(x)).reshape(P * R, 4, 4).transpose(0, 1)
-                if obs_rec is not None:
-                    o = obs[rec_env]
-                    obs_rec[s] = torch.where(on, o, torch.zeros_like(o))
-            if obs_stats:  # o(s), for the envs alive in front of step s
-                d = obs - shift_rows if has else obs
-                on = alive.unsqueeze(1)
-                s1 += torch.where(on, d, zero_nd)
-                s2 += torch.where(on, d * d, zero_nd)
-                if _OBS_STATS_LOG is not None:
-                    _OBS_STATS_LOG.append((d.double().cpu(), alive.cpu().clone()))
-            obs, r, term, trunc, info = env.step(act)
-            ret += torch.where(alive, r, torch.zeros_like(r))
-            cost += torch.where(alive, info["cost"], torch.zeros_like(r))
-            length += alive.float()
-            alive &= ~(term | trunc)
-        if metrics:
-            raw = torch.stack(acc, dim=1)
-        if obs_stats:
-            slab = _compose_slab(s1, s2)
-    ret, length, cost = ret.cpu().reshape(P, E), length.cpu().reshape(P, E), cost.cpu().reshape(P, E)
-    fm = None
-    if metrics:
-        fm = FlightMetrics(raw.cpu().reshape(P, E, len(METRIC_NAMES)), length, float(env.cfg.time_step) * int(env.cfg.aggregate_phy_steps))
-    if log_dir is not None:
-        for p in range(P):
-            d = os.path.join(log_dir, str(p))
-            os.makedirs(d, exist_ok=True)
-            with open(os.path.join(d, "returns.csv"), "w") as f:
-                f.write("\n".join(str(float(x)) for x in ret[p]) + "\n")
-            with open(os.path.join(d, "costs.csv"), "w") as f:
-                f.write("\n".join(str(float(x)) for x in cost[p]) + "\n")
-            if metrics:  # one row per episode: the eight raw values and the length
-                with open(os.path.join(d, "metrics.csv"), "w") as f:
-                    f.write(",".join(METRIC_NAMES) + ",length\n")
-                    for e in range(E):
-                        f.write(",".join(repr(float(x)) for x in fm.raw[p, e]) + f",{float(length[p, e])!r}\n")
-    out = (ret, length, cost, fm) if metrics else (ret, length, cost)
-    if obs_stats:
-        shift = population.mean.cpu().double() if population.mean is not None else torch.zeros(P, D, dtype=torch.float64)
-        out = out + (ObsSums(slab, length.double().sum(dim=1), shift),)
-    if R is not None:
-        fl = flight.permute(2, 0, 1, 3).contiguous().cpu().reshape(P, R, T, 16)  # [column, step, piece, 4]: the 12 log columns, then the action
-        out = out + (Flights(fl[..., :12], fl[..., 12:], None if obs_rec is None else obs_rec.permute(1, 0, 2).contiguous().cpu().reshape(P, R, T, D),
-                             length[:, :R], float(env.cfg.time_step) * int(env.cfg.aggregate_phy_steps), u0.reshape(P, R, 4),
-                             control_mode={v: k for k, v in native.CONTROL_MODES.items()}[int(env.cfg.control_mode)]),)
-    return out
+        flown = _fly_composed(env, population, obs, P, E, T, metrics, obs_stats, rec)
+    return _population_result(env, population, P, E, T, flown, metrics, obs_stats, rec, u0, log_dir)

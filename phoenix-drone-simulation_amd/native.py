@@ -110,6 +110,7 @@ SIGNATURES = {
     "pds_evaluate_policies": (_i32, _eval + [_vp]),
     "pds_evaluate_policies_metrics": (_i32, _eval + [_vp] * 2),
     "pds_evaluate_policies_stats": (_i32, _eval + [_vp] * 3),
+    "pds_evaluate_policies_record": (_i32, _eval + [_vp, _i64, _vp, _vp, _vp]),
     "pds_evaluate_history_supported": (_i32, [_vp, _i32]),
     "pds_evaluate_policies_history": (_i32, [_vp, _i32] + _eval[1:] + [_vp] * 2),
     "pds_mlp_param_count": (_i32, [_mp]),
@@ -147,10 +148,6 @@ SIGNATURES = {
     "pds_ddpg_explore": (_i32, [_vp, _vp, _i64, _f32, _u64, _u64, _u64, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
-# ... and of include/pds_record.h, the entry point that stands beside that ABI (tests/test_evaluate_record_cpu.py compares the two)
-RECORD_SIGNATURES = {
-    "pds_evaluate_policies_record": (_i32, _eval + [_vp, _i64, _vp, _vp, _vp]),
-}
 
 _lib = None
 
@@ -171,7 +168,7 @@ def load():
     # an OLDER build given through PDS_LIB for a same-box A/B (profiles/tools/ab_lib.sh) may lack the newer entry points: those
     # are skipped; the shipped library must have every name (AttributeError here, and tests/test_host_cpu.py)
     older = bool(os.environ.get("PDS_LIB"))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(RECORD_SIGNATURES.items()):
+    for name, (restype, argtypes) in SIGNATURES.items():
         if older and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

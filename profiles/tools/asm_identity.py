@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""asm_identity.py PARENT.s NEW.s -- are the kernels of two device assemblies of one translation unit the same, one by one?
+"""asm_identity.py [--rename REGEX=REPLACEMENT ...] PARENT.s NEW.s -- are the kernels of two device assemblies of one translation unit the same, one by one?
 
 Both files come from hipcc with the flags of build.py plus --cuda-device-only -S.  A kernel is the text from its label through
 its .end_amdhsa_kernel (instructions and kernel-descriptor directives); comments, trailing blanks, the position-dependent
 number in .LBB<n>_ / .Lfunc_end<n> / .Ltmp<n> labels and the kernel's own mangled name are normalised away, nothing else.
-Kernels are matched by their plain demangled name (c++filt).
+Kernels are matched by their plain demangled name (c++filt); --rename applies re.sub(REGEX, REPLACEMENT) to the PARENT's
+demangled names first, for a change that renames a kernel or its template arguments and nothing else.
 Prints one row per kernel (identical / gone / APPEARED / DIFFERS, instruction lines) and exits 1 unless every kernel of NEW.s
 is identical to its namesake."""
 import re, subprocess, sys
@@ -46,13 +47,23 @@ def insn_count(body):
     return n
 
 
-def load(path):
+def load(path, renames=()):
     k = kernels(path)
     names = list(k)
-    return {d: k[nm] for nm, d in zip(names, demangle(names))}
+    out = {}
+    for nm, d in zip(names, demangle(names)):
+        for pattern, replacement in renames:
+            d = re.sub(pattern, replacement, d)
+        assert d not in out, d  # (a rename must not merge two kernels)
+        out[d] = k[nm]
+    return out
 
 
-a, b = load(sys.argv[1]), load(sys.argv[2])
+argv, renames = sys.argv[1:], []
+while argv and argv[0] == "--rename":
+    renames.append(tuple(argv[1].split("=", 1)))
+    argv = argv[2:]
+a, b = load(argv[0], renames), load(argv[1])
 bad = 0
 for name in sorted(set(a) | set(b)):
     if name not in b:

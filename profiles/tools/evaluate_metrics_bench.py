@@ -22,13 +22,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import kernel_resources as kr  # noqa: E402
+import evaluate_names as en  # noqa: E402
 import phoenix_drone_simulation_amd as pds  # noqa: E402
 from phoenix_drone_simulation_amd.evaluation import PolicyPopulation, evaluate_population  # noqa: E402
 from phoenix_drone_simulation_amd.ppo import ActorCritic  # noqa: E402
 
 SHAPES = ((8, 128), (64, 1024), (64, 16384))
-HOVER_DEFAULT = "Variant<0, false, true, false, true, true, 0, false, false>"  # Hover: domain randomisation, thrust and observation noise
 TWO_TEAMS_ABOVE = 256  # tiles (kRolloutTwoTeamsAbove)
 
 
@@ -41,14 +40,7 @@ def population(P):
 
 def scratch_of_forms():
     """{(metrics form?, teams): scratch bytes per lane} of Hover's default variant, from the code objects"""
-    out = {}
-    for r in kr.kernel_table():
-        if "evaluate_kernel<" in r[0] and HOVER_DEFAULT in r[0]:
-            tail = r[0].split(HOVER_DEFAULT)[1].split(">")[0].split(",")[1:]  # TEAMS, METRICS, STATS, RECORD
-            teams, metrics, stats = int(tail[0]), tail[1].strip() == "true", tail[2].strip() == "true"
-            if not stats and tail[3].strip() != "true":  # (the stats and record forms: profiles/tools/evaluate_{stats,record}_bench.py)
-                out[(metrics, teams)] = r[5]
-    return out
+    return en.hover_default_scratch("plain", "metrics")  # (the stats and record forms: profiles/tools/evaluate_{stats,record}_bench.py)
 
 
 def teams_launched(scratch, metrics, tiles):

@@ -1,34 +1,20 @@
 #!/usr/bin/env python3
 """Writes the table of profiles/evaluate_metrics_kernel_resources.txt: every instantiation of evaluate_kernel<Variant, TEAMS,
-METRICS> in the built library, the metrics form next to the plain form, read from the code objects' metadata
+EvalForm> in the built library, plain and metrics form, the metrics form next to the plain form, read from the code objects' metadata
 (profiles/tools/kernel_resources.py: what the compiler made; no device needed).
 
   python profiles/tools/evaluate_metrics_resources.py > table.txt
 """
 import os
-import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import kernel_resources as kr  # noqa: E402
-
-NAME = re.compile(r"evaluate_kernel<pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>, (\d), (\w+)>")
-TASK = ("Hover", "Circle", "TakeOff")
-CTRL = ("PWM", "Rate", "Att")
+import evaluate_names as en  # noqa: E402
 
 
 def rows(lib=None):
     """{(task, flags, ctrl, ring, teams): {metrics form?: (vgprs, vgpr spills, sgprs, sgpr spills, scratch, lds)}}"""
-    out = {}
-    for r in kr.kernel_table(lib):
-        m = NAME.search(r[0])
-        if not m:
-            continue
-        task, motor, dr, ge, tn, on, ctrl, lat, hold, teams, metrics = m.groups()
-        flags = "".join(c for c, v in zip("MDGTO", (motor, dr, ge, tn, on)) if v == "true") or "-"
-        ring = "lat" if lat == "true" else ("hold" if hold == "true" else "")
-        out.setdefault((TASK[int(task)], flags, CTRL[int(ctrl)], ring, int(teams)), {})[metrics == "true"] = r[1:]
-    return out
+    return {key: {False: forms["plain"], True: forms["metrics"]} for key, forms in en.rows(lib).items()}
 
 
 def main():

@@ -30,9 +30,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import kernel_resources as kr  # noqa: E402
+import evaluate_names as en  # noqa: E402
 import phoenix_drone_simulation_amd as pds  # noqa: E402
-from evaluate_metrics_bench import HOVER_DEFAULT, SHAPES, TWO_TEAMS_ABOVE, population  # noqa: E402
+from evaluate_metrics_bench import SHAPES, TWO_TEAMS_ABOVE, population  # noqa: E402
 from phoenix_drone_simulation_amd import native  # noqa: E402
 from phoenix_drone_simulation_amd.evaluation import evaluate_population  # noqa: E402
 
@@ -41,13 +41,7 @@ R = 64
 
 def scratch_of_forms():
     """{(record form?, teams): scratch bytes per lane} of Hover's default variant, metrics and record form, from the code objects"""
-    out = {}
-    for r in kr.kernel_table():
-        if "evaluate_kernel<" in r[0] and HOVER_DEFAULT in r[0]:
-            tail = [x.strip() for x in r[0].split(HOVER_DEFAULT)[1].split(">")[0].split(",")[1:]]  # TEAMS, METRICS, STATS, RECORD
-            if tail[1] == "true" and tail[2] != "true":
-                out[(tail[3] == "true", int(tail[0]))] = r[5]
-    return out
+    return en.hover_default_scratch("metrics", "record")
 
 
 def teams_launched(scratch, record, tiles):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Writes the table of profiles/evaluate_record_kernel_resources.txt: every instantiation of evaluate_kernel<Variant, TEAMS,
-METRICS, STATS, RECORD> in the built library, the record form (METRICS and RECORD) next to the metrics form, read from the code
+EvalForm> in the built library, the record form next to the metrics form, read from the code
 objects' metadata (profiles/tools/kernel_resources.py: what the compiler made; no device needed) -- and compares the plain, the
 metrics and the stats form, kernel by kernel, with the rows of profiles/evaluate_metrics_kernel_resources.txt and
 profiles/evaluate_stats_kernel_resources.txt, and evaluate_hist_kernel with profiles/evaluate_history_kernel_resources.txt
@@ -14,28 +14,10 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-import kernel_resources as kr  # noqa: E402
+from evaluate_names import rows  # noqa: E402
 
-NAME = re.compile(r"evaluate_kernel<pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>, (\d), (\w+), (\w+), (\w+)>")
-TASK = ("Hover", "Circle", "TakeOff")
-CTRL = ("PWM", "Rate", "Att")
 ROW = re.compile(r"^(\w+) +(\S+) +(\w+) +(lat|hold|) +([12]) \|((?: +-?\d+){6}) +\w* *\|((?: +-?\d+){6}) +\w* *\|")
 RECORDS = (("evaluate_metrics_kernel_resources.txt", "plain", "metrics"), ("evaluate_stats_kernel_resources.txt", "metrics", "stats"))
-
-
-def rows(lib=None):
-    """{(task, flags, ctrl, ring, teams): {"plain" / "metrics" / "stats" / "record": (vgprs, vgpr spills, sgprs, sgpr spills, scratch, lds)}}"""
-    out = {}
-    for r in kr.kernel_table(lib):
-        m = NAME.search(r[0])
-        if not m:
-            continue
-        task, motor, dr, ge, tn, on, ctrl, lat, hold, teams, metrics, stats, record = m.groups()
-        flags = "".join(c for c, v in zip("MDGTO", (motor, dr, ge, tn, on)) if v == "true") or "-"
-        ring = "lat" if lat == "true" else ("hold" if hold == "true" else "")
-        form = "record" if record == "true" else ("stats" if stats == "true" else ("metrics" if metrics == "true" else "plain"))
-        out.setdefault((TASK[int(task)], flags, CTRL[int(ctrl)], ring, int(teams)), {})[form] = r[1:]
-    return out
 
 
 def recorded(name, left, right):

@@ -22,20 +22,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import evaluate_metrics_bench as mb  # noqa: E402  (population, shapes, the variant's name)
-import kernel_resources as kr  # noqa: E402
+import evaluate_names as en  # noqa: E402
 import phoenix_drone_simulation_amd as pds  # noqa: E402
 from phoenix_drone_simulation_amd.evaluation import evaluate_population  # noqa: E402
 
 
 def scratch_of_forms():
     """{(stats form?, teams): scratch bytes per lane} of Hover's default variant in its metrics and its stats form"""
-    out = {}
-    for r in kr.kernel_table():
-        if "evaluate_kernel<" in r[0] and mb.HOVER_DEFAULT in r[0]:
-            tail = r[0].split(mb.HOVER_DEFAULT)[1].split(">")[0].split(",")[1:]  # TEAMS, METRICS, STATS, RECORD
-            if tail[1].strip() == "true" and tail[3].strip() != "true":
-                out[(tail[2].strip() == "true", int(tail[0]))] = r[5]
-    return out
+    return en.hover_default_scratch("metrics", "stats")
 
 
 def timed(env, pop, fused, stats):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Writes the table of profiles/evaluate_stats_kernel_resources.txt: every instantiation of evaluate_kernel<Variant, TEAMS,
-METRICS, STATS> in the built library, the stats form (METRICS and STATS) next to the metrics form, read from the code objects'
+EvalForm> in the built library, the stats form next to the metrics form, read from the code objects'
 metadata (profiles/tools/kernel_resources.py: what the compiler made; no device needed) -- and compares the plain and the metrics
 form, kernel by kernel, with the rows of profiles/evaluate_metrics_kernel_resources.txt.
 
@@ -11,28 +11,10 @@ import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import kernel_resources as kr  # noqa: E402
+from evaluate_names import CTRL, TASK, rows  # noqa: E402,F401  (profiles/tools/evaluate_history_resources.py reads them here)
 
-NAME = re.compile(r"evaluate_kernel<pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>, (\d), (\w+), (\w+), false>")  # (the last argument: RECORD, profiles/tools/evaluate_record_resources.py)
-TASK = ("Hover", "Circle", "TakeOff")
-CTRL = ("PWM", "Rate", "Att")
 RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "evaluate_metrics_kernel_resources.txt")
 ROW = re.compile(r"^(\w+) +(\S+) +(\w+) +(lat|hold|) +([12]) \|((?: +-?\d+){6}) +\w* *\|((?: +-?\d+){6}) +\w* *\|")
-
-
-def rows(lib=None):
-    """{(task, flags, ctrl, ring, teams): {"plain" / "metrics" / "stats": (vgprs, vgpr spills, sgprs, sgpr spills, scratch, lds)}}"""
-    out = {}
-    for r in kr.kernel_table(lib):
-        m = NAME.search(r[0])
-        if not m:
-            continue
-        task, motor, dr, ge, tn, on, ctrl, lat, hold, teams, metrics, stats = m.groups()
-        flags = "".join(c for c, v in zip("MDGTO", (motor, dr, ge, tn, on)) if v == "true") or "-"
-        ring = "lat" if lat == "true" else ("hold" if hold == "true" else "")
-        form = "stats" if stats == "true" else ("metrics" if metrics == "true" else "plain")
-        out.setdefault((TASK[int(task)], flags, CTRL[int(ctrl)], ring, int(teams)), {})[form] = r[1:]
-    return out
 
 
 def recorded():

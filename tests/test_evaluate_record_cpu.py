@@ -3,13 +3,11 @@ round trip through simopt.MiniTrajectories.from_csv_dir, mini_trajectories() aga
 refusals of evaluate_population(record=...) in front of any library call, and the new symbol's declaration."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LENGTHS = [[60, 3, 0], [47, 41, 1]]  # P = 2, R = 3, T = 60: one full, short ones, an empty one, one just long enough for a slice
 
 
@@ -175,46 +173,22 @@ def test_an_accepted_record_reaches_the_env():
         evaluate_population(_Env(), pop, record=128, record_limit_bytes=500 * 2 * 128 * (64 + 4 * 34))
 
 
-def _record_table_mismatches(signatures, native):
-    """every disagreement between `signatures` and the prototypes of include/pds_record.h: names, arity, return and parameter
-    classes (the comparison tests/test_host_cpu.py makes between native.SIGNATURES and include/pds.h)"""
-    hdr = open(os.path.join(ROOT, "include", "pds_record.h")).read()
-    hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
-    protos = re.findall(r"^[ \t]*((?:const\s+)?\w+[\s\*]+)(pds_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr, flags=re.M)
-
-    def c_class(decl):
-        if "*" in decl:
-            return C.POINTER(native.Mlp) if re.search(r"\bpds_mlp\b", decl) else C.c_void_p
-        return {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float}[[w for w in decl.split() if w != "const"][0]]
-
-    bad = [f"names: {sorted(set(signatures) ^ {n for _, n, _ in protos})}"] if set(signatures) != {n for _, n, _ in protos} else []
-    for ret, name, params in protos:
-        if name in signatures:
-            restype, argtypes = signatures[name]
-            want = [c_class(p) for p in params.split(",")]
-            if restype is not c_class(ret):
-                bad.append(f"{name}: restype {restype} for `{ret.strip()}`")
-            if len(argtypes) != len(want):
-                bad.append(f"{name}: {len(argtypes)} argtypes for {len(want)} parameters")
-            bad += [f"{name}: argument {i} is {a}, the header says {w}" for i, (a, w) in enumerate(zip(argtypes, want)) if a is not w]
-    return len(protos), bad
-
-
 def test_the_record_table_matches_its_header_and_the_library_exports_the_symbol():
-    """native.RECORD_SIGNATURES against every prototype of include/pds_record.h, as native.SIGNATURES is held against include/pds.h;
+    """the row of pds_evaluate_policies_record in native.SIGNATURES against include/pds.h, by the comparison of tests/test_host_cpu.py;
     a row that lost an argument, or holds a wrong class, must not pass; the library exports the symbol and refuses a NULL handle"""
     from phoenix_drone_simulation_amd import native
-    n, bad = _record_table_mismatches(native.RECORD_SIGNATURES, native)
-    assert n == len(native.RECORD_SIGNATURES) == 1 and not bad, bad
-    restype, argtypes = native.RECORD_SIGNATURES["pds_evaluate_policies_record"]
-    _, bad = _record_table_mismatches({"pds_evaluate_policies_record": (restype, argtypes[:-1])}, native)
+    from test_host_cpu import _table_mismatches
+    n, bad = _table_mismatches(native.SIGNATURES, native)
+    assert n == len(native.SIGNATURES) and not bad, bad
+    restype, argtypes = native.SIGNATURES["pds_evaluate_policies_record"]
+    _, bad = _table_mismatches(dict(native.SIGNATURES, pds_evaluate_policies_record=(restype, argtypes[:-1])), native)
     assert bad == ["pds_evaluate_policies_record: 17 argtypes for 18 parameters"]
     wrong = list(argtypes); wrong[14] = C.c_int  # record_per_policy is an int64_t
-    _, bad = _record_table_mismatches({"pds_evaluate_policies_record": (restype, wrong)}, native)
+    _, bad = _table_mismatches(dict(native.SIGNATURES, pds_evaluate_policies_record=(restype, wrong)), native)
     assert len(bad) == 1 and "argument 14" in bad[0]
-    _, bad = _record_table_mismatches({}, native)
+    _, bad = _table_mismatches({}, native)
     assert len(bad) == 1 and bad[0].startswith("names")
-    assert not set(native.RECORD_SIGNATURES) & set(native.SIGNATURES)
+    assert "pds_evaluate_policies_record" in native.SIGNATURES
     metrics = native.SIGNATURES["pds_evaluate_policies_metrics"][1]
     assert argtypes[:14] == metrics[:14] and argtypes[-1] is metrics[-1]  # the metrics entry point's arguments, the three new ones, the stream
     lib = native.load()

@@ -1,5 +1,5 @@
 """The flight-quality metrics of the one-launch policy evaluation on the GPU (include/pds.h pds_evaluate_policies_metrics,
-csrc/pds_evaluate.h METRICS; evaluation.evaluate_population(..., metrics=True)): bit for bit what the composed path sums with
+csrc/pds_evaluate.h, the flight metrics; evaluation.evaluate_population(..., metrics=True)): bit for bit what the composed path sums with
 separate torch ops, equal to the definitions restated in float64 (evaluation.metrics_from_arrays), hand-checkable on policies
 with zero weights, and without any effect on return, length and cost."""
 import ctypes as C

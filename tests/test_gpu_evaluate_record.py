@@ -1,5 +1,5 @@
-"""The recorded flights of the one-launch policy evaluation on the GPU (include/pds_record.h pds_evaluate_policies_record,
-csrc/pds_evaluate.h RECORD; evaluation.evaluate_population(..., record=R) -> evaluation.Flights): bit for bit what the composed
+"""The recorded flights of the one-launch policy evaluation on the GPU (include/pds.h pds_evaluate_policies_record,
+csrc/pds_evaluate.h, the record; evaluation.evaluate_population(..., record=R) -> evaluation.Flights): bit for bit what the composed
 path reads in front of every step, zero past every episode's end, without any effect on what the evaluation returns, x(0) the
 reset state, hand-checkable on policies with zero weights, and enough to re-derive the flight metrics."""
 import ctypes as C

@@ -76,7 +76,7 @@ def test_signature_table_matches_the_header():
     ctypes mirrors of pds_mlp / pds_adam field by field.  A table that lost one argument must not pass."""
     from phoenix_drone_simulation_amd import native
     n, bad = _table_mismatches(native.SIGNATURES, native)
-    assert n == len(native.SIGNATURES) == 72 and not bad, bad
+    assert n == len(native.SIGNATURES) == 73 and not bad, bad
     assert native.EXPORTS == list(native.SIGNATURES) and native.SIGNATURES["pds_version"] == (C.c_int, [])
     restype, argtypes = native.SIGNATURES["pds_mlp_forward"]
     _, bad = _table_mismatches(dict(native.SIGNATURES, pds_mlp_forward=(restype, argtypes[:-1])), native)
