@@ -5,8 +5,13 @@ tests/golden/history.npz.  Experiment 04 of the reference trains with history si
 
 Deterministic configuration (no sensor / thrust noise, no domain randomisation, no reset
 distribution), so the trajectory is a pure function of the action sequence: reset, step a recorded
-action sequence until the env terminates or is truncated, reset again, a few more steps.  Only data
-is written (actions in, observations / rewards / flags out)."""
+action sequence, reset again behind every finished episode, step on.  Only data is written (actions
+in, observations / rewards / flags out).
+The file as committed holds TERMINATIONS only: `truncated` is False at every step of all six
+trajectories -- the `max_steps` stored next to them never took effect, every env ran under the default
+limit of 500.  The history restart at a TimeLimit cut is covered elsewhere: on the oracle by
+tests/test_flight_oracle_cpu.py (a flight written env by env with a limit of 6) and on the device by
+tests/test_gpu_evaluate_forms_reference.py."""
 import os
 import sys
 

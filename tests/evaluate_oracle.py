@@ -7,7 +7,10 @@ Nothing here comes from phoenix_drone_simulation_amd.evaluation: the loop is wri
 reset; until the episode's first `terminated or truncated`: act on the observation, step, add the step's reward and
 info['cost'], count the step.  The envs are an OracleBatch of P E envs with auto-reset, so that an env whose episode is over flies
 on as the device's does (its later steps are not counted); global env id = row index, seed and ticks as pds_reset / pds_step use
-them (reset at tick0, step s at tick0 + 1 + s)."""
+them (reset at tick0, step s at tick0 + 1 + s).
+tests/flight_oracle.py flies the same loop and also keeps what the metrics, stats, record and history forms report (state, action,
+observation, last_action, the PDS_EM_* values, the observation sums, the history stack); its three sums are asserted equal to
+evaluate_reference's here (tests/test_flight_oracle_cpu.py)."""
 import os
 import sys
 

@@ -1,6 +1,7 @@
 """The flight-quality metrics of the one-launch policy evaluation on the GPU (include/pds.h pds_evaluate_policies_metrics,
 csrc/pds_evaluate.h, the flight metrics; evaluation.evaluate_population(..., metrics=True)): bit for bit what the composed path sums with
-separate torch ops, equal to the definitions restated in float64 (evaluation.metrics_from_arrays), hand-checkable on policies
+separate torch ops, equal in arithmetic to evaluation.metrics_from_arrays in float64 (held to an independent reference in
+tests/test_gpu_evaluate_forms_reference.py), hand-checkable on policies
 with zero weights, and without any effect on return, length and cost."""
 import ctypes as C
 
@@ -145,7 +146,10 @@ class _Recorder:
 def test_against_the_definitions_in_float64(config):
     """every env's first episode, as the composed path saw it, through metrics_from_arrays.  Counters and tilt_max: equal.  Sums:
     within (T + 4) 2^-24 relative -- T sequential float32 additions of non-negative terms plus the roundings inside one term,
-    both sides reading the same float32 states."""
+    both sides reading the same float32 states.  This checks the ARITHMETIC of the sums only: the states, `u` and the "state
+    before step s" convention are the composed path's own (env.get_state), and metrics_from_arrays is the project's.  The
+    independent check -- the true state and last_action read off the float64 CPU oracle, the definitions restated from
+    include/pds.h -- is tests/test_gpu_evaluate_forms_reference.py (tests/flight_oracle.py)."""
     from phoenix_drone_simulation_amd.evaluation import evaluate_population, metrics_from_arrays
     P, E = 2, 64
     pop = _population(config, P)

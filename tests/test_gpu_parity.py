@@ -355,7 +355,9 @@ def test_observation_history_sizes_vs_reference_trajectories(task, H):
     """observation_history_size = 1, 4, 6, 8 (experiments/04_*; envs/base.py:303-319), composed on the
     device from the kernel's newest half: whole trajectories of the reference env (reset, recorded
     actions, terminations followed by reset(); tests/golden/history.npz from
-    oracle/refgen/gen_golden_history.py) against the HIP env with same-step auto-reset."""
+    oracle/refgen/gen_golden_history.py) against the HIP env with same-step auto-reset.  The file
+    holds terminations only (no step of it is truncated); the restart at a TimeLimit cut is covered by
+    tests/test_flight_oracle_cpu.py on the oracle and tests/test_gpu_evaluate_forms_reference.py on the device."""
     import os
     import phoenix_drone_simulation_amd as pds
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "history.npz"))

@@ -1,6 +1,7 @@
 """Every env configuration the constructor accepts, over the axes a kernel variant is chosen by, and for each whether the
 one-launch kernels (pds_rollout, pds_evaluate_policies; pds_collect: collect_family) are built for it.  TEST INFRASTRUCTURE,
-shared by tests/test_gpu_evaluate_variants.py, tests/test_gpu_collect_variants.py and the rollout sweep of tests/test_trainer.py.
+shared by tests/test_gpu_evaluate_variants.py, tests/test_gpu_evaluate_forms_variants.py, tests/test_gpu_collect_variants.py and the
+rollout sweep of tests/test_trainer.py.
 
 The axes: task (Hover, Circle, TakeOff) x motor dynamics x domain randomisation x thrust noise x observation noise x ground
 effect x control mode (PWM, AttitudeRate, Attitude) x latency ring x Kalman hold (observation_frequency = 50 < sim_freq = 100; it
@@ -59,6 +60,32 @@ def collect_family(task, motor, dr, tn, on, ge, ctrl, lat, hold):
     if task == "takeoff" and motor:
         return None
     return "collect"
+
+
+HISTORY_COUNT = 26  # literal: Hover and Circle x 3 control modes x {lean, full} x {with, without motor dynamics}, TakeOff x {lean, full}
+HISTORY_WIDTHS = (64, 96, 128, 192)  # the input widths the history kernels are instantiated for: 4, 6, 8 and 12 tiles of 16
+
+
+def history_family(task, motor, dr, tn, on, ge, ctrl, lat, hold):
+    """"history" where the observation-history evaluation (pds_evaluate_policies_history: the env configurations of
+    pds_rollout_history) is built for this configuration, else None.  The rule as the comments of include/pds.h
+    (pds_rollout_history, pds_evaluate_policies_history) state it, written out here and NOT read from the library: no latency
+    ring, no Kalman hold, no ground effect; noise all off or the reference's default; every control mode on Hover and Circle, with
+    and without motor dynamics; TakeOff with control_mode PWM, without motor dynamics.  (And at most 192 network inputs:
+    history_sizes.)"""
+    if lat or hold or ge:
+        return None
+    if not ((dr and tn and on) or not (dr or tn or on)):
+        return None
+    if task == "takeoff" and (ctrl != "PWM" or motor):
+        return None
+    return "history"
+
+
+def history_sizes(half):
+    """one observation_history_size H per input width class of the history kernel: the largest H other than 2 (H = 2 flies
+    pds_evaluate_policies) with H x half inputs inside the class -> [(H, class width)]"""
+    return [(max(H for H in range(1, 193) if H != 2 and H * half <= width), width) for width in HISTORY_WIDTHS]
 
 
 def kwargs_of(motor, dr, tn, on, ge, ctrl, lat, hold):
@@ -131,6 +158,20 @@ def collect_variants():
 
 
 COLLECT_SUPPORTED = collect_variants()
+
+
+def history_variants():
+    """[(id, env id, kwargs)] of the configurations history_family accepts"""
+    out = []
+    bb = (False, True)
+    for (task, env_id), motor, dr, tn, on, ge, ctrl, lat, hold in itertools.product(TASKS, bb, bb, bb, bb, bb, CTRL, bb, bb):
+        f = (task, motor, dr, tn, on, ge, ctrl, lat, hold)
+        if accepted(*f) and history_family(*f):
+            out.append((_name(*f), env_id, kwargs_of(*f[1:])))
+    return out
+
+
+HISTORY_SUPPORTED = history_variants()
 assert len({v[0] for v in VARIANTS}) == len(VARIANTS)
 
 
