@@ -13,7 +13,8 @@ evaluate_population (the evaluation loop of the reference's utils/evaluation.py,
   python examples/evaluate_policies.py runs/ --record 64 --record-dir flights   # the first 64 flights per checkpoint as CSV logs
 
 A group whose actors read H x half inputs (half: one [o, u] half of the env's observation) was trained on an observation history
-of H: its env is built with observation_history_size = H (inferred from the width, or --history) and flies in one launch too.
+of H: its env is built with observation_history_size = H (inferred from the width, or --history) and flies in one launch too,
+with --record as without it.
 """
 import argparse
 import json
@@ -89,7 +90,8 @@ def main():
                     help="observation_history_size of the env (default: inferred per group, actor inputs / half the env's observation width)")
     ap.add_argument("--record", type=int, default=None, metavar="R",
                     help="record the first R episodes per checkpoint (a multiple of 64, at most --episodes): state, action and "
-                         "observation of every step, from the same launch (evaluation.Flights)")
+                         "observation of every step, from the same launch (evaluation.Flights); a group of history policies "
+                         "records in its one launch too, the observation being the whole history its actors read")
     ap.add_argument("--record-dir", default=None, metavar="DIR",
                     help="with --record: one CSV log per recorded episode under <DIR>/<group>/<p>/ in the layout of the "
                          "simulation-optimisation logs (Flights.to_csv_dir; control_mode PWM)")

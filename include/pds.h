@@ -501,6 +501,8 @@ int pds_evaluate_policies_history(pds_handle *h, int history, int64_t P, int64_t
                                   const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
                                   const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics, void *stream);
 
+/* (pds_evaluate_policies_history_record, the same launch with the flights recorded, is declared in include/pds_history_record.h) */
+
 /* number of parameters; flat gradient layout = [W1, b1, W2, b2, W3, b3] (torch parameter order) */
 int pds_mlp_param_count(const pds_mlp *m);
 /* floats of scratch the *_grad entry points need (per-wave partial sums) */

@@ -1163,6 +1163,22 @@ struct EvalFormCall {
   int64_t record_per_policy;
   float *d_flight, *d_obs_rec;
 };
+// what a recording call validates about its record, in front of everything else (pds_evaluate_policies_record and
+// pds_evaluate_policies_history_record)
+static int check_record_call(pds_handle *h, const char *fn, const EvalFormCall &x, int64_t episodes_per_policy) {
+  if (x.record_per_policy < kWave || x.record_per_policy % kWave != 0 || x.record_per_policy > episodes_per_policy)
+    return fail(h, PDS_EINVAL, "%s: record_per_policy %lld is not a positive multiple of %d up to episodes_per_policy %lld", fn,
+                (long long)x.record_per_policy, kWave, (long long)episodes_per_policy);
+  if (!x.d_flight || (((uintptr_t)x.d_flight) & 15u)) return fail(h, PDS_EINVAL, "%s: d_flight must be given and 16-byte aligned", fn);
+  if (((uintptr_t)x.d_obs_rec) & 3u) return fail(h, PDS_EINVAL, "%s: d_obs_rec must be 4-byte aligned", fn);
+  return PDS_OK;
+}
+// ... and its part of the argument block
+static void fill_record_args(EvalRecordArgs &ra, const EvalFormCall &x) {
+  ra.flight = reinterpret_cast<float4 *>(x.d_flight);
+  ra.obs_rec = x.d_obs_rec;
+  ra.rec_tiles = (int)(x.record_per_policy / kWave);
+}
 template <EvalForm F>
 static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
                                   const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
@@ -1170,11 +1186,7 @@ static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int6
   constexpr bool STATS = F == EvalForm::Stats, RECORD = F == EvalForm::Record;
   if (!h) return PDS_EINVAL;
   if constexpr (RECORD) {  // (decided before the handle is looked at)
-    if (x.record_per_policy < kWave || x.record_per_policy % kWave != 0 || x.record_per_policy > episodes_per_policy)
-      return fail(h, PDS_EINVAL, "%s: record_per_policy %lld is not a positive multiple of %d up to episodes_per_policy %lld", fn,
-                  (long long)x.record_per_policy, kWave, (long long)episodes_per_policy);
-    if (!x.d_flight || (((uintptr_t)x.d_flight) & 15u)) return fail(h, PDS_EINVAL, "%s: d_flight must be given and 16-byte aligned", fn);
-    if (((uintptr_t)x.d_obs_rec) & 3u) return fail(h, PDS_EINVAL, "%s: d_obs_rec must be 4-byte aligned", fn);
+    if (const int rc = check_record_call(h, fn, x, episodes_per_policy)) return rc;
   }
   const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost ||
                         (eval_sums_metrics(F) && !RECORD && !x.d_metrics) || (STATS && !x.d_obs_sums);
@@ -1191,11 +1203,7 @@ static int evaluate_policies_call(pds_handle *h, const char *fn, int64_t P, int6
   if constexpr (F == EvalForm::Metrics) ka.metrics = x.d_metrics;
   else if constexpr (eval_sums_metrics(F)) ka.m.metrics = x.d_metrics;
   if constexpr (STATS) ka.obs_sums = x.d_obs_sums;
-  if constexpr (RECORD) {
-    ka.flight = reinterpret_cast<float4 *>(x.d_flight);
-    ka.obs_rec = x.d_obs_rec;
-    ka.rec_tiles = (int)(x.record_per_policy / kWave);
-  }
+  if constexpr (RECORD) fill_record_args(ka, x);
   if (const int rc = fill_evaluate_args(h, fn, eval_head(ka), episodes_per_policy, shape, d_params, d_mean, d_std, eps, max_steps, d_obs0,
                                         d_ret, d_len, d_cost, stream))
     return rc;
@@ -1243,19 +1251,24 @@ extern "C" int pds_evaluate_policies_record(pds_handle *h, int64_t P, int64_t ep
 }
 
 // ---- the population evaluation for observation histories: csrc/pds_evaluate_hist.h ----
-// whether pds_evaluate_policies_history has a kernel for this handle and this observation_history_size
+// whether pds_evaluate_policies_history and pds_evaluate_policies_history_record (the same variant set) have a kernel for this
+// handle and this observation_history_size
 extern "C" int pds_evaluate_history_supported(const pds_handle *h, int history) {
   if (!h) return PDS_EINVAL;
   return h->cfg.auto_reset && rollout_hist_supported(h->cfg.task, h->flags) && history >= 1 && (long long)history * (h->obs_dim / 2) <= 192 ? 1 : 0;
 }
 // P policies x E episodes in one launch, the actors reading the last `history` halves of the handle's row.  The checks and the
-// handle's state afterwards are pds_evaluate_policies'; d_metrics is optional.
-extern "C" int pds_evaluate_policies_history(pds_handle *h, int history, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
-                                             const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
-                                             const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
-                                             void *stream) {
-  const char *fn = "pds_evaluate_policies_history";
+// handle's state afterwards are pds_evaluate_policies'; d_metrics is optional.  ONE body for the two forms of the kernel (REC,
+// csrc/pds_evaluate_hist.h): the record form's checks come first, as in evaluate_policies_call, and `x` holds what it adds.
+template <bool REC>
+static int evaluate_history_call(pds_handle *h, const char *fn, int history, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                                 const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                                 const float *d_obs0, float *d_ret, float *d_len, float *d_cost, const EvalFormCall &x, void *stream) {
+  float *const d_metrics = x.d_metrics;
   if (!h) return PDS_EINVAL;
+  if constexpr (REC) {  // (decided before the handle is looked at)
+    if (const int rc = check_record_call(h, fn, x, episodes_per_policy)) return rc;
+  }
   if (history < 1) return fail(h, PDS_EINVAL, "%s: history %d", fn, history);
   const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost;
   const int half = h->obs_dim / 2;
@@ -1268,25 +1281,58 @@ extern "C" int pds_evaluate_policies_history(pds_handle *h, int history, int64_t
                                      "pds_mlp_forward + pds_step + pds_history_advance give the same bits", fn);
   DeviceGuard guard(h->cfg.device);
   PDS_HIP(h, guard.err);
-  EvalHistArgs ka;
+  EvalHistKernelArgs<REC> ka;
   memset(&ka, 0, sizeof(ka));
-  ka.m.metrics = d_metrics;
+  if constexpr (REC) {
+    ka.r.m.metrics = d_metrics;
+    fill_record_args(ka.r, x);
+  } else {
+    ka.m.metrics = d_metrics;
+  }
   ka.H = history;
-  if (const int rc = fill_evaluate_args(h, fn, ka.m.e, episodes_per_policy, shape, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret,
+  if (const int rc = fill_evaluate_args(h, fn, eval_head(ka), episodes_per_policy, shape, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret,
                                         d_len, d_cost, stream))
     return rc;
   const int hn = rollout_hist_tiles((int)HS);
   const int rc = launch_rollout(h, fn, max_steps, stream, [&](dim3 grid, hipStream_t s) {
-    if (h->flags.ctrl != 0) {  // (TakeOff fixes control_mode PWM)
-      if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_hover_pid(h->flags, hn, grid, s, ka);
-      return h->cfg.task == PDS_TASK_CIRCLE && launch_evaluate_hist_circle_pid(h->flags, hn, grid, s, ka);
+    if constexpr (REC) {
+      if (h->flags.ctrl != 0) {  // (TakeOff fixes control_mode PWM)
+        if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_record_hover_pid(h->flags, hn, grid, s, ka);
+        return h->cfg.task == PDS_TASK_CIRCLE && launch_evaluate_hist_record_circle_pid(h->flags, hn, grid, s, ka);
+      }
+      if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_record_hover(h->flags, hn, grid, s, ka);
+      if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_hist_record_circle(h->flags, hn, grid, s, ka);
+      return launch_evaluate_hist_record_takeoff(h->flags, hn, grid, s, ka);
+    } else {
+      if (h->flags.ctrl != 0) {  // (TakeOff fixes control_mode PWM)
+        if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_hover_pid(h->flags, hn, grid, s, ka);
+        return h->cfg.task == PDS_TASK_CIRCLE && launch_evaluate_hist_circle_pid(h->flags, hn, grid, s, ka);
+      }
+      if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_hover(h->flags, hn, grid, s, ka);
+      if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_hist_circle(h->flags, hn, grid, s, ka);
+      return launch_evaluate_hist_takeoff(h->flags, hn, grid, s, ka);
     }
-    if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_hover(h->flags, hn, grid, s, ka);
-    if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_hist_circle(h->flags, hn, grid, s, ka);
-    return launch_evaluate_hist_takeoff(h->flags, hn, grid, s, ka);
   });
   if (rc == PDS_OK) { h->was_reset = false; h->after_evaluate = true; }  // (tiles stopped at different steps: pds_evaluate_policies)
   return rc;
+}
+extern "C" int pds_evaluate_policies_history(pds_handle *h, int history, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                                             const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                                             const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
+                                             void *stream) {
+  return evaluate_history_call<false>(h, "pds_evaluate_policies_history", history, P, episodes_per_policy, shape, d_params, d_mean,
+                                      d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost, {d_metrics}, stream);
+}
+// the same launch that also records the flights of the first record_per_policy envs of every policy: d_flight [T, 4, N_rec, 4] and,
+// where given, d_obs_rec [T, N_rec, history x half] (include/pds_history_record.h; csrc/pds_evaluate_hist.h, the record)
+extern "C" int pds_evaluate_policies_history_record(pds_handle *h, int history, int64_t P, int64_t episodes_per_policy,
+                                                    const pds_mlp *shape, const float *d_params, const float *d_mean,
+                                                    const float *d_std, float eps, int max_steps, const float *d_obs0, float *d_ret,
+                                                    float *d_len, float *d_cost, float *d_metrics, int64_t record_per_policy,
+                                                    float *d_flight, float *d_obs_rec, void *stream) {
+  return evaluate_history_call<true>(h, "pds_evaluate_policies_history_record", history, P, episodes_per_policy, shape, d_params,
+                                     d_mean, d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost,
+                                     {d_metrics, nullptr, record_per_policy, d_flight, d_obs_rec}, stream);
 }
 
 // ---- the fused off-policy collection: csrc/pds_collect.h (OffPolicyTrainer.step_env + the bookkeeping of learn_one_epoch) ----

@@ -73,11 +73,14 @@ template <> struct EvalKernelArgsOf<EvalForm::Stats> { using type = EvalStatsArg
 template <> struct EvalKernelArgsOf<EvalForm::Record> { using type = EvalRecordArgs; };
 template <EvalForm F> using EvalKernelArgs = typename EvalKernelArgsOf<F>::type;
 // ... and the EvalArgs at its head, on the host and on the device, for a const or a mutable block (EvalHistArgs of
-// csrc/pds_evaluate_hist_args.h too: its first member is an EvalMetricsArgs `m`, like EvalStatsArgs' and EvalRecordArgs')
+// csrc/pds_evaluate_hist_args.h too: its first member is an EvalMetricsArgs `m`, like EvalStatsArgs' and EvalRecordArgs'; the
+// first member of that file's EvalHistRecordArgs is an EvalRecordArgs `r`)
+struct EvalHistRecordArgs;
 template <class KA>
 __host__ __device__ inline auto &eval_head(KA &ka) {
   if constexpr (std::is_same_v<std::remove_const_t<KA>, EvalArgs>) return ka;
   else if constexpr (std::is_same_v<std::remove_const_t<KA>, EvalMetricsArgs>) return ka.e;
+  else if constexpr (std::is_same_v<std::remove_const_t<KA>, EvalHistRecordArgs>) return ka.r.m.e;
   else return ka.m.e;
 }
 

@@ -13,6 +13,9 @@
 // Not here: action noise, log-probability and action buffer; an obs_buf store, the `fin` image and the fin_rows list (a finished
 // env's history restarts from its reset row, and nobody reads the history it had -- the newest half the per-step path takes from
 // final_obs lands in a row the restart overwrites whole); the stats form (it stays on the composed path for history envs).
+// The kernel has two forms, the template parameter REC: false is the launch above (pds_evaluate_policies_history,
+// csrc/pds_evaluate_hist_<task>*.hip), true also records the flights (pds_evaluate_policies_history_record,
+// csrc/pds_evaluate_hist_record_<task>*.hip).  Every statement the record adds is behind `if constexpr (REC)`.
 //
 // Hand-over: the two counters and the kEvalStop protocol of evaluate_kernel, stated and proved at the head of csrc/pds_evaluate.h;
 // the env wave's side of it is that file's PDS_EVAL_STEP_HEAD / PDS_EVAL_STEP_TAIL, the same statements in both kernels.  What
@@ -20,11 +23,29 @@
 // -- between its act_ready wait and its obs_ready post -- are the history tile, which the network waves read between their
 // obs_ready wait and their act_ready post, and the kernel's own [o(k), o(k + 1)] row tile, which they never touch; the action
 // slots go the other way round, and em_lds belongs to the env wave.  "o(s + 1) is in the tile" reads "the histories of step
-// s + 1 are in LDS".
+// s + 1 are in LDS".  (REC: the alive mask of a step is written and read in the history tile's windows, by the tile's writer and
+// readers, as that file says for its Stats and Record forms: no new counter, no new wait, the argument above word for word.)
 //
 // METRICS: the env wave always sums the eight PDS_EM_* values, exactly as evaluate_kernel<.., EvalForm::Metrics> does -- seven words
 // per lane in LDS, read and written back behind the act_ready wait, one rounded instruction per product and sum -- and stores the
 // [N, 8] row where d_metrics is non-NULL: one code object per variant instead of a plain and a metrics form.
+//
+// THE RECORD (REC): what evaluate_kernel<.., EvalForm::Record> does (the head of csrc/pds_evaluate.h), with the history tile in place
+// of the observation tile.  Of a policy's E / 64 tiles the first rec_tiles record (wave-uniform; eval_record_column has the column).
+//   The ENV wave stores x(s) = S.e and the raw a(s) of every lane `alive` in front of step s with PDS_ER_STEP -- four 16-byte
+//   pieces to flight[s][piece][column], behind the act_ready wait and PDS_EM_STEP, in front of step_once; nothing is carried
+//   across step_once but the column.
+//   The NETWORK waves, where obs_rec is given, copy the rows of the history tile whose env is alive in front of step s, raw (before
+//   standardisation), to obs_rec[s][column][H half]: each wave its 16 rows, the first H half floats of each at row stride S1, 16 H half
+//   contiguous floats -- between their obs_ready wait and their act_ready post (the env wave rewrites the rows behind its
+//   act_ready wait), and in front of gather_hist, so that the stores are under way while the actor computes.  One dword per lane
+//   and pass (eval_hist_copy_rows<1>), or 16 bytes (<4>) where H half is a multiple of 4 and obs_rec is 16-byte aligned: the
+//   same bits, wave-uniform, measured 12-18 % faster as a launch than the dword form (profiles/evaluate_history_record_timing.txt).
+//   The alive mask is es_lds<1>(): all ones from the prologue in front of the block barrier, then `still` from the env wave's
+//   lane 0 between PDS_EVAL_STILL and PDS_EVAL_STEP_TAIL.
+//   Nothing else is written: the rows s >= length of an env and every row of a tile that does not record keep what the caller put
+//   there; the terminal state and the terminal observation are not recorded, as at H = 2.
+//   (profiles/evaluate_history_record_kernel_resources.txt: the compiler's figures of the record's code objects.)
 #pragma once
 #include "pds_evaluate.h"
 #include "pds_evaluate_hist_args.h"
@@ -45,8 +66,29 @@ PDS_DEV void eval_hist_advance_row(float *hrow, const float *krow, int H, bool d
   }
 }
 
-template <class V_, int HN>
-__global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const EvalHistArgs ka) {
+// The record's observation copy of one network wave: of its 16 rows of the history tile (`rows16`, row stride S1 floats) the
+// first HS floats of every row whose bit of `rows` is set, to the 16 HS contiguous floats at `out`, W floats per lane and pass:
+// W = 1 dword moves, W = 4 16-byte moves (HS a multiple of 4 and `out` 16-byte aligned; S1 is a multiple of 4 and the tile aligned).
+// Piece idx = r Q + c of the 16 Q (Q = HS / W pieces a row): idx += 64 per pass, r and c follow without a division.
+template <int W>
+PDS_DEV void eval_hist_copy_rows(float *out, const float *rows16, int S1, int HS, unsigned rows, int lane) {
+  using T = std::conditional_t<W == 4, float4, float>;
+  const int Q = HS / W;
+  int r = lane / Q, c = lane - r * Q;
+  T *o = reinterpret_cast<T *>(out);
+  for (int idx = lane; idx < 16 * Q; idx += kWave) {
+    if ((rows >> r) & 1u) o[idx] = *reinterpret_cast<const T *>(rows16 + r * S1 + W * c);
+    c += kWave;
+    while (c >= Q) { c -= Q; ++r; }
+  }
+}
+
+// the metrics array of either argument block (NULL: summed, not stored)
+PDS_DEV float *eval_hist_metrics(const EvalHistArgs &kl) { return kl.m.metrics; }
+PDS_DEV float *eval_hist_metrics(const EvalHistRecordArgs &kl) { return kl.r.m.metrics; }
+
+template <class V_, int HN, bool REC = false>
+__global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const EvalHistKernelArgs<REC> ka) {
   using namespace pds_mlpf;
   const EvalArgs &ea = eval_head(ka);
   using V = std::conditional_t<regen_obs_variant<V_>(), StoredOh<V_>, V_>;
@@ -77,6 +119,7 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
   const NetLds wpi = net_lds_wide<HN>(net_pi);
   const long long t = blockIdx.x;  // this block's 64-env tile (N = P x E, E a multiple of 64: every tile is full)
   const int T = ea.T, H = ka.H;
+  [[maybe_unused]] const long long ntiles = a.n / kWave;  // (REC: PDS_ER_STEP and the observation copy size the record by it)
   const int HS = H * HALF;         // floats per history row (= the actors' d_in <= 16 HN)
 
   // ---- prologue: policy p's actor and statistics and the tile's histories into LDS ------------------------------------
@@ -94,6 +137,9 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
     }
   }
   if (tid == 0) { obs_ready = 0; act_ready = 0; }
+  if constexpr (REC) {
+    if (tid == 0) es_lds<1>()[0] = ~0ull;  // the mask of step 0
+  }
   __syncthreads();  // (the only block barrier: from here on the roles meet through the counters)
 
   if (is_env) {
@@ -109,11 +155,18 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
     float *hrow = hist + lane * S1;
     float4 *em = em_lds<1>();
     PDS_EM_INIT(em)
+    [[maybe_unused]] long long rec_col = -1;  // REC: column of lane 0 in the record, wave-uniform; < 0: this tile does not record
+    if constexpr (REC) rec_col = eval_record_column(ea, ka.r.rec_tiles, t);
     for (int s = 0; s < T; ++s) {
       const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<311, true>(ea.s, s));
       PDS_EVAL_STEP_HEAD(&act_ready, act_all)  // the network waves have read the histories and written a(s)
       {
         PDS_EM_STEP(em)
+      }
+      if constexpr (REC) {  // x(s) and a(s) where the env is in its first episode: four lines of the record, nothing carried
+        if (rec_col >= 0) {
+          PDS_ER_STEP(reinterpret_cast<const EvalRecordArgs *>(&el))
+        }
       }
       StepOut so;
       step_once<V, kWave, RM, false>(el.s, o1, rks, parity, nullptr, tile, nullptr, queue, scratch, lane_s, wave_base, ix, active, act, S,
@@ -128,24 +181,42 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       eval_hist_advance_row<HALF>(hrow, tile + lane * TS, H, dn);
       PDS_EVAL_STILL
+      if constexpr (REC) {
+        if (lane == 0) es_lds<1>()[0] = still;  // the mask of step s + 1, in front of the post
+      }
       PDS_EVAL_STEP_TAIL(&obs_ready, el)  // the histories of step s + 1 are in LDS / the env wave has left
     }
     // (pds_evaluate_policies_history leaves the handle "not reset")
-    PDS_EVAL_WAVE_END(EvalHistArgs, 312)
-    if (kl.m.metrics != nullptr) {
-      PDS_EM_STORE(em, kl.m.metrics)
+    PDS_EVAL_WAVE_END(EvalHistKernelArgs<REC>, 312)
+    if (eval_hist_metrics(kl) != nullptr) {
+      PDS_EM_STORE(em, eval_hist_metrics(kl))
     }
     return;
   }
 
   // ================================ network waves: the actor for 16 rows of the tile each ========================
   const int own = wave * 16 + n16;  // this lane's sample row
+  [[maybe_unused]] long long rec_col = -1;  // REC: as in the env wave; here < 0 also where no observations are asked for
+  if constexpr (REC) {
+    if (ka.r.obs_rec != nullptr) rec_col = eval_record_column(ea, ka.r.rec_tiles, t);
+  }
   for (int s = 0;; ++s) {
     const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<313, true>(ea.s, s));
     if (eval_wait_ge(&obs_ready, s) >= kEvalStop) break;  // the histories of step s are in LDS, or the env wave has left
 #if PDS_ROLLOUT_ACTOR_PRIO
     __builtin_amdgcn_s_setprio(PDS_ROLLOUT_ACTOR_PRIO);
 #endif
+    if constexpr (REC) {  // the histories of step s, raw, of this wave's 16 rows whose env was alive in front of step s
+      if (rec_col >= 0) {
+        const EvalRecordArgs &rl = *reinterpret_cast<const EvalRecordArgs *>(&el);
+        const long long nrec = (ntiles / rl.m.e.tiles_per_policy) * rl.rec_tiles * kWave;
+        float *out = rl.obs_rec + ((long long)s * nrec + rec_col + wave * 16) * HS;
+        const unsigned rows = (unsigned)(es_lds<1>()[0] >> (wave * 16)) & 0xFFFFu;
+        // (wave-uniform.  16-byte pieces where rows and record allow them: the same bits in a quarter of the passes)
+        if ((HS & 3) == 0 && (reinterpret_cast<uintptr_t>(rl.obs_rec) & 15u) == 0) eval_hist_copy_rows<4>(out, hist + wave * 16 * S1, S1, HS, rows, lane);
+        else eval_hist_copy_rows<1>(out, hist + wave * 16 * S1, S1, HS, rows, lane);
+      }
+    }
     f32x4 x_own[HN];
     gather_hist<HN>(hist + own * S1, HS, mus, iss, g, x_own);
     PDS_FORWARD16_WIDE(el.shape, mu)
@@ -155,12 +226,15 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
 }
 
 // flags -> variant and input width: hist_task / hist_pid of csrc/pds_rollout_hist.h over this launcher
-struct EvalHistLaunch {
+template <bool REC>
+struct EvalHistLaunchT {
   dim3 grid;  // one block per 64-env tile
   hipStream_t s;
-  const EvalHistArgs &args;
+  const EvalHistKernelArgs<REC> &args;
   template <class RV_, int HN>
-  void run() const { hipLaunchKernelGGL((evaluate_hist_kernel<RV_, HN>), grid, dim3(kRolloutThreads), 0, s, args); }
+  void run() const { hipLaunchKernelGGL((evaluate_hist_kernel<RV_, HN, REC>), grid, dim3(kRolloutThreads), 0, s, args); }
 };
+using EvalHistLaunch = EvalHistLaunchT<false>;
+using EvalHistRecordLaunch = EvalHistLaunchT<true>;  // csrc/pds_evaluate_hist_record_<task>*.hip
 
 }  // namespace pds

@@ -1,6 +1,7 @@
 // pds_evaluate_hist_args.h -- launch interface of the fused evaluation of observation-history policies
 // (csrc/pds_evaluate_hist.h; entry point pds_evaluate_policies_history in csrc/pds_api.hip).
 #pragma once
+#include "../../include/pds_history_record.h"
 #include "pds_evaluate_args.h"
 
 namespace pds {
@@ -13,6 +14,19 @@ struct EvalHistArgs {
   int H;              // observation_history_size: a history row holds H halves of the handle's own row
 };
 static_assert(offsetof(EvalHistArgs, m) == 0, "the history kernel reads the head of its argument block as an EvalMetricsArgs");
+// Arguments of the record form of evaluate_hist_kernel: the Record form's -- flight [T, 4, N_rec, 4], obs_rec [T, N_rec, H half] or
+// NULL, rec_tiles and the column of a lane as EvalRecordArgs (csrc/pds_evaluate_args.h) states them, `metrics` optional -- and
+// behind them the history size.
+struct EvalHistRecordArgs {
+  EvalRecordArgs r;  // FIRST member (the kernel reads the head of its argument block as an EvalRecordArgs, that as an EvalArgs, ...)
+  int H;             // observation_history_size
+};
+static_assert(offsetof(EvalHistRecordArgs, r) == 0, "the history record kernel reads the head of its argument block as an EvalRecordArgs");
+// the two blocks are the kernels' argument segments: size and the place of the last member, as the compiler laid them out
+static_assert(sizeof(EvalHistArgs) == 736 && offsetof(EvalHistArgs, H) == 728, "the kernarg layout of the history evaluation");
+static_assert(sizeof(EvalHistRecordArgs) == 760 && offsetof(EvalHistRecordArgs, H) == 752, "the kernarg layout of the history record");
+// REC -> the argument block of evaluate_hist_kernel<V, HN, REC>
+template <bool REC> using EvalHistKernelArgs = std::conditional_t<REC, EvalHistRecordArgs, EvalHistArgs>;
 
 // (the translation units mirror csrc/pds_rollout_hist_*.hip: the same variants, hn = rollout_hist_tiles(H x half))
 bool launch_evaluate_hist_hover(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka);
@@ -20,5 +34,11 @@ bool launch_evaluate_hist_circle(const LaunchFlags &f, int hn, dim3 grid, hipStr
 bool launch_evaluate_hist_takeoff(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka);
 bool launch_evaluate_hist_hover_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka);
 bool launch_evaluate_hist_circle_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka);
+// ... and the record form's, csrc/pds_evaluate_hist_record_*.hip: the same variants once more
+bool launch_evaluate_hist_record_hover(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
+bool launch_evaluate_hist_record_circle(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
+bool launch_evaluate_hist_record_takeoff(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
+bool launch_evaluate_hist_record_hover_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
+bool launch_evaluate_hist_record_circle_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
 
 }  // namespace pds

@@ -547,8 +547,8 @@ def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats,
                              f"{int(record_limit_bytes)}: record fewer episodes or fewer steps, or raise the limit")
     form = "record" if R is not None else "stats" if obs_stats else "metrics" if metrics else "plain"
     H = int(getattr(env, "observation_history_size", 2))
-    # (no record kernel for histories: they record through the composed path)
-    use_history = bool(history_fused) and H != 2 and R is None
+    # (the history kernel has a plain / metrics form and a record form, no stats form)
+    use_history = bool(history_fused) and H != 2
     use_kernel = False
     if fused is not False and use_history:
         built = not obs_stats and fused_history_evaluation_built(env)
@@ -568,7 +568,7 @@ def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats,
 def _fly_kernel(env, population, obs, P, E, T, form, H, rec):
     """One launch -> (ret, length, cost, raw, slab) on the device, raw / slab None where the form has none; the record is written
     into `rec`'s arrays.  Per form the entry point and what trails d_cost in its argument list; the history kernel leads with H
-    and takes d_metrics or NULL."""
+    and takes d_metrics or NULL, its record form (pds_evaluate_policies_history_record) what the record form takes."""
     dev, n = env.device, env.num_envs
     ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
     raw = torch.zeros(n, len(METRIC_NAMES), device=dev) if form != "plain" else None
@@ -579,8 +579,9 @@ def _fly_kernel(env, population, obs, P, E, T, form, H, rec):
                    "stats": ("pds_evaluate_policies_stats", (raw, slab)),
                    "record": ("pds_evaluate_policies_record", (raw, R, flight, obs_rec))}[form]
     lead = ()
-    if H is not None:  # (plain or metrics; [N, H * half]: the histories env.reset() returns)
-        obs, name, lead, trail = obs.contiguous(), "pds_evaluate_policies_history", (H,), (raw,)
+    if H is not None:  # (plain, metrics or record; [N, H * half]: the histories env.reset() returns)
+        obs, lead = obs.contiguous(), (H,)
+        name, trail = ("pds_evaluate_policies_history_record", trail) if form == "record" else ("pds_evaluate_policies_history", (raw,))
     native.call(name, env._handle, *lead, P, E, population.mlp(0), population.theta, population.mean, population.std,
                 population.eps, T, obs, ret, length, cost, *trail, on=dev, handle=env._handle)
     return ret, length, cost, raw, slab
@@ -683,8 +684,9 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     record_observations=False -- the raw observation o(s) it acted on, for every step s < length; rows past an episode's end
     are zero.  Not recorded: the terminal state x(L) and the terminal observation (a finished env is reset in place inside the
     step).  The kernel path is pds_evaluate_policies_record (it also produces the metrics: metrics=False drops them); the
-    composed path -- every env without a fused kernel, observation histories included, where o(s) is the history the actor read
-    -- reads pos, vel, rpy and omega in front of every step: the same bits.  The record takes max_steps x P x R x (64 + 4 D)
+    composed path -- every env without a fused kernel, and observation histories without history_fused=True; o(s) of a history
+    env is the history the actor read, H x half columns on either path -- reads pos, vel, rpy and omega in front of every step:
+    the same bits.  The record takes max_steps x P x R x (64 + 4 D)
     bytes on the device and again on the host; above record_limit_bytes the call raises ValueError before it allocates.
 
     fused=True: one launch (pds_evaluate_policies, csrc/pds_evaluate.h); NotImplementedError where no kernel is built --
@@ -693,8 +695,8 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     bits.  fused="auto": the kernel where it is built, the composed path elsewhere.
     history_fused=True (it changes nothing at observation_history_size == 2): an env with another history size H flies in one
     launch too (pds_evaluate_policies_history, csrc/pds_evaluate_hist.h: the same bits as its composed path, metrics=True served
-    from the same launch) where `fused_history_evaluation_built(env)` holds; where it does not, and with obs_stats=True (no stats
-    form for histories), fused=True raises NotImplementedError with the env untouched and "auto" runs the composed path.
+    from the same launch; with record=R pds_evaluate_policies_history_record, the record form of the same kernel) where
+    `fused_history_evaluation_built(env)` holds; where it does not, and with obs_stats=True (no stats form for histories), fused=True raises NotImplementedError with the env untouched and "auto" runs the composed path.
     The env is reset first and not afterwards: after the fused path it refuses to step until the next reset() of every env
     (a masked reset is refused as well).  `population` is not modified: the call works on device copies of its tensors.
     max_steps: the number of steps flown, by default the env's max_episode_steps (the TimeLimit ends every episode by then)."""

@@ -148,6 +148,11 @@ SIGNATURES = {
     "pds_ddpg_explore": (_i32, [_vp, _vp, _i64, _f32, _u64, _u64, _u64, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
+# ... and of include/pds_history_record.h, the entry point that stands beside that ABI (tests/test_evaluate_history_record_cpu.py
+# compares the two); `load` binds both tables, `call` enters either
+HISTORY_RECORD_SIGNATURES = {
+    "pds_evaluate_policies_history_record": (_i32, [_vp, _i32] + _eval[1:] + [_vp, _i64, _vp, _vp, _vp]),
+}
 
 _lib = None
 
@@ -168,7 +173,7 @@ def load():
     # an OLDER build given through PDS_LIB for a same-box A/B (profiles/tools/ab_lib.sh) may lack the newer entry points: those
     # are skipped; the shipped library must have every name (AttributeError here, and tests/test_host_cpu.py)
     older = bool(os.environ.get("PDS_LIB"))
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()):
         if older and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

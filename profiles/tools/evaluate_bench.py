@@ -15,6 +15,13 @@ history_fused=True) against fused=False on envs with observation_history_size = 
 of --reps alternating synchronised repeats.
 
   python profiles/tools/evaluate_bench.py --history 4 8 > profiles/evaluate_history_timing.txt
+
+--history H [H] --record R: the record form of the history kernel (pds_evaluate_policies_history_record) on the same envs, actors
+and shapes -- evaluate_population(fused=True, history_fused=True, metrics=True, record=R) with and without the observations against
+fused=False with the same record (the composed record) and against the history kernel's metrics launch, the same alternating
+repeats; then the launches alone, on buffers made beforehand.  Exit status 1 where the fused record is slower than the composed.
+
+  python profiles/tools/evaluate_bench.py --history 4 8 --record 64 > profiles/evaluate_history_record_timing.txt
 """
 import argparse
 import os
@@ -87,6 +94,101 @@ def history_main(args):
             env_f.close(); env_c.close()
 
 
+def timed_record(env, pop, fused, kw):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = evaluate_population(env, pop, fused=fused, history_fused=bool(fused), metrics=True, **kw)  # ends in the copies to the host
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def history_launch_ms(env, pop, H, P, E, T, R, bufs, form):
+    """device time of ONE launch of the history kernel on buffers made beforehand: form "metrics", "record" (no observations),
+    "record+obs", or "record+obs dword" -- the observations into a buffer 4 bytes off a 16-byte boundary, where the kernel copies
+    them with dword stores whatever the history size"""
+    from phoenix_drone_simulation_amd import native
+    obs, _ = env.reset()
+    obs = obs.contiguous()
+    ret, length, cost, raw, flight, obs_rec = bufs
+    where = {"record+obs": obs_rec[4:], "record+obs dword": obs_rec[1:-3], "record": None}
+    trail = (raw,) if form == "metrics" else (raw, R, flight, where[form])
+    name = "pds_evaluate_policies_history" if form == "metrics" else "pds_evaluate_policies_history_record"
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    start.record()
+    native.call(name, env._handle, H, P, E, pop.mlp(0), pop.theta, pop.mean, pop.std, pop.eps, T, obs, ret, length, cost, *trail,
+                on=env.device, handle=env._handle)
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end)
+
+
+def history_record_main(args):
+    """--history H [H] --record R: the record form of the history kernel (pds_evaluate_policies_history_record), with and without
+    the observations, against the composed record and against the history kernel's metrics launch; the launches alone as well"""
+    R = args.record
+    print(f"# evaluate_population(history_fused=True, metrics=True, record={R}) on envs with an observation history, "
+          f"{torch.cuda.get_device_name(0)}; seeded random tanh actors (64, 64)")
+    print(f"# host clock around a call that ends in a device synchronise; one warm-up per path and shape, then {args.reps} repeats of each "
+          "path, alternating; ms: median [min .. max]")
+    ok = True
+    for j, (label, env_id, kw) in enumerate(HISTORY_CASES):
+        H = args.history[min(j, len(args.history) - 1)]
+        for P, E in HISTORY_SHAPES:
+            envs = [pds.make(env_id, num_envs=P * E, seed=1, observation_history_size=H, **kw) for _ in range(4)]
+            pop = random_population(envs[0].obs_dim, P).to("cuda:0")
+            big = dict(record=R, record_limit_bytes=1 << 32)  # (64 policies x 64 episodes x 500 steps x 160 inputs: 1.4 GB)
+            paths = (("fused record+obs", envs[0], True, big), ("fused record", envs[1], True, dict(big, record_observations=False)),
+                     ("fused metrics", envs[2], True, {}), ("composed record+obs", envs[3], False, big))
+            first = {name: timed_record(env, pop, f, k)[1] for name, env, f, k in paths}  # warm-up; same seed, first call: comparable
+            a, b, m = first["fused record+obs"], first["composed record+obs"], first["fused metrics"]
+            same = all(torch.equal(x, y) for x, y in zip(list(a[:3]) + [a[3].raw, a[4].state, a[4].action, a[4].observation],
+                                                          list(b[:3]) + [b[3].raw, b[4].state, b[4].action, b[4].observation])) and \
+                all(torch.equal(x, y) for x, y in zip(list(a[:3]) + [a[3].raw], list(m[:3]) + [m[3].raw]))
+            t = {name: [] for name, *_ in paths}
+            for _ in range(args.reps):
+                for name, env, f, k in paths:
+                    t[name].append(timed_record(env, pop, f, k)[0])
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            spread = (max(t["fused metrics"]) - min(t["fused metrics"])) / med["fused metrics"]
+            passed = med["fused record+obs"] <= med["composed record+obs"]
+            ok &= passed
+            print(f"{label} H = {H} ({envs[0].obs_dim} inputs) {P:3d} x {E:5d} ({P * E // 64} tiles, {P * R} recorded envs) mean length "
+                  f"{float(m[1].mean()):6.1f}  same bits {same}")
+            for name in t:
+                print(f"    {name:20s} {1e3 * med[name]:10.2f} [{1e3 * min(t[name]):.2f} .. {1e3 * max(t[name]):.2f}] ms")
+            print(f"    record+obs / metrics = {med['fused record+obs'] / med['fused metrics']:.3f}, record / metrics = "
+                  f"{med['fused record'] / med['fused metrics']:.3f}, the metrics path's own (max - min) / median = {spread:.3f}; "
+                  f"composed / fused, both recording = {med['composed record+obs'] / med['fused record+obs']:.1f}x; {'PASS' if passed else 'FAIL'}")
+            n, T, dev = P * E, envs[0]._max_episode_steps, envs[0].device
+            bufs = (torch.zeros(n, device=dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev), torch.zeros(n, 8, device=dev),
+                    torch.zeros(T, 4, P * R, 4, device=dev), torch.zeros(T * P * R * envs[0].obs_dim + 4, device=dev))
+            assert bufs[5].data_ptr() % 16 == 0
+            del first, a, b, m
+            forms = ("record+obs", "record+obs dword", "record", "metrics")
+            k = {f: [] for f in forms}
+            for rep_ in range(args.reps + 1):  # (the first round warms up)
+                for f in forms:
+                    ms = history_launch_ms(envs[2], pop, H, P, E, T, R, bufs, f)
+                    if rep_:
+                        k[f].append(ms)
+            kmed = {f: float(np.median(v)) for f, v in k.items()}
+            kspread = (max(k["metrics"]) - min(k["metrics"])) / kmed["metrics"]
+            k_obs, k_state = kmed["record+obs"] / kmed["metrics"], kmed["record"] / kmed["metrics"]
+            print("    the launch alone: " + ", ".join(f"{f} {kmed[f]:.3f} [{min(k[f]):.3f} .. {max(k[f]):.3f}]" for f in forms) +
+                  f" ms; record+obs / metrics = {k_obs:.3f}, record+obs dword / metrics = {kmed['record+obs dword'] / kmed['metrics']:.3f}, "
+                  f"record / metrics = {k_state:.3f}, the metrics launch's own (max - min) / median = {kspread:.3f}")
+            if k_obs - 1.0 > kspread:
+                which = "the state stores (the env wave's) already exceed it" if k_state - 1.0 > kspread else \
+                    "the observation copy (the network waves') carries it: without it the ratio is inside the spread"
+                print(f"    the launch's record+obs / metrics exceeds the spread: {which}")
+            else:
+                print("    the launch's record+obs / metrics is inside the spread")
+            for env in envs:
+                env.close()
+    sys.exit(0 if ok else 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=1.0, help="least timed duration per path and shape")
@@ -94,7 +196,11 @@ def main():
     ap.add_argument("--history", type=int, nargs="+", default=None, metavar="H",
                     help="time the history form: observation_history_size on Hover at its defaults [and on lean Circle]")
     ap.add_argument("--reps", type=int, default=5, help="--history: alternating repeats per path and shape")
+    ap.add_argument("--record", type=int, default=None, metavar="R",
+                    help="--history: time the record form (pds_evaluate_policies_history_record, R episodes per policy) instead")
     args = ap.parse_args()
+    if args.history and args.record:
+        return history_record_main(args)
     if args.history:
         return history_main(args)
     print(f"# evaluate_population on DroneHoverSimpleEnv-v0 (defaults), {torch.cuda.get_device_name(0)}; host clock around a call "

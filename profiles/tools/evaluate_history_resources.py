@@ -14,7 +14,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import evaluate_stats_resources as esr  # noqa: E402
 import kernel_resources as kr  # noqa: E402
 
-NAME = re.compile(r"(evaluate_hist_kernel|rollout_hist_kernel)<pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>, (\d+)>")
+# (evaluate_hist_kernel<Variant, HN, REC>: the launch of this table is REC = false; the record form, REC = true, has a table of its
+# own -- profiles/tools/evaluate_history_record_resources.py)
+NAME = re.compile(r"(evaluate_hist_kernel|rollout_hist_kernel)<pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>, (\d+)(?:, false)?>")
 
 
 def rows(lib=None):
