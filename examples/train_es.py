@@ -44,7 +44,10 @@ def main():
     ap.add_argument("--history", type=int, default=2, help="observation_history_size of the env (the reference's experiment 04: 1, 2, 4, 6, 8)")
     ap.add_argument("--history-fused", action="store_true",
                     help="with --history other than 2: evaluate every generation in one launch (pds_evaluate_policies_history) where "
-                         "it is built, instead of the composed path; --obs-stats online stays composed there")
+                         "it is built, instead of the composed path; --obs-stats online stays composed there without --history-stats-fused")
+    ap.add_argument("--history-stats-fused", action="store_true",
+                    help="with --history-fused and --obs-stats online: the generation's launch also sums the observations "
+                         "(pds_evaluate_policies_history_stats) where it is built, instead of the composed path")
     args = ap.parse_args()
     weights = {}
     for item in args.penalise:
@@ -57,7 +60,8 @@ def main():
                    observation_history_size=args.history)  # otherwise the reference's default config
     trainer = ESTrainer(env, args.population, sigma=args.sigma, lr=args.lr, seed=args.seed,
                         obs_stats=None if args.obs_stats == "none" else args.obs_stats, eval_every=args.eval_every, fitness=fitness,
-                        shaping=args.shaping, top_b=args.top_b, history_fused=args.history_fused)
+                        shaping=args.shaping, top_b=args.top_b, history_fused=args.history_fused,
+                        history_stats_fused=args.history_stats_fused)
     t0 = time.time()
     steps = 0.0
     for g in range(args.generations):

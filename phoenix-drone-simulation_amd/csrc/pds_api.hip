@@ -1257,13 +1257,21 @@ extern "C" int pds_evaluate_history_supported(const pds_handle *h, int history) 
   if (!h) return PDS_EINVAL;
   return h->cfg.auto_reset && rollout_hist_supported(h->cfg.task, h->flags) && history >= 1 && (long long)history * (h->obs_dim / 2) <= 192 ? 1 : 0;
 }
+// ... and whether pds_evaluate_policies_history_stats has: the same question, and the stats form built for the input width
+extern "C" int pds_evaluate_history_stats_supported(const pds_handle *h, int history) {
+  const int rc = pds_evaluate_history_supported(h, history);
+  if (rc != 1) return rc;
+  return eval_hist_stats_width_built(rollout_hist_tiles(history * (h->obs_dim / 2))) ? 1 : 0;
+}
 // P policies x E episodes in one launch, the actors reading the last `history` halves of the handle's row.  The checks and the
-// handle's state afterwards are pds_evaluate_policies'; d_metrics is optional.  ONE body for the two forms of the kernel (REC,
-// csrc/pds_evaluate_hist.h): the record form's checks come first, as in evaluate_policies_call, and `x` holds what it adds.
-template <bool REC>
+// handle's state afterwards are pds_evaluate_policies'; d_metrics is optional.  ONE body for the three forms of the kernel
+// (EvalHistForm, csrc/pds_evaluate_hist.h): the record form's checks come first, as in evaluate_policies_call, the stats form's
+// behind those of the plain call, and `x` holds what a form adds.
+template <EvalHistForm F>
 static int evaluate_history_call(pds_handle *h, const char *fn, int history, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
                                  const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
                                  const float *d_obs0, float *d_ret, float *d_len, float *d_cost, const EvalFormCall &x, void *stream) {
+  constexpr bool REC = F == EvalHistForm::Record, STATS = F == EvalHistForm::Stats;
   float *const d_metrics = x.d_metrics;
   if (!h) return PDS_EINVAL;
   if constexpr (REC) {  // (decided before the handle is looked at)
@@ -1279,13 +1287,23 @@ static int evaluate_history_call(pds_handle *h, const char *fn, int history, int
   if (!rollout_hist_supported(h->cfg.task, h->flags))
     return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: what pds_rollout_history is built for) -- "
                                      "pds_mlp_forward + pds_step + pds_history_advance give the same bits", fn);
+  const int hn = rollout_hist_tiles((int)HS);
+  if constexpr (STATS) {
+    if (!x.d_obs_sums || (((uintptr_t)x.d_obs_sums) & 15u)) return fail(h, PDS_EINVAL, "%s: d_obs_sums must be given and 16-byte aligned", fn);
+    if (!eval_hist_stats_width_built(hn))
+      return fail(h, PDS_EUNSUPPORTED, "%s: the stats form is not built for %lld network inputs (%d input tiles) -- "
+                                       "pds_mlp_forward + pds_step + pds_history_advance give the same bits", fn, HS, hn);
+  }
   DeviceGuard guard(h->cfg.device);
   PDS_HIP(h, guard.err);
-  EvalHistKernelArgs<REC> ka;
+  EvalHistKernelArgs<F> ka;
   memset(&ka, 0, sizeof(ka));
   if constexpr (REC) {
     ka.r.m.metrics = d_metrics;
     fill_record_args(ka.r, x);
+  } else if constexpr (STATS) {
+    ka.st.m.metrics = d_metrics;
+    ka.st.obs_sums = x.d_obs_sums;
   } else {
     ka.m.metrics = d_metrics;
   }
@@ -1293,9 +1311,16 @@ static int evaluate_history_call(pds_handle *h, const char *fn, int history, int
   if (const int rc = fill_evaluate_args(h, fn, eval_head(ka), episodes_per_policy, shape, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret,
                                         d_len, d_cost, stream))
     return rc;
-  const int hn = rollout_hist_tiles((int)HS);
   const int rc = launch_rollout(h, fn, max_steps, stream, [&](dim3 grid, hipStream_t s) {
-    if constexpr (REC) {
+    if constexpr (STATS) {
+      if (h->flags.ctrl != 0) {  // (TakeOff fixes control_mode PWM)
+        if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_stats_hover_pid(h->flags, hn, grid, s, ka);
+        return h->cfg.task == PDS_TASK_CIRCLE && launch_evaluate_hist_stats_circle_pid(h->flags, hn, grid, s, ka);
+      }
+      if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_stats_hover(h->flags, hn, grid, s, ka);
+      if (h->cfg.task == PDS_TASK_CIRCLE) return launch_evaluate_hist_stats_circle(h->flags, hn, grid, s, ka);
+      return launch_evaluate_hist_stats_takeoff(h->flags, hn, grid, s, ka);
+    } else if constexpr (REC) {
       if (h->flags.ctrl != 0) {  // (TakeOff fixes control_mode PWM)
         if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_record_hover_pid(h->flags, hn, grid, s, ka);
         return h->cfg.task == PDS_TASK_CIRCLE && launch_evaluate_hist_record_circle_pid(h->flags, hn, grid, s, ka);
@@ -1320,7 +1345,7 @@ extern "C" int pds_evaluate_policies_history(pds_handle *h, int history, int64_t
                                              const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
                                              const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
                                              void *stream) {
-  return evaluate_history_call<false>(h, "pds_evaluate_policies_history", history, P, episodes_per_policy, shape, d_params, d_mean,
+  return evaluate_history_call<EvalHistForm::Metrics>(h, "pds_evaluate_policies_history", history, P, episodes_per_policy, shape, d_params, d_mean,
                                       d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost, {d_metrics}, stream);
 }
 // the same launch that also records the flights of the first record_per_policy envs of every policy: d_flight [T, 4, N_rec, 4] and,
@@ -1330,9 +1355,19 @@ extern "C" int pds_evaluate_policies_history_record(pds_handle *h, int history, 
                                                     const float *d_std, float eps, int max_steps, const float *d_obs0, float *d_ret,
                                                     float *d_len, float *d_cost, float *d_metrics, int64_t record_per_policy,
                                                     float *d_flight, float *d_obs_rec, void *stream) {
-  return evaluate_history_call<true>(h, "pds_evaluate_policies_history_record", history, P, episodes_per_policy, shape, d_params,
+  return evaluate_history_call<EvalHistForm::Record>(h, "pds_evaluate_policies_history_record", history, P, episodes_per_policy, shape, d_params,
                                      d_mean, d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost,
                                      {d_metrics, nullptr, record_per_policy, d_flight, d_obs_rec}, stream);
+}
+// the same launch that also sums the histories the policies acted on: d_obs_sums [tiles, 4, 2, 16 hn] (include/pds_history_stats.h;
+// csrc/pds_evaluate_hist.h, the observation sums)
+extern "C" int pds_evaluate_policies_history_stats(pds_handle *h, int history, int64_t P, int64_t episodes_per_policy,
+                                                   const pds_mlp *shape, const float *d_params, const float *d_mean,
+                                                   const float *d_std, float eps, int max_steps, const float *d_obs0, float *d_ret,
+                                                   float *d_len, float *d_cost, float *d_metrics, float *d_obs_sums, void *stream) {
+  return evaluate_history_call<EvalHistForm::Stats>(h, "pds_evaluate_policies_history_stats", history, P, episodes_per_policy, shape,
+                                                    d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost,
+                                                    {d_metrics, d_obs_sums}, stream);
 }
 
 // ---- the fused off-policy collection: csrc/pds_collect.h (OffPolicyTrainer.step_env + the bookkeeping of learn_one_epoch) ----

@@ -12,10 +12,12 @@
 //     eight PDS_EM_* flight metrics through em_lds, and the two counters with the kEvalStop protocol.
 // Not here: action noise, log-probability and action buffer; an obs_buf store, the `fin` image and the fin_rows list (a finished
 // env's history restarts from its reset row, and nobody reads the history it had -- the newest half the per-step path takes from
-// final_obs lands in a row the restart overwrites whole); the stats form (it stays on the composed path for history envs).
-// The kernel has two forms, the template parameter REC: false is the launch above (pds_evaluate_policies_history,
-// csrc/pds_evaluate_hist_<task>*.hip), true also records the flights (pds_evaluate_policies_history_record,
-// csrc/pds_evaluate_hist_record_<task>*.hip).  Every statement the record adds is behind `if constexpr (REC)`.
+// final_obs lands in a row the restart overwrites whole).
+// The kernel has three forms, EvalHistForm F of csrc/pds_evaluate_hist_args.h, one entry point and one set of translation units each:
+//   Metrics (pds_evaluate_policies_history,        csrc/pds_evaluate_hist_<task>*.hip):         the launch above
+//   Record  (pds_evaluate_policies_history_record, csrc/pds_evaluate_hist_record_<task>*.hip):  + the recorded flights
+//   Stats   (pds_evaluate_policies_history_stats,  csrc/pds_evaluate_hist_stats_<task>*.hip):   + the observation sums
+// Every statement a form adds is behind `if constexpr (REC)` / `if constexpr (STATS)`.  No form records and sums.
 //
 // Hand-over: the two counters and the kEvalStop protocol of evaluate_kernel, stated and proved at the head of csrc/pds_evaluate.h;
 // the env wave's side of it is that file's PDS_EVAL_STEP_HEAD / PDS_EVAL_STEP_TAIL, the same statements in both kernels.  What
@@ -23,8 +25,8 @@
 // -- between its act_ready wait and its obs_ready post -- are the history tile, which the network waves read between their
 // obs_ready wait and their act_ready post, and the kernel's own [o(k), o(k + 1)] row tile, which they never touch; the action
 // slots go the other way round, and em_lds belongs to the env wave.  "o(s + 1) is in the tile" reads "the histories of step
-// s + 1 are in LDS".  (REC: the alive mask of a step is written and read in the history tile's windows, by the tile's writer and
-// readers, as that file says for its Stats and Record forms: no new counter, no new wait, the argument above word for word.)
+// s + 1 are in LDS".  (REC and STATS: the alive mask of a step is written and read in the history tile's windows, by the tile's writer
+// and readers, as that file says for its Stats and Record forms: no new counter, no new wait, the argument above word for word.)
 //
 // METRICS: the env wave always sums the eight PDS_EM_* values, exactly as evaluate_kernel<.., EvalForm::Metrics> does -- seven words
 // per lane in LDS, read and written back behind the act_ready wait, one rounded instruction per product and sum -- and stores the
@@ -46,6 +48,27 @@
 //   Nothing else is written: the rows s >= length of an env and every row of a tile that does not record keep what the caller put
 //   there; the terminal state and the terminal observation are not recorded, as at H = 2.
 //   (profiles/evaluate_history_record_kernel_resources.txt: the compiler's figures of the record's code objects.)
+//
+// THE OBSERVATION SUMS (STATS): what evaluate_kernel<.., EvalForm::Stats> does (the head of csrc/pds_evaluate.h), with the history
+// tile in place of the observation tile.  gather_hist gives lane (n16, g) of wave w the features 16 kt + 4 g + q (kt < HN) of row
+// own = 16 w + n16: every (row, feature) has one owner lane, which carries S1 and S2 of its 4 HN features through the loop -- 8 HN
+// accumulators, 32 / 48 / 64 / 96 floats at HN = 4 / 6 / 8 / 12.  Per step, where row `own` is alive in front of step s (its bit of
+// es_lds<1>(), the record's mask: all ones from the prologue in front of the block barrier, then `still` from the env wave's lane 0
+// between PDS_EVAL_STILL and PDS_EVAL_STEP_TAIL), d = hist[own][k] - mus[k] (k >= H half: d = mus[k] - mus[k] = 0; without
+// statistics mus is 0 and x - 0 = x on the bits), S1 += d, S2 += d d: __fsub_rn, __fmul_rn, __fadd_rn, one rounded instruction
+// each, steps in order.  A row that is not alive is skipped by a branch, not by adding a selected 0: x + 0 = x on the bits for
+// every x but -0, and no sum is -0 (each starts at +0, and +0 + -0 = +0) -- the composed path's where(alive, d, 0) gives the same.
+//   THE WINDOW: the sums read the history tile and the mask between the wave's obs_ready wait of step s and its act_ready post,
+//   where gather_hist reads the tile; the env wave rewrites both only behind its act_ready wait of step s, i.e. behind this
+//   wave's post.  They stand BEHIND the actor pass and the action store, directly in front of the post: there the 4 HN inputs and
+//   the W1 pieces of the pass are dead, and the accumulators are all the wave carries.  In front of the pass (where the H = 2
+//   kernel has them) the kernels of HN = 8 and 12 spilled (profiles/evaluate_history_stats_kernel_resources.txt).
+//   HN = 12: 96 accumulators beside the pass are 2 registers more than the 256 a wave of this block may hold, so the last S2 quad
+//   of every lane lives in LDS (es_park_lds, 4 KB; the lane's own slot: read and written back around its four sums, no hand-over).
+//   On leaving the loop (the stop it saw in obs_ready) a wave sums its 16 rows per feature in es_tree_add's fixed tree -- rows j
+//   and j + 8, then + 4, + 2, + 1 -- and its n16 == 0 lanes store the partial with 16-byte stores to
+//   obs_sums[tile][wave][S1 / S2][W], W = 16 HN = 64 / 96 / 128 / 192: every column is written, those from H half on are zero.
+//   No atomics; the four waves of a tile are summed by the host.  The metrics are summed and stored as in the other forms.
 #pragma once
 #include "pds_evaluate.h"
 #include "pds_evaluate_hist_args.h"
@@ -83,13 +106,24 @@ PDS_DEV void eval_hist_copy_rows(float *out, const float *rows16, int S1, int HS
   }
 }
 
-// the metrics array of either argument block (NULL: summed, not stored)
+// The stats form at HN = 12 keeps the last S2 quad of every network lane here, not in a register: 96 accumulators beside the actor
+// pass's 48 inputs and its W1 pieces are two registers more than the 256 a wave of this block may hold, and the history tile's read
+// window has the time for one more b128 read and write a step.  4 KB, a lane's own slot: nobody else reads or writes it.
+PDS_DEV float4 *es_park_lds() {
+  __shared__ __attribute__((aligned(16))) float4 park[kRolloutMlpWaves * kWave];
+  return park;
+}
+
+// the metrics array of every argument block (NULL: summed, not stored)
 PDS_DEV float *eval_hist_metrics(const EvalHistArgs &kl) { return kl.m.metrics; }
 PDS_DEV float *eval_hist_metrics(const EvalHistRecordArgs &kl) { return kl.r.m.metrics; }
+PDS_DEV float *eval_hist_metrics(const EvalHistStatsArgs &kl) { return kl.st.m.metrics; }
 
-template <class V_, int HN, bool REC = false>
-__global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const EvalHistKernelArgs<REC> ka) {
+template <class V_, int HN, EvalHistForm F = EvalHistForm::Metrics>
+__global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const EvalHistKernelArgs<F> ka) {
   using namespace pds_mlpf;
+  constexpr bool REC = F == EvalHistForm::Record, STATS = F == EvalHistForm::Stats;
+  constexpr bool PARK = STATS && HN == 12;  // (es_park_lds)
   const EvalArgs &ea = eval_head(ka);
   using V = std::conditional_t<regen_obs_variant<V_>(), StoredOh<V_>, V_>;
   constexpr int D = V::D;                    // the kernel's own row: two halves
@@ -137,7 +171,7 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
     }
   }
   if (tid == 0) { obs_ready = 0; act_ready = 0; }
-  if constexpr (REC) {
+  if constexpr (REC || STATS) {
     if (tid == 0) es_lds<1>()[0] = ~0ull;  // the mask of step 0
   }
   __syncthreads();  // (the only block barrier: from here on the roles meet through the counters)
@@ -181,13 +215,13 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       eval_hist_advance_row<HALF>(hrow, tile + lane * TS, H, dn);
       PDS_EVAL_STILL
-      if constexpr (REC) {
+      if constexpr (REC || STATS) {
         if (lane == 0) es_lds<1>()[0] = still;  // the mask of step s + 1, in front of the post
       }
       PDS_EVAL_STEP_TAIL(&obs_ready, el)  // the histories of step s + 1 are in LDS / the env wave has left
     }
     // (pds_evaluate_policies_history leaves the handle "not reset")
-    PDS_EVAL_WAVE_END(EvalHistKernelArgs<REC>, 312)
+    PDS_EVAL_WAVE_END(EvalHistKernelArgs<F>, 312)
     if (eval_hist_metrics(kl) != nullptr) {
       PDS_EM_STORE(em, eval_hist_metrics(kl))
     }
@@ -199,6 +233,15 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
   [[maybe_unused]] long long rec_col = -1;  // REC: as in the env wave; here < 0 also where no observations are asked for
   if constexpr (REC) {
     if (ka.r.obs_rec != nullptr) rec_col = eval_record_column(ea, ka.r.rec_tiles, t);
+  }
+  [[maybe_unused]] EsSums<HN, STATS> es;  // STATS: the sums of this lane's 4 HN features of row `own` (nothing otherwise)
+  if constexpr (STATS) {
+#pragma unroll
+    for (int kt = 0; kt < HN; ++kt) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { es.s1[kt][q] = 0.f; es.s2[kt][q] = 0.f; }
+    }
+    if constexpr (PARK) es_park_lds()[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
   for (int s = 0;; ++s) {
     const EvalArgs &el = *reinterpret_cast<const EvalArgs *>(&reload_args<313, true>(ea.s, s));
@@ -221,20 +264,61 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
     gather_hist<HN>(hist + own * S1, HS, mus, iss, g, x_own);
     PDS_FORWARD16_WIDE(el.shape, mu)
     if (g == 0) act_all[own] = make_float4(mu[0], mu[1], mu[2], mu[3]);  // lane n16 owns sample `own`: the actor's four outputs
+    if constexpr (STATS) {  // the history of row `own` at step s, where its env was alive in front of step s (a row that is not adds nothing: x + 0 = x on the bits, no sum is -0)
+      if (((es_lds<1>()[0] >> own) & 1ull) != 0ull) {
+#pragma unroll
+        for (int kt = 0; kt < HN; ++kt) {
+          const int k0 = kt * 16 + 4 * g;  // (gather_hist's features and its reads; k >= HS: d = 0)
+          const f32x4 v = lds4(hist + own * S1 + k0), m = lds4(mus + k0);
+          if constexpr (PARK) {
+            if (kt == HN - 1) { const float4 p = es_park_lds()[tid]; es.s2[kt][0] = p.x; es.s2[kt][1] = p.y; es.s2[kt][2] = p.z; es.s2[kt][3] = p.w; }
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float d = __fsub_rn((k0 + q < HS) ? v[q] : m[q], m[q]);
+            es.s1[kt][q] = __fadd_rn(es.s1[kt][q], d);
+            es.s2[kt][q] = __fadd_rn(es.s2[kt][q], __fmul_rn(d, d));
+          }
+          if constexpr (PARK) {
+            if (kt == HN - 1) es_park_lds()[tid] = make_float4(es.s2[kt][0], es.s2[kt][1], es.s2[kt][2], es.s2[kt][3]);
+          }
+        }
+      }
+    }
     rollout_post(&act_ready, lane);  // this wave is done with the histories of step s
+  }
+  if constexpr (STATS) {  // this wave's 16 rows per feature, then [t][wave][S1 / S2][16 HN]: lane (0, g) stores the features 16 kt + 4 g ..
+    float4 *out = reinterpret_cast<float4 *>(ka.st.obs_sums) + (t * kRolloutMlpWaves + wave) * (2 * 4 * HN);
+    if constexpr (PARK) { const float4 p = es_park_lds()[tid]; es.s2[HN - 1][0] = p.x; es.s2[HN - 1][1] = p.y; es.s2[HN - 1][2] = p.z; es.s2[HN - 1][3] = p.w; }
+#pragma unroll
+    for (int kt = 0; kt < HN; ++kt) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int bit = 8; bit >= 1; bit >>= 1) {  // rows j and j + 8, then + 4, + 2, + 1
+          es.s1[kt][q] = es_tree_add(es.s1[kt][q], bit);
+          es.s2[kt][q] = es_tree_add(es.s2[kt][q], bit);
+        }
+      }
+      if (n16 == 0) {  // (every kt < HN: the whole slab is written, the features in H half .. 16 HN - 1 summed d = 0)
+        out[kt * 4 + g] = make_float4(es.s1[kt][0], es.s1[kt][1], es.s1[kt][2], es.s1[kt][3]);
+        out[4 * HN + kt * 4 + g] = make_float4(es.s2[kt][0], es.s2[kt][1], es.s2[kt][2], es.s2[kt][3]);
+      }
+    }
   }
 }
 
 // flags -> variant and input width: hist_task / hist_pid of csrc/pds_rollout_hist.h over this launcher
-template <bool REC>
+template <EvalHistForm F>
 struct EvalHistLaunchT {
   dim3 grid;  // one block per 64-env tile
   hipStream_t s;
-  const EvalHistKernelArgs<REC> &args;
+  const EvalHistKernelArgs<F> &args;
   template <class RV_, int HN>
-  void run() const { hipLaunchKernelGGL((evaluate_hist_kernel<RV_, HN, REC>), grid, dim3(kRolloutThreads), 0, s, args); }
+  void run() const { hipLaunchKernelGGL((evaluate_hist_kernel<RV_, HN, F>), grid, dim3(kRolloutThreads), 0, s, args); }
 };
-using EvalHistLaunch = EvalHistLaunchT<false>;
-using EvalHistRecordLaunch = EvalHistLaunchT<true>;  // csrc/pds_evaluate_hist_record_<task>*.hip
+using EvalHistLaunch = EvalHistLaunchT<EvalHistForm::Metrics>;
+using EvalHistRecordLaunch = EvalHistLaunchT<EvalHistForm::Record>;  // csrc/pds_evaluate_hist_record_<task>*.hip
+using EvalHistStatsLaunch = EvalHistLaunchT<EvalHistForm::Stats>;    // csrc/pds_evaluate_hist_stats_<task>*.hip
 
 }  // namespace pds

@@ -2,6 +2,7 @@
 // (csrc/pds_evaluate_hist.h; entry point pds_evaluate_policies_history in csrc/pds_api.hip).
 #pragma once
 #include "../../include/pds_history_record.h"
+#include "../../include/pds_history_stats.h"
 #include "pds_evaluate_args.h"
 
 namespace pds {
@@ -22,11 +23,31 @@ struct EvalHistRecordArgs {
   int H;             // observation_history_size
 };
 static_assert(offsetof(EvalHistRecordArgs, r) == 0, "the history record kernel reads the head of its argument block as an EvalRecordArgs");
-// the two blocks are the kernels' argument segments: size and the place of the last member, as the compiler laid them out
+// Arguments of the stats form of evaluate_hist_kernel: the Stats form's -- obs_sums [tiles, 4, 2, W] with W = 16 x rollout_hist_tiles(H half)
+// features a row (include/pds_history_stats.h), `metrics` optional -- and behind them the history size.
+struct EvalHistStatsArgs {
+  EvalStatsArgs st;  // FIRST member (the kernel reads the head of its argument block as an EvalStatsArgs, that as an EvalMetricsArgs, ...)
+  int H;             // observation_history_size
+};
+static_assert(offsetof(EvalHistStatsArgs, st) == 0, "the history stats kernel reads the head of its argument block as an EvalStatsArgs");
+// the three blocks are the kernels' argument segments: size and the place of the last member, as the compiler laid them out
 static_assert(sizeof(EvalHistArgs) == 736 && offsetof(EvalHistArgs, H) == 728, "the kernarg layout of the history evaluation");
 static_assert(sizeof(EvalHistRecordArgs) == 760 && offsetof(EvalHistRecordArgs, H) == 752, "the kernarg layout of the history record");
-// REC -> the argument block of evaluate_hist_kernel<V, HN, REC>
-template <bool REC> using EvalHistKernelArgs = std::conditional_t<REC, EvalHistRecordArgs, EvalHistArgs>;
+static_assert(sizeof(EvalHistStatsArgs) == 744 && offsetof(EvalHistStatsArgs, H) == 736, "the kernarg layout of the history stats");
+// the EvalArgs at the head of the stats block (eval_head of csrc/pds_evaluate_args.h knows the other two by their first member)
+__host__ __device__ inline EvalArgs &eval_head(EvalHistStatsArgs &ka) { return ka.st.m.e; }
+__host__ __device__ inline const EvalArgs &eval_head(const EvalHistStatsArgs &ka) { return ka.st.m.e; }
+
+// The three forms of evaluate_hist_kernel (csrc/pds_evaluate_hist.h has what each does) and of everything that launches it.
+// Metrics: pds_evaluate_policies_history; Record: pds_evaluate_policies_history_record; Stats: pds_evaluate_policies_history_stats.
+enum class EvalHistForm : int { Metrics, Record, Stats };
+// form -> the argument block of evaluate_hist_kernel<V, HN, F>
+template <EvalHistForm F>
+using EvalHistKernelArgs = std::conditional_t<F == EvalHistForm::Record, EvalHistRecordArgs, std::conditional_t<F == EvalHistForm::Stats, EvalHistStatsArgs, EvalHistArgs>>;
+// The input widths hn = rollout_hist_tiles(H half) the stats form is built for: a network lane carries 8 hn accumulators through
+// its loop, and a width whose code objects spilled a VGPR or took more scratch than their metrics twins would be left out here
+// (profiles/evaluate_history_stats_kernel_resources.txt: none does).  pds_evaluate_history_stats_supported answers by it.
+constexpr bool eval_hist_stats_width_built(int hn) { return hn == 4 || hn == 6 || hn == 8 || hn == 12; }
 
 // (the translation units mirror csrc/pds_rollout_hist_*.hip: the same variants, hn = rollout_hist_tiles(H x half))
 bool launch_evaluate_hist_hover(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka);
@@ -40,5 +61,11 @@ bool launch_evaluate_hist_record_circle(const LaunchFlags &f, int hn, dim3 grid,
 bool launch_evaluate_hist_record_takeoff(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
 bool launch_evaluate_hist_record_hover_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
 bool launch_evaluate_hist_record_circle_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
+// ... and the stats form's, csrc/pds_evaluate_hist_stats_*.hip: the same variants a third time
+bool launch_evaluate_hist_stats_hover(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
+bool launch_evaluate_hist_stats_circle(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
+bool launch_evaluate_hist_stats_takeoff(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
+bool launch_evaluate_hist_stats_hover_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
+bool launch_evaluate_hist_stats_circle_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
 
 }  // namespace pds

@@ -237,6 +237,12 @@ def fused_history_evaluation_built(env):
     return env.lib.pds_evaluate_history_supported(env._handle, int(getattr(env, "observation_history_size", 2))) == 1
 
 
+def fused_history_stats_evaluation_built(env):
+    """Whether pds_evaluate_policies_history_stats has a kernel for this env and its observation_history_size H: what
+    fused_history_evaluation_built asks, and that the stats form of the kernel is built for the input width of H x half."""
+    return env.lib.pds_evaluate_history_stats_supported(env._handle, int(getattr(env, "observation_history_size", 2))) == 1
+
+
 # ---- flight-quality metrics (include/pds.h PDS_EM_*) -------------------------------------------------------------------
 METRIC_NAMES = ("roll_sq", "pitch_sq", "rate_sq", "action_rate_sq", "tilt_max", "saturated_steps", "roll_rate_crossings",
                 "pitch_rate_crossings")  # column j of `raw` = PDS_EM_* value j
@@ -330,7 +336,17 @@ def _compose_metrics(acc, prev_neg, alive, rpy, omega, act, last):
 
 # ---- observation sums (include/pds.h pds_evaluate_policies_stats) ------------------------------------------------------
 SLAB_WAVES, SLAB_FEATURES, SLAB_ROWS = 4, 64, 16  # d_obs_sums [tiles, 4, 2, 64]; a network wave sums 16 rows of its tile
+SLAB_WIDTHS = (64, 96, 128, 192)  # ... and [tiles, 4, 2, W] for the histories (include/pds_history_stats.h): W = slab_features(H x half)
 _OBS_STATS_LOG = None  # a list: the composed path appends (d [N, D] float64, alive [N] bool), on the CPU, per step (the tests' float64 sums)
+
+
+def slab_features(d_in):
+    """The columns W of the slab for `d_in` network inputs: 16 x rollout_hist_tiles(d_in) of csrc/pds_types.h -- 64, 96, 128 or 192,
+    the smallest that holds d_in (SLAB_FEATURES up to 64 inputs)."""
+    d_in = int(d_in)
+    if d_in < 1 or d_in > SLAB_WIDTHS[-1]:
+        raise ValueError(f"{d_in} network inputs: a slab holds 1 .. {SLAB_WIDTHS[-1]} features")
+    return next(w for w in SLAB_WIDTHS if d_in <= w)
 
 
 def tree_reduce_rows(acc):
@@ -347,9 +363,9 @@ def tree_reduce_rows(acc):
 
 
 def _compose_slab(s1, s2):
-    """the per-env sums [N, D] of the composed path -> the kernel's slab [tiles, 4, 2, 64] (features >= D zero)"""
+    """the per-env sums [N, D] of the composed path -> the kernel's slab [tiles, 4, 2, W], W = slab_features(D) (features >= D zero)"""
     n, d = s1.shape
-    slab = torch.zeros(n // 64, SLAB_WAVES, 2, SLAB_FEATURES, device=s1.device)
+    slab = torch.zeros(n // 64, SLAB_WAVES, 2, slab_features(d), device=s1.device)
     slab[:, :, 0, :d] = tree_reduce_rows(s1)
     slab[:, :, 1, :d] = tree_reduce_rows(s2)
     return slab
@@ -358,7 +374,7 @@ def _compose_slab(s1, s2):
 class ObsSums:
     """What evaluate_population(..., obs_stats=True) sums over every observation o a first-episode policy acted on, per policy p
     and feature k: with d = o_k - shift[p][k], `sum_d` = sum d and `sum_d2` = sum d^2, each [P, D] float64 on the CPU -- the
-    kernel's float32 partial sums (`slab` [tiles, 4, 2, 64], raw) added over the policy's tiles and the four waves of a tile in
+    kernel's float32 partial sums (`slab` [tiles, 4, 2, W], raw; W = 64, or 96 / 128 / 192 for the wider histories: SLAB_WIDTHS, W >= D) added over the policy's tiles and the four waves of a tile in
     float64.  `count` [P] float64: the number of observations, length.sum(1).  `shift` [P, D] float64: the means that were
     subtracted (the population's own standardisation means; zeros without one).
     The float64 sums are taken where the slab lives (a population of a million envs writes 33 MB of partial sums: summed on
@@ -370,11 +386,12 @@ class ObsSums:
         self.count = torch.as_tensor(count, dtype=torch.float64).reshape(-1)
         self.shift = torch.as_tensor(shift, dtype=torch.float64)
         P, D = self.shift.shape
-        if self._slab.dim() != 4 or tuple(self._slab.shape[1:]) != (SLAB_WAVES, 2, SLAB_FEATURES) or self._slab.shape[0] % P != 0 or D > SLAB_FEATURES:
-            raise ValueError(f"slab must be [tiles, {SLAB_WAVES}, 2, {SLAB_FEATURES}] with tiles a multiple of P = {P}")
+        W = int(self._slab.shape[3]) if self._slab.dim() == 4 else 0
+        if (self._slab.dim() != 4 or tuple(self._slab.shape[1:3]) != (SLAB_WAVES, 2) or W not in SLAB_WIDTHS or self._slab.shape[0] % P != 0 or D > W):
+            raise ValueError(f"slab must be [tiles, {SLAB_WAVES}, 2, W] with W one of {SLAB_WIDTHS}, at least D = {D}, and tiles a multiple of P = {P}")
         if self.count.numel() != P:
             raise ValueError(f"count must hold {P} values")
-        per = self._slab.reshape(P, -1, 2, SLAB_FEATURES).sum(dim=1, dtype=torch.float64).cpu()
+        per = self._slab.reshape(P, -1, 2, W).sum(dim=1, dtype=torch.float64).cpu()
         self.sum_d, self.sum_d2 = per[:, 0, :D].contiguous(), per[:, 1, :D].contiguous()
 
     @property
@@ -516,7 +533,8 @@ class Flights:
         return simopt.MiniTrajectories(*[np.concatenate([part[k] for part in parts]) for k in range(3)])
 
 
-def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats, history_fused, record, record_limit_bytes):
+def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats, history_fused, record, record_limit_bytes,
+                          history_stats_fused=False):
     """The argument checks of evaluate_population and its choice of path, with the env untouched -> (P, E, T, R or None, the
     form "plain" / "metrics" / "stats" / "record", whether the kernel path flies, and H where that is the history kernel, else None)"""
     P, E = _check_population_call(env, population)
@@ -529,6 +547,8 @@ def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats,
         fused = bool(fused)  # (1, 0, numpy.bool_: below `fused is True` must mean what it says)
     if not isinstance(history_fused, (bool, np.bool_)):
         raise ValueError("history_fused: True or False")
+    if not isinstance(history_stats_fused, (bool, np.bool_)):
+        raise ValueError("history_stats_fused: True or False")
     T = int(env._max_episode_steps if max_steps is None else max_steps)
     if T < 1:
         raise ValueError(f"max_steps = {T}")
@@ -547,14 +567,18 @@ def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats,
                              f"{int(record_limit_bytes)}: record fewer episodes or fewer steps, or raise the limit")
     form = "record" if R is not None else "stats" if obs_stats else "metrics" if metrics else "plain"
     H = int(getattr(env, "observation_history_size", 2))
-    # (the history kernel has a plain / metrics form and a record form, no stats form)
+    # (the history kernel has a plain / metrics form, a record form and a stats form; the stats form flies where history_stats_fused asks for it)
     use_history = bool(history_fused) and H != 2
     use_kernel = False
     if fused is not False and use_history:
-        built = not obs_stats and fused_history_evaluation_built(env)
+        if obs_stats:
+            built = bool(history_stats_fused) and fused_history_stats_evaluation_built(env)
+        else:
+            built = fused_history_evaluation_built(env)
         if fused is True and not built:
             raise NotImplementedError("pds_evaluate_policies_history has no kernel for this call (built: auto_reset, the env configurations "
-                                      "of the history rollout, H x half <= 192 inputs, no obs_stats); fused='auto' runs the composed path")
+                                      "of the history rollout, H x half <= 192 inputs; obs_stats with history_stats_fused=True only, where "
+                                      "pds_evaluate_history_stats_supported holds); fused='auto' runs the composed path")
         use_kernel = built
     elif fused is not False:
         built = fused_evaluation_built(env)
@@ -568,20 +592,22 @@ def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats,
 def _fly_kernel(env, population, obs, P, E, T, form, H, rec):
     """One launch -> (ret, length, cost, raw, slab) on the device, raw / slab None where the form has none; the record is written
     into `rec`'s arrays.  Per form the entry point and what trails d_cost in its argument list; the history kernel leads with H
-    and takes d_metrics or NULL, its record form (pds_evaluate_policies_history_record) what the record form takes."""
+    and takes d_metrics or NULL, its record form (pds_evaluate_policies_history_record) what the record form takes, its stats form
+    (pds_evaluate_policies_history_stats) what the stats form takes, the slab slab_features(H x half) columns wide."""
     dev, n = env.device, env.num_envs
     ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
     raw = torch.zeros(n, len(METRIC_NAMES), device=dev) if form != "plain" else None
-    slab = torch.zeros(n // 64, SLAB_WAVES, 2, SLAB_FEATURES, device=dev) if form == "stats" else None
+    slab = torch.zeros(n // 64, SLAB_WAVES, 2, slab_features(population.d_in) if H is not None else SLAB_FEATURES, device=dev) if form == "stats" else None
     _, R, flight, obs_rec = rec if rec is not None else (None,) * 4
     name, trail = {"plain": ("pds_evaluate_policies", ()),
                    "metrics": ("pds_evaluate_policies_metrics", (raw,)),
                    "stats": ("pds_evaluate_policies_stats", (raw, slab)),
                    "record": ("pds_evaluate_policies_record", (raw, R, flight, obs_rec))}[form]
     lead = ()
-    if H is not None:  # (plain, metrics or record; [N, H * half]: the histories env.reset() returns)
+    if H is not None:  # ([N, H * half]: the histories env.reset() returns; the record and the stats form take what theirs take at H = 2)
         obs, lead = obs.contiguous(), (H,)
-        name, trail = ("pds_evaluate_policies_history_record", trail) if form == "record" else ("pds_evaluate_policies_history", (raw,))
+        name, trail = {"record": ("pds_evaluate_policies_history_record", trail),
+                       "stats": ("pds_evaluate_policies_history_stats", trail)}.get(form, ("pds_evaluate_policies_history", (raw,)))
     native.call(name, env._handle, *lead, P, E, population.mlp(0), population.theta, population.mean, population.std,
                 population.eps, T, obs, ret, length, cost, *trail, on=dev, handle=env._handle)
     return ret, length, cost, raw, slab
@@ -669,7 +695,7 @@ def _population_result(env, population, P, E, T, flown, metrics, obs_stats, rec,
 
 @torch.no_grad()
 def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None, metrics=False, obs_stats=False,
-                        history_fused=False, record=None, record_observations=True, record_limit_bytes=1 << 30):
+                        history_fused=False, record=None, record_observations=True, record_limit_bytes=1 << 30, history_stats_fused=False):
     """-> (returns, ep_lengths, costs), each [P, E] float32 on the CPU: policy p of `population` flies the E = num_envs / P
     envs of block p, one episode per env, deterministically (action = actor mean), as `evaluate` does for one policy.
     metrics=True: -> (returns, ep_lengths, costs, FlightMetrics) -- the first three are the same bits; the kernel path is
@@ -696,12 +722,19 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     history_fused=True (it changes nothing at observation_history_size == 2): an env with another history size H flies in one
     launch too (pds_evaluate_policies_history, csrc/pds_evaluate_hist.h: the same bits as its composed path, metrics=True served
     from the same launch; with record=R pds_evaluate_policies_history_record, the record form of the same kernel) where
-    `fused_history_evaluation_built(env)` holds; where it does not, and with obs_stats=True (no stats form for histories), fused=True raises NotImplementedError with the env untouched and "auto" runs the composed path.
+    `fused_history_evaluation_built(env)` holds; where it does not, and with obs_stats=True unless history_stats_fused=True says
+    otherwise, fused=True raises NotImplementedError with the env untouched and "auto" runs the composed path.
+    history_stats_fused=True (it changes nothing without history_fused=True and obs_stats=True, and nothing at
+    observation_history_size == 2): the observation sums of a history env come from the launch too
+    (pds_evaluate_policies_history_stats, the stats form of the same kernel: the same slab on the bits as its composed path, the
+    metrics from the same launch) where `fused_history_stats_evaluation_built(env)` holds; where it does not, fused=True raises
+    NotImplementedError with the env untouched and "auto" runs the composed path.  The slab of a history env -- on either path --
+    is [tiles, 4, 2, W] with W = slab_features(H x half): 64, 96, 128 or 192 columns.
     The env is reset first and not afterwards: after the fused path it refuses to step until the next reset() of every env
     (a masked reset is refused as well).  `population` is not modified: the call works on device copies of its tensors.
     max_steps: the number of steps flown, by default the env's max_episode_steps (the TimeLimit ends every episode by then)."""
     P, E, T, R, form, use_kernel, H = _plan_population_call(env, population, fused, max_steps, metrics, obs_stats, history_fused, record,
-                                                            record_limit_bytes)
+                                                            record_limit_bytes, history_stats_fused)
     population = population.to(env.device)
     dev, D = env.device, env.obs_dim
     rec = u0 = None

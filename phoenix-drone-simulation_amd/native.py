@@ -149,9 +149,14 @@ SIGNATURES = {
 }
 EXPORTS = list(SIGNATURES)
 # ... and of include/pds_history_record.h, the entry point that stands beside that ABI (tests/test_evaluate_history_record_cpu.py
-# compares the two); `load` binds both tables, `call` enters either
+# compares the two); `load` binds every table, `call` enters any
 HISTORY_RECORD_SIGNATURES = {
     "pds_evaluate_policies_history_record": (_i32, [_vp, _i32] + _eval[1:] + [_vp, _i64, _vp, _vp, _vp]),
+}
+# ... and of include/pds_history_stats.h, the two that stand beside it likewise (tests/test_evaluate_history_stats_cpu.py)
+HISTORY_STATS_SIGNATURES = {
+    "pds_evaluate_history_stats_supported": (_i32, [_vp, _i32]),
+    "pds_evaluate_policies_history_stats": (_i32, [_vp, _i32] + _eval[1:] + [_vp] * 3),
 }
 
 _lib = None
@@ -173,7 +178,7 @@ def load():
     # an OLDER build given through PDS_LIB for a same-box A/B (profiles/tools/ab_lib.sh) may lack the newer entry points: those
     # are skipped; the shipped library must have every name (AttributeError here, and tests/test_host_cpu.py)
     older = bool(os.environ.get("PDS_LIB"))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()):
         if older and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -22,6 +22,13 @@ fused=False with the same record (the composed record) and against the history k
 repeats; then the launches alone, on buffers made beforehand.  Exit status 1 where the fused record is slower than the composed.
 
   python profiles/tools/evaluate_bench.py --history 4 8 --record 64 > profiles/evaluate_history_record_timing.txt
+
+--history H [H] --obs-stats: the stats form of the history kernel (pds_evaluate_policies_history_stats) on the same envs, actors and
+shapes -- evaluate_population(fused=True, history_fused=True, obs_stats=True, history_stats_fused=True, metrics=True) against
+fused=False with obs_stats=True (the composed sums) and against the history kernel's metrics launch, the same alternating repeats;
+then the two launches alone, on buffers made beforehand.  Exit status 1 where the fused sums are slower than the composed.
+
+  python profiles/tools/evaluate_bench.py --history 4 8 --obs-stats > profiles/evaluate_history_stats_timing.txt
 """
 import argparse
 import os
@@ -189,6 +196,82 @@ def history_record_main(args):
     sys.exit(0 if ok else 1)
 
 
+def history_stats_launch_ms(env, pop, H, P, E, T, bufs, form):
+    """device time of ONE launch of the history kernel on buffers made beforehand: form "metrics" or "stats" """
+    from phoenix_drone_simulation_amd import native
+    obs, _ = env.reset()
+    obs = obs.contiguous()
+    ret, length, cost, raw, slab = bufs
+    name, trail = ("pds_evaluate_policies_history", (raw,)) if form == "metrics" else ("pds_evaluate_policies_history_stats", (raw, slab))
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    start.record()
+    native.call(name, env._handle, H, P, E, pop.mlp(0), pop.theta, pop.mean, pop.std, pop.eps, T, obs, ret, length, cost, *trail,
+                on=env.device, handle=env._handle)
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end)
+
+
+def history_stats_main(args):
+    """--history H [H] --obs-stats: the stats form of the history kernel against the composed sums and against the history
+    kernel's metrics launch; the launches alone as well"""
+    from phoenix_drone_simulation_amd.evaluation import fused_history_stats_evaluation_built, slab_features
+    print(f"# evaluate_population(history_fused=True, obs_stats=True, history_stats_fused=True, metrics=True) on envs with an observation "
+          f"history, {torch.cuda.get_device_name(0)}; seeded random tanh actors (64, 64)")
+    print(f"# host clock around a call that ends in a device synchronise; one warm-up per path and shape, then {args.reps} repeats of each "
+          "path, alternating; ms: median [min .. max]")
+    ok = True
+    for j, (label, env_id, kw) in enumerate(HISTORY_CASES):
+        H = args.history[min(j, len(args.history) - 1)]
+        for P, E in HISTORY_SHAPES:
+            envs = [pds.make(env_id, num_envs=P * E, seed=1, observation_history_size=H, **kw) for _ in range(3)]
+            if not fused_history_stats_evaluation_built(envs[0]):
+                print(f"{label} H = {H} ({envs[0].obs_dim} inputs): the stats form is not built for this width")
+                continue
+            pop = random_population(envs[0].obs_dim, P).to("cuda:0")
+            stats = dict(obs_stats=True, history_stats_fused=True)
+            paths = (("fused stats", envs[0], True, stats), ("fused metrics", envs[1], True, {}), ("composed stats", envs[2], False, stats))
+            first = {name: timed_record(env, pop, f, k)[1] for name, env, f, k in paths}  # warm-up; same seed, first call: comparable
+            a, b, m = first["fused stats"], first["composed stats"], first["fused metrics"]
+            same = all(torch.equal(x, y) for x, y in zip(list(a[:3]) + [a[3].raw, a[4].slab], list(b[:3]) + [b[3].raw, b[4].slab])) and \
+                all(torch.equal(x, y) for x, y in zip(list(a[:3]) + [a[3].raw], list(m[:3]) + [m[3].raw]))
+            t = {name: [] for name, *_ in paths}
+            for _ in range(args.reps):
+                for name, env, f, k in paths:
+                    t[name].append(timed_record(env, pop, f, k)[0])
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            spread = (max(t["fused metrics"]) - min(t["fused metrics"])) / med["fused metrics"]
+            passed = med["fused stats"] <= med["composed stats"]
+            ok &= passed
+            W = slab_features(envs[0].obs_dim)
+            print(f"{label} H = {H} ({envs[0].obs_dim} inputs, slab width {W}) {P:3d} x {E:5d} ({P * E // 64} tiles) mean length "
+                  f"{float(m[1].mean()):6.1f}  same bits {same}")
+            for name in t:
+                print(f"    {name:20s} {1e3 * med[name]:10.2f} [{1e3 * min(t[name]):.2f} .. {1e3 * max(t[name]):.2f}] ms")
+            print(f"    stats / metrics = {med['fused stats'] / med['fused metrics']:.3f}, the metrics path's own (max - min) / median = {spread:.3f}; "
+                  f"composed / fused, both summing = {med['composed stats'] / med['fused stats']:.1f}x; {'PASS' if passed else 'FAIL'}")
+            n, T, dev = P * E, envs[0]._max_episode_steps, envs[0].device
+            bufs = tuple(torch.zeros(n, device=dev) for _ in range(3)) + (torch.zeros(n, 8, device=dev), torch.zeros(n // 64, 4, 2, W, device=dev))
+            del first, a, b, m
+            forms = ("stats", "metrics")
+            k = {f: [] for f in forms}
+            for rep_ in range(args.reps + 1):  # (the first round warms up)
+                for f in forms:
+                    ms = history_stats_launch_ms(envs[1], pop, H, P, E, T, bufs, f)
+                    if rep_:
+                        k[f].append(ms)
+            kmed = {f: float(np.median(v)) for f, v in k.items()}
+            kspread = (max(k["metrics"]) - min(k["metrics"])) / kmed["metrics"]
+            ratio = kmed["stats"] / kmed["metrics"]
+            print("    the launch alone: " + ", ".join(f"{f} {kmed[f]:.3f} [{min(k[f]):.3f} .. {max(k[f]):.3f}]" for f in forms) +
+                  f" ms; stats / metrics = {ratio:.3f}, the metrics launch's own (max - min) / median = {kspread:.3f}: "
+                  + ("the sums exceed the spread" if ratio - 1.0 > kspread else "the sums are inside the spread"))
+            for env in envs:
+                env.close()
+    sys.exit(0 if ok else 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=1.0, help="least timed duration per path and shape")
@@ -198,7 +281,11 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="--history: alternating repeats per path and shape")
     ap.add_argument("--record", type=int, default=None, metavar="R",
                     help="--history: time the record form (pds_evaluate_policies_history_record, R episodes per policy) instead")
+    ap.add_argument("--obs-stats", action="store_true",
+                    help="--history: time the stats form (pds_evaluate_policies_history_stats) instead")
     args = ap.parse_args()
+    if args.history and args.obs_stats:
+        return history_stats_main(args)
     if args.history and args.record:
         return history_record_main(args)
     if args.history:

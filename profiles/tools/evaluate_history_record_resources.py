@@ -18,7 +18,7 @@ import evaluate_names as en  # noqa: E402
 import evaluate_record_resources as err  # noqa: E402
 import kernel_resources as kr  # noqa: E402
 
-NAME = re.compile(r"evaluate_hist_kernel<pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>, (\d+), (true|false)>")
+NAME = re.compile(r"evaluate_hist_kernel<pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>, (\d+), \(pds::EvalHistForm\)([01])>")  # (the form by value: 0 the launch without, 1 with the record; 2, the stats form, has profiles/tools/evaluate_history_stats_resources.py)
 ROW = re.compile(r"^(\w+) +(\S+) +(\w+) +(\d+) \|((?: +-?\d+){6}) \|")
 FORMS = err.RECORDS + (("evaluate_record_kernel_resources.txt", "metrics", "record"),)
 
@@ -31,7 +31,7 @@ def rows(lib=None):
         if m:
             task, motor, dr, ge, tn, on, ctrl, _, _, hn, rec = m.groups()
             flags = "".join(c for c, v in zip("MDGTO", (motor, dr, ge, tn, on)) if v == "true") or "-"
-            out.setdefault((en.TASK[int(task)], flags, en.CTRL[int(ctrl)], int(hn)), {})[rec == "true"] = r[1:]
+            out.setdefault((en.TASK[int(task)], flags, en.CTRL[int(ctrl)], int(hn)), {})[rec == "1"] = r[1:]
     return out
 
 

@@ -14,9 +14,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import evaluate_stats_resources as esr  # noqa: E402
 import kernel_resources as kr  # noqa: E402
 
-# (evaluate_hist_kernel<Variant, HN, REC>: the launch of this table is REC = false; the record form, REC = true, has a table of its
-# own -- profiles/tools/evaluate_history_record_resources.py)
-NAME = re.compile(r"(evaluate_hist_kernel|rollout_hist_kernel)<pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>, (\d+)(?:, false)?>")
+# (evaluate_hist_kernel<Variant, HN, F>: the launch of this table is F = EvalHistForm::Metrics, 0 by value -- REC = false before the
+# kernel had three forms; the record and the stats form have tables of their own -- profiles/tools/evaluate_history_record_resources.py,
+# profiles/tools/evaluate_history_stats_resources.py)
+NAME = re.compile(r"(evaluate_hist_kernel|rollout_hist_kernel)<pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>, (\d+)(?:, false|, \(pds::EvalHistForm\)0)?>")
 
 
 def rows(lib=None):
