@@ -292,7 +292,17 @@ int pds_count_nonfinite(pds_handle *h, int64_t *count, void *stream);
  * by the kernels themselves), so no kernel argument changes between two pds_step calls with the same
  * pointers: a sequence of pds_step / pds_reset calls can be captured into a hipGraph and replayed.
  * pds_tick returns the host's mirror (exact unless a captured graph was replayed);
- * pds_sync_tick(h, stream) synchronises `stream`, re-reads the device word and returns it. */
+ * pds_sync_tick(h, stream) synchronises `stream`, re-reads the device word and returns it.
+ *
+ * The tick also sets the phase of the lean configurations' state store (control_mode PWM without motor dynamics, domain
+ * randomisation, thrust / observation noise and latency; with or without the ground effect): a pds_step launched at an EVEN
+ * tick is a write step, one launched at an ODD tick a skip step, which leaves position / attitude / velocity / body rates
+ * in memory one step behind and says so in the env's counter word; the next pds_step recomputes them from the stored state
+ * and the action ring, bit for bit.  No caller sees it: every entry point that reads or edits the state brings it up to
+ * date first (one extra launch on its stream when a step has run since), and what a step returns does not depend on the
+ * phase.  Handles whose launch is at most one round of resident blocks (3 blocks of 256 envs per compute unit) store every
+ * step: such a launch is bound by a wave's latency, not by memory.  PDS_STATE_EVERY_STEP=1 / =0 in the environment of
+ * pds_create forces either form (tests, A/B runs); a library built with -DPDS_STATE_EVERY_OTHER_STEP=0 stores every step. */
 uint64_t pds_tick(const pds_handle *h);
 uint64_t pds_sync_tick(pds_handle *h, void *stream);
 /* Restore the tick of a checkpoint: a handle created with the same config whose fields were all set

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "pds_reset.h"  // (pds_types.h + regen_kept_obs for pds_get_state)
+#include "pds_physics.h"  // (the sub-step blocks for materialize_state_kernel)
 #include "pds_collect_args.h"
 #include "pds_evaluate_args.h"
 #include "pds_evaluate_hist_args.h"
@@ -235,6 +236,40 @@ __global__ __launch_bounds__(kBlock) void materialize_oh_kernel(DevState st, Con
   st.ctr[i] = c | kCtrOhBit;
 }
 
+// s0-s2 of every env whose counter word says that they are one step behind (kCtrBehindBit: the lean single-step kernels store
+// them every other step, csrc/pds_step.h skip_state_variant) are advanced by that step -- u(k-1) out of the action ring, the
+// blocks of csrc/pds_physics.h in step_once's order, so the bits the skip step computed (-ffp-contract=on: contraction is
+// decided per source expression) -- and stored, and the bit is cleared.  What the next write step would do in its prologue, as
+// a pass of its own in front of everything else that reads s0-s2, writes them for some envs only or rewrites the counter word
+// (materialize_state below).  4 B per env when no env is flagged, 72 + 52 B otherwise.
+__global__ __launch_bounds__(kBlock) void materialize_state_kernel(DevState st, Consts k, long long n, int ge) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t c = st.ctr[i];
+  if (ctr_behind(c) == 0u) return;
+  const int parity = (int)(st.clk[i / kWave].z & 1u);
+  const float4 q0 = st.s0[i], q1 = st.s1[i], q2 = st.s2[i];
+  const float4 act = st.hist[parity][i];  // u(k-1)
+  EnvRegs e{q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+  Params par;
+  default_params(k, par);
+  float xm_[4] = {0.f, 0.f, 0.f, 0.f}, ou_[4] = {0.f, 0.f, 0.f, 0.f};
+  float *xm = xm_;
+  Quat q = quat_from_euler(e.roll, e.pitch, e.yaw);
+  const float inv_m = fast_rcp(par.m), inv_Jx = fast_rcp(par.Jx), inv_Jy = fast_rcp(par.Jy), inv_Jz = fast_rcp(par.Jz);
+  for (int sub = 0; sub < k.agg; ++sub) {
+    float av[4] = {act.x, act.y, act.z, act.w};
+    float f[4], pwmv[4];
+    PDS_PWM_FROM_ACTION()
+    PDS_MOTOR_THRUST(false, false, ou_, ou_)
+    PDS_RIGID_BODY_SUBSTEP(ge != 0, true)
+  }
+  st.s0[i] = make_float4(e.px, e.py, e.pz, e.vx);
+  st.s1[i] = make_float4(e.vy, e.vz, e.roll, e.pitch);
+  st.s2[i] = make_float4(e.yaw, e.wx, e.wy, e.wz);
+  st.ctr[i] = c & ~kCtrBehindBit;
+}
+
 
 }  // namespace pds
 
@@ -249,6 +284,7 @@ struct pds_handle {
   Consts k;
   LaunchFlags flags;
   int force_tile;  // PDS_FORCE_TILE=half|full (tests / A-B runs): 1 half, 2 full, 0 pick per launch
+  bool store_every_step;  // pds_step launches the kernels that store s0-s2 every step: by size, or PDS_STATE_EVERY_STEP (pds_create)
   float2 *d_circle_ref;
   void *slab;  // one allocation holds every state array (staggered, see pds_create)
   float4 *lat_buf;  // [PDS_MAX_LATENCY_STEPS][N] delayed-action ring, allocated when latency is first enabled
@@ -260,6 +296,12 @@ struct pds_handle {
   uint64_t tick;  // host mirror of the device clock words (pds_sync_tick refreshes it)
   bool was_reset;
   bool after_evaluate;  // pds_evaluate_policies ran and no unmasked reset since: every tile stopped at a step of its own
+  // state stored every other step (kCtrBehindBit): a lean single-step launch was issued since the last materialize_state /
+  // unmasked reset, so s0-s2 of some envs may be one step behind ...
+  bool state_maybe_behind;
+  // ... and one was issued into a stream capture: a replay steps the envs without the host seeing it, so from then on the
+  // handle never knows better and materialize_state always launches its pass
+  bool step_captured;
   char err[512];
 };
 
@@ -309,6 +351,27 @@ static int materialize_kept_obs(pds_handle *h, hipStream_t s) {
   hipLaunchKernelGGL(pds::materialize_oh_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, h->st, h->k, n,
                      (unsigned long long)h->cfg.env_id_base, (uint32_t)h->cfg.seed, (uint32_t)(h->cfg.seed >> 32));
   PDS_HIP(h, hipGetLastError());
+  return PDS_OK;
+}
+
+// The configurations whose single-step kernel stores s0-s2 every other step (csrc/pds_step.h skip_state_variant).
+static bool skips_state(const pds_handle *h) {
+  const LaunchFlags &f = h->flags;
+  return PDS_STATE_EVERY_OTHER_STEP != 0 && !h->store_every_step && !f.motor && !f.dr && !f.tn && !f.on && f.ctrl == 0 && !f.lat;
+}
+
+// s0-s2 of every env up to date with its counter word, in front of everything that reads them, writes them for some envs only or
+// rewrites the counter word without going through the lean single-step kernel: pds_get_state / pds_set_state (hence checkpoint and
+// resume), a masked pds_reset*, pds_set_tick, pds_set_latency (the handle leaves the lean family), pds_step_k, pds_rollout*,
+// pds_evaluate_policies*, pds_collect, pds_simopt_evaluate, pds_count_nonfinite.  Not launched when the handle knows that no
+// lean step ran since the last pass or unmasked reset.
+static int materialize_state(pds_handle *h, hipStream_t s) {
+  if (!h->state_maybe_behind && !h->step_captured) return PDS_OK;
+  const long long n = h->cfg.num_envs;
+  hipLaunchKernelGGL(pds::materialize_state_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, h->st, h->k, n,
+                     h->flags.ge ? 1 : 0);
+  PDS_HIP(h, hipGetLastError());
+  h->state_maybe_behind = false;
   return PDS_OK;
 }
 
@@ -549,6 +612,15 @@ extern "C" int pds_create(const pds_config *cfg, pds_handle **out) {
     e = hipGetDeviceProperties(&prop, cfg->device);
     h->num_cus = (e == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
   }
+  {
+    // State every other step (kCtrBehindBit) where a launch is more than one round of resident blocks, i.e. where it is bound
+    // by what HBM takes: a launch of one round or less is bound by the latency of a single wave, and the extra pass through
+    // the physics on the write steps shows (Hover 65 536: 7.22 against 7.10 us, profiles/state_every_other_step.txt).
+    // PDS_STATE_EVERY_STEP=1: every step, =0: every other step at any size (tests / A-B runs).
+    const size_t blocks = (n + kBlock - 1) / kBlock;
+    h->store_every_step = blocks <= (size_t)kFullTileBlocksPerCU * (size_t)h->num_cus * (256 / kBlock);
+    if (const char *es = getenv("PDS_STATE_EVERY_STEP")) h->store_every_step = es[0] == '1';
+  }
   // All state arrays live in ONE slab (one allocation, one free, contiguous pages); consecutive arrays
   // are staggered by an odd multiple of 256 B so that the 6-21 concurrent streams of the step kernel do
   // not start at the same offset modulo a power of two (measured neutral on MI355X: 62.4-63.7 us for
@@ -654,6 +726,7 @@ extern "C" int pds_set_tick(pds_handle *h, uint64_t tick) {
   PDS_HIP(h, guard.err);
   PDS_HIP(h, hipDeviceSynchronize());  // no stream argument: order behind everything in flight
   if (const int rc = materialize_kept_obs(h, 0)) return rc;  // (regenerated from the OLD tick's blocks)
+  if (const int rc = materialize_state(h, 0)) return rc;     // (the new tick may change the phase of the state store)
   const long long ntiles = (h->cfg.num_envs + kWave - 1) / kWave;
   hipLaunchKernelGGL(clock_fill_kernel, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, 0, h->st.clk, ntiles,
                      (unsigned long long)tick, 1);
@@ -681,6 +754,7 @@ extern "C" int pds_set_latency(pds_handle *h, double latency) {
     const int rc = ensure_latency_buffer(h);
     if (rc != PDS_OK) return rc;
   }
+  if (const int rc = materialize_state(h, 0)) return rc;  // (the latency variants do not know kCtrBehindBit)
   h->cfg.latency = latency;
   h->cfg.use_latency = steps > 0;
   h->flags.lat = steps > 0;
@@ -730,6 +804,7 @@ extern "C" int pds_simopt_evaluate(pds_handle *h, int64_t P, const float *d_para
     return fail(h, PDS_EINVAL, "pds_simopt_evaluate: the data set arrays must be 16-byte aligned");
   DeviceGuard guard(h->cfg.device);
   PDS_HIP(h, guard.err);
+  if (const int rc = materialize_state(h, (hipStream_t)stream)) return rc;
   SimoptArgs a;
   a.k = h->k;
   a.time_step = h->cfg.time_step;
@@ -840,13 +915,16 @@ static int do_reset(pds_handle *h, const uint8_t *d_mask, const float *d_samples
   base_args(h, a);
   a.mask = d_mask; a.samples = d_samples; a.obs = d_obs;
   const dim3 grid((unsigned)((a.n + kBlock - 1) / kBlock));
-  if (d_mask != nullptr)  // (the envs outside the mask keep their episode: see materialize_kept_obs)
+  if (d_mask != nullptr) {  // (the envs outside the mask keep their episode: see materialize_kept_obs, materialize_state)
     if (const int rc = materialize_kept_obs(h, (hipStream_t)stream)) return rc;
+    if (const int rc = materialize_state(h, (hipStream_t)stream)) return rc;
+  }
   launch_family(h, kLaunchReset, h->flags, grid, (hipStream_t)stream, a);
   PDS_HIP(h, hipGetLastError());
   h->tick += 1;
   h->was_reset = true;
   h->after_evaluate = false;
+  if (d_mask == nullptr) h->state_maybe_behind = false;  // (every env's state and counter word are fresh)
   return PDS_OK;
 }
 
@@ -895,8 +973,14 @@ extern "C" int pds_step_with_variates(pds_handle *h, const float *d_actions, con
   lf.half_tile = grid.x > (unsigned)kFullTileBlocksPerCU * cus * (256 / kBlock) && grid.x <= (merged ? 5u : 8u) * cus * (256 / kBlock);
   if (h->force_tile) lf.half_tile = h->force_tile == 1;
   if (lf.on || lf.lat) lf.half_tile = false;  // (no half-tile instantiation)
-  launch_family(h, kLaunchStep, lf, grid, (hipStream_t)stream, a);
+  launch_family(h, h->store_every_step ? kLaunchStepStoreAll : kLaunchStep, lf, grid, (hipStream_t)stream, a);
   PDS_HIP(h, hipGetLastError());
+  if (skips_state(h)) {  // (see materialize_state)
+    h->state_maybe_behind = true;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) (void)hipGetLastError();
+    else if (cs != hipStreamCaptureStatusNone) h->step_captured = true;
+  }
   h->tick += 1;
   return PDS_OK;
 }
@@ -937,6 +1021,7 @@ extern "C" int pds_step_k(pds_handle *h, int k_steps, const float *d_actions, fl
   LaunchFlags lf = h->flags;
   lf.half_tile = false;
   if (const int rc = materialize_kept_obs(h, (hipStream_t)stream)) return rc;  // (the K-step kernel reads oh0-2: StoredOh)
+  if (const int rc = materialize_state(h, (hipStream_t)stream)) return rc;
   launch_family(h, kLaunchStepK, lf, grid, (hipStream_t)stream, a);
   PDS_HIP(h, hipGetLastError());
   h->tick += (uint64_t)k_steps;
@@ -1004,6 +1089,7 @@ static int launch_rollout(pds_handle *h, const char *fn, int T, void *stream, La
   PDS_HIP(h, guard.err);
   // the env waves read the kept noisy observation from oh0-2 (StoredOh, like the K-step kernel)
   if (const int rc = materialize_kept_obs(h, (hipStream_t)stream)) return rc;
+  if (const int rc = materialize_state(h, (hipStream_t)stream)) return rc;
   const dim3 grid((unsigned)((h->cfg.num_envs + kWave - 1) / kWave));
   if (!launch(grid, (hipStream_t)stream)) return fail(h, PDS_EHIP, "%s: its _supported() rule and the launchers disagree", fn);
   PDS_HIP(h, hipGetLastError());
@@ -1461,6 +1547,7 @@ static int do_field(pds_handle *h, int field, void *d_ptr, int set, void *stream
   // unedited state first and stays in oh0-2 (the reference's history keeps the row that was returned, envs/base.py:303-319)
   if (set && field != PDS_F_NOISY_OBS)
     if (const int rc = materialize_kept_obs(h, (hipStream_t)stream)) return rc;
+  if (const int rc = materialize_state(h, (hipStream_t)stream)) return rc;  // (reads too; an edit of the counter word drops kCtrBehindBit)
   a.env_id_base = (unsigned long long)h->cfg.env_id_base;
   a.seed_lo = (uint32_t)h->cfg.seed; a.seed_hi = (uint32_t)(h->cfg.seed >> 32);
   const dim3 grid((unsigned)((a.n + kBlock - 1) / kBlock));
@@ -1475,6 +1562,7 @@ extern "C" int pds_count_nonfinite(pds_handle *h, int64_t *count, void *stream) 
   DeviceGuard guard(h->cfg.device);
   PDS_HIP(h, guard.err);
   hipStream_t s = (hipStream_t)stream;
+  if (const int rc = materialize_state(h, s)) return rc;
   PDS_HIP(h, hipMemsetAsync(h->d_count, 0, sizeof(*h->d_count), s));  // handle-owned word: nothing to free
   const long long n = h->cfg.num_envs;
   hipLaunchKernelGGL(nonfinite_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->st, n, h->d_count);

@@ -65,6 +65,15 @@ constexpr bool park_variant() { return heavy_variant<V>(); }
 template <class V>
 using Idx = EnvIdxT<saddr_variant<V>()>;
 
+// The lean variants of the SINGLE-step kernel (STORE) store s0-s2 every other step (kCtrBehindBit, csrc/pds_types.h): they sit on
+// the rate HBM takes their writes at with a vector ALU that is two-thirds idle, s(k+1) is a pure function of s(k) and u(k), the
+// next launch loads s(k) anyway and finds u(k) in the action ring.  The K-step, rollout and evaluation kernels (STORE false)
+// and the heavy variants keep storing as they did.  The form is skip_step_kernel (step_once<..., SKIPSTATE>) beside step_kernel, so the
+// kernels that store every step are in the library as well -- the instantiations a -DPDS_STATE_EVERY_OTHER_STEP=0 build has
+// under the same names -- and a handle created under PDS_STATE_EVERY_STEP=1 launches those (tests, A/B runs).
+template <class V>
+constexpr bool skip_state_variant() { return PDS_STATE_EVERY_OTHER_STEP != 0 && !heavy_variant<V>(); }
+
 // Observation-noise variants without the Kalman hold do not keep the noisy o(k) in memory: it is regenerated
 // (regen_kept_obs, csrc/pds_reset.h) unless the env's counter word says it was stored (kCtrOhBit, csrc/pds_types.h).
 // The single-step kernel regenerates whatever the number of physics sub-steps: its StoredOh form, built and measured in round 5,
@@ -252,14 +261,17 @@ PDS_DEV void init_kept_obs(const StepArgs &a, const RngKey &rk, const Idx<V> ix,
 // Coalesced 16 B/lane stores of the env state.  `new_parity` = parity of the action ring AFTER the
 // stored step: slot new_parity holds u(k-1) = S.h1.  The single-step kernel leaves the other slot
 // alone (it already holds S.h2) unless the env was reset in registers (`both`); the K-step kernel
-// rewrites both slots and the randomised parameters.
+// rewrites both slots and the randomised parameters.  `behind` (skip_state_variant only): this lane leaves s0-s2 as they
+// are, one step behind S.e, and S.ctr says so (kCtrBehindBit).
 template <class V>
-PDS_DEV void store_state(const StepArgs &a, const Idx<V> i_, int new_parity, const EnvState &S, bool both) {
+PDS_DEV void store_state(const StepArgs &a, const Idx<V> i_, int new_parity, const EnvState &S, bool both, bool behind = false) {
   const EnvRegs &e = S.e;
   Idx<V> i = fresh<3>(i_);
-  st_store4(at(a.st.s0, i), make_float4(e.px, e.py, e.pz, e.vx));
-  st_store4(at(a.st.s1, i), make_float4(e.vy, e.vz, e.roll, e.pitch));
-  st_store4(at(a.st.s2, i), make_float4(e.yaw, e.wx, e.wy, e.wz));
+  if (!behind) {
+    st_store4(at(a.st.s0, i), make_float4(e.px, e.py, e.pz, e.vx));
+    st_store4(at(a.st.s1, i), make_float4(e.vy, e.vz, e.roll, e.pitch));
+    st_store4(at(a.st.s2, i), make_float4(e.yaw, e.wx, e.wy, e.wz));
+  }
   st_store4(at(a.st.hist[new_parity], i), S.h1);
   *at(a.st.ctr, i) = flags_oh_variant<V>() ? (S.ctr | kCtrOhBit) : S.ctr;
   if (V::MOTOR) *at(a.st.mx, i) = make_float4(S.xm[0], S.xm[1], S.xm[2], S.xm[3]);
@@ -516,7 +528,7 @@ struct StepOut {
 
 // `fin_lds` (optional): [64][D] LDS image that receives the last observation row of every env that finished (the
 // rows that go to final_obs); `so` (optional): reward / flags of this lane's env.
-template <class V, int TR, int RM, bool STORE>
+template <class V, int TR, int RM, bool STORE, bool SKIPSTATE = false>
 PDS_DEV bool step_once(const StepArgs &a, const long long o1, const RngKey &rk, int parity, const float2 *ref_lds,
                        float *tile, float *park, uint32_t *queue, U4 *scratch, int lane, long long wave_base, const Idx<V> ix,
                        bool active, const float4 act, EnvState &S, int &qcount, float *fin_lds, StepOut *so
@@ -580,7 +592,7 @@ PDS_DEV bool step_once(const StepArgs &a, const long long o1, const RngKey &rk, 
   // noise-free: rebuilt from the pre-step state instead of being re-read from HBM;
   // noisy: the stored noisy observation + the filtered gyro (== the low-pass state)
   Quat q = quat_from_euler(e.roll, e.pitch, e.yaw);
-  {
+  auto first_half = [&]() {
     float tx, ty, tz;
     target_at<TASK>(k, ref_lds, target_index<TASK>(step, k.agg, phase), tx, ty, tz);
     if (V::ON) {
@@ -590,6 +602,21 @@ PDS_DEV bool step_once(const StepArgs &a, const long long o1, const RngKey &rk, 
       if (ctr_sign(ctr)) { qk.x = -q.x; qk.y = -q.y; qk.z = -q.z; qk.w = -q.w; }
       put_obs_half<TASK, O + 4, VEC1>(row, e, qk, h1, tx, ty, tz, pa1);
     }
+  };
+  // State stored every other step (skip_state_variant): a lane whose counter word says that s0-s2 are one step behind has
+  // loaded s(k-1); the counter word (step count, Circle phase, quaternion sign: all of step k already) and the ring (h1 =
+  // u(k-1)) are current.  Its state is advanced to s(k) by `agg` EXTRA iterations of the sub-step loop below, in front of
+  // the step's own -- the same instruction stream that computed s(k) in the previous launch, so the same bits -- and o(k)
+  // is written between the two (iteration 0).  A wave without such a lane (every wave of a skip step) starts at iteration 0.
+  constexpr bool SKIP = SKIPSTATE;
+  static_assert(!SKIP || (STORE && skip_state_variant<V>() && RM != RM_INLINE), "state every other step: the lean single-step kernels");
+  const bool behind = SKIP && ctr_behind(ctr) != 0u;
+  int sub_first = 0;  // wave-uniform
+  float4 ua = h1;     // SKIP: the action of the current loop iteration -- u(k-1) for the advance, then this step's
+  if constexpr (SKIP) {
+    if (__ballot(behind) != 0ull) sub_first = -k.agg;
+  } else {
+    first_half();
   }
 
   // ---- aggregate_phy_steps x SimplePhysics.step_forward (envs/base.py:457-465) ---------------
@@ -598,11 +625,17 @@ PDS_DEV bool step_once(const StepArgs &a, const long long o1, const RngKey &rk, 
   uint32_t lat_idx = ctr_lat(ctr);
   // divisions by the per-env mass / inertia become multiplications by v_rcp_f32 results (1 ulp)
   const float inv_m = fast_rcp(par.m), inv_Jx = fast_rcp(par.Jx), inv_Jy = fast_rcp(par.Jy), inv_Jz = fast_rcp(par.Jz);
-  for (int sub = 0; sub < k.agg; ++sub) {
+  for (int sub = sub_first; sub < k.agg; ++sub) {
+    if constexpr (SKIP) {
+      // (the step's own action, the one load that is cold and issued last, is first touched HERE: the advance runs on u(k-1)
+      //  out of the ring while it is still in flight)
+      if (sub == 0) { first_half(); ua = act; }
+    }
     SubNoise sn;
     if (V::TN || V::ON) sub_noise<V>(a, rk, env_id, ix, sub, sn);
     // CrazyFlieAgent.apply_action, envs/agents.py:259-298 (+ PWM.act envs/control.py:94-100)
     float av[4] = {act.x, act.y, act.z, act.w};
+    if constexpr (SKIP) { av[0] = ua.x; av[1] = ua.y; av[2] = ua.z; av[3] = ua.w; }
     if (V::LAT) {  // agents.py:267-276: the controller sees the action of buf_size physics steps ago
       float4 *slot = a.st.lat + (long long)lat_idx * a.n + ix.global();  // (the ring index is per env)
       const float4 d = *slot;
@@ -620,6 +653,12 @@ PDS_DEV bool step_once(const StepArgs &a, const long long o1, const RngKey &rk, 
     // noise nothing reads the TRUE quaternion after the last sub-step (the observation carries Q(noisy rpy), the next env.step
     // rebuilds Q(rpy) from the stored angles): skip its three sincos there
     PDS_MOTOR_THRUST(V::MOTOR, V::TN, ns.ou, sn.ou)
+    if constexpr (SKIP) {
+      // (the lean variants carry nothing but e and q from sub-step to sub-step: the lanes that are not behind sit out the
+      //  advance here, under the exec mask)
+      if (sub >= 0 || behind) { PDS_RIGID_BODY_SUBSTEP(V::GE, true) }
+      continue;
+    }
     PDS_RIGID_BODY_SUBSTEP(V::GE, !V::ON || sub + 1 < k.agg)
     // envs/base.py:464: compute_observation() whose result is dropped still advances the gyro
     // bias random walk and the low-pass filter
@@ -752,10 +791,25 @@ PDS_DEV bool step_once(const StepArgs &a, const long long o1, const RngKey &rk, 
   {
   const StepArgs &a = reload_args<102, heavy_variant<V>()>(a_in, (int)o1);  // (o1: renewed per iteration of the K-step loop)
   const Consts &k = a.k;
+  // (skip steps: the lanes that were reset in registers, see below)
+  const unsigned long long fresh_lanes = SKIP ? __ballot(was_reset) : 0ull;
   if (active) {
     // (RM_INLINE: a finished env's lane stores the FRESH state from inside the reset below, nothing here: no
     //  write-after-write between the two, hence no wait for these stores)
-    if constexpr (STORE && RM != RM_INLINE) store_state<V>(a, ix, parity ^ 1, S, was_reset);
+    if constexpr (SKIP) {
+      // odd tick = skip step (include/pds.h): s0-s2 stay where they are unless the env was reset in registers (fresh state) or
+      // came in behind (a second step without a store would leave them two steps behind: never on the paths of csrc/pds_api.hip,
+      // which materialises in front of everything that moves a clock without stepping, but the rule costs nothing).  The
+      // deferred drain (TakeOff) rewrites s0-s2 and the counter word of its envs behind these stores.
+      // A fresh state leaves in whole 128-byte lines: the eight lanes that share a line of s0 / s1 / s2 with a reset lane store
+      // with it (a lone 16-byte store is a read-modify-write of its line: with Hover's 1-2 finished envs per wave it cost
+      // most of the gain, profiles/state_every_other_step.txt).
+      const bool line_mate = ((fresh_lanes >> (lane & ~7)) & 0xFFull) != 0ull;
+      const bool skip = (rk.tick_lo & 1u) != 0u && !behind && !line_mate;
+      if (skip) S.ctr |= kCtrBehindBit;
+      store_state<V>(a, ix, parity ^ 1, S, was_reset, skip);
+    }
+    if constexpr (STORE && RM != RM_INLINE && !SKIP) store_state<V>(a, ix, parity ^ 1, S, was_reset);
     if constexpr (STORE && RM == RM_INLINE) {
       if (!need_reset) store_state<V>(a, ix, parity ^ 1, S, false);
     }
@@ -1085,34 +1139,45 @@ PDS_DEV void prefetch_kernargs() {
 // (profiles/r03_ab_persistent.txt).  Waves that all start together run their load / compute / store phases in
 // lockstep across the chip; the dispatcher's staggered block starts are what overlaps one block's memory phases
 // with another's arithmetic.
+// The body of the two single-step kernels below (a macro: the kernel that stores every step keeps the tokens it had).
+// The loads are issued before anything else so that the scalar preamble of the kernel
+// (kernel-argument loads, uniform constants) overlaps with their latency.  (qcount: wave-uniform.)
+#define PDS_STEP_KERNEL_BODY(SKIPSTATE_) \
+  PDS_STAMP_DECL \
+  prefetch_kernargs(); \
+  constexpr int RM = merged_reset_variant<V, TR>() ? RM_MERGED : (inline_reset_single_step<V, TR>() ? RM_INLINE : RM_DEFERRED); \
+  PDS_WAVE_SETUP(V, TR, RM, true) \
+  Loaded cur; \
+  load_env<V>(a, ix, t, cur); \
+  __builtin_amdgcn_sched_barrier(0); \
+  PDS_STAMP(1); \
+  PDS_STAMP_WAIT(2); \
+  RngKey rk{a.seed_lo, a.seed_hi, 0u, 0u}; \
+  int parity; \
+  PDS_CLOCK_TO_KEY(cur.clk, rk, parity) \
+  EnvState S; \
+  unpack_state<V>(a.k, cur, parity, S); \
+  init_kept_obs<V>(a, rk, ix, S); \
+  int qcount = 0; \
+  step_once<V, TR, RM, true, SKIPSTATE_>(a, 0ll, rk, parity, ref_lds, tile, park, queue, scratch, lane, wave_base, ix, active, cur.act, S, qcount, nullptr, nullptr PDS_STAMP_ARG); \
+  if (RM == RM_DEFERRED && qcount > 0) { \
+    const float own_w[3] = {S.e.wx, S.e.wy, S.e.wz}; \
+    drain_reset_queue<V>(reload_args<104, heavy_variant<V>()>(a), rk, ref_lds, queue, qcount, lane, wave_base, tile, own_w, S.ns.bias); \
+  } \
+  PDS_STAMP(6); \
+  advance_clock(reload_args<105, heavy_variant<V>()>(a).st.clk, t, rk, parity ^ 1, 1u, lane); \
+  PDS_STAMP_FLUSH;
+
 template <class V, int TR>
 __global__ __launch_bounds__(kBlock, (PDS_MIN_WAVES) * (256 / kBlock)) void step_kernel(const StepArgs a) {
-  PDS_STAMP_DECL
-  prefetch_kernargs();
-  constexpr int RM = merged_reset_variant<V, TR>() ? RM_MERGED : (inline_reset_single_step<V, TR>() ? RM_INLINE : RM_DEFERRED);
-  PDS_WAVE_SETUP(V, TR, RM, true)
-  // The loads are issued before anything else so that the scalar preamble of the kernel
-  // (kernel-argument loads, uniform constants) overlaps with their latency.
-  Loaded cur;
-  load_env<V>(a, ix, t, cur);
-  __builtin_amdgcn_sched_barrier(0);
-  PDS_STAMP(1);
-  PDS_STAMP_WAIT(2);
-  RngKey rk{a.seed_lo, a.seed_hi, 0u, 0u};
-  int parity;
-  PDS_CLOCK_TO_KEY(cur.clk, rk, parity)
-  EnvState S;
-  unpack_state<V>(a.k, cur, parity, S);
-  init_kept_obs<V>(a, rk, ix, S);
-  int qcount = 0;  // wave-uniform
-  step_once<V, TR, RM, true>(a, 0ll, rk, parity, ref_lds, tile, park, queue, scratch, lane, wave_base, ix, active, cur.act, S, qcount, nullptr, nullptr PDS_STAMP_ARG);
-  if (RM == RM_DEFERRED && qcount > 0) {
-    const float own_w[3] = {S.e.wx, S.e.wy, S.e.wz};
-    drain_reset_queue<V>(reload_args<104, heavy_variant<V>()>(a), rk, ref_lds, queue, qcount, lane, wave_base, tile, own_w, S.ns.bias);
-  }
-  PDS_STAMP(6);
-  advance_clock(reload_args<105, heavy_variant<V>()>(a).st.clk, t, rk, parity ^ 1, 1u, lane);
-  PDS_STAMP_FLUSH;
+  PDS_STEP_KERNEL_BODY(false)
+}
+// ... and its form that stores s0-s2 every other step (skip_state_variant; TR first: a kernel name of its own, not a longer
+// spelling of step_kernel<V, TR>'s)
+template <int TR, class V>
+__global__ __launch_bounds__(kBlock, (PDS_MIN_WAVES) * (256 / kBlock)) void skip_step_kernel(const StepArgs a) {
+  static_assert(skip_state_variant<V>(), "the lean variants");
+  PDS_STEP_KERNEL_BODY(true)
 }
 
 // K env.step()s per launch for open-loop action sequences (pds_step_k): the env state stays in
@@ -1201,6 +1266,13 @@ inline void launch_variant(int kind, bool half_tile, dim3 grid, hipStream_t s, c
     if constexpr (step_k_rule(V::CTRL, V::GE, V::HOLD)) hipLaunchKernelGGL((step_k_kernel<V>), grid, dim3(kBlock), 0, s, a);
     else abort();
   } else {
+    if constexpr (skip_state_variant<V>()) {  // (kLaunchStepStoreAll: the handle asked for the kernels that store every step)
+      if (kind == kLaunchStep) {
+        if (half_tile) hipLaunchKernelGGL((skip_step_kernel<kHalfTileRows, V>), grid, dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((skip_step_kernel<kWave, V>), grid, dim3(kBlock), 0, s, a);
+        return;
+      }
+    }
     if constexpr (!V::ON && !V::LAT) {
       if (half_tile) {
         hipLaunchKernelGGL((step_kernel<V, kHalfTileRows>), grid, dim3(kBlock), 0, s, a);

@@ -32,7 +32,7 @@ constexpr int kMaxLatSteps = PDS_MAX_LATENCY_STEPS;  // rows of the latency acti
 
 // ---- packing of the per-env counter word --------------------------------------------------------
 // bits 0..15 env.step calls since reset | bit 16 quaternion == -Q(rpy) | bits 17..25 Circle ref_offset
-// | bits 26..28 action_idx of the latency ring (envs/agents.py:183,273) | bit 29 kCtrOhBit (below).
+// | bits 26..28 action_idx of the latency ring (envs/agents.py:183,273) | bit 29 kCtrOhBit | bit 30 kCtrBehindBit (below).
 // Circle keeps the PHASE (env.step calls + ref_offset) mod num_ref_points in bits 17..25, i.e. the index
 // of the current reference point (envs/circle.py:130): it advances by one per step with a wrap, so the
 // step needs no modulo; ref_offset itself is recovered where it is asked for (circle_ref_offset).
@@ -52,6 +52,20 @@ PDS_DEV uint32_t ctr_lat(uint32_t c) { return (c >> 26) & 0x7u; }
 // invalidate the regeneration's inputs: a masked reset (the clock of every tile advances), pds_set_tick, any pds_set_state.
 constexpr uint32_t kCtrOhBit = 1u << 29;
 PDS_DEV uint32_t ctr_oh(uint32_t c) { return (c >> 29) & 1u; }
+// bit 30 (the lean variants of the single-step kernel: control_mode PWM, no PT1 / DR / noise / latency): "s0-s2 of this env
+// are ONE STEP BEHIND" -- they hold s(k-1) while the counter word, the action ring and the outputs are those of step k.  Set
+// by a skip step (a launch whose tile clock tick is ODD) for the envs it stored no state for (all but the envs it reset and the
+// lanes that share a 128-byte line with one); the next launch of that kernel finds
+// u(k-1) in the ring, advances s(k-1) to s(k) with the instruction stream that computed it the first time, steps, stores and
+// clears the bit.  Nothing else understands the bit: csrc/pds_api.hip runs materialize_state_kernel (advance, store, clear)
+// in front of every other reader or partial writer of s0-s2 and of every rewrite of the counter word.
+// -DPDS_STATE_EVERY_OTHER_STEP=0 builds the library that stores s0-s2 every step (the bit is then never set); a handle created
+// under PDS_STATE_EVERY_STEP=1 launches those kernels out of the default library.
+#ifndef PDS_STATE_EVERY_OTHER_STEP
+#define PDS_STATE_EVERY_OTHER_STEP 1
+#endif
+constexpr uint32_t kCtrBehindBit = 1u << 30;
+PDS_DEV uint32_t ctr_behind(uint32_t c) { return (c >> 30) & 1u; }
 PDS_DEV uint32_t circle_ref_offset(uint32_t c, int ref_points) {  // not on the hot path
   const int d = (int)ctr_off(c) - (int)(ctr_step(c) % (uint32_t)ref_points);
   return (uint32_t)(d < 0 ? d + ref_points : d);
@@ -347,7 +361,8 @@ struct LaunchFlags {
 constexpr bool inline_single_step_rule(int task, bool on, bool lat, int ctrl) {
   return (on || lat) && task != PDS_TASK_TAKEOFF && !(task == PDS_TASK_CIRCLE && (lat || ctrl != 0));
 }
-enum LaunchKind { kLaunchStep = 0, kLaunchStepK = 1, kLaunchReset = 2 };
+// (kLaunchStepStoreAll: a single step with the kernel that stores s0-s2 every step, where the variant has both: kCtrBehindBit)
+enum LaunchKind { kLaunchStep = 0, kLaunchStepK = 1, kLaunchReset = 2, kLaunchStepStoreAll = 3 };
 // Which variants have a step_k_kernel (csrc/pds_step.h launch_variant instantiates by this rule, pds_step_k_fused states it for
 // the host): every control_mode PWM variant, and the PID modes in the pid family and on the latency ring -- not a PID mode
 // with the ground effect or with the Kalman hold, for which pds_step_k loops over pds_step.
