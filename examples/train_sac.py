@@ -37,15 +37,23 @@ def main():
     ap.add_argument("--no-fused", action="store_true", help="the torch autograd path")
     ap.add_argument("--fused-collect", action="store_true",
                     help="after warm-up, collect the vector steps between updates in one pds_collect launch")
+    ap.add_argument("--control-fused", action="store_true",
+                    help="with --fused-collect: the launch is pds_collect_control, which also flies AttitudeRate / Attitude and "
+                         "the latency ring on Hover and Circle")
+    ap.add_argument("--control-mode", default="PWM", choices=["PWM", "AttitudeRate", "Attitude"], help="the env's control_mode")
+    ap.add_argument("--use-latency", action="store_true", help="the env's delayed-action ring (the reference's 20 ms)")
     ap.add_argument("--log-dir", default=None, help="default: a fresh temporary directory")
     args = ap.parse_args()
-    env = pds.make(args.env, num_envs=args.num_envs, seed=args.seed)  # the reference's default config
+    env_kw = dict(control_mode=args.control_mode) if args.control_mode != "PWM" else {}  # (TakeOff fixes PWM and takes no keyword)
+    if args.use_latency:
+        env_kw["use_latency"] = True
+    env = pds.make(args.env, num_envs=args.num_envs, seed=args.seed, **env_kw)  # otherwise the reference's default config
     trainer = SACTrainer(env, epochs=args.epochs, steps_per_epoch=args.steps_per_epoch, updates_per_step=args.updates_per_step,
                          mini_batch_size=args.mini_batch_size, buffer_size=args.buffer_size, start_steps=args.start_steps,
                          lr=args.lr, alpha=args.alpha, seed=args.seed, fused=not args.no_fused,
-                         fused_collect=args.fused_collect)
+                         fused_collect=args.fused_collect, control_fused=args.control_fused)
     print(f"{args.env}: {env.num_envs} envs, obs_dim {env.obs_dim}, update path: {'fused HIP kernels' if trainer.fused else 'torch autograd'}, "
-          f"collection: {'one pds_collect launch per stretch' if trainer.collect_fused else 'per-step launches'}")
+          f"collection: {('one pds_collect_control launch per stretch' if trainer.control_fused else 'one pds_collect launch per stretch') if trainer.collect_fused else 'per-step launches'}")
     t0 = time.time()
     for e in range(args.epochs):
         i = trainer.learn_one_epoch()

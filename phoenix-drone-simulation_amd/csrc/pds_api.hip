@@ -1469,20 +1469,39 @@ extern "C" int pds_collect_supported(const pds_handle *h, const pds_mlp *pi, int
                  pi->d_out == (mode == kCollectSac ? 8 : 4) ? 1 : 0;
 }
 
-extern "C" int pds_collect(pds_handle *h, int K, int mode, const pds_mlp *pi, float act_limit, const float *d_log_std, uint64_t seed,
-                           uint64_t first_call, float *d_oa, float *d_obs2, float *d_rew, float *d_done, int64_t capacity,
-                           int64_t ptr, float *d_obs, float *d_ep_ret, float *d_ep_len, float *d_tile_stats, void *stream) {
+// what pds_collect_control flies: what pds_collect flies, and the PID control modes / the latency ring on Hover and Circle
+static bool collect_control_handle_ok(const pds_handle *h) {
+  return collect_env_supported(h->cfg.task, h->flags) || collect_control_env_supported(h->cfg.task, h->flags);
+}
+extern "C" int pds_collect_control_supported(const pds_handle *h, const pds_mlp *pi, int mode) {
+  if (!h || !pi) return PDS_EINVAL;
+  if (mode != kCollectDdpg && mode != kCollectSac) return 0;
+  return h->cfg.auto_reset && collect_control_handle_ok(h) && collect_shape_ok(h, pi) &&
+                 pi->d_out == (mode == kCollectSac ? 8 : 4) ? 1 : 0;
+}
+
+// ONE body for pds_collect and pds_collect_control (include/pds_collect_control.h): the checks, the argument block and the handle's
+// state afterwards are stated once; `control` admits the env configurations of collect_control_env_supported beside pds_collect's.
+static int collect_call(pds_handle *h, const char *fn, bool control, int K, int mode, const pds_mlp *pi, float act_limit,
+                        const float *d_log_std, uint64_t seed, uint64_t first_call, float *d_oa, float *d_obs2, float *d_rew,
+                        float *d_done, int64_t capacity, int64_t ptr, float *d_obs, float *d_ep_ret, float *d_ep_len,
+                        float *d_tile_stats, void *stream) {
   if (!h) return PDS_EINVAL;
-  const char *fn = "pds_collect";
   if (K < 1) return fail(h, PDS_EINVAL, "%s: K %d", fn, K);
   if (mode != kCollectDdpg && mode != kCollectSac) return fail(h, PDS_EINVAL, "%s: mode %d (0 DDPG, 1 SAC)", fn, mode);
   const bool any_null = !pi || (mode == kCollectDdpg && !d_log_std) || !d_oa || !d_obs2 || !d_rew || !d_done || !d_obs || !d_ep_ret ||
                         !d_ep_len || !d_tile_stats;
   if (const int rc = check_rollout_call(h, fn, any_null, nullptr, nullptr)) return rc;
-  if (!collect_env_supported(h->cfg.task, h->flags))
+  const bool plain = collect_env_supported(h->cfg.task, h->flags);
+  if (!plain && !control)
     return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: control_mode PWM without latency ring, Kalman hold "
                                      "or ground effect; noise off or the reference's default; TakeOff without motor dynamics) -- the "
                                      "per-step entry points give the same bits", fn);
+  if (!plain && !collect_control_env_supported(h->cfg.task, h->flags))
+    return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: what pds_collect flies, and Hover and Circle under "
+                                     "AttitudeRate / Attitude and / or with the latency ring; not built: Kalman hold, ground effect, "
+                                     "noise settings other than off or the reference's default, TakeOff with the latency ring or "
+                                     "motor dynamics) -- the per-step entry points give the same bits", fn);
   const int D = h->obs_dim;
   if (!collect_shape_ok(h, pi))
     return fail(h, PDS_EUNSUPPORTED, "%s: actor shape (d_in must be the observation width %d <= 64, hidden <= 64, relu or tanh)", fn, D);
@@ -1513,10 +1532,31 @@ extern "C" int pds_collect(pds_handle *h, int K, int mode, const pds_mlp *pi, fl
   ca.capacity = capacity; ca.ptr = ptr;
   ca.obs = d_obs; ca.ep_ret = d_ep_ret; ca.ep_len = d_ep_len; ca.tile_stats = d_tile_stats;
   return launch_rollout(h, fn, K, stream, [&](dim3 grid, hipStream_t s) {
-    if (h->cfg.task == PDS_TASK_HOVER) return launch_collect_hover(h->flags, grid, s, ca);
-    if (h->cfg.task == PDS_TASK_CIRCLE) return launch_collect_circle(h->flags, grid, s, ca);
-    return launch_collect_takeoff(h->flags, grid, s, ca);
+    const LaunchFlags &f = h->flags;
+    const bool hover = h->cfg.task == PDS_TASK_HOVER;
+    if (!plain) {  // (Hover or Circle: collect_control_env_supported)
+      if (!f.lat) return hover ? launch_collect_hover_pid(f, grid, s, ca) : launch_collect_circle_pid(f, grid, s, ca);
+      if (f.ctrl == 0) return hover ? launch_collect_hover_lat(f, grid, s, ca) : launch_collect_circle_lat(f, grid, s, ca);
+      return hover ? launch_collect_hover_pid_lat(f, grid, s, ca) : launch_collect_circle_pid_lat(f, grid, s, ca);
+    }
+    if (hover) return launch_collect_hover(f, grid, s, ca);
+    if (h->cfg.task == PDS_TASK_CIRCLE) return launch_collect_circle(f, grid, s, ca);
+    return launch_collect_takeoff(f, grid, s, ca);
   });
+}
+extern "C" int pds_collect(pds_handle *h, int K, int mode, const pds_mlp *pi, float act_limit, const float *d_log_std, uint64_t seed,
+                           uint64_t first_call, float *d_oa, float *d_obs2, float *d_rew, float *d_done, int64_t capacity,
+                           int64_t ptr, float *d_obs, float *d_ep_ret, float *d_ep_len, float *d_tile_stats, void *stream) {
+  return collect_call(h, "pds_collect", false, K, mode, pi, act_limit, d_log_std, seed, first_call, d_oa, d_obs2, d_rew, d_done, capacity,
+                      ptr, d_obs, d_ep_ret, d_ep_len, d_tile_stats, stream);
+}
+// the same call that also takes the PID control modes and the latency ring (include/pds_collect_control.h)
+extern "C" int pds_collect_control(pds_handle *h, int K, int mode, const pds_mlp *pi, float act_limit, const float *d_log_std,
+                                   uint64_t seed, uint64_t first_call, float *d_oa, float *d_obs2, float *d_rew, float *d_done,
+                                   int64_t capacity, int64_t ptr, float *d_obs, float *d_ep_ret, float *d_ep_len, float *d_tile_stats,
+                                   void *stream) {
+  return collect_call(h, "pds_collect_control", true, K, mode, pi, act_limit, d_log_std, seed, first_call, d_oa, d_obs2, d_rew, d_done,
+                      capacity, ptr, d_obs, d_ep_ret, d_ep_len, d_tile_stats, stream);
 }
 
 // number of envs whose dynamic state holds a NaN or an Inf (diagnostic, see pds_count_nonfinite)

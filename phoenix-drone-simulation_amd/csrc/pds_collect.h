@@ -299,4 +299,35 @@ inline bool launch_collect_task(const LaunchFlags &f, dim3 grid, hipStream_t s, 
   return collect_lean_or_full<TASK, false>(f, l);
 }
 
+// ---- the PID control modes and the latency ring (pds_collect_control, include/pds_collect_control.h) ----
+// The same kernel text: CTRL and LAT are parameters of the variant, and everything they add lives in the env wave.  The PID state
+// (rate and attitude integrals and last errors) is part of EnvState: loaded once by PDS_ENV_WAVE_BEGIN, carried in registers over
+// the K steps, zeroed in place where step_once resets a finished env (control.reset()), stored behind the loop by
+// PDS_ENV_WAVE_STORE.  The delayed-action ring [lat_steps, N] float4 stays in memory as in every other kernel on step_once; what
+// the env wave carries of it is its index (in the counter word).  Per sub-step it reads the row the index points at -- the PWM or
+// the PID targets come from that delayed action -- and overwrites it with `act`, the exploration action the network waves handed
+// over (after the rule's clamp); a finished env's rows are redrawn in place (lat_normals4).  Reward, the observation's action
+// entries and `oa` take the action the policy chose, not the delayed one.  Rows of the table: fused_lean_or_full<TASK, CTRL, LAT>
+// of csrc/pds_rollout.h ({lean, reference default} x {with, without motor dynamics}), Hover and Circle --
+// collect_control_env_supported().  One translation unit per family keeps the build parallel.
+template <int TASK>
+inline bool launch_collect_pid(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca) {  // a PID mode, no ring
+  if (!collect_control_env_supported(TASK, f) || f.lat || f.ctrl == 0) return false;
+  const CollectLaunch l{grid, s, ca};
+  if (f.ctrl == 1) return fused_lean_or_full<TASK, 1, false>(f, l);
+  return fused_lean_or_full<TASK, 2, false>(f, l);
+}
+template <int TASK>
+inline bool launch_collect_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca) {  // control_mode PWM on the ring
+  if (!collect_control_env_supported(TASK, f) || !f.lat || f.ctrl != 0) return false;
+  return fused_lean_or_full<TASK, 0, true>(f, CollectLaunch{grid, s, ca});
+}
+template <int TASK>
+inline bool launch_collect_pid_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca) {  // a PID mode on the ring
+  if (!collect_control_env_supported(TASK, f) || !f.lat || f.ctrl == 0) return false;
+  const CollectLaunch l{grid, s, ca};
+  if (f.ctrl == 1) return fused_lean_or_full<TASK, 1, true>(f, l);
+  return fused_lean_or_full<TASK, 2, true>(f, l);
+}
+
 }  // namespace pds

@@ -34,9 +34,26 @@ inline bool collect_env_supported(int task, const LaunchFlags &f) {
   return (lean || full) && !(task == PDS_TASK_TAKEOFF && f.motor);
 }
 
-// one translation unit per task: csrc/pds_collect_<task>.hip
+// What pds_collect_control (include/pds_collect_control.h) flies beside those: Hover and Circle under a PID control mode
+// (AttitudeRate, Attitude) and / or with the latency ring -- the five (control mode, latency) pairs other than (PWM, none) -- noise
+// all off or the reference's default, with and without motor dynamics.  Not built: Kalman hold, ground effect, partial noise
+// settings, TakeOff (envs/takeoff.py:225 fixes control_mode PWM; its latency form is not built either).
+inline bool collect_control_env_supported(int task, const LaunchFlags &f) {
+  if (f.ge || f.hold || task == PDS_TASK_TAKEOFF || (f.ctrl == 0 && !f.lat)) return false;
+  const bool lean = !f.dr && !f.tn && !f.on, full = f.dr && f.tn && f.on;
+  return lean || full;
+}
+
+// one translation unit per task: csrc/pds_collect_<task>.hip; the PID modes and the latency ring in three more per task:
+// csrc/pds_collect_<task>_pid.hip (a PID mode, no ring), _lat.hip (PWM on the ring), _pid_lat.hip (a PID mode on the ring)
 bool launch_collect_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca);
 bool launch_collect_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca);
 bool launch_collect_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca);
+bool launch_collect_hover_pid(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca);
+bool launch_collect_hover_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca);
+bool launch_collect_hover_pid_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca);
+bool launch_collect_circle_pid(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca);
+bool launch_collect_circle_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca);
+bool launch_collect_circle_pid_lat(const LaunchFlags &f, dim3 grid, hipStream_t s, const CollectArgs &ca);
 
 }  // namespace pds

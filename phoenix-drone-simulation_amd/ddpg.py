@@ -21,7 +21,8 @@ copy, no autograd graph.  fused=False is the same recipe in torch autograd (torc
 tested against.  fused_collect=True (csrc/pds_collect.h): once warm-up is over, the vector steps up to the next update are ONE
 launch of pds_collect -- actor, exploration noise, env step, the ring rows, the episode statistics -- where step_env issues
 about three dozen; `trainer.collect_fused` reports whether that kernel runs (pds_collect_supported: control_mode PWM, history 2,
-no latency / hold / ground effect).  With the flag on, DDPG acts through pds_ddpg_explore on the per-step path too (tanhf where
+no latency / hold / ground effect; control_fused=True asks pds_collect_control instead, which also flies AttitudeRate / Attitude
+and the latency ring on Hover and Circle, include/pds_collect_control.h -- the default False keeps every answer as it was).  With the flag on, DDPG acts through pds_ddpg_explore on the per-step path too (tanhf where
 fused_collect=False calls torch.tanh: the one documented difference between the two settings).
 Shapes the kernels are not built for (D + 4 > 64: observation_history_size >= 4, TakeOff from 3; hidden
 sizes above 64, e.g. the reference's (400, 300)) take the autograd path; `trainer.fused` reports which path is in use.
@@ -217,7 +218,8 @@ class OffPolicyTrainer:
     _init_loop() and _init_collect(), and provides get_action(obs), update(), _update_info() and _progress_columns()."""
 
     fused_collect = False   # the constructor's keyword
-    collect_fused = False   # ... and whether pds_collect runs after warm-up
+    control_fused = False   # ... and the one that lets pds_collect_control take the collection (PID control modes, latency ring)
+    collect_fused = False   # ... and whether pds_collect / pds_collect_control runs after warm-up
     collect_launches = 0
 
     def _init_loop(self):
@@ -228,15 +230,18 @@ class OffPolicyTrainer:
         self.total_steps, self.updates, self._since_update = 0, 0, 0
         self.epoch, self.log, self._t_total = 0, [], 0.0
 
-    def _init_collect(self, fused_collect, mode, log_std=None):
+    def _init_collect(self, fused_collect, mode, log_std=None, control_fused=False):
         """fused_collect=True: one pds_collect launch per stretch of vector steps between updates, where the kernel is built for the
-        env and the actor `fm_pi` (mode: fused.COLLECT_DDPG / COLLECT_SAC; log_std: DDPG's [4] log noise scale)."""
-        self.fused_collect = bool(fused_collect)
+        env and the actor `fm_pi` (mode: fused.COLLECT_DDPG / COLLECT_SAC; log_std: DDPG's [4] log noise scale).  control_fused=True
+        (it changes nothing without fused_collect=True): the launch is pds_collect_control, built for the PID control modes and the
+        latency ring as well."""
+        self.fused_collect, self.control_fused = bool(fused_collect), bool(control_fused)
         self._collect_mode, self._collect_log_std = mode, log_std
         self.collect_fused, self.collect_launches, self._cobs = False, 0, None
         if self.fused_collect and self.fused:
-            from .fused import collect_supported
-            self.collect_fused = collect_supported(self.env, self.fm_pi, mode)
+            from .fused import collect_control_supported, collect_supported
+            supported = collect_control_supported if self.control_fused else collect_supported
+            self.collect_fused = supported(self.env, self.fm_pi, mode)
 
     # ---- K vector steps in one launch ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -255,7 +260,8 @@ class OffPolicyTrainer:
         buf = self.buffer
         slab = torch.empty(collect_tiles(self.env), 8, device=self.env.device)
         fused_collect(self.env, self.fm_pi, self._collect_mode, k, self.act_limit, self._collect_log_std, self.seed,
-                      self._noise_calls + 1, buf.oa, buf.obs2, buf.rew, buf.done, buf.ptr, self._cobs, self.ep_ret, self.ep_len, slab)
+                      self._noise_calls + 1, buf.oa, buf.obs2, buf.rew, buf.done, buf.ptr, self._cobs, self.ep_ret, self.ep_len, slab,
+                      control=self.control_fused)
         self._noise_calls += k
         buf.advance(k)
         self.collect_launches += 1
@@ -363,7 +369,7 @@ class DDPGTrainer(OffPolicyTrainer):
 
     def __init__(self, env, ac_kwargs=None, gamma=0.99, polyak=0.995, pi_lr=1e-4, q_lr=1e-3, mini_batch_size=128,
                  act_noise=0.1, warmup_steps=10000, update_after=1000, update_every=50, buffer_size=int(1e6), epochs=100,
-                 steps_per_epoch=64, updates_per_step=1, seed=0, fused=True, fused_collect=False):
+                 steps_per_epoch=64, updates_per_step=1, seed=0, fused=True, fused_collect=False, control_fused=False):
         if not getattr(env, "_auto_reset", True):
             raise ValueError("DDPGTrainer needs an env with auto_reset=True")
         self.env, self.N, self.D = env, int(env.num_envs), int(env.obs_dim)
@@ -407,7 +413,7 @@ class DDPGTrainer(OffPolicyTrainer):
         self._noise_calls = 0
         self._init_loop()
         from .fused import COLLECT_DDPG
-        self._init_collect(fused_collect, COLLECT_DDPG, self._log_noise)
+        self._init_collect(fused_collect, COLLECT_DDPG, self._log_noise, control_fused=control_fused)
         self._last = None  # (loss_q, loss_pi, index) of the latest update, device tensors
 
     # ---- acting ------------------------------------------------------------------------------------------------------------

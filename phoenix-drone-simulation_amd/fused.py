@@ -241,18 +241,27 @@ def collect_supported(env, fm_pi, mode):
     return env.lib.pds_collect_supported(env._handle, C.byref(fm_pi.m), int(mode)) == 1
 
 
+def collect_control_supported(env, fm_pi, mode):
+    """True when pds_collect_control (include/pds_collect_control.h) has a kernel for this env and actor in this mode: wherever
+    collect_supported holds, and on Hover and Circle under control_mode AttitudeRate / Attitude and / or with the latency ring
+    (noise off or the reference's default, with and without motor dynamics)."""
+    return env.lib.pds_collect_control_supported(env._handle, C.byref(fm_pi.m), int(mode)) == 1
+
+
 def collect_tiles(env):
     """rows of the [tiles, 8] statistics slab of one fused_collect launch"""
     return (int(env.num_envs) + 63) // 64
 
 
 def fused_collect(env, fm_pi, mode, K, act_limit, log_std, seed, first_call, oa, obs2, rew, done, ptr, obs, ep_ret, ep_len,
-                  tile_stats):
+                  tile_stats, control=False):
     """ONE launch for K closed-loop vector steps of an off-policy trainer (include/pds.h pds_collect, csrc/pds_collect.h): step s
     fills the N rows at (ptr + s N) mod capacity of the ring oa / obs2 / rew / done (capacity = oa.shape[0]), obs [N, D] is
     o(0) on entry and o(K) on return, ep_ret / ep_len run on, tile_stats [collect_tiles(env), 8] receives the finished episodes'
-    statistics.  Raises NotImplementedError / ValueError where the entry point refuses (the env is left as it was)."""
-    native.call("pds_collect", env._handle, int(K), int(mode), fm_pi, float(act_limit), log_std, int(seed) & (2 ** 64 - 1),
+    statistics.  control=True: pds_collect_control (include/pds_collect_control.h), which also flies the PID control modes and
+    the latency ring -- collect_control_supported -- and is the same launch wherever pds_collect has one.  Raises
+    NotImplementedError / ValueError where the entry point refuses (the env is left as it was)."""
+    native.call("pds_collect_control" if control else "pds_collect", env._handle, int(K), int(mode), fm_pi, float(act_limit), log_std, int(seed) & (2 ** 64 - 1),
                 int(first_call), oa, obs2, rew, done, int(oa.shape[0]), int(ptr), obs, ep_ret, ep_len, tile_stats,
                 on=obs, handle=env._handle)
     env._last_obs = obs  # (what a masked reset() copies for the envs outside the mask)

@@ -158,6 +158,12 @@ HISTORY_STATS_SIGNATURES = {
     "pds_evaluate_history_stats_supported": (_i32, [_vp, _i32]),
     "pds_evaluate_policies_history_stats": (_i32, [_vp, _i32] + _eval[1:] + [_vp] * 3),
 }
+# ... and of include/pds_collect_control.h, the collection under the PID control modes and the latency ring
+# (tests/test_collect_control_cpu.py): the rows of pds_collect_supported and pds_collect
+COLLECT_CONTROL_SIGNATURES = {
+    "pds_collect_control_supported": SIGNATURES["pds_collect_supported"],
+    "pds_collect_control": SIGNATURES["pds_collect"],
+}
 
 _lib = None
 
@@ -178,7 +184,7 @@ def load():
     # an OLDER build given through PDS_LIB for a same-box A/B (profiles/tools/ab_lib.sh) may lack the newer entry points: those
     # are skipped; the shipped library must have every name (AttributeError here, and tests/test_host_cpu.py)
     older = bool(os.environ.get("PDS_LIB"))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()) + list(COLLECT_CONTROL_SIGNATURES.items()):
         if older and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -36,7 +36,8 @@ optimiser over both nets), the two launches of pds_sac_policy_grad, pds_polyak o
 torch autograd.  Shapes the kernels are not built for (D + 4 > 64, hidden sizes above 64 such as the reference's (400, 300))
 take the autograd path; `trainer.fused` reports which path is in use.  fused_collect=True: after warm-up the vector steps up to
 the next update are one pds_collect launch (ddpg.py, csrc/pds_collect.h); SAC already acts through pds_sac_sample, whose device
-function the kernel calls, so a run with the flag on is bitwise the run with it off.  Single process only."""
+function the kernel calls, so a run with the flag on is bitwise the run with it off.  control_fused=True: the launch is
+pds_collect_control, which also flies AttitudeRate / Attitude and the latency ring (ddpg.py).  Single process only."""
 import math
 import os
 from copy import deepcopy
@@ -189,7 +190,7 @@ class SACTrainer(OffPolicyTrainer):
 
     def __init__(self, env, ac_kwargs=None, alpha=0.2, gamma=0.99, polyak=0.995, lr=1e-3, mini_batch_size=64, start_steps=10000,
                  update_after=1000, update_every=50, buffer_size=int(1e6), epochs=100, steps_per_epoch=64, updates_per_step=1,
-                 seed=0, fused=True, fused_collect=False):
+                 seed=0, fused=True, fused_collect=False, control_fused=False):
         if not getattr(env, "_auto_reset", True):
             raise ValueError("SACTrainer needs an env with auto_reset=True")
         if int(env.act_dim) != ACT_DIM:
@@ -237,7 +238,7 @@ class SACTrainer(OffPolicyTrainer):
         self._noise_calls = 0
         self._init_loop()
         from .fused import COLLECT_SAC
-        self._init_collect(fused_collect, COLLECT_SAC)
+        self._init_collect(fused_collect, COLLECT_SAC, control_fused=control_fused)
         self._last = None  # (loss_q, loss_pi, mean logp, index) of the latest update, device tensors
 
     # ---- acting ------------------------------------------------------------------------------------------------------------

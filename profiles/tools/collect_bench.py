@@ -14,6 +14,15 @@ epoch.  The one pass condition: the fused side is not slower than the per-step s
 status 1 otherwise).
 
   python profiles/tools/collect_bench.py --out profiles/collect_timing.txt
+
+--env / --control-mode / --use-latency / --motor-dynamics choose another env configuration; --control-fused puts pds_collect_control
+(include/pds_collect_control.h) on the fused side, which is what flies a PID control mode or the latency ring.  The two sides of a
+row are timed in alternating blocks (--rounds blocks of --reps epochs each per side), so a drift of the shared host falls on both;
+the medians are over all of a side's epochs.  --append adds to --out instead of replacing it:
+
+  python profiles/tools/collect_bench.py --control-mode Attitude --control-fused --out profiles/collect_control_timing.txt
+  python profiles/tools/collect_bench.py --env DroneCircleSimpleEnv-v0 --control-mode AttitudeRate --use-latency --motor-dynamics \
+      --control-fused --out profiles/collect_control_timing.txt --append
 """
 import argparse
 import os
@@ -49,11 +58,23 @@ def timed(fn, warmup, reps):
     return [ev[k].elapsed_time(ev[k + 1]) for k in range(reps)]
 
 
+def timed_alternating(fns, warmup, reps, rounds):
+    """`rounds` blocks of `reps` timed calls per function, the functions taking turns block by block -> one list of ms per function"""
+    out = [[] for _ in fns]
+    for r in range(rounds):
+        for j, fn in enumerate(fns):
+            out[j] += timed(fn, warmup if r == 0 else 1, reps)
+    return out
+
+
+ENV_ID, ENV_KW, CONTROL_FUSED = HOVER, {}, False  # main() sets them from the command line
+
+
 def collector(algo, N, K, flag):
     """a trainer whose epochs are EPOCH vector steps of collection, an update point with no update every K of them"""
-    env = pds.make(HOVER, num_envs=N, seed=1)
+    env = pds.make(ENV_ID, num_envs=N, seed=1, **ENV_KW)
     kw = dict(seed=0, buffer_size=16 * N, update_after=0, update_every=K * N, updates_per_step=0, steps_per_epoch=EPOCH,
-              fused_collect=flag)
+              fused_collect=flag, control_fused=flag and CONTROL_FUSED)
     tr = DDPGTrainer(env, warmup_steps=0, **kw) if algo == "ddpg" else SACTrainer(env, start_steps=0, **kw)
     assert tr.fused and tr.collect_fused == flag
     return tr
@@ -63,28 +84,44 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3, help="alternating blocks of --reps epochs per side")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--append", action="store_true", help="add to --out")
+    ap.add_argument("--env", default=HOVER)
+    ap.add_argument("--control-mode", default="PWM", choices=["PWM", "AttitudeRate", "Attitude"])
+    ap.add_argument("--use-latency", action="store_true")
+    ap.add_argument("--motor-dynamics", action="store_true")
+    ap.add_argument("--control-fused", action="store_true", help="the fused side is pds_collect_control")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "collect_bench.py needs a HIP device"
-    out = open(args.out, "w") if args.out else sys.stdout
-    print(f"# collection alone, Hover at the reference defaults (D = 34), nets (64, 64) relu, {torch.cuda.get_device_name(0)}; device "
-          f"events, {args.warmup} warm-up epochs of {EPOCH} vector steps, then {args.reps}: ms per K vector steps (epoch / {EPOCH} x K), "
-          f"median [min .. max]; M env-steps/s from the medians", file=out)
+    global ENV_ID, ENV_KW, CONTROL_FUSED
+    ENV_ID, CONTROL_FUSED = args.env, args.control_fused
+    ENV_KW = dict(control_mode=args.control_mode) if args.control_mode != "PWM" else {}
+    if args.use_latency:
+        ENV_KW["use_latency"] = True
+    if args.motor_dynamics:
+        ENV_KW["use_motor_dynamics"] = True
+    entry = "pds_collect_control" if CONTROL_FUSED else "pds_collect"
+    out = open(args.out, "a" if args.append else "w") if args.out else sys.stdout
+    print(f"# collection alone, {ENV_ID} at the reference defaults {ENV_KW or ''}, nets (64, 64) relu, {torch.cuda.get_device_name(0)}; device "
+          f"events, the two sides in {args.rounds} alternating blocks of {args.reps} epochs of {EPOCH} vector steps ({args.warmup} warm-up epochs "
+          f"in front of the first block, 1 in front of the others): ms per K vector steps (epoch / {EPOCH} x K), median [min .. max] "
+          f"over a side's {args.rounds * args.reps} epochs; M env-steps/s from the medians", file=out)
     ok = True
     for algo in ("ddpg", "sac"):
         for N in (1024, 8192, 65536):
             for K in (1, 8):
                 off, on = collector(algo, N, K, False), collector(algo, N, K, True)
                 per_k = lambda ts: [t * K / EPOCH for t in ts]
-                t_off = per_k(timed(off.learn_one_epoch, args.warmup, args.reps))
-                t_on = per_k(timed(on.learn_one_epoch, args.warmup, args.reps))
+                t_off, t_on = (per_k(t) for t in timed_alternating((off.learn_one_epoch, on.learn_one_epoch), args.warmup, args.reps, args.rounds))
+                epochs = args.warmup + args.rounds - 1 + args.rounds * args.reps
+                assert on.collect_launches == EPOCH // K * epochs and off.collect_launches == 0
                 t_k = timed(lambda: on.collect(K), args.warmup, args.reps)
-                assert on.collect_launches == (EPOCH // K + 1) * (args.warmup + args.reps) and off.collect_launches == 0
                 m_off, m_on, m_k = (float(np.median(t)) for t in (t_off, t_on, t_k))
                 ratio = m_off / m_on
                 ok = ok and ratio >= 1.0
                 rate = lambda ms: K * N / ms / 1e3
-                print(f"{algo:4s} N {N:6d} K {K} | per-step ms {fmt(t_off)} = {rate(m_off):8.2f} M/s | pds_collect ms {fmt(t_on)} = "
+                print(f"{algo:4s} N {N:6d} K {K} | per-step ms {fmt(t_off)} = {rate(m_off):8.2f} M/s | {entry} ms {fmt(t_on)} = "
                       f"{rate(m_on):8.2f} M/s | per-step / fused {ratio:6.2f} | collect() alone ms {fmt(t_k)} = {rate(m_k):8.2f} M/s",
                       file=out, flush=True)
                 off.env.close(); on.env.close()
@@ -93,8 +130,8 @@ def main():
     for algo in ("ddpg", "sac"):
         ms = {}
         for flag in (False, True):
-            env = pds.make(HOVER, num_envs=1024, seed=1)
-            kw = dict(seed=0, buffer_size=1 << 18, update_after=1024, steps_per_epoch=64, fused_collect=flag)
+            env = pds.make(ENV_ID, num_envs=1024, seed=1, **ENV_KW)
+            kw = dict(seed=0, buffer_size=1 << 18, update_after=1024, steps_per_epoch=64, fused_collect=flag, control_fused=flag and CONTROL_FUSED)
             tr = DDPGTrainer(env, warmup_steps=2048, **kw) if algo == "ddpg" else SACTrainer(env, start_steps=2048, **kw)
             tr.learn_one_epoch()  # warm-up and the first updates
             ts = []
