@@ -35,9 +35,19 @@ def main():
     ap.add_argument("--observation-history-size", type=int, default=2,
                     help="the reference's history of [o, u] pairs fed to the networks (envs/base.py:44; experiments/04_*: 1, 2, 4, 6, 8); "
                          "up to 192 network inputs stay on the fused kernels and the rollout is one launch (pds_rollout_history)")
+    ap.add_argument("--use-latency", action="store_true",
+                    help="delay the actions through the reference's latency ring (CrazyFlieAgent(use_latency=True), experiments/07_*)")
+    ap.add_argument("--latency", type=float, default=0.015, help="the delay in seconds (buf_size = latency // time step rows)")
+    ap.add_argument("--history-latency", action="store_true",
+                    help="with --use-latency and a history size other than 2: resolve the history entries that alias the ring's last "
+                         "row (DroneVecEnv(history_latency=True)); without it that combination is refused")
     ap.add_argument("--pi-hidden", type=int, nargs=2, default=(50, 50), help="policy hidden sizes (experiments/04_*: 32 32 / 48 48 / 64 64)")
     args = ap.parse_args()
     env_kw = dict(observation_history_size=args.observation_history_size) if args.observation_history_size != 2 else {}
+    if args.use_latency:
+        env_kw.update(use_latency=True, latency=args.latency)
+    if args.history_latency:
+        env_kw.update(history_latency=True)
     ac_kwargs = {"pi": {"hidden_sizes": tuple(args.pi_hidden), "activation": "relu"}, "val": {"hidden_sizes": (64, 64), "activation": "tanh"}}
     # one process per GPU (the reference: mpi_fork over CPU cores, examples/train_with_multi_cores.py):
     #   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_ppo.py ...

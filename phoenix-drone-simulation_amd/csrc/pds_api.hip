@@ -18,6 +18,7 @@
 #include "pds_evaluate_args.h"
 #include "pds_evaluate_hist_args.h"
 #include "pds_simopt.h"
+#include "../../include/pds_history_latency.h"
 
 namespace pds {
 
@@ -1132,27 +1133,62 @@ extern "C" int pds_rollout(pds_handle *h, int T, const pds_mlp *pi, const pds_ml
   });
 }
 
-// One launch per rollout for observation histories other than 2: csrc/pds_rollout_hist.h.
+// One launch per rollout for observation histories other than 2: csrc/pds_rollout_hist.h.  ONE body for pds_rollout_history and
+// pds_rollout_history_latency (include/pds_history_latency.h): the checks, the argument block and the launch; `latency`: the entry
+// point that flies the latency ring (its own support rule and launchers) -- pds_rollout_history answers a latency handle as before.
+static int rollout_history_call(pds_handle *h, const char *fn, bool latency, int T, int history, const pds_mlp *pi, const float *d_mean,
+                                const float *d_std, float eps, const float *d_log_std, uint64_t seed, const uint64_t *d_call_base,
+                                uint64_t call_offset, int deterministic, float *d_obs_buf, float *d_act_buf, float *d_logp_buf,
+                                float *d_rew_buf, uint8_t *d_term_buf, uint8_t *d_trunc_buf, float *d_cost_buf, float *d_fin_rows,
+                                int32_t *d_fin_step, int slots, float *d_ep_ret, float *d_ep_len, float *d_stats, void *stream);
 extern "C" int pds_rollout_history(pds_handle *h, int T, int history, const pds_mlp *pi, const float *d_mean, const float *d_std,
                                    float eps, const float *d_log_std, uint64_t seed, const uint64_t *d_call_base,
                                    uint64_t call_offset, int deterministic, float *d_obs_buf, float *d_act_buf,
                                    float *d_logp_buf, float *d_rew_buf, uint8_t *d_term_buf, uint8_t *d_trunc_buf,
                                    float *d_cost_buf, float *d_fin_rows, int32_t *d_fin_step, int slots, float *d_ep_ret,
                                    float *d_ep_len, float *d_stats, void *stream) {
+  return rollout_history_call(h, "pds_rollout_history", false, T, history, pi, d_mean, d_std, eps, d_log_std, seed, d_call_base,
+                              call_offset, deterministic, d_obs_buf, d_act_buf, d_logp_buf, d_rew_buf, d_term_buf, d_trunc_buf,
+                              d_cost_buf, d_fin_rows, d_fin_step, slots, d_ep_ret, d_ep_len, d_stats, stream);
+}
+extern "C" int pds_rollout_history_latency_supported(const pds_handle *h, int history) {
   if (!h) return PDS_EINVAL;
-  if (T < 1 || history < 1 || slots < 1) return fail(h, PDS_EINVAL, "pds_rollout_history: T %d, history %d, slots %d", T, history, slots);
+  return h->cfg.auto_reset && rollout_hist_latency_supported(h->cfg.task, h->flags) && history >= 1 &&
+                 (long long)history * (h->obs_dim / 2) <= 192 ? 1 : 0;
+}
+extern "C" int pds_rollout_history_latency(pds_handle *h, int T, int history, const pds_mlp *pi, const float *d_mean,
+                                           const float *d_std, float eps, const float *d_log_std, uint64_t seed,
+                                           const uint64_t *d_call_base, uint64_t call_offset, int deterministic, float *d_obs_buf,
+                                           float *d_act_buf, float *d_logp_buf, float *d_rew_buf, uint8_t *d_term_buf,
+                                           uint8_t *d_trunc_buf, float *d_cost_buf, float *d_fin_rows, int32_t *d_fin_step, int slots,
+                                           float *d_ep_ret, float *d_ep_len, float *d_stats, void *stream) {
+  return rollout_history_call(h, "pds_rollout_history_latency", true, T, history, pi, d_mean, d_std, eps, d_log_std, seed, d_call_base,
+                              call_offset, deterministic, d_obs_buf, d_act_buf, d_logp_buf, d_rew_buf, d_term_buf, d_trunc_buf,
+                              d_cost_buf, d_fin_rows, d_fin_step, slots, d_ep_ret, d_ep_len, d_stats, stream);
+}
+static int rollout_history_call(pds_handle *h, const char *fn, bool latency, int T, int history, const pds_mlp *pi, const float *d_mean,
+                                const float *d_std, float eps, const float *d_log_std, uint64_t seed, const uint64_t *d_call_base,
+                                uint64_t call_offset, int deterministic, float *d_obs_buf, float *d_act_buf, float *d_logp_buf,
+                                float *d_rew_buf, uint8_t *d_term_buf, uint8_t *d_trunc_buf, float *d_cost_buf, float *d_fin_rows,
+                                int32_t *d_fin_step, int slots, float *d_ep_ret, float *d_ep_len, float *d_stats, void *stream) {
+  if (!h) return PDS_EINVAL;
+  if (T < 1 || history < 1 || slots < 1) return fail(h, PDS_EINVAL, "%s: T %d, history %d, slots %d", fn, T, history, slots);
   const bool any_null = !pi || !d_log_std || !d_obs_buf || !d_act_buf || !d_logp_buf || !d_rew_buf || !d_term_buf || !d_trunc_buf ||
                         !d_cost_buf || !d_fin_rows || !d_fin_step || !d_ep_ret || !d_ep_len || !d_stats;
-  if (const int rc = check_rollout_call(h, "pds_rollout_history", any_null, d_mean, d_std)) return rc;
+  if (const int rc = check_rollout_call(h, fn, any_null, d_mean, d_std)) return rc;
   const int half = h->obs_dim / 2, HS = history * half;
-  if (HS > 192) return fail(h, PDS_EUNSUPPORTED, "pds_rollout_history: %d x %d = %d network inputs (<= 192)", history, half, HS);
+  if (HS > 192) return fail(h, PDS_EUNSUPPORTED, "%s: %d x %d = %d network inputs (<= 192)", fn, history, half, HS);
   if (!rollout_net_ok(pi, HS) || pi->d_out != 4)
-    return fail(h, PDS_EINVAL, "pds_rollout_history: actor shape (d_in must be history x half = %d, hidden <= 64, d_out 4)", HS);
+    return fail(h, PDS_EINVAL, "%s: actor shape (d_in must be history x half = %d, hidden <= 64, d_out 4)", fn, HS);
   // max_episode_steps bounds how often the TimeLimit can cut one env within T steps; + the rollout's last step
   if (slots < T / h->cfg.max_episode_steps + 2)
-    return fail(h, PDS_EINVAL, "pds_rollout_history: slots %d < T / max_episode_steps + 2 = %d", slots, T / h->cfg.max_episode_steps + 2);
-  if (!rollout_buffers_aligned(d_act_buf, d_obs_buf)) return fail(h, PDS_EINVAL, "pds_rollout_history: alignment");
-  if (!rollout_hist_supported(h->cfg.task, h->flags))
+    return fail(h, PDS_EINVAL, "%s: slots %d < T / max_episode_steps + 2 = %d", fn, slots, T / h->cfg.max_episode_steps + 2);
+  if (!rollout_buffers_aligned(d_act_buf, d_obs_buf)) return fail(h, PDS_EINVAL, "%s: alignment", fn);
+  if (latency && !rollout_hist_latency_supported(h->cfg.task, h->flags))
+    return fail(h, PDS_EUNSUPPORTED, "pds_rollout_history_latency: no kernel for this env configuration (built: Hover and Circle on the "
+                                     "latency ring in every control mode, noise off or the reference's default; not TakeOff, the Kalman hold "
+                                     "or the ground effect) -- the per-step kernels give the same bits");
+  if (!latency && !rollout_hist_supported(h->cfg.task, h->flags))
     return fail(h, PDS_EUNSUPPORTED, "pds_rollout_history: no kernel for this env configuration (built: every control mode without latency ring, "
                                      "Kalman hold or ground effect; noise off or the reference's default; TakeOff without motor dynamics) "
                                      "-- the per-step kernels give the same bits");
@@ -1164,7 +1200,12 @@ extern "C" int pds_rollout_history(pds_handle *h, int T, int history, const pds_
   ra.obs_buf = d_obs_buf;
   ra.fin_rows = d_fin_rows; ra.fin_step = d_fin_step;
   const int hn = rollout_hist_tiles(HS);
-  return launch_rollout(h, "pds_rollout_history", T, stream, [&](dim3 grid, hipStream_t s) {
+  return launch_rollout(h, fn, T, stream, [&](dim3 grid, hipStream_t s) {
+    if (latency) {  // (Hover or Circle: rollout_hist_latency_supported)
+      const bool hover = h->cfg.task == PDS_TASK_HOVER;
+      if (h->flags.ctrl != 0) return hover ? launch_rollout_hist_hover_pid_lat(h->flags, hn, grid, s, ra) : launch_rollout_hist_circle_pid_lat(h->flags, hn, grid, s, ra);
+      return hover ? launch_rollout_hist_hover_lat(h->flags, hn, grid, s, ra) : launch_rollout_hist_circle_lat(h->flags, hn, grid, s, ra);
+    }
     if (h->flags.ctrl != 0) {  // (TakeOff fixes control_mode PWM)
       if (h->cfg.task == PDS_TASK_HOVER) return launch_rollout_hist_hover_pid(h->flags, hn, grid, s, ra);
       return h->cfg.task == PDS_TASK_CIRCLE && launch_rollout_hist_circle_pid(h->flags, hn, grid, s, ra);

@@ -165,6 +165,8 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
       rollout_wait_ge(&act_ready, kRolloutMlpWaves * (s + 1));  // the network waves have read the histories and written a(s)
       PDS_OPAQUE_STEP_COPIES
       const float4 act = act_all[lane_s];
+      [[maybe_unused]] int ep_step = 0;  // LAT: env.step()s of this env since its last reset, in front of this one
+      if constexpr (V::LAT) ep_step = (int)ctr_step(S.ctr);
       StepOut so;
       step_once<V, kWave, RM, false>(rl.s, o1, rks, parity, nullptr, tile, nullptr, queue, scratch, lane_s, wave_base, ix, active, act, S,
                                      qcount, fin, &so PDS_STAMP_ARG);
@@ -179,6 +181,23 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void rollout_hist_kernel(const 
       const float *newest = dn ? fin + lane * D + HALF : krow + HALF;
       const int keep = HS - HALF;
       PDS_HIST_SHIFT_APPEND(hrow, newest, keep)
+      // the latency ring (pds_history_advance_latency, csrc/pds_history.hip, same values): at step j = ep_step + 1 <= H of an
+      // episode the action columns of the slots 0 .. H - j are still the reference's VIEWS of action_buffer[-1]
+      // (envs/agents.py:386, envs/base.py:424-429) and show the raw action when this step's apply_action calls rewrote that row,
+      // floor(j agg / B) > floor((j - 1) agg / B) -- in the final history of an env that finishes here too, hence in front of
+      // the fin_rows copy and the restart.  Divergent, but at most H four-float LDS writes, none after step H of an episode.
+      if constexpr (V::LAT) {
+        const int views = H - ep_step;  // slots 0 .. H - j
+        if (views > 0) {
+          const int B = rl.s.k.lat_steps, agg = rl.s.k.agg;
+          if ((ep_step + 1) * agg / B > ep_step * agg / B) {
+            for (int j = 0; j < views; ++j) {
+              float *u = hrow + j * HALF + (HALF - 4);
+              u[0] = act.x; u[1] = act.y; u[2] = act.z; u[3] = act.w;
+            }
+          }
+        }
+      }
       // the final history of an env the TimeLimit cut bootstraps its path with V (also when it terminated on that step, and
       // for every env that finished on the rollout's last step: algs/iwpg/iwpg.py:374-379; the rule behind done_all[] of
       // rollout_kernel, where the reason for the two wordings is) -> the caller's slot list
@@ -302,6 +321,26 @@ template <int TASK, class L>
 inline bool hist_pid(const LaunchFlags &f, int hn, const L &l) {
   if (f.ctrl == 1) return hist_task<TASK, 1>(f, hn, l);
   return hist_task<TASK, 2>(f, hn, l);
+}
+// ... and on the latency ring (LAT = true: rollout_hist_latency_supported; csrc/pds_rollout_hist_<task>[_pid]_lat.hip).  Hover and
+// Circle only, both with motor dynamics in both noise settings.
+template <int TASK, int CTRL, class L>
+inline bool hist_lat_task(const LaunchFlags &f, int hn, const L &l) {
+  static_assert(TASK != PDS_TASK_TAKEOFF, "TakeOff on the latency ring steps per step");
+  if (!rollout_hist_latency_supported(TASK, f) || f.ctrl != CTRL) return false;
+  if (f.motor) {
+    if (f.on) hist_width<Variant<TASK, true, true, false, true, true, CTRL, true, false>>(hn, l);
+    else hist_width<Variant<TASK, true, false, false, false, false, CTRL, true, false>>(hn, l);
+  } else {
+    if (f.on) hist_width<Variant<TASK, false, true, false, true, true, CTRL, true, false>>(hn, l);
+    else hist_width<Variant<TASK, false, false, false, false, false, CTRL, true, false>>(hn, l);
+  }
+  return true;
+}
+template <int TASK, class L>
+inline bool hist_lat_pid(const LaunchFlags &f, int hn, const L &l) {
+  if (f.ctrl == 1) return hist_lat_task<TASK, 1>(f, hn, l);
+  return hist_lat_task<TASK, 2>(f, hn, l);
 }
 struct RolloutHistLaunch {
   dim3 grid;  // one block per 64-env tile

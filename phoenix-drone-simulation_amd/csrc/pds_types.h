@@ -427,6 +427,14 @@ inline bool rollout_hist_supported(int task, const LaunchFlags &f) {
   if (f.ctrl != 0) return task != PDS_TASK_TAKEOFF;  // (csrc/pds_rollout_hist_*_pid.hip)
   return !(task == PDS_TASK_TAKEOFF && f.motor);
 }
+// ... and on the latency ring (pds_rollout_history_latency, include/pds_history_latency.h; csrc/pds_rollout_hist_*_lat.hip): Hover
+// and Circle in every control mode, noise {none, reference default} x {with, without motor dynamics}; not TakeOff, not the Kalman
+// hold, not the ground effect.  A predicate of its own: rollout_hist_supported answers what it answered.
+inline bool rollout_hist_latency_supported(int task, const LaunchFlags &f) {
+  if (!f.lat || f.ge || f.hold || task == PDS_TASK_TAKEOFF) return false;
+  const bool lean = !f.dr && !f.tn && !f.on, full = f.dr && f.tn && f.on;
+  return lean || full;
+}
 // input tiles the kernels are instantiated for (d_in <= 64 / 96 / 128 / 192)
 inline int rollout_hist_tiles(int d_in) { return d_in <= 64 ? 4 : (d_in <= 96 ? 6 : (d_in <= 128 ? 8 : 12)); }
 
@@ -435,6 +443,10 @@ bool launch_rollout_hist_circle(const LaunchFlags &f, int hn, dim3 grid, hipStre
 bool launch_rollout_hist_takeoff(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
 bool launch_rollout_hist_hover_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
 bool launch_rollout_hist_circle_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
+bool launch_rollout_hist_hover_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
+bool launch_rollout_hist_circle_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
+bool launch_rollout_hist_hover_pid_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
+bool launch_rollout_hist_circle_pid_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const RolloutHistArgs &ra);
 bool launch_rollout_hover(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra);
 bool launch_rollout_circle(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra);
 bool launch_rollout_takeoff(const LaunchFlags &f, dim3 grid, hipStream_t s, const RolloutArgs &ra);

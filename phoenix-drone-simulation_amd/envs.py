@@ -73,7 +73,10 @@ class DroneVecEnv:
     (physics.py:27-58 formula as opt-in extension), init_xyz / init_rpy / init_xyz_dot / init_rpy_dot
     (the env.init_* attributes of envs/base.py:84-91), fresh_outputs (step() returns newly allocated
     tensors like the reference's fresh arrays, envs/base.py:311, instead of two alternating buffer sets
-    owned by the env: ~20 us of host time per step for callers that keep observations around).
+    owned by the env: ~20 us of host time per step for callers that keep observations around),
+    history_latency (opt-in: use_latency / set_latency together with observation_history_size != 2 -- the history
+    entries that are views of action_buffer[-1], envs/agents.py:386, are resolved by pds_history_advance_latency;
+    without it that combination raises as before).
     """
     metadata = {'render.modes': []}
     task = None
@@ -87,15 +90,17 @@ class DroneVecEnv:
                  penalty_angle=0., penalty_spin=None, penalty_terminal=100., penalty_velocity=None,
                  enable_reset_distribution=True, latency=0.015, motor_time_constant=0.080,
                  motor_thrust_noise=0.05, observation_frequency=100, observation_history_size=2,
-                 render_mode=None, debug=False, max_episode_steps=500, fresh_outputs=False):
+                 render_mode=None, debug=False, max_episode_steps=500, fresh_outputs=False,
+                 history_latency=False):
         if control_mode not in native.CONTROL_MODES:
             raise AssertionError(f'Control={control_mode} not found.')  # envs/agents.py:70-71
         if int(observation_history_size) < 1:
             raise AssertionError("observation_history_size >= 1")  # envs/base.py:135
         self.observation_history_size = int(observation_history_size)
-        if use_latency and self.observation_history_size != 2:
+        if use_latency and self.observation_history_size != 2 and not history_latency:
             # the history entries that alias drone.action_buffer (envs/agents.py:386) are resolved inside
-            # the kernel for the default history of 2 only
+            # the kernel for the default history of 2 only; history_latency=True resolves them for any history in the
+            # per-step history launch (pds_history_advance_latency)
             raise NotImplementedError("use_latency with observation_history_size != 2")
         if render_mode not in (None, 'rgb_array'):
             raise NotImplementedError("rendering is out of scope (no Bullet world on this path)")
@@ -171,6 +176,14 @@ class DroneVecEnv:
             self._hist = torch.zeros(self.num_envs, self.observation_history_size, self._half,
                                      dtype=torch.float32, device=self.device)
         self._hist_sets = None
+        # history_latency=True: the history goes through pds_history_advance_latency, which needs the env.step()s of every env
+        # since its last reset -- two env-owned int32 arrays that the launch reads and writes in turn (`_hist_steps` is the current)
+        self.history_latency = bool(history_latency) and self._hist is not None
+        if self.history_latency:
+            self._hist_steps_sets = [torch.zeros(self.num_envs, dtype=torch.int32, device=self.device) for _ in range(2)]
+            self._hist_steps = self._hist_steps_sets[0]
+            self._hist_lat_steps = int(self.lib.pds_latency_steps(self._handle))
+            self._hist_frozen = False  # set_latency since the last full reset: some views are frozen (fused.rollout_history_latency_supported)
         self._auto_reset = bool(auto_reset)
         self.act_dim = 4
         o_lim = 1000 * np.ones((self.obs_dim,), dtype=np.float32)  # envs/base.py:147-150
@@ -274,6 +287,12 @@ class DroneVecEnv:
         return torch.cat([old[:, None].expand(-1, H - 1, -1), new[:, None]], 1)
 
     def _refill_history(self, row2, mask):
+        if self.history_latency:  # the views of the ring's last row start again with the reset
+            if mask is None:
+                self._hist_steps.zero_()
+                self._hist_frozen = False
+            else:
+                self._hist_steps.masked_fill_(mask.bool(), 0)
         fresh = self._reset_rows(row2)
         self._hist = fresh if mask is None else torch.where(mask.bool()[:, None, None], fresh, self._hist)
         return self._hist.reshape(self.num_envs, -1)
@@ -289,13 +308,16 @@ class DroneVecEnv:
                                                dtype=torch.float32, device=self.device)
         own.copy_(flat.view_as(own))
         self._hist = own
+        if self.history_latency:  # whoever advanced the histories stepped the handle: its count is the one since the reset
+            self._hist_steps.copy_(self.get_state("step_count").view(-1))
 
-    def _advance_history(self, ret):
+    def _advance_history(self, ret, action=None):
         """One launch of pds_history_advance (csrc/pds_history.hip): shift the [N, H, half] history by the
         step's newest half, write the final history of the envs that finished and restart theirs from the reset
         row.  Like step()'s other outputs the returned tensors alternate between two env-owned sets (or are
         newly allocated with fresh_outputs=True); info['final_obs'] rows are defined where an env finished
-        (without auto-reset it is the returned observation itself)."""
+        (without auto-reset it is the returned observation itself).  history_latency=True: pds_history_advance_latency with the
+        step's `action` [N, 4] and the env's step counts."""
         obs2, reward, term, trunc, info = ret
         N, H, half = self.num_envs, self.observation_history_size, self._half
         if self._fresh:
@@ -313,10 +335,21 @@ class DroneVecEnv:
                 out, fin = self._hist_sets[self._hist_flip]
         # pds_history_advance has no handle argument: it launches on the CURRENT device, which must be the env's
         with (_NULL_CTX if self.device.index == torch.cuda.current_device() else torch.cuda.device(self.device)):
-            rc = self.lib.pds_history_advance(N, half, H, obs2.data_ptr(), term.data_ptr(), trunc.data_ptr(),
-                                              info["final_obs"].data_ptr() if self._auto_reset else None,
-                                              int(self._auto_reset), self._hist.data_ptr(), out.data_ptr(),
-                                              fin.data_ptr() if fin is not None else None, self._raw_stream())
+            if self.history_latency:
+                steps = self._hist_steps
+                steps_out = self._hist_steps_sets[1 if steps is self._hist_steps_sets[0] else 0]
+                rc = self.lib.pds_history_advance_latency(N, half, H, obs2.data_ptr(), term.data_ptr(), trunc.data_ptr(),
+                                                          info["final_obs"].data_ptr() if self._auto_reset else None,
+                                                          int(self._auto_reset), self._hist.data_ptr(), out.data_ptr(),
+                                                          fin.data_ptr() if fin is not None else None, action.data_ptr(),
+                                                          steps.data_ptr(), steps_out.data_ptr(), self._hist_lat_steps,
+                                                          self.aggregate_phy_steps, self._raw_stream())
+                self._hist_steps = steps_out
+            else:
+                rc = self.lib.pds_history_advance(N, half, H, obs2.data_ptr(), term.data_ptr(), trunc.data_ptr(),
+                                                  info["final_obs"].data_ptr() if self._auto_reset else None,
+                                                  int(self._auto_reset), self._hist.data_ptr(), out.data_ptr(),
+                                                  fin.data_ptr() if fin is not None else None, self._raw_stream())
         if rc != 0:
             native.check(self._handle, rc, "pds_history_advance")
         self._hist = out
@@ -324,15 +357,33 @@ class DroneVecEnv:
         final = fin.reshape(N, -1) if fin is not None else flat
         return (flat, reward, term, trunc, {"cost": info["cost"], "final_obs": final, "final_observation": final})
 
-    def _advance_history_torch(self, hist, ret):
+    def _advance_history_torch(self, hist, ret, action=None, steps=None):
         """The same update written with torch ops (the pre-round-2 implementation; tests compare the kernel with it).
-        Returns (new history [N, H, half], final history [N, H, half])."""
+        Returns (new history [N, H, half], final history [N, H, half]).  With `action` [N, 4] and `steps` [N] (the env.step()s of
+        every env since its last reset, in front of this one) it is pds_history_advance_latency's: (new history, final history,
+        new steps)."""
         obs2, reward, term, trunc, info = ret
         half = self._half
         done = (term | trunc)[:, None]
         new = obs2[:, half:]
         newest = torch.where(done, info["final_obs"][:, half:], new) if self._auto_reset else new
         final_hist = torch.cat([hist[:, 1:], newest[:, None]], 1)
+        if action is not None:
+            # the slots 0 .. H - j of step j = steps + 1 are views of the ring's last row (envs/agents.py:386, base.py:424-429),
+            # which this step's apply_action calls rewrite when floor(j agg / B) > floor((j - 1) agg / B)
+            H, B, agg = self.observation_history_size, self._hist_lat_steps, self.aggregate_phy_steps
+            j = steps.to(torch.int64) + 1
+            fires = (torch.div(j * agg, B, rounding_mode="floor") > torch.div((j - 1) * agg, B, rounding_mode="floor")) if B > 0 \
+                else torch.zeros_like(j, dtype=torch.bool)
+            slot = torch.arange(H, device=hist.device)[None, :]
+            views = (fires[:, None] & (slot <= H - j[:, None]))[:, :, None].expand(-1, -1, 4)
+            final_hist = final_hist.clone()
+            final_hist[:, :, half - 4:] = torch.where(views, action[:, None, :].expand(-1, H, -1), final_hist[:, :, half - 4:])
+            cap = torch.where(steps < (1 << 30), steps + 1, steps)
+            new_steps = torch.where(done[:, 0], torch.zeros_like(steps), cap) if self._auto_reset else cap
+            if self._auto_reset:
+                return torch.where(done[:, :, None], self._reset_rows(obs2), final_hist), final_hist, new_steps
+            return final_hist, final_hist, new_steps
         if self._auto_reset:
             return torch.where(done[:, :, None], self._reset_rows(obs2), final_hist), final_hist
         return final_hist, final_hist
@@ -362,7 +413,7 @@ class DroneVecEnv:
         if rc != 0:
             native.check(self._handle, rc, "pds_step")
         if self._hist is not None:
-            return self._advance_history(b["_ret"])
+            return self._advance_history(b["_ret"], a)
         return b["_ret"]
 
     def step_k(self, actions, out=None):
@@ -404,6 +455,8 @@ class DroneVecEnv:
             if "obs_hist" not in b:
                 b["obs_hist"] = torch.empty(K, N, H, half, dtype=torch.float32, device=self.device)
                 b["final_hist"] = torch.zeros(K, N, H, half, dtype=torch.float32, device=self.device)
+            if self.history_latency and "hist_steps" not in b:
+                b["hist_steps"] = torch.empty(K, N, dtype=torch.int32, device=self.device)
             # the history lives in ONE env-owned buffer across step_k calls (a hipGraph that captured a call re-reads and
             # re-writes that address at every replay, so the history carries from replay to replay)
             own = getattr(self, "_hist_own", None)
@@ -413,18 +466,32 @@ class DroneVecEnv:
                 own.copy_(self._hist)
                 self._hist = own
             hist = own
+            # (history_latency: the step counts live in the env-owned `_hist_steps` across calls in the same way)
+            steps = self._hist_steps if self.history_latency else None
             with (_NULL_CTX if self.device.index == torch.cuda.current_device() else torch.cuda.device(self.device)):
                 for k in range(K):
-                    rc = self.lib.pds_history_advance(N, half, H, obs[k].data_ptr(), b["terminated"][k].data_ptr(),
-                                                      b["truncated"][k].data_ptr(),
-                                                      final[k].data_ptr() if self._auto_reset else None, int(self._auto_reset),
-                                                      hist.data_ptr(), b["obs_hist"][k].data_ptr(),
-                                                      b["final_hist"][k].data_ptr() if self._auto_reset else None,
-                                                      self._raw_stream())
+                    if steps is not None:
+                        rc = self.lib.pds_history_advance_latency(N, half, H, obs[k].data_ptr(), b["terminated"][k].data_ptr(),
+                                                                  b["truncated"][k].data_ptr(),
+                                                                  final[k].data_ptr() if self._auto_reset else None,
+                                                                  int(self._auto_reset), hist.data_ptr(), b["obs_hist"][k].data_ptr(),
+                                                                  b["final_hist"][k].data_ptr() if self._auto_reset else None,
+                                                                  a[k].data_ptr(), steps.data_ptr(), b["hist_steps"][k].data_ptr(),
+                                                                  self._hist_lat_steps, self.aggregate_phy_steps, self._raw_stream())
+                        steps = b["hist_steps"][k]
+                    else:
+                        rc = self.lib.pds_history_advance(N, half, H, obs[k].data_ptr(), b["terminated"][k].data_ptr(),
+                                                          b["truncated"][k].data_ptr(),
+                                                          final[k].data_ptr() if self._auto_reset else None, int(self._auto_reset),
+                                                          hist.data_ptr(), b["obs_hist"][k].data_ptr(),
+                                                          b["final_hist"][k].data_ptr() if self._auto_reset else None,
+                                                          self._raw_stream())
                     if rc != 0:
                         native.check(self._handle, rc, "pds_history_advance")
                     hist = b["obs_hist"][k]
             own.copy_(hist)  # (the cached set is rewritten by the next call)
+            if steps is not None:
+                self._hist_steps.copy_(steps)
             obs = b["obs_hist"].reshape(K, N, H * half)
             final = b["final_hist"].reshape(K, N, H * half) if self._auto_reset else obs
         return (obs, b["reward"], b["terminated"].view(torch.bool), b["truncated"].view(torch.bool),
@@ -433,11 +500,19 @@ class DroneVecEnv:
     def set_latency(self, new_latency):
         """CrazyFlieAgent.set_latency (envs/agents.py:388-404): below one time step the delay is switched
         off, otherwise buf_size = int(latency / time_step); the action buffer of every env is zeroed."""
-        if self._hist is not None and float(new_latency) >= float(self.cfg.time_step):
+        if self._hist is not None and float(new_latency) >= float(self.cfg.time_step) and not self.history_latency:
             # the aliased action-history entries of the first two steps after a reset (agents.py:386, base.py:425-426)
             # are resolved in-kernel for observation_history_size == 2 only -- same refusal as the constructor's
+            # (history_latency=True resolves them in the per-step history launch)
             raise NotImplementedError("set_latency >= one time step with observation_history_size != 2 is not built")
         native.call("pds_set_latency", self._handle, float(new_latency), handle=self._handle)
+        if self.history_latency:
+            self._hist_lat_steps = int(self.lib.pds_latency_steps(self._handle))
+            if self._hist_lat_steps > 0:
+                # the reference allocates a NEW action_buffer (agents.py:403): the views the history still holds keep the old
+                # one, which nobody writes any more -- no rewrite until the env's next reset
+                self._hist_steps.fill_(self.observation_history_size)
+                self._hist_frozen = True
 
     @property
     def latency_steps(self):
@@ -497,14 +572,23 @@ class DroneVecEnv:
         sd["tick"] = int(self.tick)
         if self._hist is not None:
             sd["observation_history"] = self._hist.clone()
+            if self.history_latency:
+                sd["observation_history_steps"] = self._hist_steps.clone()
         return sd
 
     def load_state_dict(self, sd):
         for name, v in sd.items():
             if name == "observation_history":
                 self._hist = v.to(self.device).clone()
+            elif name == "observation_history_steps":
+                if self.history_latency:
+                    self._hist_steps.copy_(v.to(self.device))
+                    # (counts that are not the handle's own: views a set_latency call froze)
+                    self._hist_frozen = not torch.equal(self._hist_steps, self.get_state("step_count").view(-1).to(torch.int32))
             elif name != "tick":
                 self.set_state(name, v)
+        if self.history_latency and "observation_history_steps" not in sd:  # (a state saved without the switch)
+            self._hist_steps.copy_(self.get_state("step_count").view(-1))
         native.call("pds_set_tick", self._handle, int(sd["tick"]), handle=self._handle)
 
     @property

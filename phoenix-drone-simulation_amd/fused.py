@@ -308,14 +308,28 @@ def fused_rollout(env, fm_pi, fm_v, T, mean, std, eps, log_std, seed, call_offse
                 cost_buf, fval_buf, last_val, ep_ret, ep_len, stats, on=obs_buf, handle=env._handle)
 
 
+def rollout_history_latency_supported(env):
+    """True where pds_rollout_history_latency (include/pds_history_latency.h) flies this env's rollout in one launch: an env created
+    with history_latency=True on the latency ring, Hover or Circle in any control mode, noise off or the reference's default -- and
+    no set_latency call since the env's last full reset (the kernel counts the steps of the rule from the handle's own step count,
+    which knows nothing of the views such a call froze: those envs step per step until then)."""
+    if not getattr(env, "history_latency", False) or getattr(env, "_hist_frozen", False):
+        return False
+    return native.load().pds_rollout_history_latency_supported(env._handle, int(env.observation_history_size)) == 1
+
+
 def fused_rollout_history(env, fm_pi, T, H, mean, std, eps, log_std, seed, call_offset, deterministic, obs_buf, act_buf, logp_buf,
-                          rew_buf, term_buf, trunc_buf, cost_buf, fin_rows, fin_step, ep_ret, ep_len, stats, call_base=None):
+                          rew_buf, term_buf, trunc_buf, cost_buf, fin_rows, fin_step, ep_ret, ep_len, stats, call_base=None,
+                          latency=False):
     """ONE launch for the T closed-loop steps of a rollout with observation_history_size = H != 2 (include/pds.h
     pds_rollout_history, csrc/pds_rollout_hist.h): obs_buf is [T + 1, N, H * half] with the current histories in row 0; the critic
     is NOT in the kernel (the caller evaluates V over obs_buf and over the final histories in fin_rows [slots, N, H * half],
     whose fin_step [slots, N] (int32, preset to -1) names the step each belongs to).  Raises NotImplementedError for env
-    configurations the kernel is not built for (the per-step path gives the same bits)."""
-    native.call("pds_rollout_history", env._handle, int(T), int(H), fm_pi, mean, std, float(eps), log_std, int(seed), call_base,
+    configurations the kernel is not built for (the per-step path gives the same bits).  latency=True: pds_rollout_history_latency
+    (include/pds_history_latency.h), the same launch on the latency ring of an env created with history_latency=True."""
+    if latency and not rollout_history_latency_supported(env):
+        raise NotImplementedError("pds_rollout_history_latency: not built for this env (rollout_history_latency_supported)")
+    native.call("pds_rollout_history_latency" if latency else "pds_rollout_history", env._handle, int(T), int(H), fm_pi, mean, std, float(eps), log_std, int(seed), call_base,
                 int(call_offset), int(bool(deterministic)), obs_buf, act_buf, logp_buf, rew_buf, term_buf, trunc_buf, cost_buf,
                 fin_rows, fin_step, int(fin_rows.shape[0]), ep_ret, ep_len, stats, on=obs_buf, handle=env._handle)
 

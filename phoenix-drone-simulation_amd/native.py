@@ -164,6 +164,12 @@ COLLECT_CONTROL_SIGNATURES = {
     "pds_collect_control_supported": SIGNATURES["pds_collect_supported"],
     "pds_collect_control": SIGNATURES["pds_collect"],
 }
+# ... and of include/pds_history_latency.h, the per-step history launch on the latency ring (tests/test_history_latency_cpu.py)
+HISTORY_LATENCY_SIGNATURES = {
+    "pds_history_advance_latency": (_i32, [_i64, _i32, _i32] + [_vp] * 4 + [_i32] + [_vp] * 6 + [_i32, _i32, _vp]),
+    "pds_rollout_history_latency_supported": (_i32, [_vp, _i32]),
+    "pds_rollout_history_latency": SIGNATURES["pds_rollout_history"],
+}
 
 _lib = None
 
@@ -184,7 +190,7 @@ def load():
     # an OLDER build given through PDS_LIB for a same-box A/B (profiles/tools/ab_lib.sh) may lack the newer entry points: those
     # are skipped; the shipped library must have every name (AttributeError here, and tests/test_host_cpu.py)
     older = bool(os.environ.get("PDS_LIB"))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()) + list(COLLECT_CONTROL_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()) + list(COLLECT_CONTROL_SIGNATURES.items()) + list(HISTORY_LATENCY_SIGNATURES.items()):
         if older and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

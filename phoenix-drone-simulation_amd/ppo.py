@@ -418,9 +418,11 @@ class PPOTrainer:
             self._env_ids = torch.arange(N, device=self.obs.device, dtype=torch.int64)
         self._obs_buf[0].copy_(self.obs)
         self._fin_step.fill_(-1)
+        # (an env created with history_latency=True flies the latency ring: pds_rollout_history_latency, where it is built)
         fused_rollout_history(env, self.fm_pi, T, H, mean, std, eps, self.ac.pi.log_std, self._sample_seed, self._sample_calls,
                               not self.ac.training, self._obs_buf, self.act_buf, self.logp_buf, self.rew_buf, self.term_buf,
-                              self.trunc_buf, self.cost_buf, self._fin_rows, self._fin_step, self.ep_ret, self.ep_len, stats)
+                              self.trunc_buf, self.cost_buf, self._fin_rows, self._fin_step, self.ep_ret, self.ep_len, stats,
+                              latency=bool(getattr(env, "history_latency", False)))
         self._sample_calls += T
         self.fused_rollout = True
         # the critic, off the kernel: V(o(t)) for t = 0 .. T in one pass over obs_buf ...
