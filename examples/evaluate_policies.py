@@ -76,6 +76,18 @@ def infer_history(d_in, half):
     return d_in // half
 
 
+def latency_kwargs(args):
+    """the env keywords of --use-latency / --latency / --history-latency"""
+    kw = {}
+    if args.use_latency:
+        kw["use_latency"] = True
+        if args.latency is not None:
+            kw["latency"] = args.latency
+    if args.history_latency:
+        kw["history_latency"] = True
+    return kw
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("paths", nargs="+", help="run directories, or directories to search for them")
@@ -95,10 +107,19 @@ def main():
     ap.add_argument("--record-dir", default=None, metavar="DIR",
                     help="with --record: one CSV log per recorded episode under <DIR>/<group>/<p>/ in the layout of the "
                          "simulation-optimisation logs (Flights.to_csv_dir; control_mode PWM)")
+    ap.add_argument("--use-latency", action="store_true", help="delay the actions through the env's latency ring (use_latency=True)")
+    ap.add_argument("--latency", type=float, default=None, help="with --use-latency: the delay in seconds (default: the env's)")
+    ap.add_argument("--history-latency", action="store_true",
+                    help="with --use-latency and a history other than 2: build the env with history_latency=True, which resolves the "
+                         "history's views of the ring's last row for any history size")
+    ap.add_argument("--history-latency-fused", action="store_true",
+                    help="with --history-latency: evaluate on the ring in one launch (pds_evaluate_policies_history_latency*) where it "
+                         "is built, instead of the composed path")
     args = ap.parse_args()
     if args.record_dir and not args.record:
         ap.error("--record-dir needs --record R")
     fused = {"auto": "auto", "on": True, "off": False}[args.fused]
+    lat_kw = latency_kwargs(args)
 
     loaded = [(d, *load_run(d)) for d in find_run_dirs(args.paths)]
     if not loaded:
@@ -110,7 +131,7 @@ def main():
     for gi, (key, members) in enumerate(sorted(groups.items(), key=lambda kv: str(kv[0]))):
         d_in, hidden, act, _ = key
         pop = PolicyPopulation.from_actor_critics([ac for _, ac in members])
-        env = pds.make(env_id, num_envs=pop.P * args.episodes, seed=args.seed, observation_history_size=args.history or 2)
+        env = pds.make(env_id, num_envs=pop.P * args.episodes, seed=args.seed, observation_history_size=args.history or 2, **lat_kw)
         if env.obs_dim != d_in and args.history is None:  # a history policy: the env again, with the history its width says
             half = env.obs_dim // 2
             env.close()
@@ -119,12 +140,13 @@ def main():
             except ValueError as e:
                 print(f"group {gi} {key}: {e} of {env_id}: skipped")
                 continue
-            env = pds.make(env_id, num_envs=pop.P * args.episodes, seed=args.seed, observation_history_size=history)
+            env = pds.make(env_id, num_envs=pop.P * args.episodes, seed=args.seed, observation_history_size=history, **lat_kw)
         if env.obs_dim != d_in:
             print(f"group {gi} {key}: the actors read {d_in} inputs, {env_id} observes {env.obs_dim}: skipped")
             env.close()
             continue
         out = evaluate_population(env, pop, fused=fused, metrics=args.metrics, history_fused=True, record=args.record,
+                                  history_latency_fused=args.history_latency_fused,
                                   log_dir=os.path.join(args.log_dir, str(gi)) if args.log_dir else None)
         ret, length, cost = out[:3]
         table = out[3].table() if args.metrics else {}

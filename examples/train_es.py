@@ -23,6 +23,18 @@ import phoenix_drone_simulation_amd as pds  # noqa: E402
 from phoenix_drone_simulation_amd.es import ESTrainer, penalised_return  # noqa: E402
 
 
+def latency_kwargs(args):
+    """the env keywords of --use-latency / --latency / --history-latency"""
+    kw = {}
+    if args.use_latency:
+        kw["use_latency"] = True
+        if args.latency is not None:
+            kw["latency"] = args.latency
+    if args.history_latency:
+        kw["history_latency"] = True
+    return kw
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--env", default="DroneHoverSimpleEnv-v0")
@@ -48,6 +60,14 @@ def main():
     ap.add_argument("--history-stats-fused", action="store_true",
                     help="with --history-fused and --obs-stats online: the generation's launch also sums the observations "
                          "(pds_evaluate_policies_history_stats) where it is built, instead of the composed path")
+    ap.add_argument("--use-latency", action="store_true", help="delay the actions through the env's latency ring (use_latency=True)")
+    ap.add_argument("--latency", type=float, default=None, help="with --use-latency: the delay in seconds (default: the env's)")
+    ap.add_argument("--history-latency", action="store_true",
+                    help="with --use-latency and a history other than 2: build the env with history_latency=True, which resolves the "
+                         "history's views of the ring's last row for any history size")
+    ap.add_argument("--history-latency-fused", action="store_true",
+                    help="with --history-latency: evaluate on the ring in one launch (pds_evaluate_policies_history_latency*) where it "
+                         "is built, instead of the composed path")
     args = ap.parse_args()
     weights = {}
     for item in args.penalise:
@@ -57,11 +77,11 @@ def main():
         weights[name] = float(w)
     fitness = penalised_return(weights) if weights else None  # (ValueError names the metrics there are)
     env = pds.make(args.env, num_envs=args.population * args.episodes, seed=args.seed,
-                   observation_history_size=args.history)  # otherwise the reference's default config
+                   observation_history_size=args.history, **latency_kwargs(args))  # otherwise the reference's default config
     trainer = ESTrainer(env, args.population, sigma=args.sigma, lr=args.lr, seed=args.seed,
                         obs_stats=None if args.obs_stats == "none" else args.obs_stats, eval_every=args.eval_every, fitness=fitness,
                         shaping=args.shaping, top_b=args.top_b, history_fused=args.history_fused,
-                        history_stats_fused=args.history_stats_fused)
+                        history_stats_fused=args.history_stats_fused, history_latency_fused=args.history_latency_fused)
     t0 = time.time()
     steps = 0.0
     for g in range(args.generations):

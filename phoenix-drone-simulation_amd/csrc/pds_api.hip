@@ -19,6 +19,7 @@
 #include "pds_evaluate_hist_args.h"
 #include "pds_simopt.h"
 #include "../../include/pds_history_latency.h"
+#include "../../include/pds_history_latency_evaluate.h"
 
 namespace pds {
 
@@ -1393,9 +1394,11 @@ extern "C" int pds_evaluate_history_stats_supported(const pds_handle *h, int his
 // P policies x E episodes in one launch, the actors reading the last `history` halves of the handle's row.  The checks and the
 // handle's state afterwards are pds_evaluate_policies'; d_metrics is optional.  ONE body for the three forms of the kernel
 // (EvalHistForm, csrc/pds_evaluate_hist.h): the record form's checks come first, as in evaluate_policies_call, the stats form's
-// behind those of the plain call, and `x` holds what a form adds.
+// behind those of the plain call, and `x` holds what a form adds.  `latency`: the entry points of
+// include/pds_history_latency_evaluate.h, which fly the latency ring (their own support rule and launchers, as in
+// rollout_history_call) -- the others answer a ring handle as before.
 template <EvalHistForm F>
-static int evaluate_history_call(pds_handle *h, const char *fn, int history, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+static int evaluate_history_call(pds_handle *h, const char *fn, bool latency, int history, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
                                  const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
                                  const float *d_obs0, float *d_ret, float *d_len, float *d_cost, const EvalFormCall &x, void *stream) {
   constexpr bool REC = F == EvalHistForm::Record, STATS = F == EvalHistForm::Stats;
@@ -1411,7 +1414,10 @@ static int evaluate_history_call(pds_handle *h, const char *fn, int history, int
   if (HS > 192) return fail(h, PDS_EUNSUPPORTED, "%s: %d x %d = %lld network inputs (<= 192)", fn, history, half, HS);
   if (const int rc = check_evaluate_call(h, fn, any_null, P, episodes_per_policy, shape, (int)HS, d_mean, d_std, max_steps, d_metrics))
     return rc;
-  if (!rollout_hist_supported(h->cfg.task, h->flags))
+  if (latency && !rollout_hist_latency_supported(h->cfg.task, h->flags))
+    return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: what pds_rollout_history_latency is built for) -- "
+                                     "pds_mlp_forward + pds_step + pds_history_advance_latency give the same bits", fn);
+  if (!latency && !rollout_hist_supported(h->cfg.task, h->flags))
     return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: what pds_rollout_history is built for) -- "
                                      "pds_mlp_forward + pds_step + pds_history_advance give the same bits", fn);
   const int hn = rollout_hist_tiles((int)HS);
@@ -1439,6 +1445,19 @@ static int evaluate_history_call(pds_handle *h, const char *fn, int history, int
                                         d_len, d_cost, stream))
     return rc;
   const int rc = launch_rollout(h, fn, max_steps, stream, [&](dim3 grid, hipStream_t s) {
+    if (latency) {  // (Hover or Circle: rollout_hist_latency_supported)
+      const bool hover = h->cfg.task == PDS_TASK_HOVER, pid = h->flags.ctrl != 0;
+      if constexpr (STATS) {
+        if (pid) return hover ? launch_evaluate_hist_stats_hover_pid_lat(h->flags, hn, grid, s, ka) : launch_evaluate_hist_stats_circle_pid_lat(h->flags, hn, grid, s, ka);
+        return hover ? launch_evaluate_hist_stats_hover_lat(h->flags, hn, grid, s, ka) : launch_evaluate_hist_stats_circle_lat(h->flags, hn, grid, s, ka);
+      } else if constexpr (REC) {
+        if (pid) return hover ? launch_evaluate_hist_record_hover_pid_lat(h->flags, hn, grid, s, ka) : launch_evaluate_hist_record_circle_pid_lat(h->flags, hn, grid, s, ka);
+        return hover ? launch_evaluate_hist_record_hover_lat(h->flags, hn, grid, s, ka) : launch_evaluate_hist_record_circle_lat(h->flags, hn, grid, s, ka);
+      } else {
+        if (pid) return hover ? launch_evaluate_hist_hover_pid_lat(h->flags, hn, grid, s, ka) : launch_evaluate_hist_circle_pid_lat(h->flags, hn, grid, s, ka);
+        return hover ? launch_evaluate_hist_hover_lat(h->flags, hn, grid, s, ka) : launch_evaluate_hist_circle_lat(h->flags, hn, grid, s, ka);
+      }
+    }
     if constexpr (STATS) {
       if (h->flags.ctrl != 0) {  // (TakeOff fixes control_mode PWM)
         if (h->cfg.task == PDS_TASK_HOVER) return launch_evaluate_hist_stats_hover_pid(h->flags, hn, grid, s, ka);
@@ -1472,7 +1491,7 @@ extern "C" int pds_evaluate_policies_history(pds_handle *h, int history, int64_t
                                              const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
                                              const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
                                              void *stream) {
-  return evaluate_history_call<EvalHistForm::Metrics>(h, "pds_evaluate_policies_history", history, P, episodes_per_policy, shape, d_params, d_mean,
+  return evaluate_history_call<EvalHistForm::Metrics>(h, "pds_evaluate_policies_history", false, history, P, episodes_per_policy, shape, d_params, d_mean,
                                       d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost, {d_metrics}, stream);
 }
 // the same launch that also records the flights of the first record_per_policy envs of every policy: d_flight [T, 4, N_rec, 4] and,
@@ -1482,7 +1501,7 @@ extern "C" int pds_evaluate_policies_history_record(pds_handle *h, int history, 
                                                     const float *d_std, float eps, int max_steps, const float *d_obs0, float *d_ret,
                                                     float *d_len, float *d_cost, float *d_metrics, int64_t record_per_policy,
                                                     float *d_flight, float *d_obs_rec, void *stream) {
-  return evaluate_history_call<EvalHistForm::Record>(h, "pds_evaluate_policies_history_record", history, P, episodes_per_policy, shape, d_params,
+  return evaluate_history_call<EvalHistForm::Record>(h, "pds_evaluate_policies_history_record", false, history, P, episodes_per_policy, shape, d_params,
                                      d_mean, d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost,
                                      {d_metrics, nullptr, record_per_policy, d_flight, d_obs_rec}, stream);
 }
@@ -1492,8 +1511,44 @@ extern "C" int pds_evaluate_policies_history_stats(pds_handle *h, int history, i
                                                    const pds_mlp *shape, const float *d_params, const float *d_mean,
                                                    const float *d_std, float eps, int max_steps, const float *d_obs0, float *d_ret,
                                                    float *d_len, float *d_cost, float *d_metrics, float *d_obs_sums, void *stream) {
-  return evaluate_history_call<EvalHistForm::Stats>(h, "pds_evaluate_policies_history_stats", history, P, episodes_per_policy, shape,
+  return evaluate_history_call<EvalHistForm::Stats>(h, "pds_evaluate_policies_history_stats", false, history, P, episodes_per_policy, shape,
                                                     d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost,
+                                                    {d_metrics, d_obs_sums}, stream);
+}
+// ... and on the latency ring (include/pds_history_latency_evaluate.h): the same three calls with `latency` set
+extern "C" int pds_evaluate_history_latency_supported(const pds_handle *h, int history) {
+  if (!h) return PDS_EINVAL;
+  return h->cfg.auto_reset && rollout_hist_latency_supported(h->cfg.task, h->flags) && history >= 1 &&
+                 (long long)history * (h->obs_dim / 2) <= 192 ? 1 : 0;
+}
+extern "C" int pds_evaluate_history_latency_stats_supported(const pds_handle *h, int history) {
+  const int rc = pds_evaluate_history_latency_supported(h, history);
+  if (rc != 1) return rc;
+  return eval_hist_stats_width_built(rollout_hist_tiles(history * (h->obs_dim / 2))) ? 1 : 0;
+}
+extern "C" int pds_evaluate_policies_history_latency(pds_handle *h, int history, int64_t P, int64_t episodes_per_policy,
+                                                     const pds_mlp *shape, const float *d_params, const float *d_mean,
+                                                     const float *d_std, float eps, int max_steps, const float *d_obs0, float *d_ret,
+                                                     float *d_len, float *d_cost, float *d_metrics, void *stream) {
+  return evaluate_history_call<EvalHistForm::Metrics>(h, "pds_evaluate_policies_history_latency", true, history, P, episodes_per_policy, shape,
+                                                      d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost, {d_metrics}, stream);
+}
+extern "C" int pds_evaluate_policies_history_latency_record(pds_handle *h, int history, int64_t P, int64_t episodes_per_policy,
+                                                            const pds_mlp *shape, const float *d_params, const float *d_mean,
+                                                            const float *d_std, float eps, int max_steps, const float *d_obs0,
+                                                            float *d_ret, float *d_len, float *d_cost, float *d_metrics,
+                                                            int64_t record_per_policy, float *d_flight, float *d_obs_rec, void *stream) {
+  return evaluate_history_call<EvalHistForm::Record>(h, "pds_evaluate_policies_history_latency_record", true, history, P, episodes_per_policy,
+                                                     shape, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost,
+                                                     {d_metrics, nullptr, record_per_policy, d_flight, d_obs_rec}, stream);
+}
+extern "C" int pds_evaluate_policies_history_latency_stats(pds_handle *h, int history, int64_t P, int64_t episodes_per_policy,
+                                                           const pds_mlp *shape, const float *d_params, const float *d_mean,
+                                                           const float *d_std, float eps, int max_steps, const float *d_obs0,
+                                                           float *d_ret, float *d_len, float *d_cost, float *d_metrics,
+                                                           float *d_obs_sums, void *stream) {
+  return evaluate_history_call<EvalHistForm::Stats>(h, "pds_evaluate_policies_history_latency_stats", true, history, P, episodes_per_policy,
+                                                    shape, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost,
                                                     {d_metrics, d_obs_sums}, stream);
 }
 

@@ -28,6 +28,17 @@
 // s + 1 are in LDS".  (REC and STATS: the alive mask of a step is written and read in the history tile's windows, by the tile's writer
 // and readers, as that file says for its Stats and Record forms: no new counter, no new wait, the argument above word for word.)
 //
+// THE LATENCY RING (V::LAT; pds_evaluate_policies_history_latency*, include/pds_history_latency_evaluate.h;
+// csrc/pds_evaluate_hist_<task>[_pid]_lat.hip, csrc/pds_evaluate_hist_lat_{record,stats}_<task>[_pid].hip): step_once flies the
+// ring in memory as in every LAT kernel, and the env wave resolves the
+// reference's views of action_buffer[-1] in its own history row, as rollout_hist_kernel does: it reads ep_step = ctr_step(S.ctr) in
+// front of step_once, keeps the raw `act` of PDS_EVAL_STEP_HEAD, and eval_hist_advance_row<HALF, true> writes the action columns of
+// the slots 0 .. H - j between its shift and its restart.  The argument of csrc/pds_evaluate.h holds word for word: the rule
+// reads two registers of the env wave (ep_step, act) and writes this lane's own row of the history tile, inside the env wave's
+// window -- behind its act_ready wait and in front of its obs_ready post, where the shift and the restart already write that row --,
+// so the network waves see "the histories of step s + 1" behind the same post as before.  No new counter, no new wait; the alive
+// mask, the record's copy and the sums read the tile in the windows they had.
+//
 // METRICS: the env wave always sums the eight PDS_EM_* values, exactly as evaluate_kernel<.., EvalForm::Metrics> does -- seven words
 // per lane in LDS, read and written back behind the act_ready wait, one rounded instruction per product and sum -- and stores the
 // [N, 8] row where d_metrics is non-NULL: one code object per variant instead of a plain and a metrics form.
@@ -79,11 +90,21 @@ namespace pds {
 // The history of the next step for this lane's own row: PDS_HIST_SHIFT_APPEND with the second half of the step's row `krow` as
 // the newest half, and, where the env finished (`dn`: `krow` is its reset row then), PDS_HIST_RESTART.  A function around the two
 // macros of csrc/pds_rollout_hist.h, which says why each kernel keeps the form it was built on.
-template <int HALF>
-PDS_DEV void eval_hist_advance_row(float *hrow, const float *krow, int H, bool dn) {
+// LAT (the latency ring): between the two, the action columns of the slots 0 .. views - 1 become `raw` -- the rule of
+// pds_history_advance_latency, whose condition the caller has evaluated (views = 0: the rule is off on this step).  In front of the
+// restart, as in rollout_hist_kernel: a finished env's reset row is written behind the rule and whole, so the rule never shows in it.
+template <int HALF, bool LAT = false>
+PDS_DEV void eval_hist_advance_row(float *hrow, const float *krow, int H, bool dn, [[maybe_unused]] int views = 0,
+                                   [[maybe_unused]] float4 raw = make_float4(0.f, 0.f, 0.f, 0.f)) {
   const int keep = H * HALF - HALF;
   const float *newest = krow + HALF;
   PDS_HIST_SHIFT_APPEND(hrow, newest, keep)
+  if constexpr (LAT) {
+    for (int j = 0; j < views; ++j) {
+      float *u = hrow + j * HALF + (HALF - 4);
+      u[0] = raw.x; u[1] = raw.y; u[2] = raw.z; u[3] = raw.w;
+    }
+  }
   if (dn) {
     PDS_HIST_RESTART(hrow, krow, H, keep)
   }
@@ -202,6 +223,8 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
           PDS_ER_STEP(reinterpret_cast<const EvalRecordArgs *>(&el))
         }
       }
+      [[maybe_unused]] int ep_step = 0;  // LAT: env.step()s of this env since its last reset, in front of this one
+      if constexpr (V::LAT) ep_step = (int)ctr_step(S.ctr);
       StepOut so;
       step_once<V, kWave, RM, false>(el.s, o1, rks, parity, nullptr, tile, nullptr, queue, scratch, lane_s, wave_base, ix, active, act, S,
                                      qcount, nullptr, &so PDS_STAMP_ARG);
@@ -213,7 +236,19 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();  // (step_once's wave-cooperative writes of `tile` are complete)
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      eval_hist_advance_row<HALF>(hrow, tile + lane * TS, H, dn);
+      if constexpr (V::LAT) {
+        // the latency ring, as rollout_hist_kernel states it: at step j = ep_step + 1 <= H of an episode the action columns of the
+        // slots 0 .. H - j are the reference's views of action_buffer[-1] and show the raw action where this step's apply_action
+        // calls rewrote that row, floor(j agg / B) > floor((j - 1) agg / B).  Divergent, at most H four-float LDS writes.
+        int views = H - ep_step;
+        if (views > 0) {
+          const int B = el.s.k.lat_steps, agg = el.s.k.agg;
+          if (!((ep_step + 1) * agg / B > ep_step * agg / B)) views = 0;
+        }
+        eval_hist_advance_row<HALF, true>(hrow, tile + lane * TS, H, dn, views, act);
+      } else {
+        eval_hist_advance_row<HALF>(hrow, tile + lane * TS, H, dn);
+      }
       PDS_EVAL_STILL
       if constexpr (REC || STATS) {
         if (lane == 0) es_lds<1>()[0] = still;  // the mask of step s + 1, in front of the post
@@ -308,7 +343,8 @@ __global__ __launch_bounds__(kRolloutThreads, 1) void evaluate_hist_kernel(const
   }
 }
 
-// flags -> variant and input width: hist_task / hist_pid of csrc/pds_rollout_hist.h over this launcher
+// flags -> variant and input width: hist_task / hist_pid (on the ring: hist_lat_task / hist_lat_pid) of csrc/pds_rollout_hist.h over
+// this launcher
 template <EvalHistForm F>
 struct EvalHistLaunchT {
   dim3 grid;  // one block per 64-env tile

@@ -67,5 +67,20 @@ bool launch_evaluate_hist_stats_circle(const LaunchFlags &f, int hn, dim3 grid, 
 bool launch_evaluate_hist_stats_takeoff(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
 bool launch_evaluate_hist_stats_hover_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
 bool launch_evaluate_hist_stats_circle_pid(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
+// ... and the three forms on the latency ring, csrc/pds_evaluate_hist_<task>[_pid]_lat.hip and
+// csrc/pds_evaluate_hist_lat_{record,stats}_<task>[_pid].hip: the variants of csrc/pds_rollout_hist_*_lat.hip
+// (rollout_hist_latency_supported: Hover and Circle)
+bool launch_evaluate_hist_hover_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka);
+bool launch_evaluate_hist_circle_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka);
+bool launch_evaluate_hist_hover_pid_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka);
+bool launch_evaluate_hist_circle_pid_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistArgs &ka);
+bool launch_evaluate_hist_record_hover_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
+bool launch_evaluate_hist_record_circle_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
+bool launch_evaluate_hist_record_hover_pid_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
+bool launch_evaluate_hist_record_circle_pid_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistRecordArgs &ka);
+bool launch_evaluate_hist_stats_hover_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
+bool launch_evaluate_hist_stats_circle_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
+bool launch_evaluate_hist_stats_hover_pid_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
+bool launch_evaluate_hist_stats_circle_pid_lat(const LaunchFlags &f, int hn, dim3 grid, hipStream_t s, const EvalHistStatsArgs &ka);
 
 }  // namespace pds

@@ -110,13 +110,14 @@ class ESTrainer:
     evaluate_fused: the `fused` of the generation's evaluate_population call ("auto": the kernel where it is built); history_fused: its `history_fused`
     -- an env with observation_history_size != 2 flies its generations in one launch too; obs_stats="online" stays composed there unless
     history_stats_fused=True, the `history_stats_fused` of the call: the sums then come from the launch as well (pds_evaluate_policies_history_stats,
-    where it is built: the same statistics and the same centre on the bits).  eval_every: every that many generations the centre alone flies all N envs.
+    where it is built: the same statistics and the same centre on the bits).  history_latency_fused: the `history_latency_fused` of both calls --
+    an env created with history_latency=True on the latency ring flies them in one launch as well (pds_evaluate_policies_history_latency*).  eval_every: every that many generations the centre alone flies all N envs.
     fitness: None (the mean return over the E episodes) or a callable fitness(ret, length, cost, metrics) -> [P] on the [P, E]
     results and the FlightMetrics of evaluate_population(..., metrics=True), e.g. penalised_return({"action_rate_sq": 0.1})."""
 
     def __init__(self, env, population, hidden_sizes=(50, 50), activation="relu", sigma=0.02, lr=0.01, l2=0.005,
                  betas=(0.9, 0.999), seed=0, obs_stats=None, fused=True, eval_every=10, adam_eps=1e-8, fitness=None, shaping="ranks", top_b=None,
-                 evaluate_fused="auto", history_fused=False, history_stats_fused=False):
+                 evaluate_fused="auto", history_fused=False, history_stats_fused=False, history_latency_fused=False):
         P, N = int(population), int(env.num_envs)
         if P < 2 or P % 2 != 0:
             raise ValueError(f"population = {P}: antithetic pairs need an even number of policies")
@@ -139,6 +140,7 @@ class ESTrainer:
         self.evaluate_fused = evaluate_fused
         self.history_fused = history_fused
         self.history_stats_fused = history_stats_fused
+        self.history_latency_fused = history_latency_fused
         self.fitness = fitness
         self.env, self.P, self.H, self.E, self.N = env, P, P // 2, N // P, N
         self.hidden_sizes, self.activation = tuple(int(h) for h in hidden_sizes), activation
@@ -265,7 +267,7 @@ class ESTrainer:
         """The centre alone on all N envs (P = 1) -> (returns, lengths, costs), each [1, N] on the CPU."""
         oms = self.ac.obs_oms
         pop = self._population(self.mu.unsqueeze(0), oms.mean.detach().unsqueeze(0), oms.std.detach().unsqueeze(0))
-        return evaluate_population(self.env, pop, fused="auto", history_fused=self.history_fused)
+        return evaluate_population(self.env, pop, fused="auto", history_fused=self.history_fused, history_latency_fused=self.history_latency_fused)
 
     def _sync(self):
         torch.cuda.synchronize(self.env.device)
@@ -280,7 +282,8 @@ class ESTrainer:
         pop = self.ask()
         t1 = self._sync()
         out = evaluate_population(self.env, pop, fused=self.evaluate_fused, metrics=self.fitness is not None, obs_stats=self.online,
-                                  history_fused=self.history_fused, history_stats_fused=self.history_stats_fused)
+                                  history_fused=self.history_fused, history_stats_fused=self.history_stats_fused,
+                                  history_latency_fused=self.history_latency_fused)
         sums = out[-1] if self.online else None
         if self.fitness is None:
             ret, length = out[0], out[1]

@@ -243,6 +243,29 @@ def fused_history_stats_evaluation_built(env):
     return env.lib.pds_evaluate_history_stats_supported(env._handle, int(getattr(env, "observation_history_size", 2))) == 1
 
 
+def _history_latency_env(env):
+    """An env created with history_latency=True whose views are not frozen (set_latency since the last full reset): the one the
+    latency forms of the history evaluation may fly, as fused.rollout_history_latency_supported says for the rollout."""
+    return bool(getattr(env, "history_latency", False)) and not getattr(env, "_hist_frozen", False)
+
+
+def fused_history_latency_evaluation_built(env):
+    """Whether pds_evaluate_policies_history_latency (include/pds_history_latency_evaluate.h) has a kernel for this env and its
+    observation_history_size H: an env created with history_latency=True on the latency ring, Hover or Circle in any control mode,
+    noise off or the reference's default, H x half <= 192 -- and no set_latency since the last full reset (frozen views)."""
+    if not _history_latency_env(env):
+        return False
+    return env.lib.pds_evaluate_history_latency_supported(env._handle, int(env.observation_history_size)) == 1
+
+
+def fused_history_latency_stats_evaluation_built(env):
+    """Whether pds_evaluate_policies_history_latency_stats has a kernel for this env and its observation_history_size H: what
+    fused_history_latency_evaluation_built asks, and that the stats form of the kernel is built for the input width of H x half."""
+    if not _history_latency_env(env):
+        return False
+    return env.lib.pds_evaluate_history_latency_stats_supported(env._handle, int(env.observation_history_size)) == 1
+
+
 # ---- flight-quality metrics (include/pds.h PDS_EM_*) -------------------------------------------------------------------
 METRIC_NAMES = ("roll_sq", "pitch_sq", "rate_sq", "action_rate_sq", "tilt_max", "saturated_steps", "roll_rate_crossings",
                 "pitch_rate_crossings")  # column j of `raw` = PDS_EM_* value j
@@ -537,6 +560,15 @@ def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats,
                           history_stats_fused=False):
     """The argument checks of evaluate_population and its choice of path, with the env untouched -> (P, E, T, R or None, the
     form "plain" / "metrics" / "stats" / "record", whether the kernel path flies, and H where that is the history kernel, else None)"""
+    return _plan_population(env, population, fused, max_steps, metrics, obs_stats, history_fused, record, record_limit_bytes,
+                            history_stats_fused)
+
+
+def _plan_population(env, population, fused, max_steps, metrics, obs_stats, history_fused, record, record_limit_bytes,
+                     history_stats_fused=False, history_latency_fused=False):
+    """_plan_population_call (which is this plan with history_latency_fused at its default), and with history_latency_fused=True:
+    the latency forms of the history kernel count as built where their predicates hold -- an env on the ring, for which the other
+    predicates answer False; evaluate_population tells `_fly_kernel` which by the same predicate."""
     P, E = _check_population_call(env, population)
     if population.d_in != env.obs_dim:
         raise ValueError(f"the population's actors read {population.d_in} inputs, the env observes {env.obs_dim}")
@@ -549,6 +581,8 @@ def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats,
         raise ValueError("history_fused: True or False")
     if not isinstance(history_stats_fused, (bool, np.bool_)):
         raise ValueError("history_stats_fused: True or False")
+    if not isinstance(history_latency_fused, (bool, np.bool_)):
+        raise ValueError("history_latency_fused: True or False")
     T = int(env._max_episode_steps if max_steps is None else max_steps)
     if T < 1:
         raise ValueError(f"max_steps = {T}")
@@ -575,6 +609,11 @@ def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats,
             built = bool(history_stats_fused) and fused_history_stats_evaluation_built(env)
         else:
             built = fused_history_evaluation_built(env)
+        if not built and history_latency_fused:  # (on the latency ring: the predicates above answer False there)
+            if obs_stats:
+                built = bool(history_stats_fused) and fused_history_latency_stats_evaluation_built(env)
+            else:
+                built = fused_history_latency_evaluation_built(env)
         if fused is True and not built:
             raise NotImplementedError("pds_evaluate_policies_history has no kernel for this call (built: auto_reset, the env configurations "
                                       "of the history rollout, H x half <= 192 inputs; obs_stats with history_stats_fused=True only, where "
@@ -589,11 +628,12 @@ def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats,
     return P, E, T, R, form, use_kernel, (H if use_history else None)
 
 
-def _fly_kernel(env, population, obs, P, E, T, form, H, rec):
+def _fly_kernel(env, population, obs, P, E, T, form, H, rec, latency=False):
     """One launch -> (ret, length, cost, raw, slab) on the device, raw / slab None where the form has none; the record is written
     into `rec`'s arrays.  Per form the entry point and what trails d_cost in its argument list; the history kernel leads with H
     and takes d_metrics or NULL, its record form (pds_evaluate_policies_history_record) what the record form takes, its stats form
-    (pds_evaluate_policies_history_stats) what the stats form takes, the slab slab_features(H x half) columns wide."""
+    (pds_evaluate_policies_history_stats) what the stats form takes, the slab slab_features(H x half) columns wide.  latency=True:
+    the three history entry points on the latency ring (include/pds_history_latency_evaluate.h), the same argument lists."""
     dev, n = env.device, env.num_envs
     ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
     raw = torch.zeros(n, len(METRIC_NAMES), device=dev) if form != "plain" else None
@@ -608,6 +648,8 @@ def _fly_kernel(env, population, obs, P, E, T, form, H, rec):
         obs, lead = obs.contiguous(), (H,)
         name, trail = {"record": ("pds_evaluate_policies_history_record", trail),
                        "stats": ("pds_evaluate_policies_history_stats", trail)}.get(form, ("pds_evaluate_policies_history", (raw,)))
+        if latency:
+            name = name.replace("pds_evaluate_policies_history", "pds_evaluate_policies_history_latency")
     native.call(name, env._handle, *lead, P, E, population.mlp(0), population.theta, population.mean, population.std,
                 population.eps, T, obs, ret, length, cost, *trail, on=dev, handle=env._handle)
     return ret, length, cost, raw, slab
@@ -695,7 +737,8 @@ def _population_result(env, population, P, E, T, flown, metrics, obs_stats, rec,
 
 @torch.no_grad()
 def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None, metrics=False, obs_stats=False,
-                        history_fused=False, record=None, record_observations=True, record_limit_bytes=1 << 30, history_stats_fused=False):
+                        history_fused=False, record=None, record_observations=True, record_limit_bytes=1 << 30, history_latency_fused=False,
+                        history_stats_fused=False):
     """-> (returns, ep_lengths, costs), each [P, E] float32 on the CPU: policy p of `population` flies the E = num_envs / P
     envs of block p, one episode per env, deterministically (action = actor mean), as `evaluate` does for one policy.
     metrics=True: -> (returns, ep_lengths, costs, FlightMetrics) -- the first three are the same bits; the kernel path is
@@ -730,11 +773,21 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     metrics from the same launch) where `fused_history_stats_evaluation_built(env)` holds; where it does not, fused=True raises
     NotImplementedError with the env untouched and "auto" runs the composed path.  The slab of a history env -- on either path --
     is [tiles, 4, 2, W] with W = slab_features(H x half): 64, 96, 128 or 192 columns.
+    history_latency_fused=True (it changes nothing without history_fused=True, and nothing on an env without the latency ring):
+    an env created with history_latency=True on the latency ring flies in one launch as well -- the plain / metrics call
+    pds_evaluate_policies_history_latency, record=R pds_evaluate_policies_history_latency_record, obs_stats=True with
+    history_stats_fused=True pds_evaluate_policies_history_latency_stats (include/pds_history_latency_evaluate.h: the V::LAT forms
+    of the same kernel, the same bits as the composed path) -- where `fused_history_latency_evaluation_built(env)` /
+    `fused_history_latency_stats_evaluation_built(env)` hold; where they do not (TakeOff, the Kalman hold, the ground effect,
+    partial noise, views frozen by set_latency), fused=True raises NotImplementedError with the env untouched and "auto" runs the
+    composed path.
     The env is reset first and not afterwards: after the fused path it refuses to step until the next reset() of every env
     (a masked reset is refused as well).  `population` is not modified: the call works on device copies of its tensors.
     max_steps: the number of steps flown, by default the env's max_episode_steps (the TimeLimit ends every episode by then)."""
-    P, E, T, R, form, use_kernel, H = _plan_population_call(env, population, fused, max_steps, metrics, obs_stats, history_fused, record,
-                                                            record_limit_bytes, history_stats_fused)
+    P, E, T, R, form, use_kernel, H = _plan_population(env, population, fused, max_steps, metrics, obs_stats, history_fused, record,
+                                                       record_limit_bytes, history_stats_fused, history_latency_fused)
+    # (the two families of predicates exclude each other -- with and without the ring --: a kernel flight the latency one allows is its)
+    latency = use_kernel and H is not None and bool(history_latency_fused) and fused_history_latency_evaluation_built(env)
     population = population.to(env.device)
     dev, D = env.device, env.obs_dim
     rec = u0 = None
@@ -744,7 +797,7 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
         u0 = env.get_state("last_action")[rec_env].cpu()  # the command in force before the first (Flights.metrics)
         rec = (rec_env, R, torch.zeros(T, 4, P * R, 4, device=dev), torch.zeros(T, P * R, D, device=dev) if record_observations else None)
     if use_kernel:
-        flown = _fly_kernel(env, population, obs, P, E, T, form, H, rec)
+        flown = _fly_kernel(env, population, obs, P, E, T, form, H, rec, latency)
     else:
         flown = _fly_composed(env, population, obs, P, E, T, metrics, obs_stats, rec)
     return _population_result(env, population, P, E, T, flown, metrics, obs_stats, rec, u0, log_dir)

@@ -170,6 +170,15 @@ HISTORY_LATENCY_SIGNATURES = {
     "pds_rollout_history_latency_supported": (_i32, [_vp, _i32]),
     "pds_rollout_history_latency": SIGNATURES["pds_rollout_history"],
 }
+# ... and of include/pds_history_latency_evaluate.h, the evaluation of history policies on the latency ring
+# (tests/test_history_latency_evaluate_cpu.py): the rows of the three non-latency calls and of their two questions
+HISTORY_LATENCY_EVALUATE_SIGNATURES = {
+    "pds_evaluate_history_latency_supported": SIGNATURES["pds_evaluate_history_supported"],
+    "pds_evaluate_history_latency_stats_supported": HISTORY_STATS_SIGNATURES["pds_evaluate_history_stats_supported"],
+    "pds_evaluate_policies_history_latency": SIGNATURES["pds_evaluate_policies_history"],
+    "pds_evaluate_policies_history_latency_record": HISTORY_RECORD_SIGNATURES["pds_evaluate_policies_history_record"],
+    "pds_evaluate_policies_history_latency_stats": HISTORY_STATS_SIGNATURES["pds_evaluate_policies_history_stats"],
+}
 
 _lib = None
 
@@ -190,7 +199,7 @@ def load():
     # an OLDER build given through PDS_LIB for a same-box A/B (profiles/tools/ab_lib.sh) may lack the newer entry points: those
     # are skipped; the shipped library must have every name (AttributeError here, and tests/test_host_cpu.py)
     older = bool(os.environ.get("PDS_LIB"))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()) + list(COLLECT_CONTROL_SIGNATURES.items()) + list(HISTORY_LATENCY_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()) + list(COLLECT_CONTROL_SIGNATURES.items()) + list(HISTORY_LATENCY_SIGNATURES.items()) + list(HISTORY_LATENCY_EVALUATE_SIGNATURES.items()):
         if older and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

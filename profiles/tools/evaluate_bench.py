@@ -29,6 +29,14 @@ fused=False with obs_stats=True (the composed sums) and against the history kern
 then the two launches alone, on buffers made beforehand.  Exit status 1 where the fused sums are slower than the composed.
 
   python profiles/tools/evaluate_bench.py --history 4 8 --obs-stats > profiles/evaluate_history_stats_timing.txt
+
+--latency S (with --history, in each of the three forms above): the same envs on the latency ring -- use_latency=True, latency=S,
+history_latency=True -- and the launch of include/pds_history_latency_evaluate.h (history_latency_fused=True) against the composed
+path, which is what such an env ran before that launch was there.  The metrics form also times the launch alone against the
+non-latency history launch of the same shape on an env without the ring, each with its own spread.  Exit status 1 where the launch is
+slower than the composed path.
+
+  python profiles/tools/evaluate_bench.py --history 4 8 --latency 0.02 > profiles/evaluate_history_latency_timing.txt
 """
 import argparse
 import os
@@ -54,10 +62,24 @@ def population(name, P):
                                       one.mean.expand(P, -1), one.std.expand(P, -1), one.eps)
 
 
+LATENCY = None  # --latency S: the history forms fly the latency ring
+
+
+def ring(kw):
+    """the env keywords of a history case, on the latency ring where --latency asks for it"""
+    return dict(kw, use_latency=True, latency=LATENCY, history_latency=True) if LATENCY is not None else kw
+
+
+def entry(name):
+    """the history entry point `name`, or its twin on the latency ring"""
+    return name.replace("pds_evaluate_policies_history", "pds_evaluate_policies_history_latency") if LATENCY is not None else name
+
+
 def timed(env, pop, fused, history_fused=False):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = evaluate_population(env, pop, fused=fused, history_fused=history_fused)  # ends in the copies to the host: synchronised
+    out = evaluate_population(env, pop, fused=fused, history_fused=history_fused,
+                              history_latency_fused=LATENCY is not None)  # ends in the copies to the host: synchronised
     return time.perf_counter() - t0, out
 
 
@@ -80,11 +102,12 @@ def history_main(args):
     print(f"# evaluate_population(history_fused=True) on envs with an observation history, {torch.cuda.get_device_name(0)}; host clock "
           f"around a call that ends in the device-to-host copy of its results; paths alternate; median [min .. max] over {args.reps} reps")
     print("# env  H inputs  P x E | fused: ms, episodes/s | composed: ms, episodes/s | composed / fused | mean length | same bits")
+    ok = True
     for j, (label, env_id, kw) in enumerate(HISTORY_CASES):
         H = args.history[min(j, len(args.history) - 1)]
         for P, E in HISTORY_SHAPES:
-            env_f = pds.make(env_id, num_envs=P * E, seed=1, observation_history_size=H, **kw)
-            env_c = pds.make(env_id, num_envs=P * E, seed=1, observation_history_size=H, **kw)
+            env_f = pds.make(env_id, num_envs=P * E, seed=1, observation_history_size=H, **ring(kw))
+            env_c = pds.make(env_id, num_envs=P * E, seed=1, observation_history_size=H, **ring(kw))
             pop = random_population(env_f.obs_dim, P).to("cuda:0")
             _, first_f = timed(env_f, pop, True, True)  # warm-up of both paths (and the bitwise comparison: same seed, first call)
             _, first_c = timed(env_c, pop, False)
@@ -98,13 +121,35 @@ def history_main(args):
             print(f"{label:13s} {H:2d} {env_f.obs_dim:4d} {P:5d} x {E:5d} | {1e3 * mf:9.2f} [{1e3 * min(tf):.2f} .. {1e3 * max(tf):.2f}] {n / mf:12.0f} | "
                   f"{1e3 * mc:10.2f} [{1e3 * min(tc):.2f} .. {1e3 * max(tc):.2f}] {n / mc:11.0f} | {mc / mf:7.1f}x | "
                   f"{float(first_f[1].mean()):6.1f} | {same}", flush=True)
+            ok &= mf <= mc
+            if LATENCY is not None:  # the launch alone, on the ring and on an env without it
+                env_n = pds.make(env_id, num_envs=P * E, seed=1, observation_history_size=H, **kw)
+                T, dev = env_f._max_episode_steps, env_f.device
+                bufs = tuple(torch.zeros(n, device=dev) for _ in range(3)) + (torch.zeros(n, 8, device=dev), None)
+                k = {"ring": [], "no ring": []}
+                for rep_ in range(args.reps + 1):  # (the first round warms up)
+                    for which, env, name in (("ring", env_f, entry("pds_evaluate_policies_history")), ("no ring", env_n, "pds_evaluate_policies_history")):
+                        ms = history_stats_launch_ms(env, pop, H, P, E, T, bufs, "metrics", name)
+                        if rep_:
+                            k[which].append(ms)
+                kmed = {w: float(np.median(v)) for w, v in k.items()}
+                spread = {w: (max(v) - min(v)) / kmed[w] for w, v in k.items()}
+                ratio = kmed["ring"] / kmed["no ring"]
+                print("    the launch alone: " + ", ".join(f"{w} {kmed[w]:.3f} [{min(k[w]):.3f} .. {max(k[w]):.3f}] ms, (max - min) / median = {spread[w]:.3f}"
+                                                           for w in k) + f"; ring / no ring = {ratio:.3f}: " +
+                      ("outside both spreads" if abs(ratio - 1.0) > max(spread.values()) else "inside the spread") +
+                      " (the flights differ: the ring delays the actions)", flush=True)
+                env_n.close()
             env_f.close(); env_c.close()
+    if LATENCY is not None:
+        sys.exit(0 if ok else 1)
 
 
 def timed_record(env, pop, fused, kw):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = evaluate_population(env, pop, fused=fused, history_fused=bool(fused), metrics=True, **kw)  # ends in the copies to the host
+    out = evaluate_population(env, pop, fused=fused, history_fused=bool(fused), metrics=True, history_latency_fused=LATENCY is not None,
+                              **kw)  # ends in the copies to the host
     torch.cuda.synchronize()
     return time.perf_counter() - t0, out
 
@@ -119,7 +164,7 @@ def history_launch_ms(env, pop, H, P, E, T, R, bufs, form):
     ret, length, cost, raw, flight, obs_rec = bufs
     where = {"record+obs": obs_rec[4:], "record+obs dword": obs_rec[1:-3], "record": None}
     trail = (raw,) if form == "metrics" else (raw, R, flight, where[form])
-    name = "pds_evaluate_policies_history" if form == "metrics" else "pds_evaluate_policies_history_record"
+    name = entry("pds_evaluate_policies_history" if form == "metrics" else "pds_evaluate_policies_history_record")
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
     start.record()
@@ -142,7 +187,7 @@ def history_record_main(args):
     for j, (label, env_id, kw) in enumerate(HISTORY_CASES):
         H = args.history[min(j, len(args.history) - 1)]
         for P, E in HISTORY_SHAPES:
-            envs = [pds.make(env_id, num_envs=P * E, seed=1, observation_history_size=H, **kw) for _ in range(4)]
+            envs = [pds.make(env_id, num_envs=P * E, seed=1, observation_history_size=H, **ring(kw)) for _ in range(4)]
             pop = random_population(envs[0].obs_dim, P).to("cuda:0")
             big = dict(record=R, record_limit_bytes=1 << 32)  # (64 policies x 64 episodes x 500 steps x 160 inputs: 1.4 GB)
             paths = (("fused record+obs", envs[0], True, big), ("fused record", envs[1], True, dict(big, record_observations=False)),
@@ -196,13 +241,15 @@ def history_record_main(args):
     sys.exit(0 if ok else 1)
 
 
-def history_stats_launch_ms(env, pop, H, P, E, T, bufs, form):
-    """device time of ONE launch of the history kernel on buffers made beforehand: form "metrics" or "stats" """
+def history_stats_launch_ms(env, pop, H, P, E, T, bufs, form, name=None):
+    """device time of ONE launch of the history kernel on buffers made beforehand: form "metrics" or "stats"; `name`: the entry
+    point where it is not the form's own (on the ring with --latency)"""
     from phoenix_drone_simulation_amd import native
     obs, _ = env.reset()
     obs = obs.contiguous()
     ret, length, cost, raw, slab = bufs
-    name, trail = ("pds_evaluate_policies_history", (raw,)) if form == "metrics" else ("pds_evaluate_policies_history_stats", (raw, slab))
+    own, trail = ("pds_evaluate_policies_history", (raw,)) if form == "metrics" else ("pds_evaluate_policies_history_stats", (raw, slab))
+    name = name or entry(own)
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
     start.record()
@@ -216,7 +263,7 @@ def history_stats_launch_ms(env, pop, H, P, E, T, bufs, form):
 def history_stats_main(args):
     """--history H [H] --obs-stats: the stats form of the history kernel against the composed sums and against the history
     kernel's metrics launch; the launches alone as well"""
-    from phoenix_drone_simulation_amd.evaluation import fused_history_stats_evaluation_built, slab_features
+    from phoenix_drone_simulation_amd.evaluation import fused_history_latency_stats_evaluation_built, fused_history_stats_evaluation_built, slab_features
     print(f"# evaluate_population(history_fused=True, obs_stats=True, history_stats_fused=True, metrics=True) on envs with an observation "
           f"history, {torch.cuda.get_device_name(0)}; seeded random tanh actors (64, 64)")
     print(f"# host clock around a call that ends in a device synchronise; one warm-up per path and shape, then {args.reps} repeats of each "
@@ -225,8 +272,8 @@ def history_stats_main(args):
     for j, (label, env_id, kw) in enumerate(HISTORY_CASES):
         H = args.history[min(j, len(args.history) - 1)]
         for P, E in HISTORY_SHAPES:
-            envs = [pds.make(env_id, num_envs=P * E, seed=1, observation_history_size=H, **kw) for _ in range(3)]
-            if not fused_history_stats_evaluation_built(envs[0]):
+            envs = [pds.make(env_id, num_envs=P * E, seed=1, observation_history_size=H, **ring(kw)) for _ in range(3)]
+            if not (fused_history_latency_stats_evaluation_built if LATENCY is not None else fused_history_stats_evaluation_built)(envs[0]):
                 print(f"{label} H = {H} ({envs[0].obs_dim} inputs): the stats form is not built for this width")
                 continue
             pop = random_population(envs[0].obs_dim, P).to("cuda:0")
@@ -283,7 +330,15 @@ def main():
                     help="--history: time the record form (pds_evaluate_policies_history_record, R episodes per policy) instead")
     ap.add_argument("--obs-stats", action="store_true",
                     help="--history: time the stats form (pds_evaluate_policies_history_stats) instead")
+    ap.add_argument("--latency", type=float, default=None, metavar="S",
+                    help="--history: the envs on the latency ring (use_latency=True, latency=S, history_latency=True) and the launch of "
+                         "include/pds_history_latency_evaluate.h against the composed path")
     args = ap.parse_args()
+    if args.latency is not None:
+        if not args.history:
+            ap.error("--latency needs --history")
+        global LATENCY
+        LATENCY = args.latency
     if args.history and args.obs_stats:
         return history_stats_main(args)
     if args.history and args.record:

@@ -31,7 +31,9 @@ def rows(lib=None):
     for r in kr.kernel_table(lib):
         m = NAME.search(r[0])
         if m:
-            task, motor, dr, ge, tn, on, ctrl, _, _, hn, form = m.groups()
+            task, motor, dr, ge, tn, on, ctrl, lat, _, hn, form = m.groups()
+            if lat == "true":  # (on the latency ring: profiles/tools/evaluate_history_latency_resources.py)
+                continue
             flags = "".join(c for c, v in zip("MDGTO", (motor, dr, ge, tn, on)) if v == "true") or "-"
             out.setdefault((en.TASK[int(task)], flags, en.CTRL[int(ctrl)], int(hn)), {})[FORM[int(form)]] = r[1:]
     return out
