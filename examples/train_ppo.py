@@ -41,14 +41,22 @@ def main():
     ap.add_argument("--history-latency", action="store_true",
                     help="with --use-latency and a history size other than 2: resolve the history entries that alias the ring's last "
                          "row (DroneVecEnv(history_latency=True)); without it that combination is refused")
-    ap.add_argument("--pi-hidden", type=int, nargs=2, default=(50, 50), help="policy hidden sizes (experiments/04_*: 32 32 / 48 48 / 64 64)")
+    ap.add_argument("--pi-hidden", type=int, nargs="+", default=(50, 50),
+                    help="policy hidden sizes, 2 to 4 values (experiments/04_*: 32 32 / 48 48 / 64 64; experiments/01_*: 50 30 20 / "
+                         "40 40 40 / 30 30 30 / 32 32 32 32 / 25 25 25 25 -- 3 or 4 layers run on the deep kernels under ppo)")
+    ap.add_argument("--val-hidden", type=int, nargs="+", default=(64, 64), help="critic hidden sizes, 2 to 4 values")
+    ap.add_argument("--pi-activation", choices=("relu", "tanh"), default="relu", help="policy activation")
     args = ap.parse_args()
     env_kw = dict(observation_history_size=args.observation_history_size) if args.observation_history_size != 2 else {}
     if args.use_latency:
         env_kw.update(use_latency=True, latency=args.latency)
     if args.history_latency:
         env_kw.update(history_latency=True)
-    ac_kwargs = {"pi": {"hidden_sizes": tuple(args.pi_hidden), "activation": "relu"}, "val": {"hidden_sizes": (64, 64), "activation": "tanh"}}
+    for name, sizes in (("--pi-hidden", args.pi_hidden), ("--val-hidden", args.val_hidden)):
+        if not 2 <= len(sizes) <= 4:
+            ap.error(f"{name} takes 2 to 4 values, not {len(sizes)}")
+    ac_kwargs = {"pi": {"hidden_sizes": tuple(args.pi_hidden), "activation": args.pi_activation},
+                 "val": {"hidden_sizes": tuple(args.val_hidden), "activation": "tanh"}}
     # one process per GPU (the reference: mpi_fork over CPU cores, examples/train_with_multi_cores.py):
     #   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_ppo.py ...
     # every rank steps its shard of the envs; gradients and running statistics are averaged over RCCL

@@ -335,6 +335,10 @@ static int fail(pds_handle *h, int code, const char *fmt, ...) {
 }
 
 static thread_local char g_create_err[512] = "";
+namespace pds_api_detail {
+// what pds_last_error(NULL) returns on this thread, for entry points without a handle (csrc/pds_mlp_deep.hip)
+void set_thread_error(const char *msg) { snprintf(g_create_err, sizeof(g_create_err), "%s", msg); }
+}  // namespace pds_api_detail
 
 #define PDS_HIP(h, call)                                                                        \
   do {                                                                                          \

@@ -17,6 +17,9 @@ gradient for the update.  Each call replaces an autograd op chain of the referen
     ddpg_explore          get_action's clip(pi(o) + noise) behind the actor         algs/ddpg/ddpg.py:342-345
     fused_collect         roll_out: K vector steps into the replay ring, one launch algs/ddpg/ddpg.py:393-429, algs/sac/sac.py:402-437
 
+Networks with three or four hidden layers (csrc/pds_mlp_deep.hip, include/pds_mlp_deep.h) take the first three rows and
+adam_step on kernels of their own (FusedMLP.deep); every other row takes two hidden layers and refuses them.
+
 The gradients are written straight into the `.grad` storage of the torch parameters (one flat
 buffer, torch parameter order), so the optimiser step stays torch.optim.Adam like the reference's."""
 import ctypes as C
@@ -27,27 +30,51 @@ import torch.nn as nn
 from . import native
 
 _ptr, _on = native._ptr, native.on_device  # (for direct calls; every launch below enters the library through native.call)
+# the entry points behind FusedMLP.forward / ppo_grad / value_grad / adam_step: include/pds.h, include/pds_mlp_deep.h
+_SHALLOW_CALLS = ("pds_mlp_forward", "pds_ppo_policy_grad_step", "pds_value_grad_step", "pds_adam_step")
+_DEEP_CALLS = ("pds_mlp_deep_forward", "pds_mlp_deep_ppo_policy_grad_step", "pds_mlp_deep_value_grad_step", "pds_mlp_deep_adam_step")
+
+
+def _refuse_deep(what, *fms):
+    """NotImplementedError where a network with 3 or 4 hidden layers meets a kernel that takes struct pds_mlp (before any native call)"""
+    for fm in fms:
+        if getattr(fm, "deep", False):
+            raise NotImplementedError(f"{what} takes networks with 2 hidden layers; this one has {fm.n_hidden} (the deep kernels of "
+                                      "include/pds_mlp_deep.h cover forward, ppo_grad, value_grad and adam_step)")
 
 
 class FusedMLP:
     """View of `nn.Sequential(Linear, act, Linear, act, Linear[, Identity])` as a struct pds_mlp (`m`; native.call re-binds its
-    pointers wherever a FusedMLP is an argument)."""
+    pointers wherever a FusedMLP is an argument) -- or, with 4 or 5 Linear layers (`deep` is True), as a struct pds_mlp_deep
+    (include/pds_mlp_deep.h): forward, ppo_grad, value_grad, adam_step, flat_grad, stats and workspace are the same calls on the
+    deep kernels, everything else that takes a struct pds_mlp raises NotImplementedError, and there is no `m`."""
 
     def __init__(self, net, activation):
         lin = [l for l in net if isinstance(l, nn.Linear)]
-        if len(lin) != 3 or activation not in native.ACTIVATIONS:
-            raise NotImplementedError("fused kernels cover 2 hidden layers with relu or tanh")
+        if len(lin) not in (3, 4, 5) or activation not in native.ACTIVATIONS:
+            raise NotImplementedError("fused kernels cover 2, 3 or 4 hidden layers with relu or tanh")
         self.lin = lin
+        self.deep = len(lin) > 3
+        self.n_hidden = len(lin) - 1
         self.params = [p for l in lin for p in (l.weight, l.bias)]
         for p in self.params:
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                 raise ValueError("fused kernels need contiguous float32 parameters on the HIP device")
         self.lib = native.load()
-        self.m = m = native.mlp(lin[0].in_features, lin[0].out_features, lin[1].out_features, lin[2].out_features, activation,
-                                tensors=self.params)
-        n = self.lib.pds_mlp_param_count(C.byref(m))
+        if self.deep:
+            self.md = m = native.mlp_deep(lin[0].in_features, [l.out_features for l in lin[:-1]], lin[-1].out_features, activation,
+                                          tensors=self.params)
+            n = self.lib.pds_mlp_deep_param_count(C.byref(m))
+        else:
+            self.m = m = native.mlp(lin[0].in_features, lin[0].out_features, lin[1].out_features, lin[2].out_features, activation,
+                                    tensors=self.params)
+            n = self.lib.pds_mlp_param_count(C.byref(m))
         if n < 0:
-            raise ValueError("layer sizes outside the fused kernels' range (d_in <= 192, h1, h2 <= 64, d_out <= 8)")
+            raise ValueError("layer sizes outside the fused kernels' range (2 hidden layers: d_in <= 192, h1, h2 <= 64, d_out <= 8; "
+                             "3 or 4 hidden layers: d_in <= 64, every hidden width <= 64, d_out <= 8)")
+        if self.deep and self.lib.pds_mlp_deep_supported(C.byref(m)) != 1:
+            raise NotImplementedError(f"the fused kernels for {self.n_hidden} hidden layers take d_in <= 64, not {m.d_in}")
+        self._names = _DEEP_CALLS if self.deep else _SHALLOW_CALLS
         dev = self.params[0].device
         self.flat_grad = torch.zeros(n, device=dev)
         off = 0
@@ -55,11 +82,19 @@ class FusedMLP:
             p.grad = self.flat_grad[off:off + p.numel()].view_as(p)
             off += p.numel()
         self.stats = torch.zeros(4, device=dev)
-        self.workspace = torch.empty(self.lib.pds_mlp_workspace_floats(C.byref(m)), device=dev)
+        ws = self.lib.pds_mlp_deep_workspace_floats(C.byref(m)) if self.deep else self.lib.pds_mlp_workspace_floats(C.byref(m))
+        self.workspace = torch.empty(ws, device=dev)
+
+    @property
+    def d_out(self):
+        return self.lin[-1].out_features
 
     def _bind(self):
-        l = self.lin
-        native.bind_mlp(self.m, (l[0].weight, l[0].bias, l[1].weight, l[1].bias, l[2].weight, l[2].bias))
+        if self.deep:
+            native.bind_mlp_deep(self.md, self.params)
+        else:
+            l = self.lin
+            native.bind_mlp(self.m, (l[0].weight, l[0].bias, l[1].weight, l[1].bias, l[2].weight, l[2].bias))
 
     @staticmethod
     def _stream(t=None):
@@ -69,8 +104,8 @@ class FusedMLP:
     def forward(self, x, index=None, mean=None, std=None, eps=1e-5, out=None):
         """y[B, d_out] = net(standardise(x[index]))."""
         B = x.shape[0] if index is None else index.shape[0]
-        y = out if out is not None else torch.empty(B, self.m.d_out, device=x.device)
-        native.call("pds_mlp_forward", self, x, index, B, mean, std, float(eps), y, on=x)
+        y = out if out is not None else torch.empty(B, self.d_out, device=x.device)
+        native.call(self._names[0], self, x, index, B, mean, std, float(eps), y, on=x)
         return y
 
     def _adam_state(self):
@@ -93,7 +128,7 @@ class FusedMLP:
         [sum(-min(..)), sum(ratio), sum(0.5 z^2), B] (device, no sync).  adam_lr: also take the torch.optim.Adam step
         with this learning rate, in the same two launches (same bits as ppo_grad + adam_step)."""
         opt = self._adam_arg(adam_lr, betas, eps)
-        native.call("pds_ppo_policy_grad_step", self, x, act, adv, logp_old, log_std, x.shape[0], float(clip_ratio), self.flat_grad,
+        native.call(self._names[1], self, x, act, adv, logp_old, log_std, x.shape[0], float(clip_ratio), self.flat_grad,
                     self.stats, self.workspace, opt, on=x)
         return self.stats
 
@@ -101,7 +136,7 @@ class FusedMLP:
         """torch.optim.Adam.step for this network's parameters from the flat gradient, in one launch."""
         self._adam_state()
         self.adam_steps += 1
-        native.call("pds_adam_step", self, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.adam_steps, float(lr), float(betas[0]),
+        native.call(self._names[3], self, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.adam_steps, float(lr), float(betas[0]),
                     float(betas[1]), float(eps), on=self.flat_grad)
 
     def value_grad(self, x, target, index=None, adam_lr=None, betas=(0.9, 0.999), eps=1e-8):
@@ -109,10 +144,11 @@ class FusedMLP:
         adam_lr: as in ppo_grad."""
         B = x.shape[0] if index is None else index.shape[0]
         opt = self._adam_arg(adam_lr, betas, eps)
-        native.call("pds_value_grad_step", self, x, index, target, B, self.flat_grad, self.stats, self.workspace, opt, on=x)
+        native.call(self._names[2], self, x, index, target, B, self.flat_grad, self.stats, self.workspace, opt, on=x)
         return self.stats
 
     def _npg_workspace(self, candidates):
+        _refuse_deep("the natural-gradient workspace (pds_npg_workspace_floats)", self)
         n = self.lib.pds_npg_workspace_floats(C.byref(self.m), int(candidates))
         ws = getattr(self, "npg_workspace", None)
         if ws is None or ws.numel() < n:
@@ -122,6 +158,7 @@ class FusedMLP:
     def fisher_vector_product(self, x, v, log_std, damping, index=None, out=None):
         """F v + damping v (flat, param_count) over the standardised rows x[index] (csrc/pds_npg.hip): the Fisher matrix of
         the Gaussian policy with the fixed log_std at the current parameters, mean over samples x action dims."""
+        _refuse_deep("fisher_vector_product (pds_npg_fisher_vector_product)", self)
         B = x.shape[0] if index is None else index.shape[0]
         out = out if out is not None else torch.empty_like(self.flat_grad)
         native.call("pds_npg_fisher_vector_product", self, x, index, B, log_std, v, float(damping), out, self._npg_workspace(0), on=x)
@@ -131,6 +168,7 @@ class FusedMLP:
         """[J, 4] device tensor: per candidate theta + fracs[j] * step (fracs: float32 device tensor [J]) the sum of ratio * adv
         over the batch, the sum of KL(Normal(mu_old, sigma) || Normal(mu_j, sigma)) over samples x action dims, a non-finite
         flag and the sum of ratio (csrc/pds_npg.hip).  theta_out [J, param_count]: also the candidates' parameters."""
+        _refuse_deep("surrogate_kl (pds_npg_surrogate_kl)", self)
         J = int(fracs.shape[0])
         out = torch.empty(J, 4, device=x.device)
         native.call("pds_npg_surrogate_kl", self, step, fracs, J, x, act, adv, logp_old, mu_old, log_std, x.shape[0], out, theta_out,
@@ -142,6 +180,7 @@ class FusedMLP:
         -Q(o, pi(o)).mean() over the rows oa[index] = [obs | act] (index None: every row), Q = `q_fm` (read only);
         stats[0] = sum of Q(o, pi(o)), stats[3] = B (csrc/pds_ddpg.hip).  adam_lr: as in ppo_grad.
         NotImplementedError for shapes the kernel is not built for (ddpg_supported says so beforehand)."""
+        _refuse_deep("ddpg_policy_grad (pds_ddpg_policy_grad)", self, q_fm)
         B = oa.shape[0] if index is None else index.shape[0]
         ws = getattr(self, "ddpg_workspace", None)
         if ws is None:
@@ -159,6 +198,7 @@ class FusedMLP:
         squashed-Gaussian sample under the noise of (seed, call); Q1, Q2 = `q1_fm`, `q2_fm` (read only).  stats = [sum min Q,
         sum logp, 0, B] (csrc/pds_sac.hip).  adam_lr: as in ppo_grad.  NotImplementedError for shapes the kernel is not built
         for (sac_supported says so beforehand)."""
+        _refuse_deep("sac_policy_grad (pds_sac_policy_grad)", self, q1_fm, q2_fm)
         B = oa.shape[0] if index is None else index.shape[0]
         ws = getattr(self, "sac_workspace", None)
         if ws is None:
@@ -174,12 +214,14 @@ class FusedMLP:
 
 def ddpg_supported(pi_fm, q_fm):
     """True when the fused DDPG kernels cover this actor / Q pair (D + 4 <= 64, hidden <= 64, d_out 4 / 1)."""
+    _refuse_deep("ddpg_supported (pds_ddpg_supported)", pi_fm, q_fm)
     return native.load().pds_ddpg_supported(C.byref(pi_fm.m), C.byref(q_fm.m)) == 1
 
 
 def ddpg_target(pi_targ_fm, q_targ_fm, obs2, index, rew, done, gamma, act_limit, target_rows):
     """target_rows[i] = rew[i] + gamma * (1 - done[i]) * Q_targ(obs2[i], act_limit * tanh(pi_targ(obs2[i]))) for the rows
     i = index[g] (index None: every row); the other rows are left alone (include/pds.h pds_ddpg_target)."""
+    _refuse_deep("ddpg_target (pds_ddpg_target)", pi_targ_fm, q_targ_fm)
     B = obs2.shape[0] if index is None else index.shape[0]
     native.call("pds_ddpg_target", pi_targ_fm, q_targ_fm, obs2, index, B, rew, done, float(gamma), float(act_limit), target_rows,
                 on=obs2)
@@ -188,11 +230,13 @@ def ddpg_target(pi_targ_fm, q_targ_fm, obs2, index, rew, done, gamma, act_limit,
 
 def polyak(targ_fm, src_fm, rho):
     """p_targ.mul_(rho); p_targ.add_((1 - rho) * p) over the six tensors of a network pair, one launch, the same bits."""
+    _refuse_deep("polyak (pds_polyak)", targ_fm, src_fm)
     native.call("pds_polyak", targ_fm, src_fm, float(rho), on=targ_fm.params[0])
 
 
 def sac_supported(pi_fm, q1_fm, q2_fm):
     """True when the fused SAC kernels cover this actor / twin-Q triple (D + 4 <= 64, hidden <= 64, d_out 8 / 1 / 1)."""
+    _refuse_deep("sac_supported (pds_sac_supported)", pi_fm, q1_fm, q2_fm)
     return native.load().pds_sac_supported(C.byref(pi_fm.m), C.byref(q1_fm.m), C.byref(q2_fm.m)) == 1
 
 
@@ -214,6 +258,7 @@ def sac_target(pi_fm, q1_targ_fm, q2_targ_fm, obs2, index, rew, done, gamma, alp
     """target_rows[i] = rew[i] + gamma * (1 - done[i]) * (min(Q1_targ, Q2_targ)(obs2[i], a2) - alpha * logp2) for the rows
     i = index[g] (index None: every row), (a2, logp2) the sample of the CURRENT policy `pi_fm` under the noise of (seed, call)
     at position g; the other rows are left alone (include/pds.h pds_sac_target)."""
+    _refuse_deep("sac_target (pds_sac_target)", pi_fm, q1_targ_fm, q2_targ_fm)
     B = obs2.shape[0] if index is None else index.shape[0]
     native.call("pds_sac_target", pi_fm, q1_targ_fm, q2_targ_fm, obs2, index, B, rew, done, float(gamma), float(alpha),
                 float(act_limit), int(seed) & (2 ** 64 - 1), int(call), target_rows, on=obs2)
@@ -238,6 +283,7 @@ def ddpg_explore(net_out, log_std, act_limit, seed, call, id_base=0, act_out=Non
 
 def collect_supported(env, fm_pi, mode):
     """True when pds_collect has a kernel for this env and actor in this mode (COLLECT_DDPG: d_out 4, COLLECT_SAC: d_out 8)."""
+    _refuse_deep("collect_supported (pds_collect_supported)", fm_pi)
     return env.lib.pds_collect_supported(env._handle, C.byref(fm_pi.m), int(mode)) == 1
 
 
@@ -245,6 +291,7 @@ def collect_control_supported(env, fm_pi, mode):
     """True when pds_collect_control (include/pds_collect_control.h) has a kernel for this env and actor in this mode: wherever
     collect_supported holds, and on Hover and Circle under control_mode AttitudeRate / Attitude and / or with the latency ring
     (noise off or the reference's default, with and without motor dynamics)."""
+    _refuse_deep("collect_control_supported (pds_collect_control_supported)", fm_pi)
     return env.lib.pds_collect_control_supported(env._handle, C.byref(fm_pi.m), int(mode)) == 1
 
 
@@ -261,6 +308,7 @@ def fused_collect(env, fm_pi, mode, K, act_limit, log_std, seed, first_call, oa,
     statistics.  control=True: pds_collect_control (include/pds_collect_control.h), which also flies the PID control modes and
     the latency ring -- collect_control_supported -- and is the same launch wherever pds_collect has one.  Raises
     NotImplementedError / ValueError where the entry point refuses (the env is left as it was)."""
+    _refuse_deep("fused_collect (pds_collect)", fm_pi)
     native.call("pds_collect_control" if control else "pds_collect", env._handle, int(K), int(mode), fm_pi, float(act_limit), log_std, int(seed) & (2 ** 64 - 1),
                 int(first_call), oa, obs2, rew, done, int(oa.shape[0]), int(ptr), obs, ep_ret, ep_len, tile_stats,
                 on=obs, handle=env._handle)
@@ -303,6 +351,7 @@ def fused_rollout(env, fm_pi, fm_v, T, mean, std, eps, log_std, seed, call_offse
     """ONE launch for the T closed-loop steps of a rollout (include/pds.h pds_rollout, csrc/pds_rollout.h): obs_buf is
     [T + 1, N, D] with o(0) in row 0.  Raises NotImplementedError for env configurations the kernel is not built
     for (the per-step path gives the same bits)."""
+    _refuse_deep("fused_rollout (pds_rollout)", fm_pi, fm_v)
     native.call("pds_rollout", env._handle, int(T), fm_pi, fm_v, mean, std, float(eps), log_std, int(seed), call_base,
                 int(call_offset), int(bool(deterministic)), obs_buf, act_buf, logp_buf, val_buf, rew_buf, term_buf, trunc_buf,
                 cost_buf, fval_buf, last_val, ep_ret, ep_len, stats, on=obs_buf, handle=env._handle)
@@ -327,6 +376,7 @@ def fused_rollout_history(env, fm_pi, T, H, mean, std, eps, log_std, seed, call_
     whose fin_step [slots, N] (int32, preset to -1) names the step each belongs to).  Raises NotImplementedError for env
     configurations the kernel is not built for (the per-step path gives the same bits).  latency=True: pds_rollout_history_latency
     (include/pds_history_latency.h), the same launch on the latency ring of an env created with history_latency=True."""
+    _refuse_deep("fused_rollout_history (pds_rollout_history)", fm_pi)
     if latency and not rollout_history_latency_supported(env):
         raise NotImplementedError("pds_rollout_history_latency: not built for this env (rollout_history_latency_supported)")
     native.call("pds_rollout_history_latency" if latency else "pds_rollout_history", env._handle, int(T), int(H), fm_pi, mean, std, float(eps), log_std, int(seed), call_base,

@@ -41,6 +41,16 @@ class Mlp(C.Structure):
                 ("w3", C.c_void_p), ("b3", C.c_void_p)]
 
 
+MLP_DEEP_MAX_HIDDEN = 4  # PDS_MLP_DEEP_MAX_HIDDEN
+
+
+class MlpDeep(C.Structure):
+    """struct pds_mlp_deep (include/pds_mlp_deep.h): MLP with 3 or 4 hidden layers, torch nn.Linear layout, device pointers."""
+    _fields_ = [("d_in", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * MLP_DEEP_MAX_HIDDEN), ("d_out", C.c_int32),
+                ("activation", C.c_int32),
+                ("w", C.c_void_p * (MLP_DEEP_MAX_HIDDEN + 1)), ("b", C.c_void_p * (MLP_DEEP_MAX_HIDDEN + 1))]
+
+
 class Adam(C.Structure):
     """struct pds_adam (include/pds.h): the optimiser step that rides on a gradient call."""
     _fields_ = [("d_exp_avg", C.c_void_p), ("d_exp_avg_sq", C.c_void_p), ("step", C.c_int64),
@@ -179,6 +189,17 @@ HISTORY_LATENCY_EVALUATE_SIGNATURES = {
     "pds_evaluate_policies_history_latency_record": HISTORY_RECORD_SIGNATURES["pds_evaluate_policies_history_record"],
     "pds_evaluate_policies_history_latency_stats": HISTORY_STATS_SIGNATURES["pds_evaluate_policies_history_stats"],
 }
+# ... and of include/pds_mlp_deep.h, the dense kernels for networks with 3 or 4 hidden layers (tests/test_mlp_deep_cpu.py); the
+# struct pds_mlp_deep goes in by reference as a plain pointer (MlpDeep)
+MLP_DEEP_SIGNATURES = {
+    "pds_mlp_deep_supported": (_i32, [_vp]),
+    "pds_mlp_deep_param_count": (_i32, [_vp]),
+    "pds_mlp_deep_workspace_floats": (_i64, [_vp]),
+    "pds_mlp_deep_forward": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _f32, _vp, _vp]),
+    "pds_mlp_deep_ppo_policy_grad_step": (_i32, [_vp] * 6 + [_i64, _f32] + [_vp] * 3 + [_ap, _vp]),
+    "pds_mlp_deep_value_grad_step": (_i32, [_vp] * 4 + [_i64] + [_vp] * 3 + [_ap, _vp]),
+    "pds_mlp_deep_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _vp]),
+}
 
 _lib = None
 
@@ -199,7 +220,7 @@ def load():
     # an OLDER build given through PDS_LIB for a same-box A/B (profiles/tools/ab_lib.sh) may lack the newer entry points: those
     # are skipped; the shipped library must have every name (AttributeError here, and tests/test_host_cpu.py)
     older = bool(os.environ.get("PDS_LIB"))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()) + list(COLLECT_CONTROL_SIGNATURES.items()) + list(HISTORY_LATENCY_SIGNATURES.items()) + list(HISTORY_LATENCY_EVALUATE_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()) + list(COLLECT_CONTROL_SIGNATURES.items()) + list(HISTORY_LATENCY_SIGNATURES.items()) + list(HISTORY_LATENCY_EVALUATE_SIGNATURES.items()) + list(MLP_DEEP_SIGNATURES.items()):
         if older and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
@@ -244,6 +265,32 @@ def mlp(d_in, h1, h2, d_out, activation, tensors=None, base=None):
 def bind_mlp(m, tensors):
     """Point the struct at where W1, b1, W2, b2, W3, b3 are now (an optimiser or a load may have moved them)."""
     m.w1, m.b1, m.w2, m.b2, m.w3, m.b3 = [t.data_ptr() for t in tensors]
+
+
+def mlp_deep(d_in, hidden, d_out, activation, tensors=None, base=None):
+    """struct pds_mlp_deep of a d_in -> hidden[0] -> ... -> hidden[-1] -> d_out network (3 or 4 hidden layers).  Its pointers come
+    from `tensors` (W1, b1, ..., W(L+1), b(L+1)) or from `base`, the address of a flat float32 parameter row that holds them in
+    that order (pds_mlp_deep_param_count's layout)."""
+    hidden = [int(h) for h in hidden]
+    if len(hidden) > MLP_DEEP_MAX_HIDDEN:
+        raise ValueError(f"struct pds_mlp_deep holds up to {MLP_DEEP_MAX_HIDDEN} hidden layers, not {len(hidden)}")
+    m = MlpDeep(int(d_in), len(hidden), (C.c_int32 * MLP_DEEP_MAX_HIDDEN)(*hidden), int(d_out), ACTIVATIONS[activation])
+    if tensors is not None:
+        bind_mlp_deep(m, tensors)
+    elif base is not None:
+        dims = [int(d_in)] + hidden + [int(d_out)]
+        for l in range(len(hidden) + 1):
+            m.w[l] = base
+            base += 4 * dims[l + 1] * dims[l]
+            m.b[l] = base
+            base += 4 * dims[l + 1]
+    return m
+
+
+def bind_mlp_deep(m, tensors):
+    """Point the struct at where W1, b1, ..., W(L+1), b(L+1) are now (an optimiser or a load may have moved them)."""
+    for l in range(len(tensors) // 2):
+        m.w[l], m.b[l] = tensors[2 * l].data_ptr(), tensors[2 * l + 1].data_ptr()
 
 
 def _ptr(t, byte_offset=0):
@@ -296,8 +343,14 @@ def call(name, *args, on=None, handle=None):
             if hasattr(x, "data_ptr"):
                 x = x.data_ptr()
             elif hasattr(x, "_bind"):
-                x._bind()
-                x = C.byref(x.m)
+                if getattr(x, "deep", False):  # a struct pds_mlp_deep: only its own entry points may read it
+                    if name not in MLP_DEEP_SIGNATURES:
+                        raise NotImplementedError(f"{name} takes networks with 2 hidden layers (struct pds_mlp), not {x.n_hidden}")
+                    x._bind()
+                    x = C.byref(x.md)
+                else:
+                    x._bind()
+                    x = C.byref(x.m)
         a.append(x)
     if on is None:
         rc = fn(*a)

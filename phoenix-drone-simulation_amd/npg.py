@@ -79,6 +79,7 @@ class NPGTrainer(PPOTrainer):
     """NaturalPolicyGradientAlgorithm on a DroneVecEnv (algs/npg/defaults.py: target_kl 0.01, cg_damping 0.1, cg_iters 10;
     no learning-rate schedule for the policy).  Other arguments as PPOTrainer."""
     line_search = False
+    _deep_actor = False  # the Fisher-vector product and the line search take struct pds_mlp: a deeper actor runs as PyTorch ops
 
     def __init__(self, env, cg_damping=0.1, cg_iters=10, target_kl=0.01, total_steps=TOTAL_STEPS, decay=DECAY, **kwargs):
         super().__init__(env, target_kl=target_kl, **kwargs)

@@ -249,6 +249,7 @@ def avg_grads(module):
 
 class PPOTrainer:
     """IWPGAlgorithm + PPO loss on a DroneVecEnv.  steps_per_epoch = rollout_len * env.num_envs per rank."""
+    _deep_actor = True  # an actor with 3 or 4 hidden layers runs on the deep kernels (include/pds_mlp_deep.h)
 
     def __init__(self, env, rollout_len=32, epochs=300, gamma=0.99, lam=0.95, clip_ratio=0.2,
                  entropy_coef=0.01, use_entropy=False, pi_lr=3e-4, vf_lr=1e-3, train_pi_iterations=80,
@@ -308,6 +309,9 @@ class PPOTrainer:
             try:
                 self.fm_pi = FusedMLP(self.ac.pi.net, kw["pi"]["activation"])
                 self.fm_v = FusedMLP(self.ac.v.net, kw["val"]["activation"])
+                if self.fm_pi.deep and not self._deep_actor:
+                    raise NotImplementedError(f"{type(self).__name__}: the natural-gradient kernels take an actor with 2 hidden "
+                                              f"layers, not {self.fm_pi.n_hidden}")
             except (ValueError, NotImplementedError) as e:
                 # outside the fused kernels' range (layer sizes, depths, activations: fused.FusedMLP says which): the networks
                 # run as PyTorch ops on the HIP envs (same update, the path the fused kernels are tested against) -- an order
@@ -320,6 +324,12 @@ class PPOTrainer:
                 self.fused = False
                 self.graph_rollout = False
                 self.fm_pi = self.fm_v = None
+        if self.fused and (self.fm_pi.deep or self.fm_v.deep):
+            # 3 or 4 hidden layers (include/pds_mlp_deep.h): each network is its own FusedMLP on the deep kernels; the one-launch
+            # rollouts take struct pds_mlp, so the rollout runs on the per-step kernels (captured into a graph as before)
+            if self.fused_rollout:
+                raise NotImplementedError("fused_rollout=True: the one-launch rollouts take networks with 2 hidden layers "
+                                          f"(pi {self.fm_pi.n_hidden}, val {self.fm_v.n_hidden})")
         if self.fused:
             # Adam runs in pds_adam_step; the torch optimisers only carry the learning rate (LambdaLR)
             self.pi_opt._opt_called = True
