@@ -43,10 +43,17 @@ def main():
                          "row (DroneVecEnv(history_latency=True)); without it that combination is refused")
     ap.add_argument("--pi-hidden", type=int, nargs="+", default=(50, 50),
                     help="policy hidden sizes, 2 to 4 values (experiments/04_*: 32 32 / 48 48 / 64 64; experiments/01_*: 50 30 20 / "
-                         "40 40 40 / 30 30 30 / 32 32 32 32 / 25 25 25 25 -- 3 or 4 layers run on the deep kernels under ppo)")
+                         "40 40 40 / 30 30 30 / 32 32 32 32 / 25 25 25 25 -- 3 or 4 layers run on the deep kernels under ppo, and under "
+                         "npg / trpo with --deep-fused)")
     ap.add_argument("--val-hidden", type=int, nargs="+", default=(64, 64), help="critic hidden sizes, 2 to 4 values")
     ap.add_argument("--pi-activation", choices=("relu", "tanh"), default="relu", help="policy activation")
+    ap.add_argument("--deep-fused", action="store_true",
+                    help="--alg npg / trpo with 3 or 4 policy hidden layers: run the policy step on the fused natural-gradient kernels "
+                         "(NPGTrainer(deep_fused=True)) instead of PyTorch ops, e.g. the reference's architecture search: --alg trpo "
+                         "--pi-hidden 50 30 20 --pi-activation relu --deep-fused; ppo needs no keyword and rejects it")
     args = ap.parse_args()
+    if args.deep_fused and args.alg == "ppo":
+        ap.error("--deep-fused is for --alg npg / trpo; ppo runs 3 or 4 hidden layers on the deep kernels without a keyword")
     env_kw = dict(observation_history_size=args.observation_history_size) if args.observation_history_size != 2 else {}
     if args.use_latency:
         env_kw.update(use_latency=True, latency=args.latency)
@@ -70,7 +77,8 @@ def main():
     else:
         env = pds.make(args.env, num_envs=args.num_envs, seed=args.seed, **env_kw)  # the reference's default config
     cls = {"ppo": PPOTrainer, "npg": NPGTrainer, "trpo": TRPOTrainer}[args.alg]
-    trainer = cls(env, rollout_len=args.rollout_len, epochs=args.epochs, seed=args.seed, ac_kwargs=ac_kwargs)
+    alg_kw = dict(deep_fused=True) if args.deep_fused else {}
+    trainer = cls(env, rollout_len=args.rollout_len, epochs=args.epochs, seed=args.seed, ac_kwargs=ac_kwargs, **alg_kw)
     t0 = time.time()
     for e in range(args.epochs):
         i = trainer.learn_one_epoch()

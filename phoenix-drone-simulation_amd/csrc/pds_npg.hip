@@ -25,7 +25,7 @@
 // staged into LDS -- the product and the sum rounded separately (__fmul_rn / __fadd_rn, as torch's `theta + f * s` with f
 // rounded to float32), so the trainer can write the accepted candidate with the same expression, bit for bit.  Per
 // candidate: sum(ratio adv), sum of KL(p_old || q) over samples x actions and sum(ratio), in a fixed order.
-#include "pds_mlp_tile.h"
+#include "pds_npg_tile.h"
 
 namespace pds_mlp_detail {
 
@@ -44,23 +44,6 @@ struct NpgArgs {
   float *theta_out;          // surrogate: optional [J][total] candidate parameters
   int pstride;
 };
-
-// gemm_lds (pds_mlp_tile.h) with the A operand read from a row-major [rows][cols] matrix in global memory (zero outside it)
-template <int NK>
-__device__ __forceinline__ f32x4 gemm_glb(const float *V, int rows, int cols, int it, const f32x4 (&in)[NK], int n, int g,
-                                          f32x4 c) {
-  const int r = it * kTW + n;
-  const bool rin = r < rows;
-#pragma unroll
-  for (int kt = 0; kt < NK; ++kt)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int k = kt * kTW + 4 * g + j;
-      const float av = (rin && k < cols) ? V[r * cols + k] : 0.f;
-      c = PDS_MFMA(av, in[kt][j], c);
-    }
-  return c;
-}
 
 // layer 1 with the B operand (this lane's own 4 features per input tile) read back from its row of the X image instead of
 // held in 4 NK registers: what keeps the fvp kernel at 192 inputs free of spills
@@ -95,8 +78,6 @@ __device__ __forceinline__ f32x4 gemm_glb_x(const float *V, int rows, int cols, 
 
 // parameter i of the flat layout, read from the network's six tensors
 __device__ __forceinline__ float theta_at(const pds_mlp &m, const Offsets &o, int i) { return *param_ptr(m, o, i); }
-// candidate parameter theta + f s: product and sum rounded separately (no FMA contraction)
-__device__ __forceinline__ float cand(float theta, float f, float s) { return __fadd_rn(theta, __fmul_rn(f, s)); }
 
 template <int ACT, int NIN>
 __global__ __launch_bounds__(kWideWaves * 64, 1) void fvp_kernel(const NpgArgs a) {
@@ -347,6 +328,16 @@ __global__ __launch_bounds__(64) void surrogate_reduce_kernel(const float *parti
   }
 }
 
+// the launches of the two reduce kernels (declared in pds_npg_tile.h: csrc/pds_npg_deep.hip sums its partials with them too)
+void npg_reduce_fvp(hipStream_t s, const float *partials, int pstride, int nwaves, int total, float scale, float damping,
+                    const float *v, float *out) {
+  hipLaunchKernelGGL(fvp_reduce_kernel, dim3((total + 63) / 64), dim3(1024), 0, s, partials, pstride, nwaves, total, scale, damping,
+                     v, out);
+}
+void npg_reduce_surrogate(hipStream_t s, const float *partials, int nwaves, int num_candidates, float *out) {
+  hipLaunchKernelGGL(surrogate_reduce_kernel, dim3(num_candidates), dim3(64), 0, s, partials, nwaves, out);
+}
+
 // input tiles: 2 (d_in <= 32), 4 (<= 64), 8 (<= 128), 12 (<= 192)
 template <int ACT>
 static void launch_fvp(int nin, dim3 g, hipStream_t s, const NpgArgs &a) {
@@ -387,8 +378,7 @@ extern "C" int pds_npg_fisher_vector_product(const pds_mlp *m, const float *d_x,
   hipStream_t s = (hipStream_t)stream;
   if (m->activation == 0) launch_fvp<0>(nin, dim3(blocks), s, a); else launch_fvp<1>(nin, dim3(blocks), s, a);
   const float scale = 1.0f / (float)((double)B * (double)m->d_out);
-  hipLaunchKernelGGL(fvp_reduce_kernel, dim3((o.total + 63) / 64), dim3(1024), 0, s, (const float *)d_workspace, a.pstride,
-                     blocks * kWideWaves, o.total, scale, damping, d_v, d_out);
+  npg_reduce_fvp(s, d_workspace, a.pstride, blocks * kWideWaves, o.total, scale, damping, d_v, d_out);
   return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
 }
 
@@ -414,7 +404,6 @@ extern "C" int pds_npg_surrogate_kl(const pds_mlp *m, const float *d_step, const
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(blocks, num_candidates);
   if (m->activation == 0) launch_surrogate<0>(nin, g, s, a); else launch_surrogate<1>(nin, g, s, a);
-  hipLaunchKernelGGL(surrogate_reduce_kernel, dim3(num_candidates), dim3(64), 0, s, (const float *)d_workspace,
-                     blocks * kWideWaves, d_out);
+  npg_reduce_surrogate(s, d_workspace, blocks * kWideWaves, num_candidates, d_out);
   return hipGetLastError() == hipSuccess ? PDS_OK : PDS_EHIP;
 }

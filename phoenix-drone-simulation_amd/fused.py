@@ -18,7 +18,8 @@ gradient for the update.  Each call replaces an autograd op chain of the referen
     fused_collect         roll_out: K vector steps into the replay ring, one launch algs/ddpg/ddpg.py:393-429, algs/sac/sac.py:402-437
 
 Networks with three or four hidden layers (csrc/pds_mlp_deep.hip, include/pds_mlp_deep.h) take the first three rows and
-adam_step on kernels of their own (FusedMLP.deep); every other row takes two hidden layers and refuses them.
+adam_step on kernels of their own (FusedMLP.deep); every other row takes two hidden layers and refuses them -- but for
+fisher_vector_product and surrogate_kl of a FusedMLP built with npg_deep=True (csrc/pds_npg_deep.hip, include/pds_npg_deep.h).
 
 The gradients are written straight into the `.grad` storage of the torch parameters (one flat
 buffer, torch parameter order), so the optimiser step stays torch.optim.Adam like the reference's."""
@@ -33,6 +34,9 @@ _ptr, _on = native._ptr, native.on_device  # (for direct calls; every launch bel
 # the entry points behind FusedMLP.forward / ppo_grad / value_grad / adam_step: include/pds.h, include/pds_mlp_deep.h
 _SHALLOW_CALLS = ("pds_mlp_forward", "pds_ppo_policy_grad_step", "pds_value_grad_step", "pds_adam_step")
 _DEEP_CALLS = ("pds_mlp_deep_forward", "pds_mlp_deep_ppo_policy_grad_step", "pds_mlp_deep_value_grad_step", "pds_mlp_deep_adam_step")
+# the entry points behind FusedMLP._npg_workspace / fisher_vector_product / surrogate_kl: include/pds.h, include/pds_npg_deep.h
+_NPG_CALLS = ("pds_npg_workspace_floats", "pds_npg_fisher_vector_product", "pds_npg_surrogate_kl")
+_NPG_DEEP_CALLS = ("pds_npg_deep_workspace_floats", "pds_npg_deep_fisher_vector_product", "pds_npg_deep_surrogate_kl")
 
 
 def _refuse_deep(what, *fms):
@@ -47,9 +51,11 @@ class FusedMLP:
     """View of `nn.Sequential(Linear, act, Linear, act, Linear[, Identity])` as a struct pds_mlp (`m`; native.call re-binds its
     pointers wherever a FusedMLP is an argument) -- or, with 4 or 5 Linear layers (`deep` is True), as a struct pds_mlp_deep
     (include/pds_mlp_deep.h): forward, ppo_grad, value_grad, adam_step, flat_grad, stats and workspace are the same calls on the
-    deep kernels, everything else that takes a struct pds_mlp raises NotImplementedError, and there is no `m`."""
+    deep kernels, everything else that takes a struct pds_mlp raises NotImplementedError, and there is no `m`.
+    npg_deep=True: on a deep network _npg_workspace, fisher_vector_product and surrogate_kl are the same calls too, on the kernels
+    of include/pds_npg_deep.h (so conjugate_gradients works over them); on two hidden layers the keyword changes nothing."""
 
-    def __init__(self, net, activation):
+    def __init__(self, net, activation, npg_deep=False):
         lin = [l for l in net if isinstance(l, nn.Linear)]
         if len(lin) not in (3, 4, 5) or activation not in native.ACTIVATIONS:
             raise NotImplementedError("fused kernels cover 2, 3 or 4 hidden layers with relu or tanh")
@@ -75,6 +81,8 @@ class FusedMLP:
         if self.deep and self.lib.pds_mlp_deep_supported(C.byref(m)) != 1:
             raise NotImplementedError(f"the fused kernels for {self.n_hidden} hidden layers take d_in <= 64, not {m.d_in}")
         self._names = _DEEP_CALLS if self.deep else _SHALLOW_CALLS
+        self.npg_deep = bool(npg_deep) and self.deep
+        self._npg_names = _NPG_DEEP_CALLS if self.npg_deep else _NPG_CALLS
         dev = self.params[0].device
         self.flat_grad = torch.zeros(n, device=dev)
         off = 0
@@ -148,8 +156,11 @@ class FusedMLP:
         return self.stats
 
     def _npg_workspace(self, candidates):
-        _refuse_deep("the natural-gradient workspace (pds_npg_workspace_floats)", self)
-        n = self.lib.pds_npg_workspace_floats(C.byref(self.m), int(candidates))
+        if not self.npg_deep:
+            _refuse_deep("the natural-gradient workspace (pds_npg_workspace_floats)", self)
+        n = getattr(self.lib, self._npg_names[0])(C.byref(self.md if self.npg_deep else self.m), int(candidates))
+        if n < 0:
+            raise (NotImplementedError if n == native.EUNSUPPORTED else ValueError)(f"{self._npg_names[0]} -> {n}")
         ws = getattr(self, "npg_workspace", None)
         if ws is None or ws.numel() < n:
             self.npg_workspace = ws = torch.empty(n, device=self.flat_grad.device)
@@ -157,21 +168,24 @@ class FusedMLP:
 
     def fisher_vector_product(self, x, v, log_std, damping, index=None, out=None):
         """F v + damping v (flat, param_count) over the standardised rows x[index] (csrc/pds_npg.hip): the Fisher matrix of
-        the Gaussian policy with the fixed log_std at the current parameters, mean over samples x action dims."""
-        _refuse_deep("fisher_vector_product (pds_npg_fisher_vector_product)", self)
+        the Gaussian policy with the fixed log_std at the current parameters, mean over samples x action dims.  A network with 3
+        or 4 hidden layers needs npg_deep=True at construction (csrc/pds_npg_deep.hip)."""
+        if not self.npg_deep:
+            _refuse_deep("fisher_vector_product (pds_npg_fisher_vector_product)", self)
         B = x.shape[0] if index is None else index.shape[0]
         out = out if out is not None else torch.empty_like(self.flat_grad)
-        native.call("pds_npg_fisher_vector_product", self, x, index, B, log_std, v, float(damping), out, self._npg_workspace(0), on=x)
+        native.call(self._npg_names[1], self, x, index, B, log_std, v, float(damping), out, self._npg_workspace(0), on=x)
         return out
 
     def surrogate_kl(self, step, fracs, x, act, adv, logp_old, mu_old, log_std, theta_out=None):
         """[J, 4] device tensor: per candidate theta + fracs[j] * step (fracs: float32 device tensor [J]) the sum of ratio * adv
         over the batch, the sum of KL(Normal(mu_old, sigma) || Normal(mu_j, sigma)) over samples x action dims, a non-finite
         flag and the sum of ratio (csrc/pds_npg.hip).  theta_out [J, param_count]: also the candidates' parameters."""
-        _refuse_deep("surrogate_kl (pds_npg_surrogate_kl)", self)
+        if not self.npg_deep:
+            _refuse_deep("surrogate_kl (pds_npg_surrogate_kl)", self)
         J = int(fracs.shape[0])
         out = torch.empty(J, 4, device=x.device)
-        native.call("pds_npg_surrogate_kl", self, step, fracs, J, x, act, adv, logp_old, mu_old, log_std, x.shape[0], out, theta_out,
+        native.call(self._npg_names[2], self, step, fracs, J, x, act, adv, logp_old, mu_old, log_std, x.shape[0], out, theta_out,
                     self._npg_workspace(J), on=x)
         return out
 

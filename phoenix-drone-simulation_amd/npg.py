@@ -14,7 +14,11 @@ KL stays within 1.5 target_kl (TRPO).  The Fisher-vector products run over every
 fused=True: the policy gradient is pds_ppo_policy_grad with an infinite clip ratio (min(r A, clip(r) A) = r A), the Fisher
 products, the CG iterations and the line-search candidates are the kernels of csrc/pds_npg.hip -- the step up to alpha with
 one host read.  fused=False: the PyTorch-op restatement of the reference (double backward through autograd), the yardstick
-of the fused path and the fallback for networks the kernels do not cover."""
+of the fused path and the fallback for networks the kernels do not cover.
+
+An actor with 3 or 4 hidden layers (the reference's architecture search trains (50, 30, 20) and (32, 32, 32, 32) with --alg trpo)
+takes the PyTorch-op step with a warning unless the trainer is built with deep_fused=True: then the same fused step runs on the
+kernels of csrc/pds_npg_deep.hip (include/pds_npg_deep.h), for d_in <= 64."""
 import math
 
 import torch
@@ -77,11 +81,17 @@ def _set_flat(params, flat):
 
 class NPGTrainer(PPOTrainer):
     """NaturalPolicyGradientAlgorithm on a DroneVecEnv (algs/npg/defaults.py: target_kl 0.01, cg_damping 0.1, cg_iters 10;
-    no learning-rate schedule for the policy).  Other arguments as PPOTrainer."""
+    no learning-rate schedule for the policy).  deep_fused=True: an actor with 3 or 4 hidden layers and d_in <= 64 runs the fused
+    policy step on the kernels of include/pds_npg_deep.h (opt-in: without it such an actor warns and runs as PyTorch ops; with
+    two hidden layers the keyword changes nothing).  Other arguments as PPOTrainer."""
     line_search = False
     _deep_actor = False  # the Fisher-vector product and the line search take struct pds_mlp: a deeper actor runs as PyTorch ops
 
-    def __init__(self, env, cg_damping=0.1, cg_iters=10, target_kl=0.01, total_steps=TOTAL_STEPS, decay=DECAY, **kwargs):
+    def __init__(self, env, cg_damping=0.1, cg_iters=10, target_kl=0.01, total_steps=TOTAL_STEPS, decay=DECAY, deep_fused=False,
+                 **kwargs):
+        self.deep_fused = bool(deep_fused)
+        if self.deep_fused:  # (before PPOTrainer builds the actor's FusedMLP)
+            self._deep_actor, self._pi_fm_kwargs = True, {"npg_deep": True}
         super().__init__(env, target_kl=target_kl, **kwargs)
         self.cg_damping, self.cg_iters = float(cg_damping), int(cg_iters)
         self.total_steps, self.decay = int(total_steps), float(decay)  # TRPO's line search
@@ -170,7 +180,7 @@ class NPGTrainer(PPOTrainer):
                     alpha=float(alpha), final_step_norm=float(torch.norm(final)), gradient_norm=float(torch.norm(g)),
                     xHx=float(xHx), h_inv_g=float(x.norm()), candidates=cands)
 
-    # ---- the policy step on the kernels of csrc/pds_npg.hip -----------------------------------------------------------
+    # ---- the policy step on the kernels of csrc/pds_npg.hip (deep_fused: csrc/pds_npg_deep.hip) -----------------------
     def _policy_step_fused(self, data, feed=lambda steps: None, chunk=0):
         from .fused import conjugate_gradients as cg_fused
         ac, fm = self.ac, self.fm_pi

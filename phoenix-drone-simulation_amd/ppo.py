@@ -250,6 +250,7 @@ def avg_grads(module):
 class PPOTrainer:
     """IWPGAlgorithm + PPO loss on a DroneVecEnv.  steps_per_epoch = rollout_len * env.num_envs per rank."""
     _deep_actor = True  # an actor with 3 or 4 hidden layers runs on the deep kernels (include/pds_mlp_deep.h)
+    _pi_fm_kwargs = {}  # keywords a subclass passes to the actor's fused.FusedMLP (NPGTrainer: npg_deep)
 
     def __init__(self, env, rollout_len=32, epochs=300, gamma=0.99, lam=0.95, clip_ratio=0.2,
                  entropy_coef=0.01, use_entropy=False, pi_lr=3e-4, vf_lr=1e-3, train_pi_iterations=80,
@@ -307,7 +308,7 @@ class PPOTrainer:
         if self.fused:
             from .fused import FusedMLP
             try:
-                self.fm_pi = FusedMLP(self.ac.pi.net, kw["pi"]["activation"])
+                self.fm_pi = FusedMLP(self.ac.pi.net, kw["pi"]["activation"], **self._pi_fm_kwargs)
                 self.fm_v = FusedMLP(self.ac.v.net, kw["val"]["activation"])
                 if self.fm_pi.deep and not self._deep_actor:
                     raise NotImplementedError(f"{type(self).__name__}: the natural-gradient kernels take an actor with 2 hidden "
