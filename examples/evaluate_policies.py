@@ -15,6 +15,10 @@ evaluate_population (the evaluation loop of the reference's utils/evaluation.py,
 A group whose actors read H x half inputs (half: one [o, u] half of the env's observation) was trained on an observation history
 of H: its env is built with observation_history_size = H (inferred from the width, or --history) and flies in one launch too,
 with --record as without it.
+
+A group whose actors have three or four hidden layers -- the (50, 30, 20) and (32, 32, 32, 32) actors of train_ppo.py
+--pi-hidden ... --deep-fused -- flies in one launch as well (pds_evaluate_policies_deep), with --metrics from the same launch;
+--record flies such a group on the composed path and says so, and an observation history is not evaluated at these depths.
 """
 import argparse
 import json
@@ -145,6 +149,14 @@ def main():
             print(f"group {gi} {key}: the actors read {d_in} inputs, {env_id} observes {env.obs_dim}: skipped")
             env.close()
             continue
+        if pop.deep and getattr(env, "observation_history_size", 2) != 2:  # (pds_mlp_deep_forward reads up to 64 inputs: no path flies these)
+            print(f"group {gi} {key}: actors with {len(hidden)} hidden layers on an observation history of "
+                  f"{getattr(env, 'observation_history_size', 2)}: not evaluated at this depth, skipped")
+            env.close()
+            continue
+        if pop.deep and args.record and fused is not True:
+            print(f"group {gi}: {len(hidden)} hidden layers with --record: the launch for these depths has no record form, "
+                  "this group flies on the composed path (pds_mlp_deep_forward per checkpoint and step)")
         out = evaluate_population(env, pop, fused=fused, metrics=args.metrics, history_fused=True, record=args.record,
                                   history_latency_fused=args.history_latency_fused,
                                   log_dir=os.path.join(args.log_dir, str(gi)) if args.log_dir else None)

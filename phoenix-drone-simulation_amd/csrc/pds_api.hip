@@ -16,6 +16,7 @@
 #include "pds_physics.h"  // (the sub-step blocks for materialize_state_kernel)
 #include "pds_collect_args.h"
 #include "pds_evaluate_args.h"
+#include "pds_evaluate_deep_args.h"
 #include "pds_evaluate_hist_args.h"
 #include "pds_simopt.h"
 #include "../../include/pds_history_latency.h"
@@ -1253,8 +1254,9 @@ extern "C" int pds_evaluate_supported(const pds_handle *h) {
 // What every population evaluation validates about the call, in front of anything that touches the handle (`any_null`: one of the
 // entry point's required pointers is NULL; `d_in`: the inputs the handle's observation gives the actors; d_metrics: checked where
 // given).  The env configuration is the entry point's own question, behind these.
-static int check_evaluate_call(pds_handle *h, const char *fn, bool any_null, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
-                               int d_in, const float *d_mean, const float *d_std, int max_steps, const float *d_metrics) {
+// (check_evaluate_population: everything but the network's shape -- pds_evaluate_policies_deep brings a struct pds_mlp_deep)
+static int check_evaluate_population(pds_handle *h, const char *fn, bool any_null, int64_t P, int64_t episodes_per_policy,
+                                     const float *d_mean, const float *d_std, int max_steps, const float *d_metrics) {
   if (max_steps < 1) return fail(h, PDS_EINVAL, "%s: max_steps %d", fn, max_steps);
   if (const int rc = check_rollout_call(h, fn, any_null, d_mean, d_std)) return rc;
   if (((uintptr_t)d_metrics) & 15u) return fail(h, PDS_EINVAL, "%s: d_metrics must be 16-byte aligned", fn);
@@ -1264,26 +1266,40 @@ static int check_evaluate_call(pds_handle *h, const char *fn, bool any_null, int
                 (long long)episodes_per_policy, n);
   if (episodes_per_policy % kWave != 0)
     return fail(h, PDS_EINVAL, "%s: episodes_per_policy %lld is not a multiple of %d (one tile)", fn, (long long)episodes_per_policy, kWave);
+  return PDS_OK;
+}
+static int check_evaluate_call(pds_handle *h, const char *fn, bool any_null, int64_t P, int64_t episodes_per_policy, const pds_mlp *shape,
+                               int d_in, const float *d_mean, const float *d_std, int max_steps, const float *d_metrics) {
+  if (const int rc = check_evaluate_population(h, fn, any_null, P, episodes_per_policy, d_mean, d_std, max_steps, d_metrics)) return rc;
   if (shape->d_in != d_in || shape->h1 < 1 || shape->h1 > 64 || shape->h2 < 1 || shape->h2 > 64 || shape->d_out != 4 ||
       (shape->activation != 0 && shape->activation != 1))
     return fail(h, PDS_EINVAL, "%s: network shape (d_in must be the observation width %d, hidden <= 64, d_out 4, activation 0 or 1)", fn, d_in);
   return PDS_OK;
 }
 // the EvalArgs every form of the evaluation launches with; the per-step streams point at the handle's sink row
-static int fill_evaluate_args(pds_handle *h, const char *fn, EvalArgs &ea, int64_t episodes_per_policy, const pds_mlp *shape,
-                              const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
-                              const float *d_obs0, float *d_ret, float *d_len, float *d_cost, void *stream) {
+// (fill_evaluate_population_args: everything but the network's shape and its parameter count, as check_evaluate_population)
+static int fill_evaluate_population_args(pds_handle *h, const char *fn, EvalArgs &ea, int64_t episodes_per_policy,
+                                         const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                                         const float *d_obs0, float *d_ret, float *d_len, float *d_cost, void *stream) {
   base_args(h, ea.s);
   if (const int rc = point_at_step_sink(h, fn, ea.s, stream)) return rc;
   ea.s.k_steps = max_steps;
-  ea.shape = *shape;
   ea.params = d_params;
-  ea.param_count = pds_mlp_param_count(shape);
   ea.mean = d_mean; ea.stdv = d_std; ea.eps = eps;
   ea.tiles_per_policy = (int)(episodes_per_policy / kWave);
   ea.T = max_steps;
   ea.obs0 = d_obs0;
   ea.ret = d_ret; ea.len = d_len; ea.cost = d_cost;
+  return PDS_OK;
+}
+static int fill_evaluate_args(pds_handle *h, const char *fn, EvalArgs &ea, int64_t episodes_per_policy, const pds_mlp *shape,
+                              const float *d_params, const float *d_mean, const float *d_std, float eps, int max_steps,
+                              const float *d_obs0, float *d_ret, float *d_len, float *d_cost, void *stream) {
+  if (const int rc = fill_evaluate_population_args(h, fn, ea, episodes_per_policy, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret,
+                                                   d_len, d_cost, stream))
+    return rc;
+  ea.shape = *shape;
+  ea.param_count = pds_mlp_param_count(shape);
   return PDS_OK;
 }
 // ONE body for the four forms of pds_evaluate_policies (EvalForm, csrc/pds_evaluate_args.h): the checks, the argument block and the
@@ -1380,6 +1396,71 @@ extern "C" int pds_evaluate_policies_record(pds_handle *h, int64_t P, int64_t ep
   return evaluate_policies_call<EvalForm::Record>(h, "pds_evaluate_policies_record", P, episodes_per_policy, shape, d_params, d_mean, d_std,
                                                   eps, max_steps, d_obs0, d_ret, d_len, d_cost,
                                                   {d_metrics, nullptr, record_per_policy, d_flight, d_obs_rec}, stream);
+}
+
+// ---- the population evaluation for actors with three or four hidden layers: csrc/pds_evaluate_deep.h ----
+// a shape evaluate_deep_kernel can stage for a handle that observes d_in features; the struct's pointers are not looked at
+static bool evaluate_deep_shape_ok(const pds_mlp_deep *m, int d_in) {
+  if (m->n_hidden < 3 || m->n_hidden > PDS_MLP_DEEP_MAX_HIDDEN || m->d_in != d_in || d_in < 1 || d_in > 64 || m->d_out != 4 ||
+      (m->activation != 0 && m->activation != 1))
+    return false;
+  for (int l = 0; l < m->n_hidden; ++l)
+    if (m->hidden[l] < 1 || m->hidden[l] > 64) return false;
+  return true;
+}
+// floats of one policy's row: W1 b1 .. W(L+1) b(L+1) (pds_mlp_deep_param_count, which also asks for the struct's pointers)
+static int evaluate_deep_param_count(const pds_mlp_deep *m) {
+  int total = 0, in = m->d_in;
+  for (int l = 0; l <= m->n_hidden; ++l) {
+    const int out = l < m->n_hidden ? m->hidden[l] : m->d_out;
+    total += out * in + out;
+    in = out;
+  }
+  return total;
+}
+// whether pds_evaluate_policies_deep has a kernel for this handle and this shape (include/pds_evaluate_deep.h)
+extern "C" int pds_evaluate_deep_supported(const pds_handle *h, const pds_mlp_deep *shape) {
+  if (!h || !shape) return PDS_EINVAL;
+  const bool built = h->cfg.auto_reset && evaluate_deep_family(h->cfg.task, h->flags) && evaluate_deep_shape_ok(shape, h->obs_dim) &&
+                     evaluate_deep_variant_built(h->cfg.task, h->flags, shape->n_hidden);
+  return built ? 1 : 0;
+}
+// P policies x E episodes in one launch, the actors with three or four hidden layers.  The checks and the handle's state afterwards
+// are pds_evaluate_policies_metrics'; d_metrics is optional (summed either way: one code object per variant and depth).
+extern "C" int pds_evaluate_policies_deep(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp_deep *shape,
+                                          const float *d_params, const float *d_mean, const float *d_std, float eps, int32_t max_steps,
+                                          const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
+                                          void *stream) {
+  const char *fn = "pds_evaluate_policies_deep";
+  if (!h) return PDS_EINVAL;
+  const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost;
+  if (const int rc = check_evaluate_population(h, fn, any_null, P, episodes_per_policy, d_mean, d_std, max_steps, d_metrics)) return rc;
+  if (!evaluate_deep_shape_ok(shape, h->obs_dim))
+    return fail(h, PDS_EINVAL, "%s: network shape (n_hidden 3 or 4, d_in must be the observation width %d, hidden 1..64, d_out 4, "
+                               "activation 0 or 1)", fn, h->obs_dim);
+  if (!evaluate_deep_family(h->cfg.task, h->flags) || !evaluate_deep_variant_built(h->cfg.task, h->flags, shape->n_hidden))
+    return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: control_mode PWM without latency ring or Kalman "
+                                     "hold, every noise setting; motor dynamics on Hover and Circle, the ground effect on TakeOff) -- "
+                                     "pds_mlp_deep_forward + pds_step give the same bits", fn);
+  DeviceGuard guard(h->cfg.device);
+  PDS_HIP(h, guard.err);
+  EvalDeepArgs ka;
+  memset(&ka, 0, sizeof(ka));
+  ka.m.metrics = d_metrics;
+  ka.deep = *shape;
+  for (int l = 0; l <= PDS_MLP_DEEP_MAX_HIDDEN; ++l) ka.deep.w[l] = ka.deep.b[l] = nullptr;  // (the kernel lays them out per policy)
+  ka.deep_param_count = evaluate_deep_param_count(shape);
+  if (const int rc = fill_evaluate_population_args(h, fn, ka.m.e, episodes_per_policy, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret,
+                                                   d_len, d_cost, stream))
+    return rc;
+  const bool l3 = shape->n_hidden == 3;
+  const int rc = launch_rollout(h, fn, max_steps, stream, [&](dim3 grid, hipStream_t s) {
+    if (h->cfg.task == PDS_TASK_HOVER) return l3 ? launch_evaluate_deep_hover_l3(h->flags, grid, s, ka) : launch_evaluate_deep_hover_l4(h->flags, grid, s, ka);
+    if (h->cfg.task == PDS_TASK_CIRCLE) return l3 ? launch_evaluate_deep_circle_l3(h->flags, grid, s, ka) : launch_evaluate_deep_circle_l4(h->flags, grid, s, ka);
+    return l3 ? launch_evaluate_deep_takeoff_l3(h->flags, grid, s, ka) : launch_evaluate_deep_takeoff_l4(h->flags, grid, s, ka);
+  });
+  if (rc == PDS_OK) { h->was_reset = false; h->after_evaluate = true; }  // (tiles stopped at different steps: pds_evaluate_policies)
+  return rc;
 }
 
 // ---- the population evaluation for observation histories: csrc/pds_evaluate_hist.h ----

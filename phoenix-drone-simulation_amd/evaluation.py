@@ -14,7 +14,9 @@ With `metrics=True` the same launch also reports the flight-quality sums the ref
 logged flight by the same definitions.  With `obs_stats=True` it also sums the observations the policies acted on, for a running
 standardisation (`ObsSums`; include/pds.h pds_evaluate_policies_stats).  With `record=R` the launch also writes the flights
 themselves out -- state, action and observation of every step of the first R episodes per policy -- as a `Flights`
-(include/pds.h pds_evaluate_policies_record)."""
+(include/pds.h pds_evaluate_policies_record).  A population of actors with three or four hidden layers flies in one launch as well
+(include/pds_evaluate_deep.h pds_evaluate_policies_deep: the plain and the metrics call), every other form on the composed path."""
+import ctypes as C
 import math
 import os
 
@@ -92,22 +94,25 @@ def get_batch(env, policy, steps):
 
 # ---- a population of policies in one launch ----------------------------------------------------------------------------
 _ACT_MODULE = {"relu": nn.ReLU, "tanh": nn.Tanh}
+POPULATION_DEPTHS = (2, 3, 4)  # hidden layers of a population's actors: struct pds_mlp, or struct pds_mlp_deep at 3 and 4
+POPULATION_MAX_WIDTH = 64      # ... and the widest hidden layer pds_mlp_deep stages
 
 
 def _actor_shape(net):
-    """(d_in, (h1, h2), d_out, activation name) of an nn.Sequential(Linear, act, Linear, act, Linear[, Identity])."""
+    """(d_in, hidden sizes, d_out, activation name) of an nn.Sequential(Linear, act, ..., Linear[, Identity]) with two, three or
+    four hidden layers and one activation type."""
     lin = [l for l in net if isinstance(l, nn.Linear)]
     acts = [l for l in net if not isinstance(l, (nn.Linear, nn.Identity))]
-    if len(lin) != 3 or len(acts) != 2 or type(acts[0]) is not type(acts[1]):
-        raise ValueError("a population holds actors with two hidden layers and one activation")
+    if len(lin) - 1 not in POPULATION_DEPTHS or len(acts) != len(lin) - 1 or any(type(a) is not type(acts[0]) for a in acts[1:]):
+        raise ValueError("a population holds actors with two, three or four hidden layers and one activation")
     name = {nn.ReLU: "relu", nn.Tanh: "tanh"}.get(type(acts[0]))
     if name is None:
         raise ValueError(f"activation {type(acts[0]).__name__}: relu or tanh")
-    return lin[0].in_features, (lin[0].out_features, lin[1].out_features), lin[2].out_features, name
+    return lin[0].in_features, tuple(l.out_features for l in lin[:-1]), lin[-1].out_features, name
 
 
 def _flat_params(net):
-    """W1, b1, W2, b2, W3, b3 in torch parameter order: the layout of pds_mlp_param_count."""
+    """W1, b1, ..., W(L+1), b(L+1) in torch parameter order: the layout of pds_mlp_param_count / pds_mlp_deep_param_count."""
     lin = [l for l in net if isinstance(l, nn.Linear)]
     return torch.cat([t.detach().reshape(-1).float().cpu() for l in lin for t in (l.weight, l.bias)])
 
@@ -115,17 +120,25 @@ def _flat_params(net):
 class PolicyPopulation:
     """P actors of ONE shape as data: `theta` [P, param_count] float32 (row p = W1, b1, W2, b2, W3, b3 of policy p in torch
     order), the shape (d_in, hidden_sizes, d_out = 4), the activation, optional observation standardisation `mean`, `std`
-    [P, D] (both or none) and its eps.  Mixed shapes or activations raise ValueError: group by shape, one population each."""
+    [P, D] (both or none) and its eps.  Mixed shapes or activations raise ValueError: group by shape, one population each.
+    hidden_sizes holds two, three or four widths.  At three and four (`deep`) a row is W1, b1, ..., W(L+1), b(L+1) in torch order
+    (pds_mlp_deep_param_count's layout), every width is at most 64 and `mlp(p)` is a struct pds_mlp_deep."""
 
     def __init__(self, theta, d_in, hidden_sizes, activation, mean=None, std=None, eps=1e-5, d_out=4):
         hidden_sizes = tuple(int(h) for h in hidden_sizes)
-        if len(hidden_sizes) != 2:
-            raise ValueError("two hidden layers")
+        if len(hidden_sizes) not in POPULATION_DEPTHS:
+            raise ValueError(f"two, three or four hidden layers, not {len(hidden_sizes)}")
+        if len(hidden_sizes) > 2 and not all(1 <= h <= POPULATION_MAX_WIDTH for h in hidden_sizes):
+            raise ValueError(f"hidden sizes {hidden_sizes}: with {len(hidden_sizes)} hidden layers every width is 1 .. {POPULATION_MAX_WIDTH}")
         if activation not in native.ACTIVATIONS:
             raise ValueError(f"activation {activation!r}: relu or tanh")
         self.d_in, self.hidden_sizes, self.d_out, self.activation = int(d_in), hidden_sizes, int(d_out), activation
-        h1, h2 = hidden_sizes
-        self.param_count = h1 * self.d_in + h1 + h2 * h1 + h2 + self.d_out * h2 + self.d_out
+        if self.deep:
+            sizes = (self.d_in,) + hidden_sizes + (self.d_out,)
+            self.param_count = sum(sizes[j + 1] * sizes[j] + sizes[j + 1] for j in range(len(sizes) - 1))
+        else:
+            h1, h2 = hidden_sizes
+            self.param_count = h1 * self.d_in + h1 + h2 * h1 + h2 + self.d_out * h2 + self.d_out
         theta = torch.as_tensor(theta, dtype=torch.float32)
         if theta.dim() == 1:
             theta = theta.unsqueeze(0)
@@ -151,6 +164,11 @@ class PolicyPopulation:
 
     def __len__(self):
         return self.P
+
+    @property
+    def deep(self):
+        """three or four hidden layers: struct pds_mlp_deep and its entry points"""
+        return len(self.hidden_sizes) > 2
 
     @classmethod
     def _from_nets(cls, nets, means, stds, epss):
@@ -196,23 +214,25 @@ class PolicyPopulation:
                                 self.mean.to(device) if has else None, self.std.to(device) if has else None, self.eps, d_out=self.d_out)
 
     def policy(self, p):
-        """The p-th actor as nn.Sequential(Linear, act, Linear, act, Linear, Identity) on the CPU (no standardisation)."""
-        h1, h2 = self.hidden_sizes
-        sizes = [self.d_in, h1, h2, self.d_out]
+        """The p-th actor as nn.Sequential(Linear, act, ..., Linear, Identity) on the CPU (no standardisation)."""
+        sizes = [self.d_in, *self.hidden_sizes, self.d_out]
+        last = len(sizes) - 2
         row, off, layers = self.theta[p].detach().cpu(), 0, []
-        for j in range(3):
+        for j in range(last + 1):
             lin = nn.Linear(sizes[j], sizes[j + 1])
             nw, nb = sizes[j + 1] * sizes[j], sizes[j + 1]
             lin.weight.data = row[off:off + nw].reshape(sizes[j + 1], sizes[j]).clone()
             lin.bias.data = row[off + nw:off + nw + nb].clone()
             off += nw + nb
-            layers += [lin, _ACT_MODULE[self.activation]() if j < 2 else nn.Identity()]
+            layers += [lin, _ACT_MODULE[self.activation]() if j < last else nn.Identity()]
         return nn.Sequential(*layers)
 
     def mlp(self, p=0):
-        """struct pds_mlp of policy p: pointers into row p of theta."""
-        return native.mlp(self.d_in, *self.hidden_sizes, self.d_out, self.activation,
-                          base=self.theta.data_ptr() + 4 * p * self.param_count)
+        """struct pds_mlp of policy p -- struct pds_mlp_deep with three or four hidden layers --: pointers into row p of theta."""
+        base = self.theta.data_ptr() + 4 * p * self.param_count
+        if self.deep:
+            return native.mlp_deep(self.d_in, self.hidden_sizes, self.d_out, self.activation, base=base)
+        return native.mlp(self.d_in, *self.hidden_sizes, self.d_out, self.activation, base=base)
 
 
 def _check_population_call(env, population):
@@ -229,6 +249,16 @@ def fused_evaluation_built(env):
     """Whether pds_evaluate_policies has a kernel for this env: a handle with auto_reset whose configuration is one the fused
     rollout is built for, and observation_history_size == 2."""
     return getattr(env, "observation_history_size", 2) == 2 and bool(env.lib.pds_evaluate_supported(env._handle))
+
+
+def fused_deep_evaluation_built(env, population):
+    """Whether pds_evaluate_policies_deep (include/pds_evaluate_deep.h) has a kernel for this env and this population of actors
+    with three or four hidden layers: a handle with auto_reset, observation_history_size == 2, control_mode PWM without latency
+    ring or Kalman hold (every noise setting; motor dynamics on Hover and Circle, the ground effect on TakeOff), the actors
+    reading the env's observation.  False for a population with two hidden layers: that is fused_evaluation_built's question."""
+    if not getattr(population, "deep", False) or getattr(env, "observation_history_size", 2) != 2:
+        return False
+    return env.lib.pds_evaluate_deep_supported(env._handle, C.byref(population.mlp(0))) == 1
 
 
 def fused_history_evaluation_built(env):
@@ -601,6 +631,21 @@ def _plan_population(env, population, fused, max_steps, metrics, obs_stats, hist
                              f"{int(record_limit_bytes)}: record fewer episodes or fewer steps, or raise the limit")
     form = "record" if R is not None else "stats" if obs_stats else "metrics" if metrics else "plain"
     H = int(getattr(env, "observation_history_size", 2))
+    if getattr(population, "deep", False):
+        # three or four hidden layers: evaluate_deep_kernel has a plain / metrics form and no other; the composed path flies
+        # every form on pds_mlp_deep_forward, whose inputs end at 64 -- no observation history reaches it
+        if H != 2:
+            raise NotImplementedError(f"observation_history_size {H} with {len(population.hidden_sizes)} hidden layers: pds_mlp_deep_forward "
+                                      "reads up to 64 inputs, on either path")
+        use_kernel = False
+        if fused is not False:
+            built = form in ("plain", "metrics") and fused_deep_evaluation_built(env, population)
+            if fused is True and not built:
+                raise NotImplementedError("pds_evaluate_policies_deep has no kernel for this call (built: the plain and the metrics form -- "
+                                          "not obs_stats, not record --, auto_reset, control_mode PWM without latency ring or Kalman hold; "
+                                          "motor dynamics on Hover and Circle, the ground effect on TakeOff); fused='auto' runs the composed path")
+            use_kernel = built
+        return P, E, T, R, form, use_kernel, None
     # (the history kernel has a plain / metrics form, a record form and a stats form; the stats form flies where history_stats_fused asks for it)
     use_history = bool(history_fused) and H != 2
     use_kernel = False
@@ -633,12 +678,17 @@ def _fly_kernel(env, population, obs, P, E, T, form, H, rec, latency=False):
     into `rec`'s arrays.  Per form the entry point and what trails d_cost in its argument list; the history kernel leads with H
     and takes d_metrics or NULL, its record form (pds_evaluate_policies_history_record) what the record form takes, its stats form
     (pds_evaluate_policies_history_stats) what the stats form takes, the slab slab_features(H x half) columns wide.  latency=True:
-    the three history entry points on the latency ring (include/pds_history_latency_evaluate.h), the same argument lists."""
+    the three history entry points on the latency ring (include/pds_history_latency_evaluate.h), the same argument lists.
+    A deep population (plain or metrics): pds_evaluate_policies_deep, which takes d_metrics or NULL."""
     dev, n = env.device, env.num_envs
     ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
     raw = torch.zeros(n, len(METRIC_NAMES), device=dev) if form != "plain" else None
     slab = torch.zeros(n // 64, SLAB_WAVES, 2, slab_features(population.d_in) if H is not None else SLAB_FEATURES, device=dev) if form == "stats" else None
     _, R, flight, obs_rec = rec if rec is not None else (None,) * 4
+    if population.deep:  # (plain or metrics: _plan_population): one entry point, d_metrics or NULL; the struct goes in by reference
+        native.call("pds_evaluate_policies_deep", env._handle, P, E, C.byref(population.mlp(0)), population.theta, population.mean,
+                    population.std, population.eps, T, obs, ret, length, cost, raw, on=dev, handle=env._handle)
+        return ret, length, cost, raw, slab
     name, trail = {"plain": ("pds_evaluate_policies", ()),
                    "metrics": ("pds_evaluate_policies_metrics", (raw,)),
                    "stats": ("pds_evaluate_policies_stats", (raw, slab)),
@@ -657,11 +707,15 @@ def _fly_kernel(env, population, obs, P, E, T, form, H, rec, latency=False):
 
 def _fly_composed(env, population, obs, P, E, T, metrics, obs_stats, rec):
     """The same flight step by step -> _fly_kernel's tuple, the same bits: per step one pds_mlp_forward per policy on its block of
-    the observation, env.step and the accumulator updates of `evaluate`, every sum a torch op of its own."""
+    the observation (pds_mlp_deep_forward for a population with three or four hidden layers), env.step and the accumulator updates
+    of `evaluate`, every sum a torch op of its own."""
     dev, n, D = env.device, env.num_envs, env.obs_dim
     ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
     raw = slab = None
     mlps = [population.mlp(p) for p in range(P)]
+    forward = "pds_mlp_forward"
+    if population.deep:  # (three or four hidden layers: the same call on struct pds_mlp_deep, which goes in by reference)
+        forward, mlps = "pds_mlp_deep_forward", [C.byref(m) for m in mlps]
     act = torch.empty(n, 4, device=dev)
     alive = torch.ones(n, dtype=torch.bool, device=dev)
     has = population.mean is not None
@@ -677,7 +731,7 @@ def _fly_composed(env, population, obs, P, E, T, metrics, obs_stats, rec):
         if metrics:  # x(s): the state the policy acts in
             rpy, omega, last = env.get_state("rpy"), env.get_state("omega"), env.get_state("last_action")
         for p in range(P):
-            native.call("pds_mlp_forward", mlps[p], _ptr(obs, 4 * p * E * D), None, E, _ptr(population.mean, 4 * p * D) if has else None,
+            native.call(forward, mlps[p], _ptr(obs, 4 * p * E * D), None, E, _ptr(population.mean, 4 * p * D) if has else None,
                         _ptr(population.std, 4 * p * D) if has else None, population.eps, _ptr(act, 16 * p * E), on=dev)
         if metrics:
             prev_neg = _compose_metrics(acc, prev_neg, alive, rpy, omega, act, last)
@@ -781,6 +835,13 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     `fused_history_latency_stats_evaluation_built(env)` hold; where they do not (TakeOff, the Kalman hold, the ground effect,
     partial noise, views frozen by set_latency), fused=True raises NotImplementedError with the env untouched and "auto" runs the
     composed path.
+    A population of actors with THREE or FOUR hidden layers (`population.deep`) flies in one launch through
+    pds_evaluate_policies_deep (include/pds_evaluate_deep.h, csrc/pds_evaluate_deep.h: the same bits as its composed path, the
+    metrics from the same launch) where `fused_deep_evaluation_built(env, population)` holds and the call is plain or
+    metrics=True; with obs_stats=True or record=R, and on an env outside that kernel's family (the latency ring, a PID control
+    mode, the Kalman hold, the ground effect off TakeOff), fused=True raises NotImplementedError with the env untouched and "auto"
+    runs the composed path, which serves every form with one pds_mlp_deep_forward per policy and step.  An env with
+    observation_history_size != 2 raises NotImplementedError for such a population on either path; the history keywords change nothing.
     The env is reset first and not afterwards: after the fused path it refuses to step until the next reset() of every env
     (a masked reset is refused as well).  `population` is not modified: the call works on device copies of its tensors.
     max_steps: the number of steps flown, by default the env's max_episode_steps (the TimeLimit ends every episode by then)."""

@@ -37,6 +37,13 @@ non-latency history launch of the same shape on an env without the ring, each wi
 slower than the composed path.
 
   python profiles/tools/evaluate_bench.py --history 4 8 --latency 0.02 > profiles/evaluate_history_latency_timing.txt
+
+--deep: populations of actors with three and four hidden layers -- seeded random (50, 30, 20) relu and (32, 32, 32, 32) tanh actors
+on Hover at its defaults, 500 steps, P x E = 8 x 128 and 64 x 1024: the launch (pds_evaluate_policies_deep) against the composed path
+of the same call, against one evaluation.evaluate call per policy on an E-env env (what such actors ran before), and against the
+two-hidden-layer launch of a (64, 64) population; medians of --reps alternating synchronised repeats, with their spreads.
+
+  python profiles/tools/evaluate_bench.py --deep > profiles/evaluate_deep_timing.txt
 """
 import argparse
 import os
@@ -319,8 +326,74 @@ def history_stats_main(args):
     sys.exit(0 if ok else 1)
 
 
+DEEP_ACTORS = (((50, 30, 20), "relu"), ((32, 32, 32, 32), "tanh"))
+
+
+def deep_population(d_in, P, hidden, activation, seed=0):
+    """seeded actors with len(hidden) hidden layers in torch's nn.Linear initialisation, output biases spread as random_population's"""
+    g = torch.Generator().manual_seed(seed)
+    sizes = (d_in,) + tuple(hidden) + (4,)
+    blocks = [(n_in, count) for n_in, n_out in zip(sizes[:-1], sizes[1:]) for count in (n_out * n_in, n_out)]
+    theta = torch.cat([(torch.rand(P, count, generator=g) * 2 - 1) / fan_in ** 0.5 for fan_in, count in blocks], dim=1)
+    theta[:, -4:] += torch.linspace(-0.6, 0.6, P).unsqueeze(1) if P > 1 else -0.3
+    return PolicyPopulation.from_flat(theta, d_in, hidden, activation)
+
+
+def deep_main(args):
+    """--deep: pds_evaluate_policies_deep (evaluate_population(fused=True) on a population with three / four hidden layers) against
+    the composed path of the same call (fused=False: pds_mlp_deep_forward per policy and step), against what such a population
+    could run before either was there -- one evaluation.evaluate call per policy on an E-env env, the actor as PyTorch ops -- and,
+    for scale, against the two-hidden-layer launch of a (64, 64) population.  Hover at its defaults, 500 steps."""
+    from phoenix_drone_simulation_amd.evaluation import evaluate, fused_deep_evaluation_built
+    env_id = "DroneHoverSimpleEnv-v0"
+    print(f"# evaluate_population on a population of actors with three / four hidden layers, {env_id} at its defaults (500 steps), "
+          f"{torch.cuda.get_device_name(0)}; seeded random actors")
+    print(f"# host clock around work that ends in a device synchronise; one warm-up per side and shape, then {args.reps} repeats of each "
+          "side, alternating; ms: median [min .. max]; spread = (max - min) / median")
+    for hidden, activation in DEEP_ACTORS:
+        for P, E in HISTORY_SHAPES:
+            envs = [pds.make(env_id, num_envs=P * E, seed=1) for _ in range(3)]
+            env_one = pds.make(env_id, num_envs=E, seed=1)
+            pop = deep_population(envs[0].obs_dim, P, hidden, activation).to("cuda:0")
+            two = random_population(envs[0].obs_dim, P).to("cuda:0")
+            assert fused_deep_evaluation_built(envs[0], pop)
+            actors = [pop.policy(p).to("cuda:0") for p in range(P)]
+
+            def per_policy():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = [evaluate(env_one, a) for a in actors]  # (each ends in its copies to the host)
+                return time.perf_counter() - t0, out
+
+            sides = (("launch", lambda: timed(envs[0], pop, True)), ("composed", lambda: timed(envs[1], pop, False)),
+                     ("per-policy evaluate", per_policy), ("two-hidden-layer launch (64, 64)", lambda: timed(envs[2], two, True)))
+            first = {name: f()[1] for name, f in sides}  # warm-up; the first calls of same-seed envs: comparable
+            same = all(torch.equal(x, y) for x, y in zip(first["launch"], first["composed"]))
+            t = {name: [] for name, _ in sides}
+            for _ in range(args.reps):
+                for name, f in sides:
+                    t[name].append(f()[0])
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            spread = {k: (max(v) - min(v)) / med[k] for k, v in t.items()}
+            print(f"{hidden} {activation} {P:3d} x {E:5d} ({P * E // 64} tiles) mean length {float(first['launch'][1].mean()):6.1f}  "
+                  f"launch and composed: same bits {same}")
+            for name in t:
+                print(f"    {name:34s} {1e3 * med[name]:10.2f} [{1e3 * min(t[name]):.2f} .. {1e3 * max(t[name]):.2f}] ms  spread {spread[name]:.3f}  "
+                      f"{P * E / med[name]:12.0f} episodes/s")
+            r = med["composed"] / med["launch"]
+            verdict = "the launch is faster beyond both spreads" if r - 1.0 > max(spread["launch"], spread["composed"]) else \
+                ("the launch is SLOWER beyond both spreads" if 1.0 / r - 1.0 > max(spread["launch"], spread["composed"]) else "inside the spreads")
+            print(f"    composed / launch = {r:.2f}x ({verdict}); per-policy evaluate / launch = {med['per-policy evaluate'] / med['launch']:.1f}x; "
+                  f"launch / two-hidden-layer launch = {med['launch'] / med['two-hidden-layer launch (64, 64)']:.2f}x", flush=True)
+            for env in envs + [env_one]:
+                env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--deep", action="store_true",
+                    help="time the launch for actors with three / four hidden layers (pds_evaluate_policies_deep) against its composed "
+                         "path, one evaluation.evaluate per policy and the two-hidden-layer launch")
     ap.add_argument("--seconds", type=float, default=1.0, help="least timed duration per path and shape")
     ap.add_argument("--max-reps", type=int, default=50)
     ap.add_argument("--history", type=int, nargs="+", default=None, metavar="H",
@@ -339,6 +412,8 @@ def main():
             ap.error("--latency needs --history")
         global LATENCY
         LATENCY = args.latency
+    if args.deep:
+        return deep_main(args)
     if args.history and args.obs_stats:
         return history_stats_main(args)
     if args.history and args.record:
