@@ -22,7 +22,8 @@ from phoenix_drone_simulation_amd.npg import NPGTrainer, TRPOTrainer  # noqa: E4
 from phoenix_drone_simulation_amd.ppo import PPOTrainer  # noqa: E402
 
 
-def main():
+def parse_args(argv=None):
+    """the command line -> (parser, args); main() and tests/test_rollout_deep_cpu.py"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--alg", choices=("ppo", "npg", "trpo"), default="ppo",
                     help="the reference's on-policy trainers (train.py --alg): PPO, natural policy gradient, TRPO")
@@ -51,9 +52,20 @@ def main():
                     help="--alg npg / trpo with 3 or 4 policy hidden layers: run the policy step on the fused natural-gradient kernels "
                          "(NPGTrainer(deep_fused=True)) instead of PyTorch ops, e.g. the reference's architecture search: --alg trpo "
                          "--pi-hidden 50 30 20 --pi-activation relu --deep-fused; ppo needs no keyword and rejects it")
-    args = ap.parse_args()
+    ap.add_argument("--deep-rollout", action="store_true",
+                    help="every --alg with 3 or 4 policy hidden layers: roll out in one launch (PPOTrainer(deep_rollout=True), "
+                         "pds_rollout_deep) where the env is control_mode PWM without latency ring or Kalman hold, instead of the "
+                         "per-step kernels (same bits); with --alg npg / trpo together with --deep-fused -- the whole of the "
+                         "reference's architecture search on fused kernels: --alg trpo --pi-hidden 50 30 20 --pi-activation relu "
+                         "--deep-fused --deep-rollout; 2 policy hidden layers ignore it")
+    args = ap.parse_args(argv)
     if args.deep_fused and args.alg == "ppo":
         ap.error("--deep-fused is for --alg npg / trpo; ppo runs 3 or 4 hidden layers on the deep kernels without a keyword")
+    return ap, args
+
+
+def main():
+    ap, args = parse_args()
     env_kw = dict(observation_history_size=args.observation_history_size) if args.observation_history_size != 2 else {}
     if args.use_latency:
         env_kw.update(use_latency=True, latency=args.latency)
@@ -78,6 +90,8 @@ def main():
         env = pds.make(args.env, num_envs=args.num_envs, seed=args.seed, **env_kw)  # the reference's default config
     cls = {"ppo": PPOTrainer, "npg": NPGTrainer, "trpo": TRPOTrainer}[args.alg]
     alg_kw = dict(deep_fused=True) if args.deep_fused else {}
+    if args.deep_rollout:
+        alg_kw.update(deep_rollout=True)
     trainer = cls(env, rollout_len=args.rollout_len, epochs=args.epochs, seed=args.seed, ac_kwargs=ac_kwargs, **alg_kw)
     t0 = time.time()
     for e in range(args.epochs):

@@ -18,6 +18,7 @@
 #include "pds_evaluate_args.h"
 #include "pds_evaluate_deep_args.h"
 #include "pds_evaluate_hist_args.h"
+#include "pds_rollout_deep_args.h"
 #include "pds_simopt.h"
 #include "../../include/pds_history_latency.h"
 #include "../../include/pds_history_latency_evaluate.h"
@@ -1068,10 +1069,11 @@ static bool rollout_net_ok(const pds_mlp *m, int d_in) {
 static bool rollout_buffers_aligned(const float *d_act_buf, const float *d_obs_buf) {
   return !((((uintptr_t)d_act_buf) & 15u) || (((uintptr_t)d_obs_buf) & 3u));
 }
-// The StepArgs head and the fields RolloutArgs and RolloutHistArgs share (csrc/pds_types.h); reward / term / trunc / cost
-// point at the [T, N] rollout buffers.  s.obs and what only one of the structs has are the caller's.
-template <class RA>
-static void fill_rollout_args(pds_handle *h, RA &ra, int T, const pds_mlp *pi, const float *d_mean, const float *d_std, float eps,
+// The StepArgs head and the fields RolloutArgs, RolloutHistArgs and RolloutDeepArgs share (csrc/pds_types.h,
+// csrc/pds_rollout_deep_args.h); reward / term / trunc / cost point at the [T, N] rollout buffers.  s.obs and what only one of the
+// structs has are the caller's.  Net: the struct's actor, struct pds_mlp or struct pds_mlp_deep.
+template <class RA, class Net>
+static void fill_rollout_args(pds_handle *h, RA &ra, int T, const Net *pi, const float *d_mean, const float *d_std, float eps,
                               const float *d_log_std, uint64_t seed, const uint64_t *d_call_base, uint64_t call_offset,
                               int deterministic, float *d_act_buf, float *d_logp_buf, float *d_rew_buf, uint8_t *d_term_buf,
                               uint8_t *d_trunc_buf, float *d_cost_buf, float *d_ep_ret, float *d_ep_len, float *d_stats) {
@@ -1461,6 +1463,56 @@ extern "C" int pds_evaluate_policies_deep(pds_handle *h, int64_t P, int64_t epis
   });
   if (rc == PDS_OK) { h->was_reset = false; h->after_evaluate = true; }  // (tiles stopped at different steps: pds_evaluate_policies)
   return rc;
+}
+
+// ---- the one-launch rollout for actors with three or four hidden layers: csrc/pds_rollout_deep.h ----
+// (an actor rollout_deep_kernel can stage is a shape evaluate_deep_kernel can: evaluate_deep_shape_ok)
+// whether pds_rollout_deep has a kernel for this handle and this actor (include/pds_rollout_deep.h)
+extern "C" int pds_rollout_deep_supported(const pds_handle *h, const pds_mlp_deep *pi) {
+  if (!h || !pi) return PDS_EINVAL;
+  const bool built = h->cfg.auto_reset && rollout_deep_family(h->cfg.task, h->flags) && evaluate_deep_shape_ok(pi, h->obs_dim) &&
+                     rollout_deep_variant_built(h->cfg.task, h->flags, pi->n_hidden);
+  return built ? 1 : 0;
+}
+// One launch per rollout, the actor with three or four hidden layers and the critic outside.  The checks are pds_rollout_history's.
+extern "C" int pds_rollout_deep(pds_handle *h, int T, const pds_mlp_deep *pi, const float *d_mean, const float *d_std, float eps,
+                                const float *d_log_std, uint64_t seed, const uint64_t *d_call_base, uint64_t call_offset,
+                                int deterministic, float *d_obs_buf, float *d_act_buf, float *d_logp_buf, float *d_rew_buf,
+                                uint8_t *d_term_buf, uint8_t *d_trunc_buf, float *d_cost_buf, float *d_fin_rows, int32_t *d_fin_step,
+                                int slots, float *d_ep_ret, float *d_ep_len, float *d_stats, void *stream) {
+  const char *fn = "pds_rollout_deep";
+  if (!h) return PDS_EINVAL;
+  if (T < 1 || slots < 1) return fail(h, PDS_EINVAL, "%s: T %d, slots %d", fn, T, slots);
+  const bool any_null = !pi || !d_log_std || !d_obs_buf || !d_act_buf || !d_logp_buf || !d_rew_buf || !d_term_buf || !d_trunc_buf ||
+                        !d_cost_buf || !d_fin_rows || !d_fin_step || !d_ep_ret || !d_ep_len || !d_stats;
+  if (const int rc = check_rollout_call(h, fn, any_null, d_mean, d_std)) return rc;
+  const int D = h->obs_dim;
+  bool tensors = true;
+  for (int l = 0; l <= pi->n_hidden && l <= PDS_MLP_DEEP_MAX_HIDDEN; ++l) tensors = tensors && pi->w[l] && pi->b[l];
+  if (!evaluate_deep_shape_ok(pi, D) || !tensors)
+    return fail(h, PDS_EINVAL, "%s: actor shape (n_hidden 3 or 4, d_in must be the observation width %d, hidden 1..64, d_out 4, "
+                               "activation 0 or 1, all 2 (n_hidden + 1) tensors)", fn, D);
+  // max_episode_steps bounds how often the TimeLimit can cut one env within T steps; + the rollout's last step
+  if (slots < T / h->cfg.max_episode_steps + 2)
+    return fail(h, PDS_EINVAL, "%s: slots %d < T / max_episode_steps + 2 = %d", fn, slots, T / h->cfg.max_episode_steps + 2);
+  if (!rollout_buffers_aligned(d_act_buf, d_obs_buf)) return fail(h, PDS_EINVAL, "%s: alignment", fn);
+  if (!rollout_deep_family(h->cfg.task, h->flags) || !rollout_deep_variant_built(h->cfg.task, h->flags, pi->n_hidden))
+    return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: control_mode PWM without latency ring or Kalman "
+                                     "hold, every noise setting; motor dynamics on Hover and Circle, the ground effect on TakeOff) -- "
+                                     "the per-step kernels give the same bits", fn);
+  RolloutDeepArgs ra;
+  fill_rollout_args(h, ra, T, pi, d_mean, d_std, eps, d_log_std, seed, d_call_base, call_offset, deterministic, d_act_buf, d_logp_buf,
+                    d_rew_buf, d_term_buf, d_trunc_buf, d_cost_buf, d_ep_ret, d_ep_len, d_stats);
+  ra.s.obs = d_obs_buf + (long long)h->cfg.num_envs * D;  // step t writes o(t + 1) into row t + 1
+  ra.obs0 = d_obs_buf;
+  ra.slots = slots;
+  ra.fin_rows = d_fin_rows; ra.fin_step = d_fin_step;
+  const bool l3 = pi->n_hidden == 3;
+  return launch_rollout(h, fn, T, stream, [&](dim3 grid, hipStream_t s) {
+    if (h->cfg.task == PDS_TASK_HOVER) return l3 ? launch_rollout_deep_hover_l3(h->flags, grid, s, ra) : launch_rollout_deep_hover_l4(h->flags, grid, s, ra);
+    if (h->cfg.task == PDS_TASK_CIRCLE) return l3 ? launch_rollout_deep_circle_l3(h->flags, grid, s, ra) : launch_rollout_deep_circle_l4(h->flags, grid, s, ra);
+    return l3 ? launch_rollout_deep_takeoff_l3(h->flags, grid, s, ra) : launch_rollout_deep_takeoff_l4(h->flags, grid, s, ra);
+  });
 }
 
 // ---- the population evaluation for observation histories: csrc/pds_evaluate_hist.h ----

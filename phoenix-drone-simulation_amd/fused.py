@@ -19,7 +19,8 @@ gradient for the update.  Each call replaces an autograd op chain of the referen
 
 Networks with three or four hidden layers (csrc/pds_mlp_deep.hip, include/pds_mlp_deep.h) take the first three rows and
 adam_step on kernels of their own (FusedMLP.deep); every other row takes two hidden layers and refuses them -- but for
-fisher_vector_product and surrogate_kl of a FusedMLP built with npg_deep=True (csrc/pds_npg_deep.hip, include/pds_npg_deep.h).
+fisher_vector_product and surrogate_kl of a FusedMLP built with npg_deep=True (csrc/pds_npg_deep.hip, include/pds_npg_deep.h);
+fused_rollout_deep is the one-launch rollout under such an actor (csrc/pds_rollout_deep.h, include/pds_rollout_deep.h).
 
 The gradients are written straight into the `.grad` storage of the torch parameters (one flat
 buffer, torch parameter order), so the optimiser step stays torch.optim.Adam like the reference's."""
@@ -394,6 +395,29 @@ def fused_rollout_history(env, fm_pi, T, H, mean, std, eps, log_std, seed, call_
     if latency and not rollout_history_latency_supported(env):
         raise NotImplementedError("pds_rollout_history_latency: not built for this env (rollout_history_latency_supported)")
     native.call("pds_rollout_history_latency" if latency else "pds_rollout_history", env._handle, int(T), int(H), fm_pi, mean, std, float(eps), log_std, int(seed), call_base,
+                int(call_offset), int(bool(deterministic)), obs_buf, act_buf, logp_buf, rew_buf, term_buf, trunc_buf, cost_buf,
+                fin_rows, fin_step, int(fin_rows.shape[0]), ep_ret, ep_len, stats, on=obs_buf, handle=env._handle)
+
+
+def rollout_deep_supported(env, fm_pi):
+    """True where pds_rollout_deep (include/pds_rollout_deep.h) flies this env's rollout in one launch under this actor: 3 or 4
+    hidden layers, observation_history_size 2, control_mode PWM without latency ring or Kalman hold, every noise setting, motor
+    dynamics on Hover and Circle, the ground effect on TakeOff."""
+    if not getattr(fm_pi, "deep", False) or getattr(env, "observation_history_size", 2) != 2:
+        return False
+    return native.load().pds_rollout_deep_supported(env._handle, C.byref(fm_pi.md)) == 1
+
+
+def fused_rollout_deep(env, fm_pi, T, mean, std, eps, log_std, seed, call_offset, deterministic, obs_buf, act_buf, logp_buf,
+                       rew_buf, term_buf, trunc_buf, cost_buf, fin_rows, fin_step, ep_ret, ep_len, stats, call_base=None):
+    """ONE launch for the T closed-loop steps of a rollout under an actor with 3 or 4 hidden layers (include/pds_rollout_deep.h
+    pds_rollout_deep, csrc/pds_rollout_deep.h): obs_buf is [T + 1, N, D] with o(0) in row 0; the critic is NOT in the kernel (the
+    caller evaluates V over obs_buf and over the final observations in fin_rows [slots, N, D], whose fin_step [slots, N] (int32,
+    preset to -1) names the step each belongs to).  Raises NotImplementedError where the kernel is not built, before the env is
+    touched (the per-step path gives the same bits)."""
+    if not rollout_deep_supported(env, fm_pi):
+        raise NotImplementedError("pds_rollout_deep: not built for this env and actor (rollout_deep_supported)")
+    native.call("pds_rollout_deep", env._handle, int(T), fm_pi, mean, std, float(eps), log_std, int(seed), call_base,
                 int(call_offset), int(bool(deterministic)), obs_buf, act_buf, logp_buf, rew_buf, term_buf, trunc_buf, cost_buf,
                 fin_rows, fin_step, int(fin_rows.shape[0]), ep_ret, ep_len, stats, on=obs_buf, handle=env._handle)
 

@@ -247,6 +247,13 @@ def avg_grads(module):
         off += g.numel()
 
 
+# deep_rollout=True with fused_rollout=None keeps the per-step kernels from this env count upward: at 2^20 envs x 8 steps -- 16 384
+# tiles on one team per block, there is no two-team form -- the one launch measured 8.60 / 9.59 ms against 7.42 / 8.55 ms launch by
+# launch, beyond both sides' ranges; it is ahead at 8 192 x 64 (0.89 vs 4.26 ms) and 65 536 x 32 (1.92 vs 3.37 ms), the sizes
+# measured below it (profiles/rollout_deep_timing.txt).  fused_rollout=True still takes the launch.
+DEEP_ROLLOUT_PER_STEP_FROM = 1 << 20
+
+
 class PPOTrainer:
     """IWPGAlgorithm + PPO loss on a DroneVecEnv.  steps_per_epoch = rollout_len * env.num_envs per rank."""
     _deep_actor = True  # an actor with 3 or 4 hidden layers runs on the deep kernels (include/pds_mlp_deep.h)
@@ -258,7 +265,7 @@ class PPOTrainer:
                  use_linear_lr_decay=True, use_exploration_noise_anneal=True, use_reward_scaling=True,
                  use_standardized_obs=True, use_max_grad_norm=False, max_grad_norm=0.5, ac_kwargs=None,
                  seed=0, fused=None, graph_rollout=None, fused_rollout=None, reset_each_rollout=False,
-                 overlap_value_update=True, log_reference_columns=False):
+                 overlap_value_update=True, log_reference_columns=False, deep_rollout=False):
         self.env, self.T, self.N = env, int(rollout_len), env.num_envs
         self.overlap_value_update, self._side_stream = bool(overlap_value_update), None
         # also log what the reference's progress.csv carries per epoch besides EpRet / EpLen (Values/V/Mean, Misc/RewScaleMean,
@@ -325,10 +332,14 @@ class PPOTrainer:
                 self.fused = False
                 self.graph_rollout = False
                 self.fm_pi = self.fm_v = None
+        # deep_rollout=True (opt-in): an ACTOR with 3 or 4 hidden layers rolls out in one launch where pds_rollout_deep is built
+        # (include/pds_rollout_deep.h, csrc/pds_rollout_deep.h: the critic, of any depth, runs behind the launch); with two hidden
+        # layers in the actor the keyword changes nothing
+        self.deep_rollout = bool(deep_rollout) and self.fused and self.fm_pi.deep
         if self.fused and (self.fm_pi.deep or self.fm_v.deep):
             # 3 or 4 hidden layers (include/pds_mlp_deep.h): each network is its own FusedMLP on the deep kernels; the one-launch
             # rollouts take struct pds_mlp, so the rollout runs on the per-step kernels (captured into a graph as before)
-            if self.fused_rollout:
+            if self.fused_rollout and not self.deep_rollout:
                 raise NotImplementedError("fused_rollout=True: the one-launch rollouts take networks with 2 hidden layers "
                                           f"(pi {self.fm_pi.n_hidden}, val {self.fm_v.n_hidden})")
         if self.fused:
@@ -343,7 +354,7 @@ class PPOTrainer:
         self.val_buf, self._last_val_buf = self._val_store[:T], self._val_store[T]
         self.act_buf = torch.zeros(T, N, 4, **f)
         self.rew_buf, self.logp_buf, self.fval_buf = (torch.zeros(T, N, **f) for _ in range(3))
-        self._fin_rows = self._fin_step = None         # pds_rollout_history's slot list (allocated at its first call)
+        self._fin_rows = self._fin_step = None         # the slot list of pds_rollout_history / pds_rollout_deep (allocated at its first call)
         self.term_buf = torch.zeros(T, N, device=dev, dtype=torch.uint8)
         self.trunc_buf = torch.zeros(T, N, device=dev, dtype=torch.uint8)
         self.ep_ret = torch.zeros(N, **f)
@@ -383,6 +394,10 @@ class PPOTrainer:
             try:
                 if getattr(self.env, "observation_history_size", 2) != 2:
                     return self._roll_out_fused_history()
+                if self.deep_rollout:
+                    if self.fused_rollout is None and self.N >= DEEP_ROLLOUT_PER_STEP_FROM:
+                        raise NotImplementedError("deep_rollout: the per-step kernels are faster at this env count")
+                    return self._roll_out_fused_deep()
                 return self._roll_out_fused()
             except NotImplementedError:
                 if self.fused_rollout:  # asked for explicitly
@@ -416,19 +431,11 @@ class PPOTrainer:
         the critic over the whole rollout in one pds_mlp_forward (V(o(0..T)): val_buf and last_val) and one over the final
         histories of the paths that bootstrap with V.  Same draws and same bits as the per-step path."""
         from .fused import fused_rollout_history
-        env, T, N = self.env, self.T, self.N
-        H, D = env.observation_history_size, env.obs_dim
+        env, T, H = self.env, self.T, self.env.observation_history_size
         mean, std, eps = self._oms()
         stats = torch.zeros(3, device=self.obs.device)
-        if self._fin_rows is None:
-            slots = T // int(env.cfg.max_episode_steps) + 2
-            self._fin_rows = torch.zeros(slots, N, D, device=self.obs.device)
-            self._fin_step = torch.empty(slots, N, dtype=torch.int32, device=self.obs.device)
-            self._fval_store = torch.zeros(T * N + 1, device=self.obs.device)  # (+ 1: where the unused slots' values go)
-            self.fval_buf = self._fval_store[:T * N].view(T, N)
-            self._env_ids = torch.arange(N, device=self.obs.device, dtype=torch.int64)
         self._obs_buf[0].copy_(self.obs)
-        self._fin_step.fill_(-1)
+        self._clear_slot_list()
         # (an env created with history_latency=True flies the latency ring: pds_rollout_history_latency, where it is built)
         fused_rollout_history(env, self.fm_pi, T, H, mean, std, eps, self.ac.pi.log_std, self._sample_seed, self._sample_calls,
                               not self.ac.training, self._obs_buf, self.act_buf, self.logp_buf, self.rew_buf, self.term_buf,
@@ -436,16 +443,55 @@ class PPOTrainer:
                               latency=bool(getattr(env, "history_latency", False)))
         self._sample_calls += T
         self.fused_rollout = True
-        # the critic, off the kernel: V(o(t)) for t = 0 .. T in one pass over obs_buf ...
+        self._critic_behind_the_launch(mean, std, eps)
+        env.adopt_history(self.obs)
+        return stats
+
+    def _clear_slot_list(self):
+        """fin_rows / fin_step of the launches that keep the critic outside (pds_rollout_history, pds_rollout_deep), allocated at the
+        first call, every slot marked unused"""
+        T, N, D = self.T, self.N, self.env.obs_dim
+        if self._fin_rows is None:
+            slots = T // int(self.env.cfg.max_episode_steps) + 2
+            self._fin_rows = torch.zeros(slots, N, D, device=self.obs.device)
+            self._fin_step = torch.empty(slots, N, dtype=torch.int32, device=self.obs.device)
+            self._fval_store = torch.zeros(T * N + 1, device=self.obs.device)  # (+ 1: where the unused slots' values go)
+            self.fval_buf = self._fval_store[:T * N].view(T, N)
+            self._env_ids = torch.arange(N, device=self.obs.device, dtype=torch.int64)
+        self._fin_step.fill_(-1)
+
+    def _critic_behind_the_launch(self, mean, std, eps):
+        """the critic, off the kernel (2, 3 or 4 hidden layers): V(o(t)) for t = 0 .. T in one pass over obs_buf -> val_buf and
+        last_val, and V(final row) of the paths that bootstrap with it -> fval_buf[fin_step, env]; the rollout's last row becomes
+        the current observation"""
+        T, N, D = self.T, self.N, self.env.obs_dim
         self.fm_v.forward(self._obs_buf.view((T + 1) * N, D), mean=mean, std=std, eps=eps, out=self._val_store.view(-1, 1))
-        # ... and V(final history) of the paths that bootstrap with it -> fval_buf[fin_step, env]
         vfin = self.fm_v.forward(self._fin_rows.view(-1, D), mean=mean, std=std, eps=eps).view(-1, N)
         step = self._fin_step.to(torch.int64)
         target = torch.where(step >= 0, step * N + self._env_ids, torch.full_like(step, T * N))
         self._fval_store.scatter_(0, target.view(-1), vfin.reshape(-1))
         self.obs = self._obs_buf[T]
-        env.adopt_history(self.obs)
         self.last_val = self._last_val_buf
+
+    @torch.no_grad()
+    def _roll_out_fused_deep(self):
+        """deep_rollout=True, an actor with 3 or 4 hidden layers: actor, sampling and env step in one launch (pds_rollout_deep), then
+        the critic -- 2, 3 or 4 hidden layers -- over the whole rollout in one forward (V(o(0..T)): val_buf and last_val) and one
+        over the final observations of the paths that bootstrap with V: _roll_out_fused_history without the history.  Same draws
+        and same bits as the per-step path.  NotImplementedError (fused_rollout_deep) where the kernel is not built, with the env
+        untouched."""
+        from .fused import fused_rollout_deep
+        env, T = self.env, self.T
+        mean, std, eps = self._oms()
+        stats = torch.zeros(3, device=self.obs.device)
+        self._obs_buf[0].copy_(self.obs)
+        self._clear_slot_list()
+        fused_rollout_deep(env, self.fm_pi, T, mean, std, eps, self.ac.pi.log_std, self._sample_seed, self._sample_calls,
+                           not self.ac.training, self._obs_buf, self.act_buf, self.logp_buf, self.rew_buf, self.term_buf,
+                           self.trunc_buf, self.cost_buf, self._fin_rows, self._fin_step, self.ep_ret, self.ep_len, stats)
+        self._sample_calls += T
+        self.fused_rollout = True
+        self._critic_behind_the_launch(mean, std, eps)
         return stats
 
     def _roll_out_graph(self):
