@@ -18,7 +18,8 @@ with --record as without it.
 
 A group whose actors have three or four hidden layers -- the (50, 30, 20) and (32, 32, 32, 32) actors of train_ppo.py
 --pi-hidden ... --deep-fused -- flies in one launch as well (pds_evaluate_policies_deep), with --metrics from the same launch;
---record flies such a group on the composed path and says so, and an observation history is not evaluated at these depths.
+--record flies such a group on the composed path and says so -- with --deep-forms-fused it takes the launch too
+(pds_evaluate_policies_deep_record, where it is built) --, and an observation history is not evaluated at these depths.
 """
 import argparse
 import json
@@ -29,7 +30,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import phoenix_drone_simulation_amd as pds  # noqa: E402
-from phoenix_drone_simulation_amd.evaluation import PolicyPopulation, evaluate_population  # noqa: E402
+from phoenix_drone_simulation_amd.evaluation import PolicyPopulation, evaluate_population, fused_deep_forms_evaluation_built  # noqa: E402
 from phoenix_drone_simulation_amd.ppo import ActorCritic  # noqa: E402
 
 
@@ -119,6 +120,9 @@ def main():
     ap.add_argument("--history-latency-fused", action="store_true",
                     help="with --history-latency: evaluate on the ring in one launch (pds_evaluate_policies_history_latency*) where it "
                          "is built, instead of the composed path")
+    ap.add_argument("--deep-forms-fused", action="store_true",
+                    help="with --record and checkpoints of three or four hidden layers: record in the one launch "
+                         "(pds_evaluate_policies_deep_record) where it is built, instead of the composed path")
     args = ap.parse_args()
     if args.record_dir and not args.record:
         ap.error("--record-dir needs --record R")
@@ -154,11 +158,13 @@ def main():
                   f"{getattr(env, 'observation_history_size', 2)}: not evaluated at this depth, skipped")
             env.close()
             continue
-        if pop.deep and args.record and fused is not True:
-            print(f"group {gi}: {len(hidden)} hidden layers with --record: the launch for these depths has no record form, "
-                  "this group flies on the composed path (pds_mlp_deep_forward per checkpoint and step)")
+        in_launch = args.deep_forms_fused and pop.deep and fused_deep_forms_evaluation_built(env, pop, "record")
+        if pop.deep and args.record and fused is not True and not in_launch:
+            print(f"group {gi}: {len(hidden)} hidden layers with --record: " +
+                  ("the record form of the launch is not built for this env, " if args.deep_forms_fused else
+                   "without --deep-forms-fused ") + "this group flies on the composed path (pds_mlp_deep_forward per checkpoint and step)")
         out = evaluate_population(env, pop, fused=fused, metrics=args.metrics, history_fused=True, record=args.record,
-                                  history_latency_fused=args.history_latency_fused,
+                                  history_latency_fused=args.history_latency_fused, deep_forms_fused=args.deep_forms_fused,
                                   log_dir=os.path.join(args.log_dir, str(gi)) if args.log_dir else None)
         ret, length, cost = out[:3]
         table = out[3].table() if args.metrics else {}

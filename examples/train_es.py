@@ -10,6 +10,10 @@ The checkpoint is PPOTrainer's (`torch_save/model.pt` + `model.json`): examples/
 
 --penalise NAME=W (repeatable) trains on return - W x the raw flight metric NAME (es.penalised_return; the names are
 evaluation.METRIC_NAMES), e.g. --penalise action_rate_sq=0.5 against chattering motor commands.
+
+--hidden H1 H2 [H3 [H4]] sets the actor's hidden widths: two, or three or four of at most 64 each -- the small deep actors of the
+reference's architecture search, e.g. --hidden 50 30 20 or --hidden 32 32 32 32 --activation tanh.  At three and four hidden
+layers --obs-stats online takes its sums from the generation's launch with --deep-forms-fused (pds_evaluate_policies_deep_stats).
 """
 import argparse
 import os
@@ -41,6 +45,12 @@ def main():
     ap.add_argument("--population", type=int, default=4096, help="policies per generation (even: antithetic pairs)")
     ap.add_argument("--episodes", type=int, default=64, help="episodes per policy, a multiple of 64")
     ap.add_argument("--generations", type=int, default=100)
+    ap.add_argument("--hidden", type=int, nargs="+", default=[50, 50], metavar="H",
+                    help="hidden widths of the actor: two, or three or four of at most 64 each")
+    ap.add_argument("--activation", choices=("relu", "tanh"), default="relu", help="the actor's activation")
+    ap.add_argument("--deep-forms-fused", action="store_true",
+                    help="with three or four hidden widths and --obs-stats online: the generation's launch also sums the observations "
+                         "(pds_evaluate_policies_deep_stats) where it is built, instead of the composed path")
     ap.add_argument("--sigma", type=float, default=0.02, help="standard deviation of the parameter noise")
     ap.add_argument("--lr", type=float, default=0.01, help="Adam's learning rate on the centre")
     ap.add_argument("--seed", type=int, default=0)
@@ -78,7 +88,8 @@ def main():
     fitness = penalised_return(weights) if weights else None  # (ValueError names the metrics there are)
     env = pds.make(args.env, num_envs=args.population * args.episodes, seed=args.seed,
                    observation_history_size=args.history, **latency_kwargs(args))  # otherwise the reference's default config
-    trainer = ESTrainer(env, args.population, sigma=args.sigma, lr=args.lr, seed=args.seed,
+    trainer = ESTrainer(env, args.population, hidden_sizes=tuple(args.hidden), activation=args.activation,
+                        deep_forms_fused=args.deep_forms_fused, sigma=args.sigma, lr=args.lr, seed=args.seed,
                         obs_stats=None if args.obs_stats == "none" else args.obs_stats, eval_every=args.eval_every, fitness=fitness,
                         shaping=args.shaping, top_b=args.top_b, history_fused=args.history_fused,
                         history_stats_fused=args.history_stats_fused, history_latency_fused=args.history_latency_fused)

@@ -17,6 +17,7 @@
 #include "pds_collect_args.h"
 #include "pds_evaluate_args.h"
 #include "pds_evaluate_deep_args.h"
+#include "pds_evaluate_deep_forms_args.h"
 #include "pds_evaluate_hist_args.h"
 #include "pds_rollout_deep_args.h"
 #include "pds_simopt.h"
@@ -1427,42 +1428,95 @@ extern "C" int pds_evaluate_deep_supported(const pds_handle *h, const pds_mlp_de
                      evaluate_deep_variant_built(h->cfg.task, h->flags, shape->n_hidden);
   return built ? 1 : 0;
 }
-// P policies x E episodes in one launch, the actors with three or four hidden layers.  The checks and the handle's state afterwards
-// are pds_evaluate_policies_metrics'; d_metrics is optional (summed either way: one code object per variant and depth).
-extern "C" int pds_evaluate_policies_deep(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp_deep *shape,
-                                          const float *d_params, const float *d_mean, const float *d_std, float eps, int32_t max_steps,
-                                          const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
-                                          void *stream) {
-  const char *fn = "pds_evaluate_policies_deep";
+// P policies x E episodes in one launch, the actors with three or four hidden layers: ONE body for the three forms of
+// evaluate_deep_kernel (csrc/pds_evaluate_deep.h), as evaluate_policies_call is for evaluate_kernel's.  The checks and the handle's
+// state afterwards are those of the form's two-hidden-layer entry point -- the record's own checks first, d_obs_sums given and
+// aligned --; d_metrics is optional in every form (summed either way); the struct and the family are this kernel's questions.
+template <EvalForm F>
+static int evaluate_policies_deep_call(pds_handle *h, const char *fn, int64_t P, int64_t episodes_per_policy, const pds_mlp_deep *shape,
+                                       const float *d_params, const float *d_mean, const float *d_std, float eps, int32_t max_steps,
+                                       const float *d_obs0, float *d_ret, float *d_len, float *d_cost, const EvalFormCall &x, void *stream) {
+  constexpr bool STATS = F == EvalForm::Stats, RECORD = F == EvalForm::Record;
   if (!h) return PDS_EINVAL;
-  const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost;
-  if (const int rc = check_evaluate_population(h, fn, any_null, P, episodes_per_policy, d_mean, d_std, max_steps, d_metrics)) return rc;
+  if constexpr (RECORD) {  // (decided before the handle is looked at)
+    if (const int rc = check_record_call(h, fn, x, episodes_per_policy)) return rc;
+  }
+  const bool any_null = !shape || !d_params || !d_obs0 || !d_ret || !d_len || !d_cost || (STATS && !x.d_obs_sums);
+  if (const int rc = check_evaluate_population(h, fn, any_null, P, episodes_per_policy, d_mean, d_std, max_steps, x.d_metrics)) return rc;
+  if (STATS && (((uintptr_t)x.d_obs_sums) & 15u)) return fail(h, PDS_EINVAL, "%s: d_obs_sums must be 16-byte aligned", fn);
   if (!evaluate_deep_shape_ok(shape, h->obs_dim))
     return fail(h, PDS_EINVAL, "%s: network shape (n_hidden 3 or 4, d_in must be the observation width %d, hidden 1..64, d_out 4, "
                                "activation 0 or 1)", fn, h->obs_dim);
-  if (!evaluate_deep_family(h->cfg.task, h->flags) || !evaluate_deep_variant_built(h->cfg.task, h->flags, shape->n_hidden))
+  const bool built = F == EvalForm::Metrics ? evaluate_deep_variant_built(h->cfg.task, h->flags, shape->n_hidden)
+                                            : evaluate_deep_forms_variant_built(h->cfg.task, h->flags, shape->n_hidden, F);
+  if (!evaluate_deep_family(h->cfg.task, h->flags) || !built)
     return fail(h, PDS_EUNSUPPORTED, "%s: no kernel for this env configuration (built: control_mode PWM without latency ring or Kalman "
                                      "hold, every noise setting; motor dynamics on Hover and Circle, the ground effect on TakeOff) -- "
                                      "pds_mlp_deep_forward + pds_step give the same bits", fn);
   DeviceGuard guard(h->cfg.device);
   PDS_HIP(h, guard.err);
-  EvalDeepArgs ka;
+  EvalDeepKernelArgs<F> ka;
   memset(&ka, 0, sizeof(ka));
-  ka.m.metrics = d_metrics;
+  EvalMetricsArgs &head = eval_deep_head(ka);
+  head.metrics = x.d_metrics;
+  if constexpr (STATS) ka.st.obs_sums = x.d_obs_sums;
+  if constexpr (RECORD) fill_record_args(ka.r, x);
   ka.deep = *shape;
   for (int l = 0; l <= PDS_MLP_DEEP_MAX_HIDDEN; ++l) ka.deep.w[l] = ka.deep.b[l] = nullptr;  // (the kernel lays them out per policy)
   ka.deep_param_count = evaluate_deep_param_count(shape);
-  if (const int rc = fill_evaluate_population_args(h, fn, ka.m.e, episodes_per_policy, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret,
+  if (const int rc = fill_evaluate_population_args(h, fn, head.e, episodes_per_policy, d_params, d_mean, d_std, eps, max_steps, d_obs0, d_ret,
                                                    d_len, d_cost, stream))
     return rc;
   const bool l3 = shape->n_hidden == 3;
+  const int task = h->cfg.task;
   const int rc = launch_rollout(h, fn, max_steps, stream, [&](dim3 grid, hipStream_t s) {
-    if (h->cfg.task == PDS_TASK_HOVER) return l3 ? launch_evaluate_deep_hover_l3(h->flags, grid, s, ka) : launch_evaluate_deep_hover_l4(h->flags, grid, s, ka);
-    if (h->cfg.task == PDS_TASK_CIRCLE) return l3 ? launch_evaluate_deep_circle_l3(h->flags, grid, s, ka) : launch_evaluate_deep_circle_l4(h->flags, grid, s, ka);
-    return l3 ? launch_evaluate_deep_takeoff_l3(h->flags, grid, s, ka) : launch_evaluate_deep_takeoff_l4(h->flags, grid, s, ka);
+    if constexpr (STATS) {
+      if (task == PDS_TASK_HOVER) return l3 ? launch_evaluate_stats_deep_hover_l3(h->flags, grid, s, ka) : launch_evaluate_stats_deep_hover_l4(h->flags, grid, s, ka);
+      if (task == PDS_TASK_CIRCLE) return l3 ? launch_evaluate_stats_deep_circle_l3(h->flags, grid, s, ka) : launch_evaluate_stats_deep_circle_l4(h->flags, grid, s, ka);
+      return l3 ? launch_evaluate_stats_deep_takeoff_l3(h->flags, grid, s, ka) : launch_evaluate_stats_deep_takeoff_l4(h->flags, grid, s, ka);
+    } else if constexpr (RECORD) {
+      if (task == PDS_TASK_HOVER) return l3 ? launch_evaluate_record_deep_hover_l3(h->flags, grid, s, ka) : launch_evaluate_record_deep_hover_l4(h->flags, grid, s, ka);
+      if (task == PDS_TASK_CIRCLE) return l3 ? launch_evaluate_record_deep_circle_l3(h->flags, grid, s, ka) : launch_evaluate_record_deep_circle_l4(h->flags, grid, s, ka);
+      return l3 ? launch_evaluate_record_deep_takeoff_l3(h->flags, grid, s, ka) : launch_evaluate_record_deep_takeoff_l4(h->flags, grid, s, ka);
+    } else {
+      if (task == PDS_TASK_HOVER) return l3 ? launch_evaluate_deep_hover_l3(h->flags, grid, s, ka) : launch_evaluate_deep_hover_l4(h->flags, grid, s, ka);
+      if (task == PDS_TASK_CIRCLE) return l3 ? launch_evaluate_deep_circle_l3(h->flags, grid, s, ka) : launch_evaluate_deep_circle_l4(h->flags, grid, s, ka);
+      return l3 ? launch_evaluate_deep_takeoff_l3(h->flags, grid, s, ka) : launch_evaluate_deep_takeoff_l4(h->flags, grid, s, ka);
+    }
   });
   if (rc == PDS_OK) { h->was_reset = false; h->after_evaluate = true; }  // (tiles stopped at different steps: pds_evaluate_policies)
   return rc;
+}
+extern "C" int pds_evaluate_policies_deep(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp_deep *shape,
+                                          const float *d_params, const float *d_mean, const float *d_std, float eps, int32_t max_steps,
+                                          const float *d_obs0, float *d_ret, float *d_len, float *d_cost, float *d_metrics,
+                                          void *stream) {
+  return evaluate_policies_deep_call<EvalForm::Metrics>(h, "pds_evaluate_policies_deep", P, episodes_per_policy, shape, d_params, d_mean, d_std,
+                                                        eps, max_steps, d_obs0, d_ret, d_len, d_cost, {d_metrics}, stream);
+}
+// ---- its stats and record forms: include/pds_evaluate_deep_forms.h ----
+extern "C" int pds_evaluate_deep_forms_supported(const pds_handle *h, const pds_mlp_deep *shape, int32_t form) {
+  if (!h || !shape || (form != PDS_EVALUATE_DEEP_FORM_STATS && form != PDS_EVALUATE_DEEP_FORM_RECORD)) return PDS_EINVAL;
+  const bool built = h->cfg.auto_reset && evaluate_deep_family(h->cfg.task, h->flags) && evaluate_deep_shape_ok(shape, h->obs_dim) &&
+                     evaluate_deep_forms_variant_built(h->cfg.task, h->flags, shape->n_hidden,
+                                                       form == PDS_EVALUATE_DEEP_FORM_STATS ? EvalForm::Stats : EvalForm::Record);
+  return built ? 1 : 0;
+}
+extern "C" int pds_evaluate_policies_deep_stats(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp_deep *shape,
+                                                const float *d_params, const float *d_mean, const float *d_std, float eps,
+                                                int32_t max_steps, const float *d_obs0, float *d_ret, float *d_len, float *d_cost,
+                                                float *d_metrics, float *d_obs_sums, void *stream) {
+  return evaluate_policies_deep_call<EvalForm::Stats>(h, "pds_evaluate_policies_deep_stats", P, episodes_per_policy, shape, d_params, d_mean,
+                                                      d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost, {d_metrics, d_obs_sums}, stream);
+}
+extern "C" int pds_evaluate_policies_deep_record(pds_handle *h, int64_t P, int64_t episodes_per_policy, const pds_mlp_deep *shape,
+                                                 const float *d_params, const float *d_mean, const float *d_std, float eps,
+                                                 int32_t max_steps, const float *d_obs0, float *d_ret, float *d_len, float *d_cost,
+                                                 float *d_metrics, int64_t record_per_policy, float *d_flight, float *d_obs_rec,
+                                                 void *stream) {
+  return evaluate_policies_deep_call<EvalForm::Record>(h, "pds_evaluate_policies_deep_record", P, episodes_per_policy, shape, d_params, d_mean,
+                                                       d_std, eps, max_steps, d_obs0, d_ret, d_len, d_cost,
+                                                       {d_metrics, nullptr, record_per_policy, d_flight, d_obs_rec}, stream);
 }
 
 // ---- the one-launch rollout for actors with three or four hidden layers: csrc/pds_rollout_deep.h ----

@@ -1,0 +1,6 @@
+// pds_evaluate_record_deep_circle_l4.hip -- evaluate_deep_kernel (pds_evaluate_deep.h), the record form, 4 hidden layers: control_mode PWM, every noise setting x motor dynamics.
+#include "pds_evaluate_deep.h"
+
+namespace pds {
+PDS_EVALUATE_DEEP_FORM_UNIT(launch_evaluate_record_deep_circle_l4, PDS_TASK_CIRCLE, 4, EvalForm::Record)
+}  // namespace pds

@@ -1,0 +1,6 @@
+// pds_evaluate_stats_deep_circle_l3.hip -- evaluate_deep_kernel (pds_evaluate_deep.h), the stats form, 3 hidden layers: control_mode PWM, every noise setting x motor dynamics.
+#include "pds_evaluate_deep.h"
+
+namespace pds {
+PDS_EVALUATE_DEEP_FORM_UNIT(launch_evaluate_stats_deep_circle_l3, PDS_TASK_CIRCLE, 3, EvalForm::Stats)
+}  // namespace pds

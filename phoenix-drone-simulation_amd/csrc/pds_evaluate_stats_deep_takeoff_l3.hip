@@ -1,0 +1,6 @@
+// pds_evaluate_stats_deep_takeoff_l3.hip -- evaluate_deep_kernel (pds_evaluate_deep.h), the stats form, 3 hidden layers: control_mode PWM, every noise setting x the ground effect.
+#include "pds_evaluate_deep.h"
+
+namespace pds {
+PDS_EVALUATE_DEEP_FORM_UNIT(launch_evaluate_stats_deep_takeoff_l3, PDS_TASK_TAKEOFF, 3, EvalForm::Stats)
+}  // namespace pds

@@ -1,0 +1,6 @@
+// pds_evaluate_stats_deep_takeoff_l4.hip -- evaluate_deep_kernel (pds_evaluate_deep.h), the stats form, 4 hidden layers: control_mode PWM, every noise setting x the ground effect.
+#include "pds_evaluate_deep.h"
+
+namespace pds {
+PDS_EVALUATE_DEEP_FORM_UNIT(launch_evaluate_stats_deep_takeoff_l4, PDS_TASK_TAKEOFF, 4, EvalForm::Stats)
+}  // namespace pds

@@ -98,7 +98,13 @@ class ESTrainer:
     The defaults are starting values, not tuned ones.
 
     The centre is an ActorCritic (ppo.py) whose `pi.net` parameters are views into ONE flat float32 tensor `mu` in the layout
-    of pds_mlp_param_count, so checkpoints are the reference's (`save_checkpoint`).  obs_stats: None (mean 0, std 1), a
+    of pds_mlp_param_count, so checkpoints are the reference's (`save_checkpoint`).  hidden_sizes: two widths, or THREE or FOUR
+    widths of 1 .. 64 each (include/pds_mlp_deep.h: the (50, 30, 20) and (32, 32, 32, 32) actors of the reference's architecture
+    search) -- `mu` is then W1 b1 .. W(L+1) b(L+1), the layout of pds_mlp_deep_param_count and of PolicyPopulation.from_flat, the
+    Adam step pds_mlp_deep_adam_step, the generation's launch pds_evaluate_policies_deep; an env with observation_history_size != 2
+    has no path at these depths (ValueError).  deep_forms_fused: the `deep_forms_fused` of the generation's call -- with
+    obs_stats="online" the sums of a deep centre's generation come from the launch too (pds_evaluate_policies_deep_stats, where it
+    is built: the same statistics and the same centre on the bits); it changes nothing at two hidden layers.  obs_stats: None (mean 0, std 1), a
     (mean, std) pair, or "warmup" (WARMUP_STEPS random-action steps through OnlineMeanStd); frozen afterwards -- the
     statistics are not perturbed.  obs_stats="online" starts as "warmup" does and then keeps them running: every generation's
     launch also sums the observations its policies acted on (evaluate_population(..., obs_stats=True)), and their pooled
@@ -117,8 +123,18 @@ class ESTrainer:
 
     def __init__(self, env, population, hidden_sizes=(50, 50), activation="relu", sigma=0.02, lr=0.01, l2=0.005,
                  betas=(0.9, 0.999), seed=0, obs_stats=None, fused=True, eval_every=10, adam_eps=1e-8, fitness=None, shaping="ranks", top_b=None,
-                 evaluate_fused="auto", history_fused=False, history_stats_fused=False, history_latency_fused=False):
+                 evaluate_fused="auto", history_fused=False, history_stats_fused=False, history_latency_fused=False,
+                 deep_forms_fused=False):
         P, N = int(population), int(env.num_envs)
+        hidden_sizes = tuple(int(h) for h in hidden_sizes)
+        if not 2 <= len(hidden_sizes) <= native.MLP_DEEP_MAX_HIDDEN:
+            raise ValueError(f"hidden_sizes = {hidden_sizes}: 2 to {native.MLP_DEEP_MAX_HIDDEN} hidden layers")
+        deep = len(hidden_sizes) > 2
+        if deep and any(h < 1 or h > 64 for h in hidden_sizes):
+            raise ValueError(f"hidden_sizes = {hidden_sizes}: with {len(hidden_sizes)} hidden layers every width is 1 to 64")
+        if deep and int(getattr(env, "observation_history_size", 2)) != 2:
+            raise ValueError(f"hidden_sizes = {hidden_sizes} on an env with observation_history_size {env.observation_history_size}: "
+                             "3 and 4 hidden layers fly at observation_history_size 2 only (2 hidden layers: any)")
         if P < 2 or P % 2 != 0:
             raise ValueError(f"population = {P}: antithetic pairs need an even number of policies")
         if N % P != 0:
@@ -141,9 +157,11 @@ class ESTrainer:
         self.history_fused = history_fused
         self.history_stats_fused = history_stats_fused
         self.history_latency_fused = history_latency_fused
+        self.deep_forms_fused = bool(deep_forms_fused)
+        self.deep = deep
         self.fitness = fitness
         self.env, self.P, self.H, self.E, self.N = env, P, P // 2, N // P, N
-        self.hidden_sizes, self.activation = tuple(int(h) for h in hidden_sizes), activation
+        self.hidden_sizes, self.activation = hidden_sizes, activation
         self.sigma, self.lr, self.l2, self.betas, self.adam_eps = float(sigma), float(lr), float(l2), tuple(betas), float(adam_eps)
         self.seed, self.fused, self.eval_every = int(seed) & 0xFFFFFFFFFFFFFFFF, bool(fused), int(eval_every)
         self.pair_base = 0  # (a later multi-rank form gives each rank a slice of the pairs)
@@ -153,7 +171,7 @@ class ESTrainer:
         self.ac = ActorCritic(env.obs_dim, env.act_dim,
                               {"pi": {"hidden_sizes": self.hidden_sizes, "activation": activation},
                                "val": {"hidden_sizes": (64, 64), "activation": "tanh"}}).to(dev)
-        # the flat centre: W1, b1, W2, b2, W3, b3 in torch parameter order; the actor's parameters become views into it
+        # the flat centre: W1, b1, ..., W(L+1), b(L+1) in torch parameter order; the actor's parameters become views into it
         lin = [l for l in self.ac.pi.net if isinstance(l, torch.nn.Linear)]
         params = [p for l in lin for p in (l.weight, l.bias)]
         self.n = sum(p.numel() for p in params)
@@ -162,9 +180,14 @@ class ESTrainer:
         for p in params:
             p.data = self.mu[off:off + p.numel()].view_as(p)
             off += p.numel()
-        m = native.mlp(env.obs_dim, *self.hidden_sizes, env.act_dim, activation, tensors=params)
-        if self.lib.pds_mlp_param_count(C.byref(m)) != self.n:
-            raise ValueError("layer sizes outside the fused kernels' range (d_in <= 192, h1, h2 <= 64, d_out <= 8)")
+        if deep:  # struct pds_mlp_deep: read by pds_mlp_deep_adam_step (by reference)
+            m = native.mlp_deep(env.obs_dim, self.hidden_sizes, env.act_dim, activation, tensors=params)
+            if self.lib.pds_mlp_deep_param_count(C.byref(m)) != self.n:
+                raise ValueError("layer sizes outside the deep kernels' range (d_in <= 64, 3 or 4 hidden widths of 1 .. 64, d_out <= 8)")
+        else:
+            m = native.mlp(env.obs_dim, *self.hidden_sizes, env.act_dim, activation, tensors=params)
+            if self.lib.pds_mlp_param_count(C.byref(m)) != self.n:
+                raise ValueError("layer sizes outside the fused kernels' range (d_in <= 192, h1, h2 <= 64, d_out <= 8)")
         self._mlp = m
         self.Q = (self.n + 7) // 8
         self.grad = torch.zeros(self.n, device=dev)
@@ -232,6 +255,14 @@ class ESTrainer:
         theta = self._theta
         if self.fused:
             native.call("pds_es_perturb", self.mu, self.n, self.H, self.sigma, self.seed, self.generation, self.pair_base, theta, on=theta)
+        elif self.deep:
+            # a deep centre: the contract of pds_es_perturb as tests/test_gpu_es.py states it, float32(float64(mu) +- float64(sigma)
+            # float64(eps)) -- the product of two float32 values is exact in float64, so this is the kernel's fmaf up to the double
+            # rounding, and the two recipes hand the same population to the launch.  (Two hidden layers keep the float32 ops below,
+            # whose bits their runs have.)
+            step = float(torch.tensor(self.sigma, dtype=torch.float32)) * self._noise().double()
+            theta[0::2] = (self.mu.double() + step).float()
+            theta[1::2] = (self.mu.double() - step).float()
         else:
             step = self.sigma * self._noise()
             theta[0::2] = self.mu + step
@@ -258,7 +289,9 @@ class ESTrainer:
                         self.grad, self._workspace, on=w)
         else:
             self.grad.copy_(scale * (w @ self._noise()) + self.l2 * self.mu)
-        native.call("pds_adam_step", self._mlp, self.grad, self.exp_avg, self.exp_avg_sq, self.generation + 1, self.lr, self.betas[0],
+        # (a deep centre: the same step over struct pds_mlp_deep's 2 (L + 1) tensors, which are `mu` end to end)
+        name, m = ("pds_mlp_deep_adam_step", C.byref(self._mlp)) if self.deep else ("pds_adam_step", self._mlp)
+        native.call(name, m, self.grad, self.exp_avg, self.exp_avg_sq, self.generation + 1, self.lr, self.betas[0],
                     self.betas[1], self.adam_eps, on=self.mu)
         self.generation += 1
 
@@ -283,7 +316,7 @@ class ESTrainer:
         t1 = self._sync()
         out = evaluate_population(self.env, pop, fused=self.evaluate_fused, metrics=self.fitness is not None, obs_stats=self.online,
                                   history_fused=self.history_fused, history_stats_fused=self.history_stats_fused,
-                                  history_latency_fused=self.history_latency_fused)
+                                  history_latency_fused=self.history_latency_fused, deep_forms_fused=self.deep_forms_fused)
         sums = out[-1] if self.online else None
         if self.fitness is None:
             ret, length = out[0], out[1]

@@ -15,7 +15,8 @@ logged flight by the same definitions.  With `obs_stats=True` it also sums the o
 standardisation (`ObsSums`; include/pds.h pds_evaluate_policies_stats).  With `record=R` the launch also writes the flights
 themselves out -- state, action and observation of every step of the first R episodes per policy -- as a `Flights`
 (include/pds.h pds_evaluate_policies_record).  A population of actors with three or four hidden layers flies in one launch as well
-(include/pds_evaluate_deep.h pds_evaluate_policies_deep: the plain and the metrics call), every other form on the composed path."""
+(include/pds_evaluate_deep.h pds_evaluate_policies_deep: the plain and the metrics call; with deep_forms_fused=True the stats and
+the record call of include/pds_evaluate_deep_forms.h too), every other form on the composed path."""
 import ctypes as C
 import math
 import os
@@ -259,6 +260,19 @@ def fused_deep_evaluation_built(env, population):
     if not getattr(population, "deep", False) or getattr(env, "observation_history_size", 2) != 2:
         return False
     return env.lib.pds_evaluate_deep_supported(env._handle, C.byref(population.mlp(0))) == 1
+
+
+def fused_deep_forms_evaluation_built(env, population, form):
+    """Whether the stats (`form` "stats": pds_evaluate_policies_deep_stats) or the record form ("record":
+    pds_evaluate_policies_deep_record; include/pds_evaluate_deep_forms.h) of the deep evaluation has a kernel for this env and this
+    population: what fused_deep_evaluation_built asks, and the form's code object of the env's variant being one the library
+    launches.  False for a population with two hidden layers."""
+    if form not in ("stats", "record"):
+        raise ValueError("form: 'stats' or 'record'")
+    if not getattr(population, "deep", False) or getattr(env, "observation_history_size", 2) != 2:
+        return False
+    code = native.EVALUATE_DEEP_FORM_STATS if form == "stats" else native.EVALUATE_DEEP_FORM_RECORD
+    return env.lib.pds_evaluate_deep_forms_supported(env._handle, C.byref(population.mlp(0)), code) == 1
 
 
 def fused_history_evaluation_built(env):
@@ -595,10 +609,11 @@ def _plan_population_call(env, population, fused, max_steps, metrics, obs_stats,
 
 
 def _plan_population(env, population, fused, max_steps, metrics, obs_stats, history_fused, record, record_limit_bytes,
-                     history_stats_fused=False, history_latency_fused=False):
+                     history_stats_fused=False, history_latency_fused=False, deep_forms_fused=False):
     """_plan_population_call (which is this plan with history_latency_fused at its default), and with history_latency_fused=True:
     the latency forms of the history kernel count as built where their predicates hold -- an env on the ring, for which the other
-    predicates answer False; evaluate_population tells `_fly_kernel` which by the same predicate."""
+    predicates answer False; evaluate_population tells `_fly_kernel` which by the same predicate.  deep_forms_fused=True: the stats
+    and the record form of a deep population count as built where fused_deep_forms_evaluation_built holds."""
     P, E = _check_population_call(env, population)
     if population.d_in != env.obs_dim:
         raise ValueError(f"the population's actors read {population.d_in} inputs, the env observes {env.obs_dim}")
@@ -613,6 +628,8 @@ def _plan_population(env, population, fused, max_steps, metrics, obs_stats, hist
         raise ValueError("history_stats_fused: True or False")
     if not isinstance(history_latency_fused, (bool, np.bool_)):
         raise ValueError("history_latency_fused: True or False")
+    if not isinstance(deep_forms_fused, (bool, np.bool_)):
+        raise ValueError("deep_forms_fused: True or False")
     T = int(env._max_episode_steps if max_steps is None else max_steps)
     if T < 1:
         raise ValueError(f"max_steps = {T}")
@@ -632,17 +649,21 @@ def _plan_population(env, population, fused, max_steps, metrics, obs_stats, hist
     form = "record" if R is not None else "stats" if obs_stats else "metrics" if metrics else "plain"
     H = int(getattr(env, "observation_history_size", 2))
     if getattr(population, "deep", False):
-        # three or four hidden layers: evaluate_deep_kernel has a plain / metrics form and no other; the composed path flies
-        # every form on pds_mlp_deep_forward, whose inputs end at 64 -- no observation history reaches it
+        # three or four hidden layers: evaluate_deep_kernel's plain / metrics form, and where deep_forms_fused asks for them its
+        # stats and record forms; the composed path flies every form on pds_mlp_deep_forward, whose inputs end at 64 -- no
+        # observation history reaches it
         if H != 2:
             raise NotImplementedError(f"observation_history_size {H} with {len(population.hidden_sizes)} hidden layers: pds_mlp_deep_forward "
                                       "reads up to 64 inputs, on either path")
         use_kernel = False
         if fused is not False:
-            built = form in ("plain", "metrics") and fused_deep_evaluation_built(env, population)
+            if form in ("plain", "metrics"):
+                built = fused_deep_evaluation_built(env, population)
+            else:
+                built = bool(deep_forms_fused) and fused_deep_forms_evaluation_built(env, population, form)
             if fused is True and not built:
                 raise NotImplementedError("pds_evaluate_policies_deep has no kernel for this call (built: the plain and the metrics form -- "
-                                          "not obs_stats, not record --, auto_reset, control_mode PWM without latency ring or Kalman hold; "
+                                          "obs_stats and record with deep_forms_fused=True only --, auto_reset, control_mode PWM without latency ring or Kalman hold; "
                                           "motor dynamics on Hover and Circle, the ground effect on TakeOff); fused='auto' runs the composed path")
             use_kernel = built
         return P, E, T, R, form, use_kernel, None
@@ -679,15 +700,19 @@ def _fly_kernel(env, population, obs, P, E, T, form, H, rec, latency=False):
     and takes d_metrics or NULL, its record form (pds_evaluate_policies_history_record) what the record form takes, its stats form
     (pds_evaluate_policies_history_stats) what the stats form takes, the slab slab_features(H x half) columns wide.  latency=True:
     the three history entry points on the latency ring (include/pds_history_latency_evaluate.h), the same argument lists.
-    A deep population (plain or metrics): pds_evaluate_policies_deep, which takes d_metrics or NULL."""
+    A deep population: pds_evaluate_policies_deep (plain or metrics), which takes d_metrics or NULL, and for the stats and the
+    record form pds_evaluate_policies_deep_stats / _deep_record (include/pds_evaluate_deep_forms.h), the same trailing arguments
+    as at two hidden layers."""
     dev, n = env.device, env.num_envs
     ret = torch.zeros(n, device=dev); cost = torch.zeros(n, device=dev); length = torch.zeros(n, device=dev)
     raw = torch.zeros(n, len(METRIC_NAMES), device=dev) if form != "plain" else None
     slab = torch.zeros(n // 64, SLAB_WAVES, 2, slab_features(population.d_in) if H is not None else SLAB_FEATURES, device=dev) if form == "stats" else None
     _, R, flight, obs_rec = rec if rec is not None else (None,) * 4
-    if population.deep:  # (plain or metrics: _plan_population): one entry point, d_metrics or NULL; the struct goes in by reference
-        native.call("pds_evaluate_policies_deep", env._handle, P, E, C.byref(population.mlp(0)), population.theta, population.mean,
-                    population.std, population.eps, T, obs, ret, length, cost, raw, on=dev, handle=env._handle)
+    if population.deep:  # d_metrics or NULL in every form; the struct goes in by reference
+        name, trail = {"stats": ("pds_evaluate_policies_deep_stats", (slab,)),
+                       "record": ("pds_evaluate_policies_deep_record", (R, flight, obs_rec))}.get(form, ("pds_evaluate_policies_deep", ()))
+        native.call(name, env._handle, P, E, C.byref(population.mlp(0)), population.theta, population.mean,
+                    population.std, population.eps, T, obs, ret, length, cost, raw, *trail, on=dev, handle=env._handle)
         return ret, length, cost, raw, slab
     name, trail = {"plain": ("pds_evaluate_policies", ()),
                    "metrics": ("pds_evaluate_policies_metrics", (raw,)),
@@ -792,7 +817,7 @@ def _population_result(env, population, P, E, T, flown, metrics, obs_stats, rec,
 @torch.no_grad()
 def evaluate_population(env, population, fused="auto", log_dir=None, *, max_steps=None, metrics=False, obs_stats=False,
                         history_fused=False, record=None, record_observations=True, record_limit_bytes=1 << 30, history_latency_fused=False,
-                        history_stats_fused=False):
+                        deep_forms_fused=False, history_stats_fused=False):
     """-> (returns, ep_lengths, costs), each [P, E] float32 on the CPU: policy p of `population` flies the E = num_envs / P
     envs of block p, one episode per env, deterministically (action = actor mean), as `evaluate` does for one policy.
     metrics=True: -> (returns, ep_lengths, costs, FlightMetrics) -- the first three are the same bits; the kernel path is
@@ -842,11 +867,17 @@ def evaluate_population(env, population, fused="auto", log_dir=None, *, max_step
     mode, the Kalman hold, the ground effect off TakeOff), fused=True raises NotImplementedError with the env untouched and "auto"
     runs the composed path, which serves every form with one pds_mlp_deep_forward per policy and step.  An env with
     observation_history_size != 2 raises NotImplementedError for such a population on either path; the history keywords change nothing.
+    deep_forms_fused=True (it changes nothing for a population with two hidden layers, and nothing for the plain and the metrics
+    call): obs_stats=True and record=R of a deep population come from one launch as well -- pds_evaluate_policies_deep_stats and
+    pds_evaluate_policies_deep_record (include/pds_evaluate_deep_forms.h: the stats and the record form of the same kernel, the
+    same slab and the same record on the bits as the composed path, the metrics from the same launch; record_observations=False
+    hands the kernel no observation array) -- where `fused_deep_forms_evaluation_built(env, population, form)` holds; where it does
+    not, fused=True raises NotImplementedError with the env untouched and "auto" runs the composed path.
     The env is reset first and not afterwards: after the fused path it refuses to step until the next reset() of every env
     (a masked reset is refused as well).  `population` is not modified: the call works on device copies of its tensors.
     max_steps: the number of steps flown, by default the env's max_episode_steps (the TimeLimit ends every episode by then)."""
     P, E, T, R, form, use_kernel, H = _plan_population(env, population, fused, max_steps, metrics, obs_stats, history_fused, record,
-                                                       record_limit_bytes, history_stats_fused, history_latency_fused)
+                                                       record_limit_bytes, history_stats_fused, history_latency_fused, deep_forms_fused)
     # (the two families of predicates exclude each other -- with and without the ring --: a kernel flight the latency one allows is its)
     latency = use_kernel and H is not None and bool(history_latency_fused) and fused_history_latency_evaluation_built(env)
     population = population.to(env.device)

@@ -213,6 +213,14 @@ EVALUATE_DEEP_SIGNATURES = {
     "pds_evaluate_deep_supported": (_i32, [_vp, _vp]),
     "pds_evaluate_policies_deep": (_i32, _eval[:3] + [_vp] + _eval[4:] + [_vp] * 2),
 }
+# ... and of include/pds_evaluate_deep_forms.h, the stats and the record form of that evaluation
+# (tests/test_evaluate_deep_forms_cpu.py): pds_evaluate_policies_deep's row with what pds_evaluate_policies_stats / _record add
+EVALUATE_DEEP_FORMS_SIGNATURES = {
+    "pds_evaluate_deep_forms_supported": (_i32, [_vp, _vp, _i32]),
+    "pds_evaluate_policies_deep_stats": (_i32, EVALUATE_DEEP_SIGNATURES["pds_evaluate_policies_deep"][1][:-1] + [_vp] * 2),
+    "pds_evaluate_policies_deep_record": (_i32, EVALUATE_DEEP_SIGNATURES["pds_evaluate_policies_deep"][1][:-1] + [_i64, _vp, _vp, _vp]),
+}
+EVALUATE_DEEP_FORM_STATS, EVALUATE_DEEP_FORM_RECORD = 0, 1  # the `form` of pds_evaluate_deep_forms_supported
 # ... and of include/pds_rollout_deep.h, the one-launch rollout for actors with 3 or 4 hidden layers (tests/test_rollout_deep_cpu.py):
 # pds_rollout_history's row without the history, behind the struct pds_mlp_deep pointer
 ROLLOUT_DEEP_SIGNATURES = {
@@ -239,7 +247,7 @@ def load():
     # an OLDER build given through PDS_LIB for a same-box A/B (profiles/tools/ab_lib.sh) may lack the newer entry points: those
     # are skipped; the shipped library must have every name (AttributeError here, and tests/test_host_cpu.py)
     older = bool(os.environ.get("PDS_LIB"))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()) + list(COLLECT_CONTROL_SIGNATURES.items()) + list(HISTORY_LATENCY_SIGNATURES.items()) + list(HISTORY_LATENCY_EVALUATE_SIGNATURES.items()) + list(MLP_DEEP_SIGNATURES.items()) + list(NPG_DEEP_SIGNATURES.items()) + list(EVALUATE_DEEP_SIGNATURES.items()) + list(ROLLOUT_DEEP_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()) + list(COLLECT_CONTROL_SIGNATURES.items()) + list(HISTORY_LATENCY_SIGNATURES.items()) + list(HISTORY_LATENCY_EVALUATE_SIGNATURES.items()) + list(MLP_DEEP_SIGNATURES.items()) + list(NPG_DEEP_SIGNATURES.items()) + list(EVALUATE_DEEP_SIGNATURES.items()) + list(EVALUATE_DEEP_FORMS_SIGNATURES.items()) + list(ROLLOUT_DEEP_SIGNATURES.items()):
         if older and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
@@ -363,7 +371,7 @@ def call(name, *args, on=None, handle=None):
                 x = x.data_ptr()
             elif hasattr(x, "_bind"):
                 if getattr(x, "deep", False):  # a struct pds_mlp_deep: only its own entry points may read it
-                    if name not in MLP_DEEP_SIGNATURES and name not in NPG_DEEP_SIGNATURES and name not in EVALUATE_DEEP_SIGNATURES and name not in ROLLOUT_DEEP_SIGNATURES:
+                    if name not in MLP_DEEP_SIGNATURES and name not in NPG_DEEP_SIGNATURES and name not in EVALUATE_DEEP_SIGNATURES and name not in EVALUATE_DEEP_FORMS_SIGNATURES and name not in ROLLOUT_DEEP_SIGNATURES:
                         raise NotImplementedError(f"{name} takes networks with 2 hidden layers (struct pds_mlp), not {x.n_hidden}")
                     x._bind()
                     x = C.byref(x.md)

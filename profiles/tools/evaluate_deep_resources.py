@@ -16,7 +16,7 @@ import kernel_resources as kr  # noqa: E402
 
 TASK = {0: "Hover", 1: "Circle", 2: "TakeOff"}
 VARIANT = r"pds::Variant<(\d), (\w+), (\w+), (\w+), (\w+), (\w+), (\d), (\w+), (\w+)>"
-DEEP = re.compile(r"evaluate_deep_kernel<" + VARIANT + r", (\d)>")
+DEEP = re.compile(r"evaluate_deep_kernel<" + VARIANT + r", (\d)(?:, \(pds::EvalForm\)1)?>")  # (the plain / metrics form)
 TWIN = re.compile(r"evaluate_kernel<" + VARIANT + r", 1, \(pds::EvalForm\)1>")
 LDS_LIMIT = 160 * 1024
 
