@@ -40,6 +40,11 @@ def main():
     ap.add_argument("--control-fused", action="store_true",
                     help="with --fused-collect: the launch is pds_collect_control, which also flies AttitudeRate / Attitude and "
                          "the latency ring on Hover and Circle")
+    ap.add_argument("--pi-hidden", type=int, nargs=2, default=[64, 64], metavar=("H1", "H2"), help="the actor's hidden sizes")
+    ap.add_argument("--q-hidden", type=int, nargs=2, default=[64, 64], metavar=("H1", "H2"), help="the Q network's hidden sizes")
+    ap.add_argument("--broad-fused", action="store_true",
+                    help="run hidden sizes above 64 (up to 512) on the fused kernels of include/pds_mlp_broad.h: with --pi-hidden 400 "
+                         "300 --q-hidden 400 300 the reference's default configuration, fused")
     ap.add_argument("--control-mode", default="PWM", choices=["PWM", "AttitudeRate", "Attitude"], help="the env's control_mode")
     ap.add_argument("--use-latency", action="store_true", help="the env's delayed-action ring (the reference's 20 ms)")
     ap.add_argument("--log-dir", default=None, help="default: a fresh temporary directory")
@@ -51,8 +56,10 @@ def main():
     trainer = DDPGTrainer(env, epochs=args.epochs, steps_per_epoch=args.steps_per_epoch, updates_per_step=args.updates_per_step,
                           mini_batch_size=args.mini_batch_size, buffer_size=args.buffer_size, warmup_steps=args.warmup_steps,
                           pi_lr=args.pi_lr, q_lr=args.q_lr, act_noise=args.act_noise, seed=args.seed, fused=not args.no_fused,
-                          fused_collect=args.fused_collect, control_fused=args.control_fused)
-    print(f"{args.env}: {env.num_envs} envs, obs_dim {env.obs_dim}, update path: {'fused HIP kernels' if trainer.fused else 'torch autograd'}, "
+                          fused_collect=args.fused_collect, control_fused=args.control_fused, broad_fused=args.broad_fused,
+                          ac_kwargs={"pi": {"hidden_sizes": tuple(args.pi_hidden)}, "q": {"hidden_sizes": tuple(args.q_hidden)}})
+    path = ("fused HIP kernels for widths above 64" if trainer.broad else "fused HIP kernels") if trainer.fused else "torch autograd"
+    print(f"{args.env}: {env.num_envs} envs, obs_dim {env.obs_dim}, nets {tuple(args.pi_hidden)} / {tuple(args.q_hidden)}, update path: {path}, "
           f"collection: {('one pds_collect_control launch per stretch' if trainer.control_fused else 'one pds_collect launch per stretch') if trainer.collect_fused else 'per-step launches'}")
     t0 = time.time()
     for e in range(args.epochs):

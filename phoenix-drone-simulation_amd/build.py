@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 _UNITS = ["pds_task_hover.hip", "pds_task_circle.hip", "pds_task_takeoff.hip", "pds_task_hover_lat.hip",
           "pds_task_circle_lat.hip", "pds_task_hover_pid.hip", "pds_task_circle_pid.hip", "pds_task_takeoff_lat.hip",
-          "pds_mlp.hip", "pds_mlp_wide.hip", "pds_mlp_deep.hip", "pds_npg_deep.hip", "pds_task_hover_hold.hip", "pds_task_circle_hold.hip", "pds_task_takeoff_hold.hip",
+          "pds_mlp.hip", "pds_mlp_wide.hip", "pds_mlp_deep.hip", "pds_npg_deep.hip", "pds_mlp_broad.hip", "pds_ddpg_broad.hip", "pds_task_hover_hold.hip", "pds_task_circle_hold.hip", "pds_task_takeoff_hold.hip",
           "pds_task_hover_pid_ge.hip", "pds_task_circle_pid_ge.hip", "pds_rollout_hover_pwm.hip", "pds_rollout_circle_pwm.hip", "pds_rollout_hover_lat.hip", "pds_rollout_circle_lat.hip",
           "pds_evaluate_hover_pwm.hip", "pds_evaluate_circle_pwm.hip", "pds_evaluate_hover_lat.hip", "pds_evaluate_circle_lat.hip",
           "pds_evaluate_metrics_hover_pwm.hip", "pds_evaluate_metrics_circle_pwm.hip", "pds_evaluate_metrics_hover_lat.hip",
@@ -56,8 +56,8 @@ _UNITS = ["pds_task_hover.hip", "pds_task_circle.hip", "pds_task_takeoff.hip", "
           "pds_evaluate_record_deep_circle_l4.hip", "pds_evaluate_record_deep_takeoff_l3.hip", "pds_evaluate_record_deep_takeoff_l4.hip",
           "pds_rollout_deep_hover_l3.hip", "pds_rollout_deep_hover_l4.hip", "pds_rollout_deep_circle_l3.hip",
           "pds_rollout_deep_circle_l4.hip", "pds_rollout_deep_takeoff_l3.hip", "pds_rollout_deep_takeoff_l4.hip"]  # longest first; the latency forms of the history evaluation, the deep evaluation, its stats and record forms and the deep rollout last; the stats, history, record, history-record and history-stats forms of the evaluation, the PID / latency forms of the collection and the latency forms of the history rollout appended
-_HEADERS = ["pds_device.h", "pds_types.h", "pds_reset.h", "pds_step.h", "pds_mlp_fwd.h", "pds_rollout.h", "pds_rollout_hist.h", "pds_mlp_common.h", "pds_mlp_tile.h", "pds_mlp_deep_tile.h", "pds_npg_tile.h", "pds_actor_critic.h", "pds_physics.h", "pds_simopt.h", "pds_evaluate.h", "pds_evaluate_args.h", "pds_evaluate_hist.h", "pds_evaluate_hist_args.h", "pds_evaluate_deep.h", "pds_evaluate_deep_args.h", "pds_evaluate_deep_forms_args.h", "pds_rollout_deep.h", "pds_rollout_deep_args.h", "pds_collect.h", "pds_collect_args.h", "pds_explore.h"]
-_DEPS = [os.path.join(_CSRC, f) for f in _UNITS + _HEADERS] + [os.path.join(_HERE, "..", "include", h) for h in ("pds.h", "pds_history_record.h", "pds_history_stats.h", "pds_collect_control.h", "pds_history_latency.h", "pds_history_latency_evaluate.h", "pds_mlp_deep.h", "pds_npg_deep.h", "pds_evaluate_deep.h", "pds_evaluate_deep_forms.h", "pds_rollout_deep.h")]
+_HEADERS = ["pds_device.h", "pds_types.h", "pds_reset.h", "pds_step.h", "pds_mlp_fwd.h", "pds_rollout.h", "pds_rollout_hist.h", "pds_mlp_common.h", "pds_mlp_tile.h", "pds_mlp_deep_tile.h", "pds_mlp_broad_tile.h", "pds_npg_tile.h", "pds_actor_critic.h", "pds_physics.h", "pds_simopt.h", "pds_evaluate.h", "pds_evaluate_args.h", "pds_evaluate_hist.h", "pds_evaluate_hist_args.h", "pds_evaluate_deep.h", "pds_evaluate_deep_args.h", "pds_evaluate_deep_forms_args.h", "pds_rollout_deep.h", "pds_rollout_deep_args.h", "pds_collect.h", "pds_collect_args.h", "pds_explore.h"]
+_DEPS = [os.path.join(_CSRC, f) for f in _UNITS + _HEADERS] + [os.path.join(_HERE, "..", "include", h) for h in ("pds.h", "pds_history_record.h", "pds_history_stats.h", "pds_collect_control.h", "pds_history_latency.h", "pds_history_latency_evaluate.h", "pds_mlp_deep.h", "pds_mlp_broad.h", "pds_npg_deep.h", "pds_evaluate_deep.h", "pds_evaluate_deep_forms.h", "pds_rollout_deep.h")]
 _LIB = os.path.join(_HERE, "libpds_hip.so")
 _OBJ = os.path.join(_HERE, "build")
 # -ffp-contract=on: fuse a*b+c only where one source expression says so (the frontend decides), not

@@ -26,6 +26,10 @@ and the latency ring on Hover and Circle, include/pds_collect_control.h -- the d
 fused_collect=False calls torch.tanh: the one documented difference between the two settings).
 Shapes the kernels are not built for (D + 4 > 64: observation_history_size >= 4, TakeOff from 3; hidden
 sizes above 64, e.g. the reference's (400, 300)) take the autograd path; `trainer.fused` reports which path is in use.
+broad_fused=True (csrc/pds_mlp_broad.hip, csrc/pds_ddpg_broad.hip, include/pds_mlp_broad.h): hidden sizes above 64, up to 512 in
+both networks, run the same six-step update and the policy action on kernels that keep the weights in L2 -- nine launches an
+update; `trainer.broad` reports it.  The keyword changes nothing for shapes up to 64, the collection under it stays per step
+(`collect_fused` is False), and the default False keeps every answer as it was.
 Single process only."""
 import math
 import os
@@ -40,12 +44,26 @@ from .ppo import _mlp
 # the limits of csrc/pds_ddpg.hip (include/pds.h: "Built for D + 4 <= 64 and h1, h2 <= 64 of both networks")
 FUSED_MAX_INPUT = 64
 FUSED_MAX_HIDDEN = 64
+# ... and of csrc/pds_ddpg_broad.hip (include/pds_mlp_broad.h), which broad_fused=True asks for: widths above 64 up to this
+BROAD_MAX_HIDDEN = 512
+# broad_fused=True keeps the autograd path from this mini-batch size upward: at (400, 300) the fused update was measured faster
+# than autograd at 128 .. 16384 rows and slower at 32768 and 65536 (profiles/ddpg_broad_timing.txt, README.md); sizes between
+# 16384 and 32768 were not measured
+BROAD_AUTOGRAD_FROM = 32768
+# ... and policy_action of a broad trainer is the torch module from this many rows (envs) upward: the fused forward was measured
+# faster at 128 .. 8192 rows and slower from 16384 on (the same file)
+BROAD_ACTION_TORCH_FROM = 16384
 ACT_DIM = 4
 
 
-def fused_supported(obs_dim, pi_hidden, q_hidden, pi_activation="relu", q_activation="relu"):
-    """pds_ddpg_supported mirrored in Python: two hidden layers of at most 64 units, relu or tanh, D + 4 <= 64."""
-    ok = lambda h: len(h) == 2 and all(1 <= int(u) <= FUSED_MAX_HIDDEN for u in h)
+def fused_supported(obs_dim, pi_hidden, q_hidden, pi_activation="relu", q_activation="relu", broad=False):
+    """pds_ddpg_supported mirrored in Python: two hidden layers of at most 64 units, relu or tanh, D + 4 <= 64.
+    broad=True: pds_ddpg_broad_supported (include/pds_mlp_broad.h) instead -- two hidden layers of at most 512 units with one
+    above 64, in BOTH networks; the shapes of the first question get False from this one."""
+    if broad:
+        ok = lambda h: len(h) == 2 and all(1 <= int(u) <= BROAD_MAX_HIDDEN for u in h) and max(int(u) for u in h) > FUSED_MAX_HIDDEN
+    else:
+        ok = lambda h: len(h) == 2 and all(1 <= int(u) <= FUSED_MAX_HIDDEN for u in h)
     return (1 <= int(obs_dim) and int(obs_dim) + ACT_DIM <= FUSED_MAX_INPUT and ok(pi_hidden) and ok(q_hidden) and
             pi_activation in ("relu", "tanh") and q_activation in ("relu", "tanh"))
 
@@ -76,7 +94,7 @@ class DDPGQFunction(nn.Module):
 
 class DDPGActorCritic(nn.Module):
     """MLPActorCritic (ddpg.py:53-85).  ac_kwargs: {"pi": {"hidden_sizes", "activation"}, "q": {...}}; default (64, 64) relu
-    for both (the reference's (400, 300) is accepted; it runs on the autograd path)."""
+    for both (the reference's (400, 300) is accepted; it runs on the autograd path unless DDPGTrainer gets broad_fused=True)."""
 
     def __init__(self, obs_dim, act_dim=ACT_DIM, ac_kwargs=None, act_limit=1.0):
         super().__init__()
@@ -238,7 +256,7 @@ class OffPolicyTrainer:
         self.fused_collect, self.control_fused = bool(fused_collect), bool(control_fused)
         self._collect_mode, self._collect_log_std = mode, log_std
         self.collect_fused, self.collect_launches, self._cobs = False, 0, None
-        if self.fused_collect and self.fused:
+        if self.fused_collect and self.fused and not getattr(self, "broad", False):  # (a broad actor collects per step)
             from .fused import collect_control_supported, collect_supported
             supported = collect_control_supported if self.control_fused else collect_supported
             self.collect_fused = supported(self.env, self.fm_pi, mode)
@@ -369,7 +387,8 @@ class DDPGTrainer(OffPolicyTrainer):
 
     def __init__(self, env, ac_kwargs=None, gamma=0.99, polyak=0.995, pi_lr=1e-4, q_lr=1e-3, mini_batch_size=128,
                  act_noise=0.1, warmup_steps=10000, update_after=1000, update_every=50, buffer_size=int(1e6), epochs=100,
-                 steps_per_epoch=64, updates_per_step=1, seed=0, fused=True, fused_collect=False, control_fused=False):
+                 steps_per_epoch=64, updates_per_step=1, seed=0, fused=True, broad_fused=False, fused_collect=False,
+                 control_fused=False):
         if not getattr(env, "_auto_reset", True):
             raise ValueError("DDPGTrainer needs an env with auto_reset=True")
         self.env, self.N, self.D = env, int(env.num_envs), int(env.obs_dim)
@@ -392,11 +411,18 @@ class DDPGTrainer(OffPolicyTrainer):
         self.buffer = ReplayBuffer(cap, self.D, dev, num_envs=self.N, act_dim=env.act_dim, seed=self.seed)
         self.fused = bool(fused) and fused_supported(self.D, kw["pi"]["hidden_sizes"], kw["q"]["hidden_sizes"],
                                                      kw["pi"]["activation"], kw["q"]["activation"])
+        # broad_fused=True: hidden widths above 64 (the reference's default (400, 300)) run on the kernels of
+        # include/pds_mlp_broad.h; a shape the kernels above cover is untouched by the keyword
+        self.broad = (bool(fused) and bool(broad_fused) and not self.fused and self.mini_batch_size < BROAD_AUTOGRAD_FROM and
+                      fused_supported(self.D, kw["pi"]["hidden_sizes"], kw["q"]["hidden_sizes"], kw["pi"]["activation"],
+                                      kw["q"]["activation"], broad=True))
+        self.fused = self.fused or self.broad
         if self.fused:
             from .fused import FusedMLP, ddpg_supported
-            self.fm_pi, self.fm_q = FusedMLP(self.ac.pi.pi, kw["pi"]["activation"]), FusedMLP(self.ac.q.q, kw["q"]["activation"])
-            self.fm_pi_targ = FusedMLP(self.ac_targ.pi.pi, kw["pi"]["activation"])
-            self.fm_q_targ = FusedMLP(self.ac_targ.q.q, kw["q"]["activation"])
+            mk = lambda net, act: FusedMLP(net, act, broad=self.broad)
+            self.fm_pi, self.fm_q = mk(self.ac.pi.pi, kw["pi"]["activation"]), mk(self.ac.q.q, kw["q"]["activation"])
+            self.fm_pi_targ = mk(self.ac_targ.pi.pi, kw["pi"]["activation"])
+            self.fm_q_targ = mk(self.ac_targ.q.q, kw["q"]["activation"])
             if not ddpg_supported(self.fm_pi, self.fm_q):
                 raise RuntimeError("pds_ddpg_supported disagrees with ddpg.fused_supported")  # (the two are pinned by a test)
             self.target_rows = torch.zeros(cap, device=dev)
@@ -420,7 +446,7 @@ class DDPGTrainer(OffPolicyTrainer):
     @torch.no_grad()
     def policy_action(self, obs):
         """act_limit * tanh(pi(obs)), no noise"""
-        if self.fused:
+        if self.fused and not (self.broad and obs.shape[0] >= BROAD_ACTION_TORCH_FROM):
             return self.act_limit * torch.tanh(self.fm_pi.forward(obs))
         return self.ac.pi(obs)
 

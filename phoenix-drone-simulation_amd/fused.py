@@ -21,6 +21,9 @@ Networks with three or four hidden layers (csrc/pds_mlp_deep.hip, include/pds_ml
 adam_step on kernels of their own (FusedMLP.deep); every other row takes two hidden layers and refuses them -- but for
 fisher_vector_product and surrogate_kl of a FusedMLP built with npg_deep=True (csrc/pds_npg_deep.hip, include/pds_npg_deep.h);
 fused_rollout_deep is the one-launch rollout under such an actor (csrc/pds_rollout_deep.h, include/pds_rollout_deep.h).
+Two hidden layers with a width above 64, up to 512 -- the reference's (400, 300) for DDPG -- are FusedMLP(..., broad=True)
+(csrc/pds_mlp_broad.hip, csrc/pds_ddpg_broad.hip, include/pds_mlp_broad.h): forward, value_grad, adam_step, ddpg_policy_grad,
+ddpg_target and polyak run on kernels that keep the weights in L2; every other row refuses such a network.
 
 The gradients are written straight into the `.grad` storage of the torch parameters (one flat
 buffer, torch parameter order), so the optimiser step stays torch.optim.Adam like the reference's."""
@@ -34,6 +37,7 @@ from . import native
 _ptr, _on = native._ptr, native.on_device  # (for direct calls; every launch below enters the library through native.call)
 # the entry points behind FusedMLP.forward / ppo_grad / value_grad / adam_step: include/pds.h, include/pds_mlp_deep.h
 _SHALLOW_CALLS = ("pds_mlp_forward", "pds_ppo_policy_grad_step", "pds_value_grad_step", "pds_adam_step")
+_BROAD_CALLS = ("pds_mlp_broad_forward", None, "pds_mlp_broad_value_grad_step", "pds_mlp_broad_adam_step")  # include/pds_mlp_broad.h
 _DEEP_CALLS = ("pds_mlp_deep_forward", "pds_mlp_deep_ppo_policy_grad_step", "pds_mlp_deep_value_grad_step", "pds_mlp_deep_adam_step")
 # the entry points behind FusedMLP._npg_workspace / fisher_vector_product / surrogate_kl: include/pds.h, include/pds_npg_deep.h
 _NPG_CALLS = ("pds_npg_workspace_floats", "pds_npg_fisher_vector_product", "pds_npg_surrogate_kl")
@@ -54,9 +58,13 @@ class FusedMLP:
     (include/pds_mlp_deep.h): forward, ppo_grad, value_grad, adam_step, flat_grad, stats and workspace are the same calls on the
     deep kernels, everything else that takes a struct pds_mlp raises NotImplementedError, and there is no `m`.
     npg_deep=True: on a deep network _npg_workspace, fisher_vector_product and surrogate_kl are the same calls too, on the kernels
-    of include/pds_npg_deep.h (so conjugate_gradients works over them); on two hidden layers the keyword changes nothing."""
+    of include/pds_npg_deep.h (so conjugate_gradients works over them); on two hidden layers the keyword changes nothing.
+    broad=True: a network with two hidden layers of which one is wider than 64 (up to 512; d_in <= 64) is accepted (`broad` is
+    True): forward, value_grad, adam_step and ddpg_policy_grad are the same calls on the kernels of include/pds_mlp_broad.h,
+    ppo_grad and everything else raise NotImplementedError.  On widths up to 64 the keyword changes nothing; without it such a
+    network is refused as before."""
 
-    def __init__(self, net, activation, npg_deep=False):
+    def __init__(self, net, activation, npg_deep=False, broad=False):
         lin = [l for l in net if isinstance(l, nn.Linear)]
         if len(lin) not in (3, 4, 5) or activation not in native.ACTIVATIONS:
             raise NotImplementedError("fused kernels cover 2, 3 or 4 hidden layers with relu or tanh")
@@ -68,6 +76,7 @@ class FusedMLP:
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                 raise ValueError("fused kernels need contiguous float32 parameters on the HIP device")
         self.lib = native.load()
+        self.broad = bool(broad) and not self.deep and max(lin[0].out_features, lin[1].out_features) > 64
         if self.deep:
             self.md = m = native.mlp_deep(lin[0].in_features, [l.out_features for l in lin[:-1]], lin[-1].out_features, activation,
                                           tensors=self.params)
@@ -75,13 +84,18 @@ class FusedMLP:
         else:
             self.m = m = native.mlp(lin[0].in_features, lin[0].out_features, lin[1].out_features, lin[2].out_features, activation,
                                     tensors=self.params)
-            n = self.lib.pds_mlp_param_count(C.byref(m))
+            n = (self.lib.pds_mlp_broad_param_count if self.broad else self.lib.pds_mlp_param_count)(C.byref(m))
+        if n < 0 and self.broad:
+            raise ValueError("layer sizes outside the broad kernels' range (2 hidden layers: d_in <= 64, h1, h2 <= 512 with one of "
+                             "them above 64, d_out <= 8)")
         if n < 0:
             raise ValueError("layer sizes outside the fused kernels' range (2 hidden layers: d_in <= 192, h1, h2 <= 64, d_out <= 8; "
                              "3 or 4 hidden layers: d_in <= 64, every hidden width <= 64, d_out <= 8)")
         if self.deep and self.lib.pds_mlp_deep_supported(C.byref(m)) != 1:
             raise NotImplementedError(f"the fused kernels for {self.n_hidden} hidden layers take d_in <= 64, not {m.d_in}")
-        self._names = _DEEP_CALLS if self.deep else _SHALLOW_CALLS
+        if self.broad and self.lib.pds_mlp_broad_supported(C.byref(m)) != 1:
+            raise NotImplementedError(f"the fused kernels for hidden widths above 64 take d_in <= 64, not {m.d_in}")
+        self._names = _DEEP_CALLS if self.deep else (_BROAD_CALLS if self.broad else _SHALLOW_CALLS)
         self.npg_deep = bool(npg_deep) and self.deep
         self._npg_names = _NPG_DEEP_CALLS if self.npg_deep else _NPG_CALLS
         dev = self.params[0].device
@@ -91,8 +105,24 @@ class FusedMLP:
             p.grad = self.flat_grad[off:off + p.numel()].view_as(p)
             off += p.numel()
         self.stats = torch.zeros(4, device=dev)
+        if self.broad:  # the activations of a whole batch, hundreds of MB: allocated by the first gradient call (_broad_workspace)
+            self.workspace = None
+            return
         ws = self.lib.pds_mlp_deep_workspace_floats(C.byref(m)) if self.deep else self.lib.pds_mlp_workspace_floats(C.byref(m))
         self.workspace = torch.empty(ws, device=dev)
+
+    def _broad_workspace(self, attr, q_fm=None):
+        """The workspace of a broad gradient call (pds_mlp_broad_workspace_floats; with `q_fm` pds_ddpg_broad_workspace_floats),
+        kept in self.<attr>: a forward-only network (a target network) never allocates one."""
+        ws = getattr(self, attr, None)
+        if ws is None:
+            n = (self.lib.pds_mlp_broad_workspace_floats(C.byref(self.m)) if q_fm is None else
+                 self.lib.pds_ddpg_broad_workspace_floats(C.byref(self.m), C.byref(q_fm.m)))
+            if n < 0:
+                raise (NotImplementedError if n == native.EUNSUPPORTED else ValueError)(f"pds_*_broad_workspace_floats -> {n}")
+            ws = torch.empty(n, device=self.flat_grad.device)
+            setattr(self, attr, ws)
+        return ws
 
     @property
     def d_out(self):
@@ -136,6 +166,9 @@ class FusedMLP:
         """Fills the parameters' .grad with d loss_pi / d theta; returns the stats tensor
         [sum(-min(..)), sum(ratio), sum(0.5 z^2), B] (device, no sync).  adam_lr: also take the torch.optim.Adam step
         with this learning rate, in the same two launches (same bits as ppo_grad + adam_step)."""
+        if self.broad:
+            raise NotImplementedError("ppo_grad takes hidden widths up to 64 (include/pds_mlp_broad.h has forward, value_grad, "
+                                      "adam_step and DDPG's update)")
         opt = self._adam_arg(adam_lr, betas, eps)
         native.call(self._names[1], self, x, act, adv, logp_old, log_std, x.shape[0], float(clip_ratio), self.flat_grad,
                     self.stats, self.workspace, opt, on=x)
@@ -152,8 +185,9 @@ class FusedMLP:
         """Fills .grad with d mse(net(x[index]), target[index]) / d theta; stats[0] = sum of squared errors.
         adam_lr: as in ppo_grad."""
         B = x.shape[0] if index is None else index.shape[0]
+        ws = self._broad_workspace("workspace") if self.broad else self.workspace
         opt = self._adam_arg(adam_lr, betas, eps)
-        native.call(self._names[2], self, x, index, target, B, self.flat_grad, self.stats, self.workspace, opt, on=x)
+        native.call(self._names[2], self, x, index, target, B, self.flat_grad, self.stats, ws, opt, on=x)
         return self.stats
 
     def _npg_workspace(self, candidates):
@@ -194,9 +228,16 @@ class FusedMLP:
         """This network as the DDPG actor (output act_limit * tanh): fills .grad with the gradient of
         -Q(o, pi(o)).mean() over the rows oa[index] = [obs | act] (index None: every row), Q = `q_fm` (read only);
         stats[0] = sum of Q(o, pi(o)), stats[3] = B (csrc/pds_ddpg.hip).  adam_lr: as in ppo_grad.
-        NotImplementedError for shapes the kernel is not built for (ddpg_supported says so beforehand)."""
+        NotImplementedError for shapes the kernel is not built for (ddpg_supported says so beforehand).  A broad actor takes a
+        broad Q (csrc/pds_ddpg_broad.hip)."""
         _refuse_deep("ddpg_policy_grad (pds_ddpg_policy_grad)", self, q_fm)
         B = oa.shape[0] if index is None else index.shape[0]
+        if self.broad:
+            ws = self._broad_workspace("ddpg_workspace", q_fm)
+            opt = self._adam_arg(adam_lr, betas, eps)
+            native.call("pds_ddpg_broad_policy_grad", self, q_fm, oa, index, B, float(act_limit), self.flat_grad, self.stats, ws, opt,
+                        on=oa)
+            return self.stats
         ws = getattr(self, "ddpg_workspace", None)
         if ws is None:
             n = self.lib.pds_ddpg_workspace_floats(C.byref(self.m), C.byref(q_fm.m))
@@ -230,6 +271,8 @@ class FusedMLP:
 def ddpg_supported(pi_fm, q_fm):
     """True when the fused DDPG kernels cover this actor / Q pair (D + 4 <= 64, hidden <= 64, d_out 4 / 1)."""
     _refuse_deep("ddpg_supported (pds_ddpg_supported)", pi_fm, q_fm)
+    if pi_fm.broad or q_fm.broad:  # (include/pds_mlp_broad.h: both networks with a hidden width above 64, up to 512)
+        return pi_fm.broad and q_fm.broad and native.load().pds_ddpg_broad_supported(C.byref(pi_fm.m), C.byref(q_fm.m)) == 1
     return native.load().pds_ddpg_supported(C.byref(pi_fm.m), C.byref(q_fm.m)) == 1
 
 
@@ -238,7 +281,7 @@ def ddpg_target(pi_targ_fm, q_targ_fm, obs2, index, rew, done, gamma, act_limit,
     i = index[g] (index None: every row); the other rows are left alone (include/pds.h pds_ddpg_target)."""
     _refuse_deep("ddpg_target (pds_ddpg_target)", pi_targ_fm, q_targ_fm)
     B = obs2.shape[0] if index is None else index.shape[0]
-    native.call("pds_ddpg_target", pi_targ_fm, q_targ_fm, obs2, index, B, rew, done, float(gamma), float(act_limit), target_rows,
+    native.call("pds_ddpg_broad_target" if pi_targ_fm.broad else "pds_ddpg_target", pi_targ_fm, q_targ_fm, obs2, index, B, rew, done, float(gamma), float(act_limit), target_rows,
                 on=obs2)
     return target_rows
 
@@ -246,7 +289,7 @@ def ddpg_target(pi_targ_fm, q_targ_fm, obs2, index, rew, done, gamma, act_limit,
 def polyak(targ_fm, src_fm, rho):
     """p_targ.mul_(rho); p_targ.add_((1 - rho) * p) over the six tensors of a network pair, one launch, the same bits."""
     _refuse_deep("polyak (pds_polyak)", targ_fm, src_fm)
-    native.call("pds_polyak", targ_fm, src_fm, float(rho), on=targ_fm.params[0])
+    native.call("pds_polyak_broad" if targ_fm.broad else "pds_polyak", targ_fm, src_fm, float(rho), on=targ_fm.params[0])
 
 
 def sac_supported(pi_fm, q1_fm, q2_fm):

@@ -228,6 +228,23 @@ ROLLOUT_DEEP_SIGNATURES = {
     "pds_rollout_deep": (_i32, SIGNATURES["pds_rollout_history"][1][:2] + [_vp] + SIGNATURES["pds_rollout_history"][1][4:]),
 }
 
+# ... and of include/pds_mlp_broad.h, the dense kernels and DDPG's update for two-hidden-layer networks with a hidden width above
+# 64 (tests/test_mlp_broad_cpu.py): the rows of the include/pds.h entry points of the same names, on the same struct pds_mlp
+MLP_BROAD_SIGNATURES = {
+    "pds_mlp_broad_supported": (_i32, [_mp]),
+    "pds_mlp_broad_param_count": SIGNATURES["pds_mlp_param_count"],
+    "pds_mlp_broad_workspace_floats": SIGNATURES["pds_mlp_workspace_floats"],
+    "pds_mlp_broad_forward": SIGNATURES["pds_mlp_forward"],
+    "pds_mlp_broad_value_grad_step": SIGNATURES["pds_value_grad_step"],
+    "pds_mlp_broad_adam_step": SIGNATURES["pds_adam_step"],
+    "pds_ddpg_broad_supported": SIGNATURES["pds_ddpg_supported"],
+    "pds_ddpg_broad_workspace_floats": SIGNATURES["pds_ddpg_workspace_floats"],
+    "pds_ddpg_broad_policy_grad": SIGNATURES["pds_ddpg_policy_grad"],
+    "pds_ddpg_broad_target": SIGNATURES["pds_ddpg_target"],
+    "pds_polyak_broad": SIGNATURES["pds_polyak"],
+}
+MLP_BROAD_MAX_HIDDEN, MLP_BROAD_MAX_BATCH = 512, 65536  # PDS_MLP_BROAD_MAX_HIDDEN, PDS_MLP_BROAD_MAX_BATCH
+
 _lib = None
 
 
@@ -247,7 +264,7 @@ def load():
     # an OLDER build given through PDS_LIB for a same-box A/B (profiles/tools/ab_lib.sh) may lack the newer entry points: those
     # are skipped; the shipped library must have every name (AttributeError here, and tests/test_host_cpu.py)
     older = bool(os.environ.get("PDS_LIB"))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()) + list(COLLECT_CONTROL_SIGNATURES.items()) + list(HISTORY_LATENCY_SIGNATURES.items()) + list(HISTORY_LATENCY_EVALUATE_SIGNATURES.items()) + list(MLP_DEEP_SIGNATURES.items()) + list(NPG_DEEP_SIGNATURES.items()) + list(EVALUATE_DEEP_SIGNATURES.items()) + list(EVALUATE_DEEP_FORMS_SIGNATURES.items()) + list(ROLLOUT_DEEP_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(HISTORY_RECORD_SIGNATURES.items()) + list(HISTORY_STATS_SIGNATURES.items()) + list(COLLECT_CONTROL_SIGNATURES.items()) + list(HISTORY_LATENCY_SIGNATURES.items()) + list(HISTORY_LATENCY_EVALUATE_SIGNATURES.items()) + list(MLP_DEEP_SIGNATURES.items()) + list(NPG_DEEP_SIGNATURES.items()) + list(EVALUATE_DEEP_SIGNATURES.items()) + list(EVALUATE_DEEP_FORMS_SIGNATURES.items()) + list(ROLLOUT_DEEP_SIGNATURES.items()) + list(MLP_BROAD_SIGNATURES.items()):
         if older and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
@@ -376,6 +393,10 @@ def call(name, *args, on=None, handle=None):
                     x._bind()
                     x = C.byref(x.md)
                 else:
+                    if getattr(x, "broad", False) != (name in MLP_BROAD_SIGNATURES):  # a width above 64: only its own entry points
+                        raise NotImplementedError(f"{name} takes networks with hidden widths " +
+                                                  ("above 64 (include/pds_mlp_broad.h)" if name in MLP_BROAD_SIGNATURES else
+                                                   "up to 64, not a network built with broad=True (include/pds_mlp_broad.h)"))
                     x._bind()
                     x = C.byref(x.m)
         a.append(x)
